@@ -12,7 +12,11 @@ code/MultiKE_model.py:304-310).  Workload at N=1: BASELINE.json configs[1] shape
 
     python bench.py --config c5        # BASELINE.json configs[4] per-GPU shape (|E|=2M, |R|=2K, dim=256, neg=64): the
                                        # HBM-resident size (2 GB table; C2's 192 MB working set sits in the Infinity Cache)
+    python bench.py --full             # + repeated windows (spread), the instrumented pass (roofline), the side lines
+                                       # (C5, Zipf, reference defaults, attribute view, PyTorch port) and the CPU baseline
+    python bench.py --dump-outputs DIR # + what the last timed step left: DIR/<name>.npy (see dump_outputs)
 
+A plain run sets up, warms up, times exactly --steps steps and prints the headline; everything else is behind --full.
 Prints ONE JSON line on rank 0 (see DESIGN.md §6 for every field).
 """
 import argparse
@@ -62,20 +66,25 @@ def parse():
     ap.add_argument("--dim", type=int, default=None)
     ap.add_argument("--neg", type=int, default=None)
     ap.add_argument("--batch", type=int, default=None)
-    ap.add_argument("--no-variants", action="store_true", help="skip the reference-default-shape side lines (N=10, truncated)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline window: repeated windows, the instrumented pass (roofline), the side lines and the "
+                         "CPU baseline (a plain run does none of these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one left (loss, sampled table rows) as DIR/<name>.npy")
+    ap.add_argument("--no-variants", action="store_true", help="--full: skip the side lines (C5, Zipf, reference defaults, ...)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="time budget of each cpu_baseline leg")
     ap.add_argument("--sample-chunk", type=int, default=0, help="steps sampled per sampler launch (0 = whole epoch)")
     ap.add_argument("--rel-grad-copies", type=int, default=8, help="privatised copies of the relation gradient scratch (the model's default: MultiKE_model.REL_GRAD_COPIES)")
     ap.add_argument("--force-sharded", action="store_true", help="run the row-sharded multi-GPU path even at N=1")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--prewarm-epochs", type=int, default=1,
                     help="whole untimed epochs run BEFORE the --warmup steps (clocks, caches, first launches); the timed region "
                          "is unchanged: exactly --steps complete steps")
     ap.add_argument("--cpu-steps", type=int, default=360, help="upper bound of steps per cpu_baseline leg")
     ap.add_argument("--windows", type=int, default=None,
-                    help="how many times the --steps window is timed (same bracket every time; `value` = the median window, the "
-                         "first window is reported beside it).  Default: as many as make the timed work >= 60 ms, at least 50 "
-                         "for windows of <= 100 steps, 5 otherwise")
+                    help="how many times the --steps window is timed (same bracket every time; `value` = the first window, the "
+                         "median is reported beside it).  Default: 1; with --full as many as make the timed work >= 60 ms, at "
+                         "least 50 for windows of <= 100 steps, 5 otherwise")
     ap.add_argument("--zipf", type=float, default=0.0, help="Zipf exponent of the head / tail entities of the synthetic triples (0 = uniform)")
     ap.add_argument("--rel-zipf", type=float, default=0.0, help="Zipf exponent of the relation ids of the synthetic triples (0 = uniform)")
     a = ap.parse_args()
@@ -687,6 +696,45 @@ class FusedWorkload:
         return roofline
 
 
+DUMP_ARRAY_BYTES = 15 << 20    # per dumped table array: four of them stay under 64 MB
+
+
+def dump_rows(n_rows, dim):
+    """Row ids a dumped table array holds: every row when [n_rows, dim] float32 fits DUMP_ARRAY_BYTES, else a fixed, seeded,
+    sorted sample of as many rows as fit (the same ids in every run of the same shape)."""
+    k = min(n_rows, DUMP_ARRAY_BYTES // (4 * dim))
+    if k == n_rows:
+        return np.arange(n_rows)
+    return np.sort(np.random.default_rng(0).choice(n_rows, k, replace=False))
+
+
+def dump_outputs(out_dir, tables, dim, loss=None, dist=None, world=1, rank=0):
+    """--dump-outputs: what the timed path left after its last step, as float32 / float64 arrays in out_dir/<name>.npy —
+    the entity and relation rows and their Adagrad accumulators (dump_rows' ids of each table) and, on the single-GPU path,
+    that step's loss.  `tables`: name -> (device array [rows, stride], sharded by id % world or replicated, global rows).
+    Called by every rank (the sharded rows are gathered to rank 0, which writes)."""
+    out = {}
+    for name, (arr, sharded, n_rows) in tables.items():
+        ids = dump_rows(n_rows, dim)
+        if sharded and world > 1:
+            mine = ids[ids % world == rank]
+            part = (mine, arr[torch.as_tensor(mine // world, device=arr.device), :dim].cpu().numpy())
+            parts = [None] * world
+            dist.all_gather_object(parts, part)
+            rows = np.zeros((len(ids), dim), dtype=np.float32)
+            for got_ids, got_rows in parts:
+                rows[np.searchsorted(ids, got_ids)] = got_rows
+        else:                                  # replicated, or the one shard of a one-rank group
+            rows = arr[torch.as_tensor(ids, device=arr.device), :dim].cpu().numpy()
+        out[name] = rows.astype(np.float32)
+    if loss is not None:
+        out["loss_last_step"] = np.array([loss], dtype=np.float64)
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        for name, a in out.items():
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -805,21 +853,36 @@ def main():
             dt_ = float(tmax)
         return dt_
 
-    # The contract's timed region (W warm-up steps, then exactly K steps) is the FIRST window.  It is then repeated, same
-    # bracket, same K, so that the line carries a spread: `value` / `ms_per_step` are the MEDIAN window (first window beside it).
+    # The contract's timed region (W warm-up steps, then exactly K steps) is the FIRST window: `value` / `ms_per_step`.  With
+    # --full (or --windows) it is then repeated, same bracket, same K, so that the line carries a spread and the median window.
     first = args_w0 + args.warmup
     if fused is not None:
         first = fused.window_start(first, args.steps)
     dt_first = time_window(first)
+    nxt = first + args.steps
+    if args.dump_outputs:                            # the state the last timed step left, before anything else runs
+        last = nxt - 1
+        if sharded:
+            tables = {"ent_embeds_rows": (trainer.ent, True, args.n_ent), "ent_accumulator_rows": (trainer.ent_acc, True, args.n_ent),
+                      "rel_embeds_rows": (trainer.rel, False, args.n_rel), "rel_accumulator_rows": (trainer.rel_acc, False, args.n_rel)}
+            loss = None                              # the sharded trainers report their loss per epoch (epoch_loss)
+        else:
+            E, R = fused.E, fused.R
+            tables = {"ent_embeds_rows": (E.data, False, E.n_rows), "ent_accumulator_rows": (E.slot("relation"), False, E.n_rows),
+                      "rel_embeds_rows": (R.data, False, R.n_rows), "rel_accumulator_rows": (R.slot("relation"), False, R.n_rows)}
+            loss = float(fused.runner.step_losses()[last % n_steps_epoch])
+        dump_outputs(args.dump_outputs, tables, d, loss, dist, world, rank)
     n_win = args.windows
-    if n_win is None:
+    if n_win is None and not args.full:
+        n_win = 1
+    elif n_win is None:
         n_win = max(50 if args.steps <= 100 else 5, int(np.ceil(0.060 / max(dt_first, 1e-6))))
         n_win = min(n_win, 400)
     win_dt, win_scored = [dt_first], [sum(triples_of(i) for i in range(first, first + args.steps))]
-    nxt = first + args.steps
-    # the window count is planned from the first window; if that one was an outlier (cold caches, a host hiccup) windows are added
-    # until the timed region holds 60 ms (never with an explicit --windows, never beyond 400)
-    while len(win_dt) < max(1, n_win) or (args.windows is None and sum(win_dt) < 0.060 and len(win_dt) < 400):
+    # --full: the window count is planned from the first window; if that one was an outlier (cold caches, a host hiccup) windows are
+    # added until the timed region holds 60 ms (never with an explicit --windows, never beyond 400)
+    grow = args.full and args.windows is None
+    while len(win_dt) < max(1, n_win) or (grow and sum(win_dt) < 0.060 and len(win_dt) < 400):
         if fused is not None:
             nxt = fused.window_start(nxt, args.steps)
         win_dt.append(time_window(nxt))
@@ -846,7 +909,7 @@ def main():
     args_end = nxt                                   # first global step index after the timed windows
 
     roofline = None
-    if not sharded:
+    if args.full and not sharded:
         base = args_end
         n_inst = max(min(args.steps, 300), 100)      # >= 100 launches whatever --steps is (the driver passes 20)
         # PMC bytes per launch of this kernel (separate rocprofv3 --pmc passes), or None
@@ -854,7 +917,7 @@ def main():
         roofline["launch_histogram"] = fused.last_hist
 
     variants = None
-    if not sharded and not args.no_variants and args.config == "c2" and not getattr(args, "custom", False) and not args.zipf and not args.rel_zipf:
+    if args.full and not sharded and not args.no_variants and args.config == "c2" and not getattr(args, "custom", False) and not args.zipf and not args.rel_zipf:
         variants = reference_default_variants(args, kgs, ent0, rel0, fused.sides)
         del fused
         torch.cuda.empty_cache()
@@ -865,7 +928,7 @@ def main():
         torch.cuda.empty_cache()
         variants.insert(0, hbm_resident_variant(args))
 
-    if sharded:
+    if args.full and sharded:
         # same instrumentation on the sharded path: events around this rank's score-kernel launches (extra steps)
         trainer.score_events = []
         base = args_end
@@ -931,7 +994,7 @@ def main():
         from multike_amd.tables import PLACEMENT_LOG
         if PLACEMENT_LOG and variants is None:       # arrays of >= 1 GB placed by trial (the C5 variant carries its own log)
             out["placement"] = PLACEMENT_LOG
-        if not sharded and not args.no_cpu_baseline:
+        if args.full and not sharded and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, kgs, ent0, rel0)
         line = json.dumps(out)
     else:

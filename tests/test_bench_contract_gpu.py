@@ -1,5 +1,5 @@
-"""bench.py's output contract (one JSON line with the fields the driver reads) on a short run, N=1 and the 1-rank
-sharded path."""
+"""bench.py's output contract (one JSON line with the fields the driver reads) on a short run: the plain run (headline only,
+--dump-outputs), --full at N=1 and on the 1-rank sharded path."""
 import json
 import os
 import subprocess
@@ -39,7 +39,7 @@ def _check_roofline(r):
 
 
 def test_n1_line():
-    d = _run([])
+    d = _run(["--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -88,9 +88,41 @@ def test_n1_line():
 
 
 def test_sharded_line_one_rank():
-    d = _run(["--force-sharded"])
+    d = _run(["--full", "--force-sharded"])
     assert d["n_gpus"] == 1 and d["roofline"]["achieved"] > 0 and "cpu_baseline" not in d
     assert d["rccl"]["world"] == 1 and d["rccl"]["backend"].startswith("nccl")      # a real one-rank RCCL group
+
+
+DUMPED = ("ent_embeds_rows", "ent_accumulator_rows", "rel_embeds_rows", "rel_accumulator_rows", "loss_last_step")
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """The plain run is the headline alone: exactly --steps timed steps in one window, nothing of --full.  --dump-outputs writes
+    what the last timed step left (float32 / float64, at most 64 MB), and two runs with the same arguments agree on it up to
+    the order of the kernels' floating-point atomics."""
+    import numpy as np
+    runs = []
+    for name in ("a", "b"):
+        d = _run(["--dump-outputs", str(tmp_path / name)])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 12 and d["warmup"] == 3 and d["n_gpus"] == 1 and d["dtype"] == "f32"
+        assert abs(d["value"] - d["config"]["scored_per_step"] / (d["ms_per_step"] * 1e-3)) / d["value"] < 0.02
+        w = d["window_ms"]
+        assert w["n"] == 1 and w["steps_per_window"] == 12 and abs(w["first_window"] - d["ms_per_step"] * 12) < 1e-9
+        assert d["roofline"] is None and "variants" not in d and "cpu_baseline" not in d
+        files = sorted(os.listdir(tmp_path / name))
+        assert files == sorted(n + ".npy" for n in DUMPED), files
+        assert sum(os.path.getsize(tmp_path / name / f) for f in files) <= 64 << 20
+        out = {n: np.load(tmp_path / name / (n + ".npy")) for n in DUMPED}
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in out.values())
+        c = d["config"]
+        assert out["rel_embeds_rows"].shape == (c["n_rel"], c["dim"]) and out["ent_embeds_rows"].shape[1] == c["dim"]
+        assert out["loss_last_step"].shape == (1,) and out["loss_last_step"][0] > 0
+        assert (out["ent_accumulator_rows"] > 0.1).any() and (out["rel_accumulator_rows"] > 0.1).all()   # Adagrad ran (init 0.1)
+        runs.append(out)
+    for n in DUMPED:
+        np.testing.assert_allclose(runs[0][n], runs[1][n], rtol=1e-4, atol=1e-6, err_msg=n)
 
 
 @pytest.mark.timeout(700)

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf $root/gpurun_out/pmc_${cfg}_$c
   rocprofv3 --kernel-trace --pmc $c -d $root/gpurun_out/pmc_${cfg}_$c -o p -- \
-    python $root/bench.py --config $cfg --steps 40 --warmup 5 --no-cpu-baseline --no-variants "$@" \
+    python $root/bench.py --config $cfg --steps 40 --warmup 5 --full --no-cpu-baseline --no-variants "$@" \
     > $root/gpurun_out/pmc_${cfg}_$c.log 2>&1
 done
 cd $root
