@@ -907,7 +907,7 @@ int mke_oc_apply(const mke_oc_step* step, const float* gv, void* stream);
 #define MKE_OC_BASES 1
 #define MKE_OC_COUNT 2
 #define MKE_OC_SCORE 4
-#define MKE_OC_APPLY 8
+#define MKE_OC_APPLY 8      /* atomics form only: with em_coef != NULL mke_oc_apply / mke_oc_run return MKE_E_UNSUPPORTED */
 #define MKE_OC_UPDATE 16   /* mke_rows_update_multi: relation table (every row) + the shard's touched rows (entity-major: relation table only) */
 #define MKE_OC_PASS2 32    /* entity-major second pass over the touched owned rows of the global step (after the LAST part's reduce-scatter) */
 int mke_oc_run(const mke_oc_step* step, int phases, float* send_block, const float* v_all, int64_t block_floats, float* g_all,
@@ -948,7 +948,7 @@ typedef struct mke_oc_em_plan_args {
   int64_t* step_item0; int64_t* step_long0; int64_t* step_part0;
   void* temp; int64_t temp_bytes;
 } mke_oc_em_plan_args;
-int64_t mke_oc_em_plan_temp_bytes(int64_t capacity);
+int64_t mke_oc_em_plan_temp_bytes(int64_t capacity);   /* covers the sort of capacity + 1 keys and every scan of the plan */
 int mke_oc_em_plan(const mke_oc_em_plan_args* args, void* stream);
 /* the second pass of the step `step` describes (its em_* fields; launched once per global step) */
 int mke_oc_pass2(const mke_oc_step* step, void* stream);

@@ -508,8 +508,8 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_oc_score_q(const OcParams p) {
 }
 
 // quarter-wave per owned slot: the summed gradient vector goes to the head (+) / tail (-) row's gradient and to the
-// relation row's
-template <int FPL, bool ENT = true>   // ENT false (entity-major step): the relation rows only — the head / tail rows take gv in mke_oc_pass2
+// relation row's (atomics form only: an entity-major step takes both in mke_oc_pass2)
+template <int FPL>
 __global__ __launch_bounds__(MKE_BLOCK) void k_oc_apply(const OcParams p) {
   const mke_oc_step& s = p.s;
   const int j = threadIdx.x & 15;
@@ -518,7 +518,7 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_oc_apply(const OcParams p) {
   const bool is_h = sub < s.n_own_h;
   const int64_t k = is_h ? sub : sub - s.n_own_h;
   const int32_t pos = is_h ? s.own_h[k] : s.own_t[k];
-  const int row = ENT ? oc_div(oc_divisor(s.n_ranks), is_h ? s.pos_h[pos] : s.pos_t[pos]) : 0;
+  const int row = oc_div(oc_divisor(s.n_ranks), is_h ? s.pos_h[pos] : s.pos_t[pos]);
   const int r = s.pos_r[pos];
   float v[FPL];
   load_row<FPL>(p.gv, (is_h ? 0 : s.capacity) + k, s.stride, j, v);
@@ -531,11 +531,11 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_oc_apply(const OcParams p) {
       for (int c = 0; c < FPL; ++c) v[c] += w[c];
     }
   }
-  if constexpr (ENT) atomic_add_row<FPL>(s.ent_grad, oc_grad_row(s, row, sub), s.stride, s.dim, j, v, is_h ? 1.0f : -1.0f);
+  atomic_add_row<FPL>(s.ent_grad, oc_grad_row(s, row, sub), s.stride, s.dim, j, v, is_h ? 1.0f : -1.0f);
   float* grel = s.rel_grad + (sub % s.rel_grad_copies) * (s.n_rel * (int64_t)s.stride);
   atomic_add_row<FPL>(grel, r, s.stride, s.dim, j, v, 1.0f);
   if (j == 0) {
-    if constexpr (ENT) s.ent_touched[row] = s.tag;
+    s.ent_touched[row] = s.tag;
     s.rel_touched[r] = s.tag;
   }
 }
@@ -778,18 +778,15 @@ extern "C" int mke_oc_apply(const mke_oc_step* s, const float* gv, void* stream)
   using namespace mke;
   int rc = oc_check(s, "mke_oc_apply");
   if (rc) return rc;
+  if (s->em_coef) { set_error("mke_oc_apply: an entity-major step (em_coef != NULL) takes its gradient vectors in mke_oc_pass2"); return MKE_E_UNSUPPORTED; }
   const int64_t subs = s->n_own_h + s->n_own_t;
   if (subs == 0) return MKE_OK;
-  const bool em = s->em_coef != nullptr;
-  if (!gv || !s->rel_grad || !s->rel_touched || (!em && (!s->ent_grad || !s->ent_touched))) { set_error("mke_oc_apply: NULL pointer"); return MKE_E_NULL; }
+  if (!gv || !s->rel_grad || !s->rel_touched || !s->ent_grad || !s->ent_touched) { set_error("mke_oc_apply: NULL pointer"); return MKE_E_NULL; }
   OcParams p{};
   p.s = *s; p.gv = gv;
   const int fpl = s->stride / 16;
   const dim3 grid((unsigned)((subs + MKE_SUBS_PER_BLOCK - 1) / MKE_SUBS_PER_BLOCK));
-  MKE_DISPATCH_FPL(fpl, {
-    if (em) hipLaunchKernelGGL((k_oc_apply<FPL, false>), grid, dim3(MKE_BLOCK), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((k_oc_apply<FPL>), grid, dim3(MKE_BLOCK), 0, (hipStream_t)stream, p);
-  });
+  MKE_DISPATCH_FPL(fpl, { hipLaunchKernelGGL((k_oc_apply<FPL>), grid, dim3(MKE_BLOCK), 0, (hipStream_t)stream, p); });
   return check_launch("k_oc_apply");
 }
 
@@ -806,6 +803,10 @@ extern "C" int mke_oc_run(const mke_oc_step* s, int phases, float* send_block, c
   mke::TuningScope scope((s && s->tuning) ? s->tuning : nullptr);   // the step's knobs for the duration of this call
   using namespace mke;
   int rc = MKE_OK;
+  if (s && s->em_coef && (phases & MKE_OC_APPLY)) {                        // refused before any phase runs
+    set_error("mke_oc_run: an entity-major step (em_coef != NULL) takes no MKE_OC_APPLY: mke_oc_pass2 applies its gradient vectors");
+    return MKE_E_UNSUPPORTED;
+  }
   if (s && s->em_coef) phases &= ~MKE_OC_COUNT;                              // entity-major: nothing is reference-counted
   const bool both = (phases & MKE_OC_BASES) && (phases & MKE_OC_COUNT);   // one launch: the counting rides with the bases
   if ((phases & MKE_OC_BASES) && (rc = oc_bases_impl(s, send_block, both, stream))) return rc;

@@ -41,10 +41,9 @@ extern int g_oc_em_keys64;   // option "oc_em_keys64" (mke_api.hip)
 struct EmPlanParams {
   mke_oc_em_plan_args a;
   uint32_t ep;          // elements per positive: neg_per_pos + 5
-  uint64_t ep_magic;    // ceil(2^40 / ep)
   int64_t n_codes;      // n_all * neg_per_pos: elements [0, n_codes) are the negatives in code order, [n_codes, n_codes + 5 n_all) the
                         // five other elements of every position
-  uint64_t n_magic;     // ceil(2^40 / neg_per_pos)
+  uint64_t n_magic;     // ceil(2^40 / neg_per_pos), or 0 when it is not exact over [0, n_codes) (em_locate divides then)
   int64_t total;        // n_codes + 5 n_all
   int g_shift;          // log2(n_ranks) when it is a power of two, else -1
   int64_t rows_tot;     // n_local + n_rel: the relation rows follow the shard's rows
@@ -109,7 +108,9 @@ __device__ __forceinline__ void em_locate(const EmPlanParams& pp, int64_t t, EmE
   if (e.kind >= 0) return;
   const mke_oc_em_plan_args& a = pp.a;
   const int N = a.neg_per_pos;
-  const int64_t p = pp.n_codes <= 0xFFFFFFFFll ? (int64_t)(((uint64_t)(uint32_t)t * pp.n_magic) >> 40) : t / N;
+  // p = t / N as bits 40.. of the 128-bit product t * n_magic (a 64-bit product wraps from position 2^24 on)
+  const uint64_t tu = (uint64_t)t;
+  const int64_t p = pp.n_magic ? (int64_t)((__umul64hi(tu, pp.n_magic) << 24) | ((tu * pp.n_magic) >> 40)) : t / N;
   e.p = p;
   e.kind = (int)(t - p * N);
   e.sh = a.slot_h[p]; e.st = a.slot_t[p]; e.ph = a.pos_h[p]; e.pt = a.pos_t[p];
@@ -399,7 +400,9 @@ static int em_plan_sorted(const EmPlanParams& pp, int key_bits, hipStream_t st) 
   if (nu64 > a.capacity + 1) nu64 = a.capacity + 1;
   const int nu = (int)nu64;
   ip.cap = nu64 - 1;
-  const dim3 ugrid((unsigned)((nu64 + MKE_BLOCK - 1) / MKE_BLOCK));
+  // k_em_items also writes the n_steps + 1 step entries: the grid covers them when the capacity is below the step count
+  const int64_t ut = nu64 > (int64_t)a.n_steps + 1 ? nu64 : (int64_t)a.n_steps + 1;
+  const dim3 ugrid((unsigned)((ut + MKE_BLOCK - 1) / MKE_BLOCK));
   hipLaunchKernelGGL(k_em_nseg, ugrid, dim3(MKE_BLOCK), 0, st, ip);
   if ((rc = check_launch("k_em_nseg"))) return rc;
   int32_t* const ins[3] = {ip.nseg, ip.lflag, ip.lns};
@@ -610,6 +613,9 @@ extern "C" int64_t mke_oc_em_plan_temp_bytes(int64_t capacity) {
   size_t a = 0, b = 0;
   (void)hipcub::DeviceRadixSort::SortPairs(nullptr, a, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)(capacity + 1), 0, 64, (hipStream_t)0);
   (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const int32_t*)nullptr, (int32_t*)nullptr, (int)(capacity + 1), (hipStream_t)0);
+  size_t c = 0;     // the scan of the wavefront counts: up to MKE_OC_EM_WAVES + 1 items whatever the capacity
+  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, c, (const int32_t*)nullptr, (int32_t*)nullptr, MKE_OC_EM_WAVES + 1, (hipStream_t)0);
+  if (c > b) b = c;
   return (int64_t)(a > b ? a : b) + 256;
 }
 
@@ -631,9 +637,11 @@ extern "C" int mke_oc_em_plan(const mke_oc_em_plan_args* args, void* stream) {
   EmPlanParams pp;
   pp.a = a;
   pp.ep = (uint32_t)a.neg_per_pos + 5u;
-  pp.ep_magic = ((1ull << 40) + pp.ep - 1) / pp.ep;
   pp.n_codes = a.n_all * (int64_t)a.neg_per_pos;
   pp.n_magic = a.neg_per_pos > 0 ? ((1ull << 40) + a.neg_per_pos - 1) / a.neg_per_pos : 0;
+  // with n_magic N = 2^40 + err, floor(t n_magic / 2^40) = floor(t / N) whenever t err < 2^40: checked for the largest t
+  const uint64_t err = pp.n_magic * (uint64_t)a.neg_per_pos - (1ull << 40);
+  if (pp.n_magic && err && (uint64_t)(pp.n_codes - 1) >= ((1ull << 40) - 1) / err) pp.n_magic = 0;
   pp.total = pp.n_codes + 5 * a.n_all;
   pp.g_shift = (a.n_ranks & (a.n_ranks - 1)) == 0 ? __builtin_ctz((unsigned)a.n_ranks) : -1;
   pp.rows_tot = a.n_local + a.n_rel;

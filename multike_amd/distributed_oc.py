@@ -123,7 +123,7 @@ class OcHipBackend:
         s.ent_grad = _lib.ptr(tr.ent_grad, f32, "grad") if tr.ent_grad is not None else None      # entity-major: no entity scratch
         s.ent_touched = _lib.ptr(tr.ent_touched, i32, "touched") if tr.ent_touched is not None else None
         s.ref_count = _lib.ptr(tr.ref_count, i32, "ref_count") if tr.ref_count is not None else None
-        s.n_local = tr.n_local
+        s.n_local = max(1, tr.n_local)     # as in the plan (em_plan): pass 2 finds relation row r at n_local + r
         s.rel, s.rel_grad = _lib.ptr(tr.rel, f32, "rel"), _lib.ptr(tr.rel_grad, f32, "rel_grad")
         s.rel_grad_copies = 1 if tr.rel_grad.dim() == 2 else tr.rel_grad.shape[0]     # privatised relation gradient (all-reduced whole)
         s.rel_acc = _lib.ptr(tr.rel_acc, f32, "rel_acc")

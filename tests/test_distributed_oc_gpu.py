@@ -366,7 +366,7 @@ def test_one_rank_across_the_epoch_boundary_equals_single_table_path(chunks):
     np.testing.assert_allclose(tr.rel[:, :d].cpu().numpy(), R.raw().cpu().numpy(), rtol=1e-4, atol=1e-6)
 
 
-def _two_rank_worker(rank, world, port, ret, chunks, steps, peer=False, neg=NEG, em=None, native=False):
+def _two_rank_worker(rank, world, port, ret, chunks, steps, peer=False, neg=NEG, em=None, native=False, n_ent=N_ENT, b=B):
     import torch.distributed as dist
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     dist.init_process_group("gloo", init_method=f"file://{port}", rank=rank, world_size=world)   # `port`: a rendezvous FILE (no TCP port to collide on)
@@ -375,7 +375,7 @@ def _two_rank_worker(rank, world, port, ret, chunks, steps, peer=False, neg=NEG,
         torch.cuda.set_device(0)
         if native == "overlap":         # the reduce-scatter on the communication stream, the second pass's gv-free work items under it
             os.environ["MKE_OC_OVERLAP_RS"] = "1"
-        tr = _make(rank, world, comm=OcHostStagedComm(), chunks=chunks, peer=peer, neg=neg, em=em)
+        tr = _make(rank, world, comm=OcHostStagedComm(), chunks=chunks, peer=peer, neg=neg, em=em, n_ent=n_ent, b=b)
         if native:                      # mke_oc_steps: the schedule (two streams when chunks > 1) enqueued from C++, collectives by callback
             assert tr._native_loop()[0]
             tr.run(0, steps)
@@ -447,6 +447,57 @@ def test_eight_ranks_on_one_gpu_equal_dense_oracle(world, chunks, em, native):
     np.testing.assert_allclose(loss, sum(losses), rtol=2e-6)
     np.testing.assert_allclose(full, e, rtol=2e-4, atol=2e-6)
     np.testing.assert_allclose(rel, r, rtol=2e-4, atol=2e-6)
+
+
+@pytest.mark.timeout(900)
+def test_ranks_without_entity_rows_equal_dense_oracle():
+    """world 8 over a KG of 6 entities (3 per KG half): ranks 6 and 7 own no entity row — their shard is the one padding row
+    the plan and the step both count (relation row r is local row max(1, n_local) + r for the second pass) — and still score
+    their share of the negatives and store their partial relation gradient.  Entity-major, native step loop, 8 positives
+    and 2 negatives each per global step, against the float64 dense oracle."""
+    import torch.multiprocessing as mp
+    import tempfile
+    port = tempfile.mktemp(prefix="mke_rdv_")
+    world, steps, n_ent, b, neg = 8, 3, 6, 1, 2
+    ctx = mp.get_context("spawn")
+    ret = ctx.Queue()
+    procs = [ctx.Process(target=_two_rank_worker, args=(r, world, port, ret, 1, steps, False, neg, True, True, n_ent, b))
+             for r in range(world)]
+    for p in procs:
+        p.start()
+    full, rel, loss, ok = ret.get(timeout=800)
+    for p in procs:
+        p.join(180)
+        assert p.exitcode == 0
+    e, r, losses, spe = _reference(world, steps, n_ent=n_ent, neg=neg, b=b)
+    assert steps <= spe and ok
+    np.testing.assert_allclose(loss, sum(losses), rtol=2e-6)
+    np.testing.assert_allclose(full, e, rtol=2e-4, atol=2e-6)
+    np.testing.assert_allclose(rel, r, rtol=2e-4, atol=2e-6)
+
+
+def test_apply_phase_on_an_entity_major_step_is_refused():
+    """mke_oc_apply and mke_oc_run(MKE_OC_APPLY) on an entity-major step (em_coef != NULL) return MKE_E_UNSUPPORTED and leave
+    the relation gradient alone: the second pass stores this rank's relation gradient itself, an apply would count it twice."""
+    import ctypes as C
+    from multike_amd import _lib
+    tr = _make(0, 1, em=True)
+    tr.step(0)
+    torch.cuda.synchronize()
+    s = tr.backend._steps[0]
+    assert s.em_coef
+    gv = tr._gv[0]
+    gv.fill_(1.0)
+    tr.rel_grad.zero_()
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    L = _lib.lib()
+    assert L.mke_oc_apply(C.byref(s), C.c_void_p(gv.data_ptr()), stream) == -3          # MKE_E_UNSUPPORTED
+    a = tr._addr[0]
+    for phases in (_lib.OC_APPLY, _lib.OC_SCORE | _lib.OC_APPLY):
+        assert L.mke_oc_run(C.byref(s), C.c_int(phases), C.c_void_p(a[0]), C.c_void_p(a[1]), C.c_int64(tr.block), C.c_void_p(a[2]),
+                            C.c_void_p(a[3]), C.c_void_p(tr.loss_ring.data_ptr()), stream) == -3
+    torch.cuda.synchronize()
+    assert float(tr.rel_grad.abs().max()) == 0.0
 
 
 def test_one_rank_rccl_collectives_run():

@@ -166,3 +166,128 @@ def test_overflow_reports_the_count_and_writes_inside_the_capacity():
     n_refs = sum(len(v) for v in want.values())
     out = _plan(ph, pr, pt, codes, N, sh, st, step_lo, G, rank, n_local, 6, capacity=n_refs // 3)
     assert int(out["n_refs"][0]) == n_refs            # the caller re-plans at this size (distributed_oc._finish_plan)
+
+
+def _check_plan(out, want, n_steps):
+    """Every output of the plan against the direct enumeration `want`: the count, the touched rows and their steps, every
+    row's list, and the work items with their long rows, partial slots and per-step offsets (the header's definition)."""
+    n_refs = sum(len(v) for v in want.values())
+    assert int(out["n_refs"][0]) == n_refs
+    keys = sorted(want)
+    steps = np.array([s for s, _ in keys], dtype=np.int64)
+    np.testing.assert_array_equal(out["row0"], np.searchsorted(steps, np.arange(n_steps + 1)))
+    np.testing.assert_array_equal(out["rows"][:len(keys)], [r for _, r in keys])
+    refs = out["refs"].view(np.uint32).reshape(-1, 2)
+    off = [0]
+    for key in keys:
+        off.append(off[-1] + len(want[key]))
+    np.testing.assert_array_equal(out["off"][:len(keys) + 1], off)
+    got = [(int(a), int(b)) for a, b in refs[:n_refs]]
+    assert got == [ref for key in keys for ref in want[key]]
+    item_row, item_off, item_part, long_row, long_part0 = [], [], [], [], []
+    step_firsts = np.zeros((3, n_steps + 1), dtype=np.int64)
+    part = 0
+    for u, (s, row) in enumerate(keys):
+        lo, hi = off[u], off[u + 1]
+        nseg = -(-(hi - lo) // 32)
+        if nseg > 1:
+            long_row.append(row)
+            long_part0.append(part)
+        for k in range(nseg):
+            gv = nseg > 1 or bool((refs[lo + 32 * k:min(hi, lo + 32 * k + 32), 0] & GV).any())
+            item_row.append(row | (0x80000000 if nseg > 1 else 0) | (0x40000000 if gv else 0))
+            item_off.append(lo + 32 * k)
+            item_part.append(part + k if nseg > 1 else -1)
+        part += nseg if nseg > 1 else 0
+        step_firsts[:, s + 1:] = np.array([len(item_row), len(long_row), part])[:, None]
+    long_part0.append(part)
+    item_off.append(n_refs)
+    n_items = len(item_row)
+    np.testing.assert_array_equal(out["item_row"][:n_items].view(np.uint32), item_row)
+    np.testing.assert_array_equal(out["item_off"][:n_items + 1], item_off)
+    np.testing.assert_array_equal(out["item_part"][:n_items], item_part)
+    np.testing.assert_array_equal(out["long_row"][:len(long_row)], long_row)
+    np.testing.assert_array_equal(out["long_part0"][:len(long_part0)], long_part0)
+    np.testing.assert_array_equal(out["steps3"], step_firsts)
+
+
+@pytest.mark.parametrize("N", [1, 3])
+def test_lists_past_two_to_the_24_positions(N):
+    """An epoch of 2^24 + 3000 positives (the size where a 64-bit product t * ceil(2^40 / N) wraps): rank 3 of 8 owns nothing
+    but the ids of a window of 5000 positions around position 2^24, so the expected lists are the direct enumeration of the
+    window alone (positions shifted, coefficient indices relative to the true steps).  Four steps, the third spanning 2^24."""
+    G, rank, n_ent, n_rel = 8, 3, 1000, 6
+    n_local = n_ent // G
+    n_all, w0 = (1 << 24) + 3000, (1 << 24) - 2000
+    step_lo = np.array([0, 1 << 23, (1 << 24) - 700, (1 << 24) + 900, n_all], dtype=np.int64)
+    sizes = np.diff(np.clip(step_lo, w0, n_all))
+    wh, wr, wt, wc, wsh, wst, _ = _case(40 + N, G, rank, n_ent, n_rel, [int(x) for x in sizes if x], N)
+    # outside the window: entity 0 everywhere (rank 0's) — no element there is rank 3's
+    ph, pr, pt = (np.zeros(n_all, dtype=np.int32) for _ in range(3))
+    sh, st = np.zeros(n_all, dtype=np.int32), np.full(n_all, -1, dtype=np.int32)
+    codes = np.zeros(n_all * N, dtype=np.int32)
+    ph[w0:], pr[w0:], pt[w0:], sh[w0:], st[w0:] = wh, wr, wt, wsh, wst
+    codes[w0 * N:] = wc
+    want = _expected(wh, wr, wt, wc, N, wsh, wst, step_lo - w0, G, rank, n_local)
+    assert min(s for s, _ in want) == 1 and max(s for s, _ in want) == 3
+    n_refs = sum(len(v) for v in want.values())
+    out = _plan(ph, pr, pt, codes, N, sh, st, step_lo, G, rank, n_local, n_rel, capacity=n_refs + 17)
+    _check_plan(out, want, len(step_lo) - 1)
+
+
+def test_sort_keys_above_32_bits_chosen_by_size():
+    """n_steps * (n_local + n_rel) >= 2^32 without the oc_em_keys64 option: the plan sorts 64-bit keys with key_bits > 32 (the
+    upper word of the sort in use).  One rank, 24 steps, a shard of nearly 2^28 rows; the last two steps reference the top rows
+    of the shard and the relation rows after them."""
+    G, rank, N, n_rel = 1, 0, 3, 7
+    n_local = (1 << 28) - 5
+    sizes = [6] * 24
+    assert len(sizes) * (n_local + n_rel) >= 1 << 32 and _lib.get_option("oc_em_keys64") == 0
+    ph, pr, pt, codes, sh, st, step_lo = _case(77, G, rank, n_local, n_rel, sizes, N)
+    top = np.arange(12)
+    ph[-12:], pt[-12:] = n_local - 1 - top, n_local - 1 - top[::-1]
+    pr[-12:] = n_rel - 1 - top % 2
+    codes[-12 * N:] = ((n_local - 1 - np.arange(12 * N) % 5) << 1) | (codes[-12 * N:] & 1)
+    want = _expected(ph, pr, pt, codes, N, sh, st, step_lo, G, rank, n_local)
+    assert max(r for _, r in want) == n_local + n_rel - 1 and (23, n_local - 1) in want
+    n_refs = sum(len(v) for v in want.values())
+    out = _plan(ph, pr, pt, codes, N, sh, st, step_lo, G, rank, n_local, n_rel, capacity=n_refs + 5)
+    _check_plan(out, want, len(sizes))
+
+
+def test_small_capacity_on_an_epoch_of_all_wavefront_ranges_reports_the_count():
+    """An epoch of 2^21 + 1000 positives with 3 negatives each (8 elements per positive: all MKE_OC_EM_WAVES wavefront ranges,
+    whose counts are scanned in the temp storage) planned with a capacity of 64: MKE_OK and n_refs beyond the capacity — the
+    caller grows the buffers and plans again."""
+    G, rank, N, n_rel = 1, 0, 3, 5
+    n_all = (1 << 21) + 1000
+    rng = np.random.default_rng(9)
+    ph, pt, pr = rng.integers(0, 5000, n_all), rng.integers(0, 5000, n_all), rng.integers(0, n_rel, n_all)
+    codes = (rng.integers(0, 5000, n_all * N) << 1)                    # every negative corrupts the head: HR travels
+    sh, st = np.arange(n_all) % 100_000, np.full(n_all, -1)
+    step_lo = np.arange(0, n_all + 100_000, 100_000)
+    step_lo[-1] = n_all
+    assert n_all * (N + 5) >= 512 * _lib.OC_EM_WAVES
+    out = _plan(ph, pr, pt, codes, N, sh, st, step_lo, G, rank, 5000, n_rel, capacity=64)
+    # per position: N negatives, the own term, the head's gradient vector and the relation row's
+    assert int(out["n_refs"][0]) == n_all * (N + 3)
+
+
+def test_capacity_below_the_step_count_fills_every_step_entry():
+    """400 steps of one positive and a capacity of a dozen references: the per-step first item / long row / partial slot of
+    all 401 entries (not only of as many as the capacity's launch grid covers)."""
+    G, rank, N, n_rel = 8, 3, 2, 4
+    n_all = 400
+    rng = np.random.default_rng(3)
+    ph, pt, pr = 8 * rng.integers(0, 50, n_all), 8 * rng.integers(0, 50, n_all), rng.integers(0, n_rel, n_all)
+    codes = (8 * rng.integers(0, 50, n_all * N)) << 1                  # rank 0's entities, heads corrupted: HR travels
+    for p in (10, 100, 200, 300, 390):                                  # five positions with a rank-3 head
+        ph[p] = 8 * p + 3
+    codes[2 * N + 1] = (8 * 7 + 3) << 1                                 # and one rank-3 corrupt entity
+    sh, st = np.zeros(n_all, dtype=np.int64), np.full(n_all, -1)
+    step_lo = np.arange(n_all + 1)
+    want = _expected(ph, pr, pt, codes, N, sh, st, step_lo, G, rank, 500)
+    n_refs = sum(len(v) for v in want.values())
+    assert n_refs < 16
+    out = _plan(ph, pr, pt, codes, N, sh, st, step_lo, G, rank, 500, n_rel, capacity=n_refs + 1)
+    _check_plan(out, want, n_all)

@@ -535,3 +535,98 @@ def test_row_update_one_flag_per_lane(d):
     finally:
         _lib.set_option("update_chunk", old)
 
+
+
+def _with_offsets32(value, test, *args):
+    """`test` with option "score_offsets32" at `value` (0: the 64-bit row-offset instances of the training kernel at any size)."""
+    from multike_amd import _lib
+    old = _lib.set_option("score_offsets32", value)
+    try:
+        test(*args)
+    finally:
+        _lib.set_option("score_offsets32", old)
+
+
+@pytest.mark.parametrize("o32", [0, 1])
+@pytest.mark.parametrize("copies", [1, 8])
+@pytest.mark.parametrize("ci", range(5))
+def test_golden_three_steps_both_row_offset_widths(losses_golden, ci, copies, o32):
+    _with_offsets32(o32, test_golden_three_steps, losses_golden, ci, copies)
+
+
+@pytest.mark.parametrize("o32", [0, 1])
+@pytest.mark.parametrize("P,N,half", [(333, 10, 12), (333, 10, 0), (77, 1, 12), (333, 25, 64), (51, 64, 64), (333, 25, -1)])
+def test_two_groups_per_wavefront_both_row_offset_widths(P, N, half, o32):
+    _with_offsets32(o32, test_two_groups_per_wavefront_equals_one, P, N, half)
+
+
+@pytest.mark.parametrize("o32", [0, 1])
+@pytest.mark.parametrize("n_ent,P,N", [(300, 400, 25), (5000, 2000, 10)])
+def test_heavy_collisions_both_row_offset_widths(n_ent, P, N, o32):
+    _with_offsets32(o32, test_heavy_collisions_exclusive_row_path, n_ent, P, N)
+
+
+def test_table_past_two_to_the_30_floats_vs_compact_f64_oracle():
+    """|E| = 4.3M rows at dim 256: 1.1G floats, past the 2^30 bound of the 32-bit row offsets, so the exclusive-row training
+    kernel takes its 64-bit-offset instances by size (option at its default).  Positives and negatives on rows below and above
+    row 2^30 / 256 = 4,194,304 (explicit triples up there, not left to sampling).  The float64 C oracle runs on the rows the
+    two steps touch, renumbered; the untouched rows and their accumulators stay bit-identical."""
+    from multike_amd import _lib
+    from multike_amd.tables import EmbeddingTable, StepEngine
+    n_ent, n_rel, d, N, P = 4_300_000, 300, 256, 16, 2000
+    edge = (1 << 30) // d
+    assert _lib.get_option("score_offsets32") == 1
+    g = torch.Generator(device="cuda")
+    g.manual_seed(8)
+    sigma = float(np.sqrt(2.6 / (n_ent + d)))
+    E = EmbeddingTable(n_ent, d, "ent", trainable=False)
+    E.trainable = True
+    assert n_ent * E.stride >= 1 << 30
+    E.data[:, :d] = torch.randn(n_ent, d, device="cuda", generator=g).clamp_(-2, 2) * sigma
+    R = EmbeddingTable(n_rel, d, "rel", values=mo.xavier_truncated_normal((n_rel, d), np.random.default_rng(9)))
+    eng = StepEngine()
+    rng = np.random.default_rng(10)
+    steps = []
+    for _ in range(2):
+        ph, pr, pt = rng.integers(0, n_ent, P), rng.integers(0, n_rel, P), rng.integers(0, n_ent, P)
+        k = rng.permutation(P)[:300]                          # explicit triples on the far side of the bound, and across it
+        ph[k[:100]] = rng.integers(edge, n_ent, 100)
+        pt[k[:100]] = rng.integers(edge, n_ent, 100)
+        ph[k[100:200]] = rng.integers(edge, n_ent, 100)
+        pt[k[200:]] = rng.integers(edge, n_ent, 100)
+        ph[k[0]], pt[k[1]] = n_ent - 1, edge                  # the last row and the first row past the bound
+        nh, nr, nt = np.repeat(ph, N), np.repeat(pr, N), np.repeat(pt, N)
+        side = rng.integers(0, 2, P * N).astype(bool)
+        c = rng.integers(0, n_ent, P * N)
+        c[::7] = rng.integers(edge - 50, n_ent, len(c[::7]))
+        nh, nt = np.where(side, c, nh), np.where(side, nt, c)
+        steps.append(tuple(torch.as_tensor(a.astype(np.int32), device="cuda") for a in (ph, pr, pt, nh, nr, nt)))
+    used = torch.unique(torch.cat([x.long() for s in steps for x in (s[0], s[2], s[3], s[5])]))
+    assert int((used < edge).sum()) > 1000 and int((used >= edge).sum()) > 1000
+    remap = torch.full((n_ent,), -1, dtype=torch.int64, device="cuda")
+    remap[used] = torch.arange(used.numel(), device="cuda")
+    e64 = E.raw()[used].double().cpu().numpy()
+    r64 = R.raw().double().cpu().numpy()
+    a64, b64 = np.full_like(e64, 0.1), np.full_like(r64, 0.1)
+    orc = co.RelationStepOracle(len(e64), n_rel, d, np.float64)
+    before = E.data.clone()
+    for ph, pr, pt, nh, nr, nt in steps:
+        lp = eng.relation_step(E, R, "relation", (ph, pr, pt), (nh, nr, nt), neg_per_pos=N, lr=0.001)
+        cp = (remap[ph.long()].cpu().numpy(), pr.cpu().numpy(), remap[pt.long()].cpu().numpy())
+        cn = (remap[nh.long()].cpu().numpy(), nr.cpu().numpy(), remap[nt.long()].cpu().numpy())
+        L = orc.step(e64, r64, a64, b64, cp, cn, 0.001)
+        np.testing.assert_allclose(float(lp.sum()), L, rtol=LOSS_RTOL)
+    np.testing.assert_allclose(E.raw()[used].cpu().numpy(), e64, rtol=1e-4, atol=5e-7)
+    np.testing.assert_allclose(R.raw().cpu().numpy(), r64, rtol=1e-4, atol=5e-7)
+    np.testing.assert_allclose(E.slot("relation")[used][:, :d].cpu().numpy(), a64, rtol=1e-3, atol=1e-7)
+    mask = torch.ones(n_ent, dtype=torch.bool, device="cuda")
+    mask[used] = False
+    acc = E.slot("relation")
+    for lo in range(0, n_ent, 1 << 20):                         # the untouched rows, a slice at a time (bounded scratch)
+        hi = min(n_ent, lo + (1 << 20))
+        m = mask[lo:hi]
+        assert torch.equal(E.data[lo:hi][m], before[lo:hi][m]), lo
+        a = acc[lo:hi][m]
+        assert float(a.min()) == float(a.max()) == np.float32(0.1), lo
+    assert float(E.grad.abs().max()) == 0.0 and float(R.grad.abs().max()) == 0.0
+    assert int(E.refcount.abs().sum()) == 0
