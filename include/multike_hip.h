@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MKE_VERSION 105 /* 0.1.5: + entity-major second pass of the owner-computes step (mke_oc_step.em_*, mke_oc_em_plan, MKE_OC_PASS2: additions only), + mke_oc_steps / mke_oc_comm (the G > 1 step loop as ONE native call), per-plan tuning (mke_tuning); 0.1.4: mke_oc_* exchange ONE vector per positive (the side its negatives corrupt): group flags in the codes, slot -1, mke_oc_plan takes the codes, mke_oc_step.hot (hub rows of the shard), mke_attr_step_args.attr_grad_copies, + mke_probe_rows; 0.1.3: + hub rows (mke_hot_rows: mke_triple_score_fwd_bwd_xch, mke_update_table.hot, mke_relation_plan.hot; additions only); 0.1.2: + mke_oc_plan, mke_topk_long, options "attr_fused_bwd" / "oc_score_quarter" (additions only); 0.1.1: mke_align_rank gained `ties` */
+#define MKE_VERSION 106 /* 0.1.6: + CSLS re-scoring and the euclidean metric of the alignment evaluator (mke_align_topk_mean, mke_align_topk_mean_temp_bytes, mke_align_rank_ex: additions only); 0.1.5: + entity-major second pass of the owner-computes step (mke_oc_step.em_*, mke_oc_em_plan, MKE_OC_PASS2: additions only), + mke_oc_steps / mke_oc_comm (the G > 1 step loop as ONE native call), per-plan tuning (mke_tuning); 0.1.4: mke_oc_* exchange ONE vector per positive (the side its negatives corrupt): group flags in the codes, slot -1, mke_oc_plan takes the codes, mke_oc_step.hot (hub rows of the shard), mke_attr_step_args.attr_grad_copies, + mke_probe_rows; 0.1.3: + hub rows (mke_hot_rows: mke_triple_score_fwd_bwd_xch, mke_update_table.hot, mke_relation_plan.hot; additions only); 0.1.2: + mke_oc_plan, mke_topk_long, options "attr_fused_bwd" / "oc_score_quarter" (additions only); 0.1.1: mke_align_rank gained `ties` */
 
 /* error codes (negative = argument errors) */
 #define MKE_OK 0
@@ -733,6 +733,68 @@ int mke_dense_update(float* param, float* acc /*nullable for SGD*/, float* grad,
 int mke_align_rank(const float* emb1, int ld1, const float* emb2, int ld2, int kpad, int64_t n1, int64_t n2,
                    int32_t* rank, int32_t* ties /* nullable: ties[i] += #{j : sim[i][j] == sim[i][i]} (j = i included) */,
                    uint64_t* best, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * (9b) Alignment evaluator with a metric and CSLS re-scoring (version 106), still without the n1 x n2 matrix.
+ *
+ * replaces: code/base/similarity.py:9-81 (sim with metric 'inner' / 'euclidean' / 'cosine', csls_sim, calculate_nearest_k)
+ *           + code/base/alignment.py:8-79 greedy_alignment with metric / csls_k (code/base/evaluation.py:6-24 valid / test).
+ *
+ *   METRIC(i, j):  MKE_METRIC_INNER: dot = a_i . b_j (an f32 MFMA fma chain over k, as mke_align_rank);
+ *                  MKE_METRIC_EUCLIDEAN: 1 - sqrt(max(sq_a[i] + sq_b[j] - 2 dot, 0)), sq_* the squared row norms given by the
+ *                  caller (code/base/similarity.py:38-41: 1 - euclidean_distances).  'cosine' is the inner product of
+ *                  normalised rows (the caller normalises).
+ *
+ *   mke_align_topk_mean: out[i] = mean of the k largest METRIC(i, j) over the n_b rows j of b, for the n_a rows of a: the
+ *     exact top-k multiset of f32 values, summed in float64 in descending order, divided by k, rounded to f32 (deterministic
+ *     run to run; code/base/similarity.py:78-81 sums np.partition's order in float32: a few ulp apart).  a = E1, b = E2 gives
+ *     csls r_T; a = E2, b = E1 gives r_S (calculate_nearest_k(sim_mat.T, k): over the n1 source rows only).
+ *     1 <= k <= n_b - 2 (np.partition(-sim, k + 1) needs k + 1 < n_b), else MKE_E_SHAPE.  k <= 32: one sweep keeps a running
+ *     top-k per row in LDS per column chunk, a second launch merges the chunks; k > 32: whole similarity rows of bounded row
+ *     rounds (<= 2^26 floats) through the same f32 chains, then the same merge.  temp: mke_align_topk_mean_temp_bytes bytes.
+ *     lda / ldb: multiples of 4 >= kpad; rows zero in [dim, kpad).
+ *   mke_align_topk_mean_temp_bytes: scratch bytes for (n_a, n_b, kpad, k), or a negative MKE_E_* for arguments it rejects.
+ *     Scratch is indexed with 64-bit offsets; k > 2^30 (the large-k sort counts with 32-bit ints) or a scratch above 2^40
+ *     floats returns MKE_E_RANGE.
+ *
+ *   mke_align_rank_ex: mke_align_rank with every similarity s = METRIC(i, j) and, with csls_row / csls_col set (both, or
+ *     neither), s = (2 s - csls_row[i]) - csls_col[j] in f32 (code/base/similarity.py:73-74).  rank[i] += #{j : s_ij > s_ii},
+ *     ties[i] += #{j : s_ij == s_ii} (j = i included), best[i] = max of (ordered(s_ij) << 32 | 0xFFFFFFFF - j) as
+ *     mke_align_rank's; rank, ties, best zeroed by the caller.  The gold s_ii comes from the same diagonal MFMA product
+ *     through the same epilogue.  ties is required here.  Unknown metric: MKE_E_UNSUPPORTED.
+ * ------------------------------------------------------------------------------------------------ */
+#define MKE_METRIC_INNER 0
+#define MKE_METRIC_EUCLIDEAN 1
+typedef struct mke_topk_mean_args {
+  const float* a; int lda;          /* [n_a][lda] */
+  const float* b; int ldb;          /* [n_b][ldb] */
+  int kpad;
+  int64_t n_a, n_b;
+  int metric;
+  const float* sq_a;                /* [n_a], euclidean only (nullable otherwise) */
+  const float* sq_b;                /* [n_b], euclidean only */
+  int k;
+  float* out;                       /* [n_a] */
+  void* temp; int64_t temp_bytes;   /* >= mke_align_topk_mean_temp_bytes(n_a, n_b, kpad, k) */
+} mke_topk_mean_args;
+int64_t mke_align_topk_mean_temp_bytes(int64_t n_a, int64_t n_b, int kpad, int k);
+int mke_align_topk_mean(const mke_topk_mean_args* args, void* stream);
+
+typedef struct mke_align_args {
+  const float* emb1; int ld1;       /* [n1][ld1] */
+  const float* emb2; int ld2;       /* [n2][ld2], n2 >= n1 (gold column of row i = i) */
+  int kpad;
+  int64_t n1, n2;
+  int metric;
+  const float* sq1;                 /* [n1], euclidean only (nullable otherwise) */
+  const float* sq2;                 /* [n2], euclidean only */
+  const float* csls_row;            /* [n1] r_T, or NULL: no CSLS */
+  const float* csls_col;            /* [n2] r_S, or NULL (NULL exactly when csls_row is) */
+  int32_t* rank;                    /* [n1] */
+  int32_t* ties;                    /* [n1] */
+  uint64_t* best;                   /* [n1] */
+} mke_align_args;
+int mke_align_rank_ex(const mke_align_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * (10) Small dense f32 GEMM on the matrix cores (v_mfma_f32_32x32x2_f32, exact f32) with arbitrary operand strides:

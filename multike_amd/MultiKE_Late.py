@@ -76,8 +76,15 @@ def test(model, embed_choice='avg', w=(1, 1, 1)):
     k = model.kgs
     embeds1, embeds2 = _eval_pair(model, embed_choice, w, "test1", lambda: k.test_entities1, "test2", lambda: k.test_entities2)
     print(embed_choice, 'test results:')
-    _, mrr_12 = eva.valid(embeds1, embeds2, None, model.args.top_k, model.args.test_threads_num, normalize=True)
+    _, mrr_12 = eva.valid(embeds1, embeds2, None, model.args.top_k, model.args.test_threads_num, normalize=True,
+                          csls_k=_csls_k(model))
     return mrr_12
+
+
+def _csls_k(model):
+    """Hyper-parameter `csls` (OpenEA's key; 0 = off): CSLS re-scoring of the test-time evaluations only — validation and
+    early stopping stay plain."""
+    return int(getattr(model.args, "csls", 0) or 0)
 
 
 def _unit_rows(x):
@@ -104,7 +111,7 @@ def wva(embeds1, embeds2, embeds3):
             _compute_weight(embeds3, embeds1, embeds2))
 
 
-def _wva_eval(model, ents1, ents2, label, keys=None):
+def _wva_eval(model, ents1, ents2, label, keys=None, csls_k=0):
     tabs = (model.name_embeds, model.rv_ent_embeds, model.av_ent_embeds)
     if keys is not None and getattr(model, "device", None) is not None and all(hasattr(t, "lookup") for t in tabs):
         ids1, ids2 = _device_ids(model, keys[0], lambda: ents1), _device_ids(model, keys[1], lambda: ents2)
@@ -120,7 +127,7 @@ def _wva_eval(model, ents1, ents2, label, keys=None):
     embeds1 = sum(float(w) * v for w, v in zip(wsum, v1))
     embeds2 = sum(float(w) * v for w, v in zip(wsum, v2))
     print(label)
-    _, mrr_12 = eva.valid(embeds1, embeds2, None, model.args.top_k, model.args.test_threads_num, normalize=True)
+    _, mrr_12 = eva.valid(embeds1, embeds2, None, model.args.top_k, model.args.test_threads_num, normalize=True, csls_k=csls_k)
     return mrr_12
 
 
@@ -132,7 +139,8 @@ def valid_WVA(model):
 
 def test_WVA(model):
     """code/MultiKE_Late.py:138-173."""
-    return _wva_eval(model, model.kgs.test_entities1, model.kgs.test_entities2, 'wvag test results:', keys=("test1", "test2"))
+    return _wva_eval(model, model.kgs.test_entities1, model.kgs.test_entities2, 'wvag test results:', keys=("test1", "test2"),
+                     csls_k=_csls_k(model))
 
 
 class _ScheduledMultiKE(MultiKE):

@@ -36,6 +36,7 @@ SYMBOLS = (
     "mke_topk_long", "mke_probe_rows", "mke_oc_block_floats", "mke_oc_pack_codes", "mke_oc_plan", "mke_oc_bases", "mke_oc_count", "mke_oc_score", "mke_oc_apply", "mke_oc_run",
     "mke_oc_em_plan_temp_bytes", "mke_oc_em_plan", "mke_oc_pass2", "mke_oc_steps",
     "mke_tuning_init", "mke_triple_score_fwd_bwd_t", "mke_rows_update_multi_t",
+    "mke_align_topk_mean_temp_bytes", "mke_align_topk_mean", "mke_align_rank_ex",
 )
 ACT_NONE, ACT_TANH, ACT_SIGMOID = 0, 1, 2
 AE_MAX_LAYERS = 4
@@ -255,6 +256,7 @@ def lib():
         L.mke_ae_scratch_floats.restype = C.c_int64
         L.mke_oc_block_floats.restype = C.c_int64
         L.mke_oc_em_plan_temp_bytes.restype = C.c_int64
+        L.mke_align_topk_mean_temp_bytes.restype = C.c_int64
         _lib = L
         # MKE_OPTIONS="name=value,name=value": mke_set_option calls applied at load (performance knobs for experiments)
         for kv in filter(None, os.environ.get("MKE_OPTIONS", "").split(",")):
@@ -934,6 +936,54 @@ def align_rank(emb1, emb2, kpad, n1, n2, rank, best, ties=None):
                               _dev(rank, torch.int32, "rank"), _dev(ties, torch.int32, "ties"), _dev(best, torch.int64, "best"),
                               _stream())
     _check(rc, "mke_align_rank")
+
+
+METRIC_INNER, METRIC_EUCLIDEAN = 0, 1   # MKE_METRIC_*
+
+
+class TopkMeanArgs(C.Structure):
+    """mke_topk_mean_args"""
+    _fields_ = [("a", C.c_void_p), ("lda", C.c_int), ("b", C.c_void_p), ("ldb", C.c_int), ("kpad", C.c_int),
+                ("n_a", C.c_int64), ("n_b", C.c_int64), ("metric", C.c_int), ("sq_a", C.c_void_p), ("sq_b", C.c_void_p),
+                ("k", C.c_int), ("out", C.c_void_p), ("temp", C.c_void_p), ("temp_bytes", C.c_int64)]
+
+
+class AlignArgs(C.Structure):
+    """mke_align_args"""
+    _fields_ = [("emb1", C.c_void_p), ("ld1", C.c_int), ("emb2", C.c_void_p), ("ld2", C.c_int), ("kpad", C.c_int),
+                ("n1", C.c_int64), ("n2", C.c_int64), ("metric", C.c_int), ("sq1", C.c_void_p), ("sq2", C.c_void_p),
+                ("csls_row", C.c_void_p), ("csls_col", C.c_void_p), ("rank", C.c_void_p), ("ties", C.c_void_p),
+                ("best", C.c_void_p)]
+
+
+def align_topk_mean_temp_bytes(n_a: int, n_b: int, kpad: int, k: int) -> int:
+    """mke_align_topk_mean_temp_bytes; raises on the arguments mke_align_topk_mean would reject."""
+    r = int(lib().mke_align_topk_mean_temp_bytes(C.c_int64(n_a), C.c_int64(n_b), C.c_int(kpad), C.c_int(k)))
+    _check(r if r < 0 else 0, "mke_align_topk_mean_temp_bytes")
+    return r
+
+
+def align_topk_mean(a, b, kpad, k, metric=METRIC_INNER, sq_a=None, sq_b=None):
+    """mke_align_topk_mean over row-major padded a [n_a, lda] / b [n_b, ldb] -> float32 [n_a]: the mean of each a row's k
+    largest similarities to the b rows."""
+    n_a, n_b = a.shape[0], b.shape[0]
+    need = align_topk_mean_temp_bytes(n_a, n_b, kpad, k)
+    out = torch.empty(n_a, dtype=torch.float32, device=a.device)
+    temp = torch.empty(max(need, 4) // 4, dtype=torch.float32, device=a.device)
+    args = TopkMeanArgs(_dev(a, torch.float32, "a"), a.shape[1], _dev(b, torch.float32, "b"), b.shape[1], kpad, n_a, n_b, metric,
+                        _dev(sq_a, torch.float32, "sq_a"), _dev(sq_b, torch.float32, "sq_b"), k, _dev(out, torch.float32, "out"),
+                        _dev(temp, torch.float32, "temp"), temp.numel() * 4)
+    _check(lib().mke_align_topk_mean(C.byref(args), _stream()), "mke_align_topk_mean")
+    return out
+
+
+def align_rank_ex(emb1, emb2, kpad, rank, ties, best, metric=METRIC_INNER, sq1=None, sq2=None, csls_row=None, csls_col=None):
+    """mke_align_rank_ex over row-major padded emb1 [n1, ld1] / emb2 [n2, ld2] (rank / ties / best zeroed by the caller)."""
+    args = AlignArgs(_dev(emb1, torch.float32, "emb1"), emb1.shape[1], _dev(emb2, torch.float32, "emb2"), emb2.shape[1], kpad,
+                     emb1.shape[0], emb2.shape[0], metric, _dev(sq1, torch.float32, "sq1"), _dev(sq2, torch.float32, "sq2"),
+                     _dev(csls_row, torch.float32, "csls_row"), _dev(csls_col, torch.float32, "csls_col"),
+                     _dev(rank, torch.int32, "rank"), _dev(ties, torch.int32, "ties"), _dev(best, torch.int64, "best"))
+    _check(lib().mke_align_rank_ex(C.byref(args), _stream()), "mke_align_rank_ex")
 
 
 def gemm_f32(lhs, rhs, out, transpose_a=False, transpose_b=False, splits=1, accumulate=False):

@@ -1,5 +1,6 @@
 """base/alignment.py surface of the reference (code/base/alignment.py:8-79): `greedy_alignment` — Hits@k / MR / MRR of
-the gold counterpart under the (normalised) inner-product similarity — on the f32 matrix cores via `mke_align_rank`.
+the gold counterpart under the (normalised) inner-product similarity — on the f32 matrix cores via `mke_align_rank`; the
+euclidean metric and CSLS re-scoring via `mke_align_topk_mean` + `mke_align_rank_ex`.
 The n1 x n2 similarity matrix is never materialised (the reference holds 60K x 60K fp32 = 14 GB and argsorts its rows
 in `nums_threads` worker processes)."""
 from __future__ import annotations
@@ -20,22 +21,82 @@ def _prep(x, device, normalize):
     return t
 
 
-def alignment_counts(embed1, embed2, normalize=True, device="cuda"):
+SUPPORTED_METRICS = ("inner", "cosine", "euclidean")
+
+
+def _check_metric(metric, normalize):
+    if metric not in SUPPORTED_METRICS:
+        raise _lib.MultiKEHipError(f"greedy_alignment: metric {metric!r} is not built (supported: 'inner', 'cosine', 'euclidean'; "
+                                   "the other cdist metrics are not GEMM-shaped)")
+
+
+def _padded(x, kpad, device):
+    n, d = x.shape
+    p = torch.zeros(n, kpad, dtype=torch.float32, device=device)
+    p[:, :d] = x
+    return p
+
+
+def _kpad_for(d):
+    if d > _lib.SIM_SELECT_KPADS[-1]:      # wider than the widest table the package supports (MKE_MAX_STRIDE): no second backend
+        raise _lib.MultiKEHipError(f"greedy_alignment: rows of {d} floats exceed the widest k_align_rank instantiation "
+                                   f"({_lib.SIM_SELECT_KPADS[-1]} = MKE_MAX_STRIDE)")
+    return min(x for x in _lib.SIM_SELECT_KPADS if x >= d)
+
+
+def prepare_operands(embed1, embed2, metric="inner", normalize=True, device="cuda"):
+    """(a, b, kpad, metric code, sq_a, sq_b): the zero-padded f32 operands of the native evaluator.  'cosine' is the inner
+    product of unit rows (code/base/similarity.py:34-44: normalised or not, cosine similarity is that); 'euclidean' hands the
+    squared row norms over (1 - euclidean_distances, :38-41)."""
+    _check_metric(metric, normalize)
+    a, b = _prep(embed1, device, normalize or metric == "cosine"), _prep(embed2, device, normalize or metric == "cosine")
+    kpad = _kpad_for(a.shape[1])
+    ap, bp = _padded(a, kpad, device), _padded(b, kpad, device)
+    if metric == "euclidean":
+        return ap, bp, kpad, _lib.METRIC_EUCLIDEAN, (a * a).sum(1).contiguous(), (b * b).sum(1).contiguous()
+    return ap, bp, kpad, _lib.METRIC_INNER, None, None
+
+
+def csls_means(a, b, kpad, metric_code, sq_a, sq_b, csls_k):
+    """(r_T [n1], r_S [n2]) of code/base/similarity.py:69-70 from padded operands: r_T(i) = mean of row i's k largest
+    similarities to the n2 targets, r_S(j) = mean of column j's k largest similarities to the n1 sources."""
+    r_t = _lib.align_topk_mean(a, b, kpad, csls_k, metric_code, sq_a, sq_b)
+    r_s = _lib.align_topk_mean(b, a, kpad, csls_k, metric_code, sq_b, sq_a)
+    return r_t, r_s
+
+
+def alignment_counts(embed1, embed2, normalize=True, device="cuda", metric="inner", csls_k=0, csls=None):
     """(greater [n1] int64, ties [n1] int64, best [n1] int64): greater_i = #{j: sim_ij > sim_ii}, ties_i = #{j: sim_ij ==
-    sim_ii} (the gold column included, so >= 1), best_i = argmax_j sim_ij."""
+    sim_ii} (the gold column included, so >= 1), best_i = argmax_j sim_ij.  `metric` 'inner' / 'cosine' / 'euclidean';
+    csls_k > 0 re-scores every similarity by CSLS (code/base/similarity.py:56-75).  `csls` = (r_T, r_S) given by the caller
+    (the sharded driver, which computes them over all ranks) in place of computing them here."""
+    _check_metric(metric, normalize)
+    if (not csls_k or csls_k <= 0) and csls is None and (metric == "inner" or (metric == "cosine" and normalize)):
+        return _counts_inner(embed1, embed2, normalize, device)
+    a, b, kpad, code, sq1, sq2 = prepare_operands(embed1, embed2, metric, normalize, device)
+    n1, n2 = a.shape[0], b.shape[0]
+    if n2 < n1:
+        raise _lib.MultiKEHipError("greedy_alignment: gold column = row index needs len(embed2) >= len(embed1)")
+    if csls is None and csls_k and csls_k > 0:
+        csls = csls_means(a, b, kpad, code, sq1, sq2, int(csls_k))
+    rank = torch.zeros(n1, dtype=torch.int32, device=device)
+    ties = torch.zeros(n1, dtype=torch.int32, device=device)
+    best = torch.zeros(n1, dtype=torch.int64, device=device)
+    r_t, r_s = csls if csls is not None else (None, None)
+    _lib.align_rank_ex(a, b, kpad, rank, ties, best, code, sq1, sq2, r_t, r_s)
+    col = 0xFFFFFFFF - (best & 0xFFFFFFFF)
+    return rank.long(), ties.long().clamp_min(1), col
+
+
+def _counts_inner(embed1, embed2, normalize, device):
     a, b = _prep(embed1, device, normalize), _prep(embed2, device, normalize)
     n1, d = a.shape
     n2 = b.shape[0]
     if n2 < n1:
         raise _lib.MultiKEHipError("greedy_alignment: gold column = row index needs len(embed2) >= len(embed1)")
-    if d > _lib.SIM_SELECT_KPADS[-1]:      # wider than the widest table the package supports (MKE_MAX_STRIDE): no second backend
-        raise _lib.MultiKEHipError(f"greedy_alignment: rows of {d} floats exceed the widest k_align_rank instantiation "
-                                   f"({_lib.SIM_SELECT_KPADS[-1]} = MKE_MAX_STRIDE)")
-    kpad = min(x for x in _lib.SIM_SELECT_KPADS if x >= d)
-    ap = torch.zeros(n1, kpad, dtype=torch.float32, device=device)
-    ap[:, :d] = a
-    bp = torch.zeros(n2, kpad, dtype=torch.float32, device=device)
-    bp[:, :d] = b
+    kpad = _kpad_for(d)
+    ap = _padded(a, kpad, device)
+    bp = _padded(b, kpad, device)
     rank = torch.zeros(n1, dtype=torch.int32, device=device)
     ties = torch.zeros(n1, dtype=torch.int32, device=device)
     best = torch.zeros(n1, dtype=torch.int64, device=device)
@@ -44,11 +105,11 @@ def alignment_counts(embed1, embed2, normalize=True, device="cuda"):
     return rank.long(), ties.long().clamp_min(1), col
 
 
-def alignment_ranks(embed1, embed2, normalize=True, device="cuda"):
+def alignment_ranks(embed1, embed2, normalize=True, device="cuda", metric="inner", csls_k=0):
     """(rank [n1] float64, best [n1] int64): rank_i = greater_i + (ties_i - 1) / 2 — the gold's EXPECTED 0-based position when
     the columns that tie with it are ordered at random.  The reference's argsort / argpartition leaves the gold at an arbitrary
     position among them (code/base/alignment.py:152-160).  Without ties this is the reference's rank exactly."""
-    greater, ties, col = alignment_counts(embed1, embed2, normalize, device)
+    greater, ties, col = alignment_counts(embed1, embed2, normalize, device, metric=metric, csls_k=csls_k)
     return greater.double() + (ties.double() - 1.0) * 0.5, col
 
 
@@ -90,23 +151,33 @@ def _harmonic(n):
 
 def greedy_alignment(embed1, embed2, top_k, nums_threads, metric, normalize, csls_k, accurate, want_pairs=True):
     """code/base/alignment.py:8-79.  Returns (alignment_rest, hits1, mr, mrr).  `nums_threads` is accepted and ignored
-    (one kernel launch).  Only the path the reference uses is built: inner product (or cosine == inner product of
-    normalised rows), csls_k == 0.  want_pairs = False (base.evaluation.valid, which drops them): alignment_rest is None —
-    the set of (row, best column) tuples is a Python object per row."""
-    if csls_k and csls_k > 0:
-        raise _lib.MultiKEHipError("greedy_alignment: CSLS re-scoring is not built (the reference never enables it)")
-    if not (metric == "inner" or (metric == "cosine" and normalize)):
-        raise _lib.MultiKEHipError(f"greedy_alignment: metric {metric!r} is not built (the reference uses 'inner')")
+    (one kernel launch; five with CSLS).  Metrics: 'inner', 'cosine' (== inner product of normalised rows), 'euclidean';
+    csls_k > 0 re-scores by CSLS (code/base/similarity.py:56-75); the other cdist metrics raise.  want_pairs = False (base.evaluation.valid, which drops them): alignment_rest is None — the set of (row, best
+    column) tuples is a Python object per row."""
+    _check_metric(metric, normalize)
+    csls_k = int(csls_k or 0)
     assert 1 in top_k
     t = time.time()
-    greater, ties, best = alignment_counts(embed1, embed2, normalize)
+    greater, ties, best = alignment_counts(embed1, embed2, normalize, metric=metric, csls_k=csls_k)
     num = greater.numel()
     hits, mr, mrr = tie_aware_metrics(greater, ties, top_k)
     hits = np.round(np.array(hits) / num * 100, 3)
     alignment_rest = set(zip(range(num), best.cpu().tolist())) if want_pairs else None
     cost = time.time() - t
-    if accurate:
-        print("accurate results: hits@{} = {}%, mr = {:.3f}, mrr = {:.6f}, time = {:.3f} s ".format(top_k, hits, mr, mrr, cost))
-    else:
-        print("quick results: hits@{} = {}%, time = {:.3f} s ".format(top_k, hits, cost))
+    print_results(top_k, hits, mr, mrr, cost, accurate, csls_k)
     return alignment_rest, hits[0], mr, mrr
+
+
+def print_results(top_k, hits, mr, mrr, cost, accurate, csls_k=0):
+    """The reference's result lines (code/base/alignment.py:64-73)."""
+    if accurate:
+        if csls_k > 0:
+            print("accurate results with csls: csls={}, hits@{} = {}%, mr = {:.3f}, mrr = {:.6f}, time = {:.3f} s ".
+                  format(csls_k, top_k, hits, mr, mrr, cost))
+        else:
+            print("accurate results: hits@{} = {}%, mr = {:.3f}, mrr = {:.6f}, time = {:.3f} s ".format(top_k, hits, mr, mrr, cost))
+    else:
+        if csls_k > 0:
+            print("quick results with csls: csls={}, hits@{} = {}%, time = {:.3f} s ".format(csls_k, top_k, hits, cost))
+        else:
+            print("quick results: hits@{} = {}%, time = {:.3f} s ".format(top_k, hits, cost))

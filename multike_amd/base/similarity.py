@@ -1,0 +1,95 @@
+"""base/similarity.py surface of the reference (code/base/similarity.py:9-81): `sim`, `csls_sim`, `calculate_nearest_k`, with
+the reference's positional signatures.  They return the n1 x n2 matrix, as the reference's do — that is their contract — so
+they are meant for small inputs; the evaluator itself (base.alignment.greedy_alignment with metric / csls_k) never builds it.
+
+NumPy arrays are handled on the host as the reference does (float32 matrix; euclidean and unnormalised cosine through float64,
+rounded to float32).  Device tensors go through the package's kernels: the products are the f32 MFMA chains of
+`mke_sim_sample`, the k nearest are selected by `mke_topk_long` (no sort)."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .. import _lib
+
+_METRICS = ("inner", "cosine", "euclidean")
+
+
+def _check(metric):
+    if metric not in _METRICS:
+        raise _lib.MultiKEHipError(f"sim: metric {metric!r} is not built (supported: 'inner', 'cosine', 'euclidean')")
+
+
+def _unit(x):
+    """sklearn.preprocessing.normalize: zero rows stay zero."""
+    if isinstance(x, torch.Tensor):
+        n = torch.linalg.norm(x, dim=1, keepdim=True)
+        return x / torch.where(n == 0, torch.ones_like(n), n)
+    n = np.linalg.norm(x, axis=1, keepdims=True)
+    return x / np.where(n == 0, 1, n).astype(x.dtype)
+
+
+def _device_products(a, b):
+    """a . b^T on the device through mke_sim_sample (rows padded to a supported width)."""
+    kpad = min(x for x in _lib.SIM_SELECT_KPADS if x >= a.shape[1]) if a.shape[1] <= _lib.SIM_SELECT_KPADS[-1] else None
+    if kpad is None:
+        raise _lib.MultiKEHipError(f"sim: rows of {a.shape[1]} floats exceed MKE_MAX_STRIDE")
+    ap = torch.zeros(a.shape[0], kpad, dtype=torch.float32, device=a.device)
+    ap[:, :a.shape[1]] = a
+    bp = torch.zeros(b.shape[0], kpad, dtype=torch.float32, device=a.device)
+    bp[:, :b.shape[1]] = b
+    return _lib.sim_sample(ap, kpad, 0, a.shape[0], bp)
+
+
+def sim(embed1, embed2, metric='inner', normalize=False, csls_k=0):
+    """code/base/similarity.py:9-53: the n1 x n2 similarity matrix (float32) under `metric`, CSLS re-scored when csls_k > 0."""
+    _check(metric)
+    if isinstance(embed1, torch.Tensor) or isinstance(embed2, torch.Tensor):
+        dev = embed1.device if isinstance(embed1, torch.Tensor) else embed2.device
+        a = torch.as_tensor(embed1, device=dev).float()
+        b = torch.as_tensor(embed2, device=dev).float()
+        if normalize or metric == "cosine":
+            a, b = _unit(a), _unit(b)
+        dot = _device_products(a, b)
+        if metric == "euclidean":
+            sq_a, sq_b = (a * a).sum(1), (b * b).sum(1)
+            mat = 1.0 - torch.sqrt(torch.clamp_min(sq_a[:, None] + sq_b[None, :] - 2.0 * dot, 0.0))
+        else:
+            mat = dot
+    else:
+        a, b = np.asarray(embed1), np.asarray(embed2)
+        if normalize:
+            a, b = _unit(a), _unit(b)
+        if metric == "inner" or (metric == "cosine" and normalize):
+            mat = np.matmul(a, b.T)
+        elif metric == "euclidean":       # 1 - euclidean_distances: |a|^2 - 2 a.b + |b|^2 in float64
+            a64, b64 = a.astype(np.float64), b.astype(np.float64)
+            d2 = (a64 * a64).sum(1)[:, None] - 2.0 * (a64 @ b64.T) + (b64 * b64).sum(1)[None, :]
+            mat = (1.0 - np.sqrt(np.maximum(d2, 0.0))).astype(np.float32)
+        else:                             # 1 - cdist(cosine) in float64
+            a64, b64 = _unit(a.astype(np.float64)), _unit(b.astype(np.float64))
+            mat = (a64 @ b64.T).astype(np.float32)
+    if csls_k > 0:
+        mat = csls_sim(mat, csls_k)
+    return mat
+
+
+def csls_sim(sim_mat, k):
+    """code/base/similarity.py:56-75: (2 sim - r_T[:, None]) - r_S[None, :]."""
+    nearest_values1 = calculate_nearest_k(sim_mat, k)
+    nearest_values2 = calculate_nearest_k(sim_mat.T, k)
+    return (2 * sim_mat - nearest_values1[:, None]) - nearest_values2[None, :]
+
+
+def calculate_nearest_k(sim_mat, k):
+    """code/base/similarity.py:78-81: per row the mean of the k largest values (1 <= k <= columns - 2)."""
+    n = sim_mat.shape[1]
+    if not 1 <= k <= n - 2:
+        raise _lib.MultiKEHipError(f"calculate_nearest_k: need 1 <= k <= {n - 2} (k = {k})")
+    if isinstance(sim_mat, torch.Tensor):
+        m = sim_mat.float().contiguous()
+        idx = _lib.topk_long(m, k)
+        vals = torch.gather(m, 1, idx.long())
+        return vals.double().sum(1).div(k).float()
+    sorted_mat = -np.partition(-sim_mat, k + 1, axis=1)
+    return np.mean(sorted_mat[:, 0:k], axis=1)

@@ -1,0 +1,504 @@
+// mke_csls.hip — CSLS re-scoring and the euclidean metric for the alignment evaluator (gfx950), without the n1 x n2 matrix.
+//
+// What it computes = code/base/similarity.py:9-81 as used by code/base/alignment.py:8-79 with metric / csls_k:
+//   sim(i, j)  = METRIC(E1_i . E2_j):  inner: the dot product;  euclidean: 1 - sqrt(max(|E1_i|^2 + |E2_j|^2 - 2 dot, 0))
+//   r_T(i)     = mean of the k largest sim(i, j) over the n2 columns     (calculate_nearest_k(sim_mat, k))
+//   r_S(j)     = mean of the k largest sim(i, j) over the n1 rows        (calculate_nearest_k(sim_mat.T, k))
+//   csls(i, j) = (2 sim(i, j) - r_T(i)) - r_S(j)                         (csls_sim, f32, in this order)
+// and the rank of the gold column under it.  The reference builds the matrix (60K x 60K fp32 = 14 GB) and partitions it
+// twice; here every similarity is made by the f32 MFMA sweep of mke_simtile.h and folded in registers / LDS:
+//
+//   k_topk_partial  the top-k of every row of A against one column chunk of B: a per-row LDS buffer of 64 floats takes the
+//                   values above the row's running threshold tau (ballot per accumulator register, as k_sim_select); a full
+//                   buffer is compacted to its k largest (rank by comparison inside the half-wave that owns the row) and
+//                   tau rises to the k-th.  k values per (row, chunk) go out.  LDS: 32 KB of buffers + the sweep's tiles
+//                   (43 KB at kpad 80: two blocks per CU on the 160 KB of gfx950).
+//   k_topk_mean     per row of a list of values (the chunk partials, or a whole similarity row in the large-k path): exact
+//                   k-th largest by a byte-wise radix select, the values above it sorted descending (bitonic), summed in
+//                   float64 in descending order with the ties of the k-th last, divided by k, rounded to f32 — a unique,
+//                   run-to-run identical mean of the exact top-k multiset.
+//   k_align_rank_ex the fold of k_align_rank (greater / ties counters, best column with the lowest column winning a tie) with
+//                   every similarity passed through METRIC and, with CSLS, the re-scoring.  The gold is the diagonal MFMA
+//                   product through the SAME epilogue, so a row never counts itself and ties are exact comparisons.
+#include "mke_simtile.h"
+
+#include <math.h>
+
+namespace mke {
+
+#define CSLS_BUF 64          // per-row LDS buffer of k_topk_partial
+#define CSLS_FAST_K 32       // k <= CSLS_FAST_K: the partial sweep; above: whole rows through mke_sim_sample + k_topk_mean
+#define CSLS_MAX_CHUNKS 64
+#define CSLS_SORT_LDS 4096   // k_topk_mean sorts up to this many values in LDS, more in the caller's scratch
+
+template <int MET>
+__device__ __forceinline__ float metric_value(float dot, float sqi, float sqj) {
+  if (MET == MKE_METRIC_EUCLIDEAN) return 1.0f - sqrtf(fmaxf(sqi + sqj - 2.0f * dot, 0.0f));
+  return dot;
+}
+
+__device__ __forceinline__ unsigned csls_key(float v) {  // order-preserving integer image (+0 and -0 one key)
+  unsigned u = __float_as_uint(v);
+  if (u == 0x80000000u) u = 0u;
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float csls_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
+
+__device__ __forceinline__ void wave_sync_lds() {
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// ------------------------------------------------------------------------------------------------ top-k partials
+struct TopkPartialParams {
+  const float* __restrict__ a;  // [n_a][lda]
+  int lda;
+  const float* __restrict__ b;  // [n_b][ldb]
+  int ldb;
+  int n_a, n_b;
+  const float* __restrict__ sq_a;  // euclidean: squared row norms
+  const float* __restrict__ sq_b;
+  int k, chunks, tiles_per_chunk;
+  float* __restrict__ part;  // [n_a][chunks][k]
+};
+
+// The buffer of a row holds n values (n <= CSLS_BUF); the 32 lanes of the owning half-wave rank them (ties by position) and
+// write the k largest, descending, to the front.  Returns the k-th largest.
+__device__ __attribute__((noinline)) float csls_compact(float* buf, int n, int k, int l31) {
+  const float x0 = l31 < n ? buf[l31] : 0.f;
+  const float x1 = l31 + 32 < n ? buf[l31 + 32] : 0.f;
+  int r0 = 0, r1 = 0;
+  for (int j = 0; j < n; ++j) {
+    const float y = buf[j];
+    r0 += (y > x0 || (y == x0 && j < l31)) ? 1 : 0;
+    r1 += (y > x1 || (y == x1 && j < l31 + 32)) ? 1 : 0;
+  }
+  wave_sync_lds();  // every read of the buffer is done before it is rewritten
+  if (l31 < n && r0 < k) buf[r0] = x0;
+  if (l31 + 32 < n && r1 < k) buf[r1] = x1;
+  wave_sync_lds();
+  return buf[k - 1];
+}
+
+template <int KS, int MET>
+__global__ __launch_bounds__(MKE_BLOCK) void k_topk_partial(const TopkPartialParams p) {
+  __shared__ float s_buf[SIMT_BM][CSLS_BUF];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int half = lane >> 5, l31 = lane & 31;
+  const int strip0 = blockIdx.x * SIMT_BM + wv * 32;
+  float a[KS * 8];
+  {
+    const int r = strip0 + l31;
+    const bool ok = r < p.n_a;
+    simt_load_fragment<KS>(p.a + (int64_t)(ok ? r : 0) * p.lda, ok, half, a);
+  }
+  float tau[16], sqi[16];
+  int cnt[16];
+#pragma unroll
+  for (int reg = 0; reg < 16; ++reg) {
+    const int r = strip0 + (reg & 3) + 8 * (reg >> 2) + 4 * half;
+    tau[reg] = -INFINITY;
+    cnt[reg] = 0;
+    sqi[reg] = (MET == MKE_METRIC_EUCLIDEAN && r < p.n_a) ? p.sq_a[r] : 0.f;
+  }
+  const int ntiles = (p.n_b + SIMT_BN_FOR(KS) - 1) / SIMT_BN_FOR(KS);
+  const int t0 = blockIdx.y * p.tiles_per_chunk;
+  const int t1 = min(ntiles, t0 + p.tiles_per_chunk);
+  const unsigned lt = (1u << l31) - 1u;
+  const int k = p.k;
+  simt_sweep<KS>(a, p.b, p.ldb, p.n_b, t0, t1, [&](const f32x16& acc, int col, bool col_ok) {
+    const float sqj = (MET == MKE_METRIC_EUCLIDEAN && col_ok) ? p.sq_b[col] : 0.f;
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+      const float v = col_ok ? metric_value<MET>(acc[reg], sqi[reg], sqj) : -INFINITY;
+      const bool hit = v > tau[reg];
+      const uint64_t m = __builtin_amdgcn_ballot_w64(hit);
+      if (m == 0) continue;  // wave-uniform
+      const unsigned mh = half ? (unsigned)(m >> 32) : (unsigned)m;  // the 32 lanes of a half hold 32 columns of ONE row
+      const int nh = __popc(mh);
+      float* buf = s_buf[wv * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * half];
+      if (cnt[reg] + nh > CSLS_BUF) {  // uniform in the half: cnt > CSLS_BUF - 32 >= k, keep the k largest
+        tau[reg] = csls_compact(buf, cnt[reg], k, l31);
+        cnt[reg] = k;  // k + nh <= 64: the hits still fit (they beat the old tau; extra ones go at the next compaction)
+      }
+      if (hit) buf[cnt[reg] + __popc(mh & lt)] = v;
+      cnt[reg] += nh;
+    }
+  });
+  wave_sync_lds();
+#pragma unroll
+  for (int reg = 0; reg < 16; ++reg) {
+    const int rr = (reg & 3) + 8 * (reg >> 2) + 4 * half;
+    float* buf = s_buf[wv * 32 + rr];
+    if (cnt[reg] > k) csls_compact(buf, cnt[reg], k, l31);
+    const int row = strip0 + rr;
+    if (row < p.n_a && l31 < k) {  // k <= 32: one value per lane; a chunk with fewer than k columns pads with -inf
+      const int64_t o = ((int64_t)row * p.chunks + blockIdx.y) * p.k + l31;
+      p.part[o] = l31 < cnt[reg] ? buf[l31] : -INFINITY;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ exact top-k mean
+struct TopkMeanParams {
+  const float* __restrict__ vals;  // [rows][ld], m values per row
+  int64_t ld;
+  int m, k;
+  int metric;                       // MKE_METRIC_EUCLIDEAN: vals are dot products, turned into similarities on the fly
+  const float* __restrict__ sq_a;   // [rows] (offset to the launch's first row)
+  const float* __restrict__ sq_b;   // [m]
+  unsigned* __restrict__ sort_tmp;  // [rows][sort_ld] when k > CSLS_SORT_LDS
+  int64_t sort_ld;
+  float* __restrict__ out;  // [rows]
+};
+
+__device__ __forceinline__ float mean_value(const TopkMeanParams& p, const float* v, float sqi, int i) {
+  return p.metric == MKE_METRIC_EUCLIDEAN ? metric_value<MKE_METRIC_EUCLIDEAN>(v[i], sqi, p.sq_b[i]) : v[i];
+}
+
+__global__ __launch_bounds__(MKE_BLOCK) void k_topk_mean(const TopkMeanParams p) {
+  static_assert(MKE_BLOCK == 256, "one histogram bin per thread");
+  __shared__ int s_hist[MKE_BLOCK / 64][256];
+  __shared__ int s_wave[MKE_BLOCK / 64];
+  __shared__ unsigned s_prefix;
+  __shared__ int s_need, s_gt;
+  __shared__ unsigned s_sort[CSLS_SORT_LDS];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int64_t row = blockIdx.x;
+  const float* __restrict__ v = p.vals + row * p.ld;
+  const float sqi = p.metric == MKE_METRIC_EUCLIDEAN ? p.sq_a[row] : 0.f;
+  if (tid == 0) { s_prefix = 0u; s_need = p.k; s_gt = 0; }
+  __syncthreads();
+  for (int hi = 32; hi > 0; hi -= 8) {  // the k-th largest key, most significant byte first (as k_topk_long)
+    const int shift = hi - 8;
+#pragma unroll
+    for (int q = 0; q < MKE_BLOCK / 64; ++q) s_hist[q][tid] = 0;
+    __syncthreads();
+    const unsigned pre = s_prefix;
+    const int need = s_need;
+    for (int i = tid; i < p.m; i += MKE_BLOCK) {
+      const unsigned kx = csls_key(mean_value(p, v, sqi, i));
+      if (hi >= 32 || (kx >> hi) == (pre >> hi)) atomicAdd(&s_hist[wv][(kx >> shift) & 255u], 1);
+    }
+    __syncthreads();
+    const int dgt = 255 - tid;
+    const int h = s_hist[0][dgt] + s_hist[1][dgt] + s_hist[2][dgt] + s_hist[3][dgt];
+    int incl = h;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int o = __shfl_up(incl, off, 64);
+      if (lane >= off) incl += o;
+    }
+    if (lane == 63) s_wave[wv] = incl;
+    __syncthreads();
+    for (int q = 0; q < wv; ++q) incl += s_wave[q];
+    if (incl >= need && incl - h < need) {
+      s_prefix = pre | ((unsigned)dgt << shift);
+      s_need = need - (incl - h);
+    }
+    __syncthreads();
+  }
+  const unsigned kth = s_prefix;
+  const int ties = s_need;  // copies of the k-th value in the top k; the other k - ties values are above it
+  const int gt = p.k - ties;
+  int np2 = 1;
+  while (np2 < gt) np2 <<= 1;
+  unsigned* buf = p.k <= CSLS_SORT_LDS ? s_sort : p.sort_tmp + row * p.sort_ld;
+  for (int i = tid; i < p.m; i += MKE_BLOCK) {
+    const unsigned kx = csls_key(mean_value(p, v, sqi, i));
+    if (kx > kth) buf[atomicAdd(&s_gt, 1)] = kx;
+  }
+  __syncthreads();
+  for (int i = gt + tid; i < np2; i += MKE_BLOCK) buf[i] = 0u;  // below every float key: sorts last
+  __syncthreads();
+  for (int size = 2; size <= np2; size <<= 1) {  // bitonic sort, descending
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int i = tid; i < np2 / 2; i += MKE_BLOCK) {
+        const int lo = 2 * i - (i & (stride - 1));
+        const int hi2 = lo + stride;
+        const bool desc = (lo & size) == 0;
+        const unsigned x = buf[lo], y = buf[hi2];
+        if ((x < y) == desc) { buf[lo] = y; buf[hi2] = x; }
+      }
+      __syncthreads();
+    }
+  }
+  if (tid == 0) {
+    double s = 0.0;
+    for (int i = 0; i < gt; ++i) s += (double)csls_unkey(buf[i]);
+    const double kv = (double)csls_unkey(kth);
+    for (int i = 0; i < ties; ++i) s += kv;
+    p.out[row] = (float)(s / (double)p.k);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ rank sweep with metric / CSLS
+struct AlignRankExParams {
+  const float* __restrict__ emb1;
+  int ld1;
+  const float* __restrict__ emb2;
+  int ld2;
+  int n1, n2;
+  int tiles_per_chunk;
+  const float* __restrict__ sq1;
+  const float* __restrict__ sq2;
+  const float* __restrict__ csls_row;
+  const float* __restrict__ csls_col;
+  int32_t* __restrict__ rank;
+  int32_t* __restrict__ ties;
+  unsigned long long* __restrict__ best;
+};
+
+template <int MET, bool CSLS>
+__device__ __forceinline__ float rescore(float dot, float sqi, float sqj, float rt, float rs) {
+  float v = metric_value<MET>(dot, sqi, sqj);
+  if (CSLS) v = (2.0f * v - rt) - rs;
+  return v;
+}
+
+template <int KS, int MET, bool CSLS>
+__global__ __launch_bounds__(MKE_BLOCK) void k_align_rank_ex(const AlignRankExParams p) {
+  constexpr bool EUC = MET == MKE_METRIC_EUCLIDEAN;
+  __shared__ float s_gold[MKE_BLOCK / 64][32];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int half = lane >> 5, l31 = lane & 31;
+  const int strip0 = blockIdx.x * SIMT_BM + wv * 32;
+  float a[KS * 8];
+  float gold[16], sqi[16], rti[16];
+#pragma unroll
+  for (int reg = 0; reg < 16; ++reg) {
+    const int r = strip0 + (reg & 3) + 8 * (reg >> 2) + 4 * half;
+    sqi[reg] = (EUC && r < p.n1) ? p.sq1[r] : 0.f;
+    rti[reg] = (CSLS && r < p.n1) ? p.csls_row[r] : 0.f;
+  }
+  {
+    const int r = strip0 + l31;
+    const bool ok = r < p.n1;
+    simt_load_fragment<KS>(p.emb1 + (int64_t)(ok ? r : 0) * p.ld1, ok, half, a);
+    float b[KS * 8];
+    simt_load_fragment<KS>(p.emb2 + (int64_t)(ok ? r : 0) * p.ld2, ok, half, b);  // gold column i = row i (n2 >= n1)
+    const f32x16 d = simt_fragment_product<KS>(a, b);
+    const float sqj = (EUC && ok) ? p.sq2[r] : 0.f;  // this lane's column of the product is r
+    const float rsj = (CSLS && ok) ? p.csls_col[r] : 0.f;
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+      const int m = (reg & 3) + 8 * (reg >> 2) + 4 * half;
+      if (m == l31) s_gold[wv][m] = rescore<MET, CSLS>(d[reg], sqi[reg], sqj, rti[reg], rsj);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) gold[reg] = s_gold[wv][(reg & 3) + 8 * (reg >> 2) + 4 * half];
+  }
+  int cnt[16], eq[16];
+  float bestv[16];
+  int bestc[16];
+#pragma unroll
+  for (int reg = 0; reg < 16; ++reg) { cnt[reg] = 0; eq[reg] = 0; bestv[reg] = -INFINITY; bestc[reg] = 0x7FFFFFFF; }
+  const int ntiles = (p.n2 + SIMT_BN_FOR(KS) - 1) / SIMT_BN_FOR(KS);
+  const int t0 = blockIdx.y * p.tiles_per_chunk;
+  const int t1 = min(ntiles, t0 + p.tiles_per_chunk);
+  simt_sweep<KS>(a, p.emb2, p.ld2, p.n2, t0, t1, [&](const f32x16& acc, int col, bool col_ok) {
+    const float sqj = (EUC && col_ok) ? p.sq2[col] : 0.f;
+    const float rsj = (CSLS && col_ok) ? p.csls_col[col] : 0.f;
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+      const float s = rescore<MET, CSLS>(acc[reg], sqi[reg], sqj, rti[reg], rsj);
+      cnt[reg] += (col_ok && s > gold[reg]) ? 1 : 0;
+      eq[reg] += (col_ok && s == gold[reg]) ? 1 : 0;
+      if (col_ok && (s > bestv[reg] || (s == bestv[reg] && col < bestc[reg]))) { bestv[reg] = s; bestc[reg] = col; }
+    }
+  });
+#pragma unroll
+  for (int reg = 0; reg < 16; ++reg) {
+    int c = cnt[reg], ce = eq[reg];
+    float bv = bestv[reg];
+    int bc = bestc[reg];
+#pragma unroll
+    for (int off = 1; off < 32; off <<= 1) {
+      c += __shfl_xor(c, off, 64);
+      ce += __shfl_xor(ce, off, 64);
+      const float ov = __shfl_xor(bv, off, 64);
+      const int oc = __shfl_xor(bc, off, 64);
+      if (ov > bv || (ov == bv && oc < bc)) { bv = ov; bc = oc; }
+    }
+    const int row = strip0 + (reg & 3) + 8 * (reg >> 2) + 4 * half;
+    if (l31 == 0 && row < p.n1 && t0 < t1) {
+      atomicAdd(&p.rank[row], c);
+      atomicAdd(&p.ties[row], ce);
+    }
+    if (l31 == 0 && row < p.n1 && t0 < t1 && bc != 0x7FFFFFFF) {  // bc unset: every similarity of the chunk was NaN
+      unsigned u = __float_as_uint(bv);
+      u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+      const unsigned long long key = ((unsigned long long)u << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)bc);
+      atomicMax(&p.best[row], key);
+    }
+  }
+}
+
+// (row blocks, column chunks) of a sweep: enough items to fill the chip several times over, a chunk at least 16 tiles
+static int sweep_chunks(int64_t rows, int ntiles, int target, int cap) {
+  const int row_blocks = (int)((rows + SIMT_BM - 1) / SIMT_BM);
+  int chunks = (target + row_blocks - 1) / row_blocks;
+  if (chunks > (ntiles + 15) / 16) chunks = (ntiles + 15) / 16;
+  if (chunks > cap) chunks = cap;
+  if (chunks < 1) chunks = 1;
+  const int per = (ntiles + chunks - 1) / chunks;
+  return (ntiles + per - 1) / per;  // no empty chunk
+}
+
+static bool kpad_ok(int kpad) {
+  switch (kpad) {
+    case 16: case 32: case 48: case 64: case 80: case 96: case 112: case 128: case 160: case 192: case 208: case 256: case 320:
+      return true;
+    default:
+      return false;
+  }
+}
+
+// rows of the large-k path per round: the similarity rows of one round stay under 2^26 floats (256 MB)
+static int64_t fallback_rows(int64_t n_a, int64_t n_b) {
+  int64_t r = ((int64_t)1 << 26) / n_b;
+  r = r / SIMT_BM * SIMT_BM;
+  if (r < SIMT_BM) r = SIMT_BM;
+  return r < n_a ? r : n_a;
+}
+
+static int64_t pow2_at_least(int64_t x) {
+  int64_t p = 1;
+  while (p < x) p <<= 1;
+  return p;
+}
+
+}  // namespace mke
+
+static int topk_mean_temp(int64_t n_a, int64_t n_b, int kpad, int k, int64_t* bytes) {
+  using namespace mke;
+  *bytes = 0;
+  if (n_a < 0 || n_b < 0 || n_a > 0x7FFFFF00LL || n_b > 0x7FFFFF00LL) { set_error("mke_align_topk_mean: bad n_a / n_b"); return MKE_E_SHAPE; }
+  if (kpad <= 0 || kpad % 16 != 0 || kpad > MKE_MAX_STRIDE) { set_error("mke_align_topk_mean: kpad must be a multiple of 16 <= %d", MKE_MAX_STRIDE); return MKE_E_SHAPE; }
+  if (k < 1 || (int64_t)k > n_b - 2) { set_error("mke_align_topk_mean: need 1 <= k <= n_b - 2 (k = %d, n_b = %lld)", k, (long long)n_b); return MKE_E_SHAPE; }
+  if (k > (1 << 30)) { set_error("mke_align_topk_mean: k above 2^30 (the sort of the large-k path counts with 32-bit ints)"); return MKE_E_RANGE; }
+  if (n_a == 0) return MKE_OK;
+  int64_t floats;
+  if (k <= CSLS_FAST_K) {
+    const int bn = SIMT_BN_FOR(kpad / 16);
+    const int chunks = sweep_chunks(n_a, (int)((n_b + bn - 1) / bn), 6144, CSLS_MAX_CHUNKS);
+    floats = n_a * chunks * k;  // < 2^31 * 64 * 32: the kernels index it with int64 offsets
+  } else {
+    const int64_t r = fallback_rows(n_a, n_b);
+    floats = r * n_b + (k > CSLS_SORT_LDS ? r * pow2_at_least(k) : 0);
+  }
+  if (floats > ((int64_t)1 << 40)) { set_error("mke_align_topk_mean: scratch beyond 2^40 floats"); return MKE_E_RANGE; }
+  *bytes = floats * 4;
+  return MKE_OK;
+}
+
+extern "C" int64_t mke_align_topk_mean_temp_bytes(int64_t n_a, int64_t n_b, int kpad, int k) {
+  int64_t bytes = 0;
+  const int rc = topk_mean_temp(n_a, n_b, kpad, k, &bytes);
+  return rc != MKE_OK ? rc : bytes;
+}
+
+extern "C" int mke_align_topk_mean(const mke_topk_mean_args* args, void* stream) {
+  using namespace mke;
+  if (!args) { set_error("mke_align_topk_mean: NULL args"); return MKE_E_NULL; }
+  const mke_topk_mean_args& g = *args;
+  int64_t need = 0;
+  const int rc = topk_mean_temp(g.n_a, g.n_b, g.kpad, g.k, &need);
+  if (rc != MKE_OK) return rc;
+  if (g.metric != MKE_METRIC_INNER && g.metric != MKE_METRIC_EUCLIDEAN) { set_error("mke_align_topk_mean: unknown metric %d", g.metric); return MKE_E_UNSUPPORTED; }
+  if (g.n_a == 0) return MKE_OK;
+  if (!g.a || !g.b || !g.out || (need > 0 && !g.temp)) { set_error("mke_align_topk_mean: NULL pointer"); return MKE_E_NULL; }
+  if (g.metric == MKE_METRIC_EUCLIDEAN && (!g.sq_a || !g.sq_b)) { set_error("mke_align_topk_mean: euclidean needs sq_a and sq_b"); return MKE_E_NULL; }
+  if (g.lda < g.kpad || g.ldb < g.kpad || g.lda % 4 != 0 || g.ldb % 4 != 0) { set_error("mke_align_topk_mean: lda, ldb must be multiples of 4 >= kpad"); return MKE_E_SHAPE; }
+  if (!kpad_ok(g.kpad)) { set_error("mke_align_topk_mean: unsupported kpad %d", g.kpad); return MKE_E_UNSUPPORTED; }
+  if (g.temp_bytes < need) { set_error("mke_align_topk_mean: temp below mke_align_topk_mean_temp_bytes (%lld)", (long long)need); return MKE_E_SHAPE; }
+  hipStream_t st = (hipStream_t)stream;
+  TopkMeanParams mp;
+  mp.k = g.k; mp.metric = g.metric; mp.sort_tmp = nullptr; mp.sort_ld = 0;
+  if (g.k <= CSLS_FAST_K) {
+    TopkPartialParams p;
+    p.a = g.a; p.lda = g.lda; p.b = g.b; p.ldb = g.ldb; p.n_a = (int)g.n_a; p.n_b = (int)g.n_b; p.sq_a = g.sq_a; p.sq_b = g.sq_b;
+    p.k = g.k;
+    const int bn = SIMT_BN_FOR(g.kpad / 16);
+    const int ntiles = (int)((g.n_b + bn - 1) / bn);
+    p.chunks = sweep_chunks(g.n_a, ntiles, 6144, CSLS_MAX_CHUNKS);
+    p.tiles_per_chunk = (ntiles + p.chunks - 1) / p.chunks;
+    p.part = (float*)g.temp;
+    dim3 grid((unsigned)((g.n_a + SIMT_BM - 1) / SIMT_BM), (unsigned)p.chunks);
+#define TP_CASE(K)                                                                                              \
+  case K:                                                                                                       \
+    if (g.metric == MKE_METRIC_EUCLIDEAN) hipLaunchKernelGGL((k_topk_partial<K / 16, MKE_METRIC_EUCLIDEAN>), grid, dim3(MKE_BLOCK), 0, st, p); \
+    else hipLaunchKernelGGL((k_topk_partial<K / 16, MKE_METRIC_INNER>), grid, dim3(MKE_BLOCK), 0, st, p);       \
+    break;
+    switch (g.kpad) {
+      TP_CASE(16) TP_CASE(32) TP_CASE(48) TP_CASE(64) TP_CASE(80) TP_CASE(96) TP_CASE(112) TP_CASE(128) TP_CASE(160)
+      TP_CASE(192) TP_CASE(208) TP_CASE(256) TP_CASE(320)
+    }
+#undef TP_CASE
+    const int e = check_launch("k_topk_partial");
+    if (e) return e;
+    mp.vals = p.part; mp.ld = (int64_t)p.chunks * g.k; mp.m = p.chunks * g.k;
+    mp.metric = MKE_METRIC_INNER;  // the partials are similarities already
+    mp.sq_a = nullptr; mp.sq_b = nullptr; mp.out = g.out;
+    hipLaunchKernelGGL(k_topk_mean, dim3((unsigned)g.n_a), dim3(MKE_BLOCK), 0, st, mp);
+    return check_launch("k_topk_mean");
+  }
+  // large k: whole similarity rows of a bounded round of rows (the f32 MFMA chains of mke_sim_sample), then the same mean
+  const int64_t r = fallback_rows(g.n_a, g.n_b);
+  float* simrows = (float*)g.temp;
+  mp.ld = g.n_b; mp.m = (int)g.n_b; mp.sq_b = g.sq_b;
+  if (g.k > CSLS_SORT_LDS) { mp.sort_tmp = (unsigned*)(simrows + r * g.n_b); mp.sort_ld = pow2_at_least(g.k); }
+  for (int64_t lo = 0; lo < g.n_a; lo += r) {
+    const int64_t hi = lo + r < g.n_a ? lo + r : g.n_a;
+    int e = mke_sim_sample(g.a, g.lda, g.kpad, g.n_a, lo, hi, g.b, g.ldb, (int)g.n_b, simrows, stream);
+    if (e) return e;
+    mp.vals = simrows; mp.sq_a = g.sq_a ? g.sq_a + lo : nullptr; mp.out = g.out + lo;
+    hipLaunchKernelGGL(k_topk_mean, dim3((unsigned)(hi - lo)), dim3(MKE_BLOCK), 0, st, mp);
+    e = check_launch("k_topk_mean");
+    if (e) return e;
+  }
+  return MKE_OK;
+}
+
+extern "C" int mke_align_rank_ex(const mke_align_args* args, void* stream) {
+  using namespace mke;
+  if (!args) { set_error("mke_align_rank_ex: NULL args"); return MKE_E_NULL; }
+  const mke_align_args& g = *args;
+  if (g.n1 < 0 || g.n2 < 0 || g.n1 > 0x7FFFFF00LL || g.n2 > 0x7FFFFF00LL) { set_error("mke_align_rank_ex: bad n1/n2"); return MKE_E_SHAPE; }
+  if (g.metric != MKE_METRIC_INNER && g.metric != MKE_METRIC_EUCLIDEAN) { set_error("mke_align_rank_ex: unknown metric %d", g.metric); return MKE_E_UNSUPPORTED; }
+  if ((g.csls_row == nullptr) != (g.csls_col == nullptr)) { set_error("mke_align_rank_ex: csls_row and csls_col are both NULL or both set"); return MKE_E_NULL; }
+  if (g.n1 == 0) return MKE_OK;
+  if (!g.emb1 || !g.emb2 || !g.rank || !g.ties || !g.best) { set_error("mke_align_rank_ex: NULL pointer"); return MKE_E_NULL; }
+  if (g.metric == MKE_METRIC_EUCLIDEAN && (!g.sq1 || !g.sq2)) { set_error("mke_align_rank_ex: euclidean needs sq1 and sq2"); return MKE_E_NULL; }
+  if (g.kpad <= 0 || g.kpad % 16 != 0 || g.kpad > MKE_MAX_STRIDE || g.ld1 < g.kpad || g.ld2 < g.kpad || g.ld1 % 4 != 0 || g.ld2 % 4 != 0) {
+    set_error("mke_align_rank_ex: kpad must be a multiple of 16 <= %d and <= ld1, ld2 (both multiples of 4)", MKE_MAX_STRIDE);
+    return MKE_E_SHAPE;
+  }
+  if (g.n2 < g.n1) { set_error("mke_align_rank_ex: gold column = row index needs n2 >= n1"); return MKE_E_SHAPE; }
+  if (!kpad_ok(g.kpad)) { set_error("mke_align_rank_ex: unsupported kpad %d", g.kpad); return MKE_E_UNSUPPORTED; }
+  AlignRankExParams p;
+  p.emb1 = g.emb1; p.ld1 = g.ld1; p.emb2 = g.emb2; p.ld2 = g.ld2; p.n1 = (int)g.n1; p.n2 = (int)g.n2;
+  p.sq1 = g.sq1; p.sq2 = g.sq2; p.csls_row = g.csls_row; p.csls_col = g.csls_col;
+  p.rank = g.rank; p.ties = g.ties; p.best = (unsigned long long*)g.best;
+  const int bn = SIMT_BN_FOR(g.kpad / 16);
+  const int ntiles = (int)((g.n2 + bn - 1) / bn);
+  const int chunks = sweep_chunks(g.n1, ntiles, 6144, 1 << 16);
+  p.tiles_per_chunk = (ntiles + chunks - 1) / chunks;
+  dim3 grid((unsigned)((g.n1 + SIMT_BM - 1) / SIMT_BM), (unsigned)chunks);
+  hipStream_t st = (hipStream_t)stream;
+  const bool csls = g.csls_row != nullptr, euc = g.metric == MKE_METRIC_EUCLIDEAN;
+#define RX_CASE(K)                                                                                                             \
+  case K:                                                                                                                      \
+    if (euc && csls) hipLaunchKernelGGL((k_align_rank_ex<K / 16, MKE_METRIC_EUCLIDEAN, true>), grid, dim3(MKE_BLOCK), 0, st, p);  \
+    else if (euc) hipLaunchKernelGGL((k_align_rank_ex<K / 16, MKE_METRIC_EUCLIDEAN, false>), grid, dim3(MKE_BLOCK), 0, st, p);  \
+    else if (csls) hipLaunchKernelGGL((k_align_rank_ex<K / 16, MKE_METRIC_INNER, true>), grid, dim3(MKE_BLOCK), 0, st, p);      \
+    else hipLaunchKernelGGL((k_align_rank_ex<K / 16, MKE_METRIC_INNER, false>), grid, dim3(MKE_BLOCK), 0, st, p);               \
+    break;
+  switch (g.kpad) {
+    RX_CASE(16) RX_CASE(32) RX_CASE(48) RX_CASE(64) RX_CASE(80) RX_CASE(96) RX_CASE(112) RX_CASE(128) RX_CASE(160)
+    RX_CASE(192) RX_CASE(208) RX_CASE(256) RX_CASE(320)
+  }
+#undef RX_CASE
+  return check_launch("k_align_rank_ex");
+}

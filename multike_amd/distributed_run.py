@@ -28,7 +28,7 @@ import torch.distributed as dist
 
 from . import _lib
 from .attr_cnn import AttrCNN
-from .base.alignment import alignment_counts, tie_aware_metrics
+from .base.alignment import alignment_counts, csls_means, prepare_operands, print_results, tie_aware_metrics
 from .base.batch import neighbour_table
 from .distributed_model import ShardedITC
 from .MultiKE_CSL import MultiKE_CV
@@ -136,31 +136,42 @@ class _ShardedMixin:
         self._vc.all_reduce(out)
         return out
 
-    def _rank_block(self, e1: torch.Tensor, e2: torch.Tensor, top_k):
+    def _rank_block(self, e1: torch.Tensor, e2: torch.Tensor, top_k, csls_k=0):
         """Hits@k / MR / MRR of e1 rows against e2 rows (gold column = row index), the rows split over the ranks: this rank ranks
         rows [lo, hi); the columns are rotated so that its block's gold columns come first (a permutation of the columns does
-        not change a rank)."""
+        not change a rank).  csls_k > 0: CSLS re-scoring — this rank computes r_T of its rows and r_S of its slice of the
+        columns, both are all-gathered (a sum over zero-filled vectors: exact), and r_S is rotated with the columns."""
         n1 = e1.shape[0]
         lo, hi = n1 * self.rank // self.world, n1 * (self.rank + 1) // self.world
         acc = torch.zeros(len(top_k) + 2, dtype=torch.float64, device=self.device)
+        csls = None
+        if csls_k > 0:
+            n2 = e2.shape[0]
+            clo, chi = n2 * self.rank // self.world, n2 * (self.rank + 1) // self.world
+            a, b, kpad, code, sq1, sq2 = prepare_operands(e1, e2, "inner", True, self.device)
+            both = torch.zeros(n1 + n2, dtype=torch.float32, device=self.device)
+            if hi > lo:
+                both[lo:hi] = _lib.align_topk_mean(a[lo:hi], b, kpad, csls_k, code)
+            if chi > clo:
+                both[n1 + clo:n1 + chi] = _lib.align_topk_mean(b[clo:chi], a, kpad, csls_k, code)
+            self._vc.all_reduce(both)
+            r_t, r_s = both[:n1], both[n1:]
+            csls = (r_t[lo:hi].contiguous(), torch.cat([r_s[lo:hi], r_s[:lo], r_s[hi:]]).contiguous())
         if hi > lo:
             cols = torch.cat([e2[lo:hi], e2[:lo], e2[hi:]], 0)
-            greater, ties, _ = alignment_counts(e1[lo:hi], cols, normalize=True, device=self.device)
+            greater, ties, _ = alignment_counts(e1[lo:hi], cols, normalize=True, device=self.device, csls_k=csls_k, csls=csls)
             hits, mr, mrr = tie_aware_metrics(greater, ties, top_k)
             acc += torch.tensor(list(hits) + [mr * (hi - lo), mrr * (hi - lo)], dtype=torch.float64, device=self.device)
         self._vc.all_reduce(acc)
         acc = acc.cpu().numpy() / n1
         return np.round(acc[:len(top_k)] * 100, 3), float(acc[-2]), float(acc[-1])
 
-    def _evaluate(self, e1, e2, label, accurate):
+    def _evaluate(self, e1, e2, label, accurate, csls_k=0):
         t = time.time()
-        hits, mr, mrr = self._rank_block(e1, e2, self.args.top_k)
+        hits, mr, mrr = self._rank_block(e1, e2, self.args.top_k, csls_k)
         if self.rank == 0:
             print(label)
-            if accurate:
-                print("accurate results: hits@{} = {}%, mr = {:.3f}, mrr = {:.6f}, time = {:.3f} s ".format(self.args.top_k, hits, mr, mrr, time.time() - t))
-            else:
-                print("quick results: hits@{} = {}%, time = {:.3f} s ".format(self.args.top_k, hits, time.time() - t))
+            print_results(self.args.top_k, hits, mr, mrr, time.time() - t, accurate, csls_k)
         self.last_hits = hits
         return mrr
 
@@ -172,9 +183,13 @@ class _ShardedMixin:
     def _test(self, embed_choice, w=(1, 1, 1)):
         k = self.kgs
         return self._evaluate(self.rows(embed_choice, k.test_entities1, w), self.rows(embed_choice, k.test_entities2, w),
-                              f"{embed_choice} test results:", True)
+                              f"{embed_choice} test results:", True, self._csls_k())
 
-    def _wva(self, ents1, ents2, label, accurate):
+    def _csls_k(self):
+        """Hyper-parameter `csls`: CSLS re-scoring of the final tests only (validation and early stopping stay plain)."""
+        return int(getattr(self.args, "csls", 0) or 0)
+
+    def _wva(self, ents1, ents2, label, accurate, csls_k=0):
         """code/MultiKE_Late.py:99-173: the three views weighted by their mean cosine to the views' average."""
         v1 = [self.rows(c, ents1).cpu().numpy() for c in ("nv", "rv", "av")]
         v2 = [self.rows(c, ents2).cpu().numpy() for c in ("nv", "rv", "av")]
@@ -188,14 +203,14 @@ class _ShardedMixin:
         dev = lambda a: torch.as_tensor(a, dtype=torch.float32, device=self.device)
         e1 = dev(sum(x * v for x, v in zip(wsum, v1)))
         e2 = dev(sum(x * v for x, v in zip(wsum, v2)))
-        return self._evaluate(e1, e2, label, accurate)
+        return self._evaluate(e1, e2, label, accurate, csls_k)
 
     def _valid_WVA(self):
         k = self.kgs
         return self._wva(k.valid_entities1, k.valid_entities2 + k.test_entities2, 'wvag valid results:', False)
 
     def _test_WVA(self):
-        return self._wva(self.kgs.test_entities1, self.kgs.test_entities2, 'wvag test results:', True)
+        return self._wva(self.kgs.test_entities1, self.kgs.test_entities2, 'wvag test results:', True, self._csls_k())
 
     # --- the training phases ---------------------------------------------------------------------------------------
     def _phase(self, name, text, epoch, scale=1.0):

@@ -42,6 +42,8 @@ def default_args(**over):
         batch_threads_num=4, test_threads_num=8,
         # validation / early stopping
         start_valid=100, eval_freq=10, stop_metric="mrr", top_k=[1, 5, 10, 50], is_save=True,
+        # CSLS re-scoring of the final tests (OpenEA's key `csls`; 0 = off, the reference's evaluation)
+        csls=0,
         # view combination and predicate soft alignment
         orthogonal_weight=2, cv_name_weight=1, cv_weight=1, start_predicate_soft_alignment=10, predicate_soft_sim=0.85,
         predicate_init_sim=0.90)
