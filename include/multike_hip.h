@@ -301,7 +301,7 @@ typedef struct mke_kg_side {
   const int32_t* cand_table;   /* nullable [n_ent_total][cand_k]: truncated-sampling neighbours, indexed by entity id */
   const uint8_t* cand_valid;   /* nullable [n_ent_total]: entity has a neighbour list (dict membership, batch.py:94-95) */
   int32_t cand_k;
-  const uint64_t* known_keys;  /* nullable: hash set built by mke_tripleset_build */
+  const uint64_t* known_keys;  /* nullable: hash set built by mke_tripleset_build (its prefilter is found by this address) */
   uint64_t known_capacity;     /* power of two */
 } mke_kg_side;
 
@@ -342,6 +342,25 @@ int mke_tripleset_build(
     const int32_t* h, const int32_t* r, const int32_t* t, int64_t n,
     uint64_t* keys, uint64_t capacity, void* stream);
 
+/* Prefilter of the set.  The sampler asks a set of C2's size (8 MB of slots per KG) 23 M times per epoch and almost
+ * always hears "not known", each time at the price of one random read past the L2.  So mke_tripleset_build also keeps a
+ * one-hash Bloom filter per set (8 bits per slot, at most 4 MB): device memory that the LIBRARY owns, found by
+ * (keys, capacity) on the host when mke_neg_sample / mke_neg_sample_at launch.  A clear bit answers "not known" from L2;
+ * a set bit falls through to the table, so the sampler's output does not depend on whether a set has a filter.
+ *
+ * What keeps the filter in step with the set: mke_tripleset_build writes both, on the same stream.  The first build call
+ * on a table creates the filter from whatever the table already holds plus the new keys; every later call adds its keys to
+ * both.  A filter therefore never lacks a key that went into its table through mke_tripleset_build, however the calls
+ * interleave with sampling (stream order, as for the table itself).  A table the library never built (copied from another
+ * one, say) has no filter and is probed directly.  The one thing the library cannot see is a table that is re-filled by
+ * other means at an address it has a filter for: before an address is used for a table that mke_tripleset_build does not
+ * fill, and when a table is freed, call mke_tripleset_forget(keys).  (A new set BUILT at the address of a freed one is
+ * safe without it: a filter of another capacity is dropped, one of the same capacity keeps the old set's bits and only
+ * filters less.)  mke_tripleset_forget frees the filter after waiting for the device; unknown addresses are ignored. */
+int mke_tripleset_forget(const uint64_t* keys);
+/* Bytes of the filter the sampler would use for (keys, capacity); 0 = none: the set is probed directly. */
+int64_t mke_tripleset_filter_bytes(const uint64_t* keys, uint64_t capacity);
+
 /* Membership query (used by tests and by the host-side mirror of the filter): out[i] = 1 if present. */
 int mke_tripleset_query(
     const int32_t* h, const int32_t* r, const int32_t* t, int64_t n,
@@ -355,6 +374,19 @@ int mke_tripleset_query(
  * oracle/sampler_oracle.py:distinct_sample restates it. */
 int mke_sample_distinct(int64_t n, int batch, int n_steps, uint32_t seed_lo, uint32_t seed_hi, uint32_t stream_id,
                         int32_t* out /* [n_steps][batch] */, void* stream);
+
+/* The epoch boundary of the relation view in one launch: random.shuffle of both positive lists
+ * (code/MultiKE_model.py:314-315) and the new epoch's positives in step order (code/base/batch.py:36-54).
+ *   list1 / list2: the KGs' current lists, [n][3] (h, r, t); perm1 / perm2 (nullable = identity): a permutation of [0, n)
+ *   each, every entry in range.  Shuffled list: listK_out[i] = listK[permK[i]] (nullable; not the input buffer), the list
+ *   the NEXT call is given, so that permutations compose from epoch to epoch as the reference's in-place shuffle does.
+ *   Step s < n_steps takes shuffled positions [s*b1, (s+1)*b1) of KG 1, then [s*b2, (s+1)*b2) of KG 2, each cut at its
+ *   list's end; the steps follow one another in pos_h / pos_r / pos_t, which hold
+ *   min(n_steps*b1, n1) + min(n_steps*b2, n2) entries. */
+int mke_epoch_positives(const int32_t* list1, const int32_t* list2, int64_t n1, int64_t n2, const int64_t* perm1 /*nullable*/,
+                        const int64_t* perm2 /*nullable*/, int64_t b1, int64_t b2, int64_t n_steps,
+                        int32_t* list1_out /*nullable*/, int32_t* list2_out /*nullable*/,
+                        int32_t* pos_h, int32_t* pos_r, int32_t* pos_t, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * (4) Loss ops over ALREADY GATHERED rows — the losses.py surface itself (forward + gradient w.r.t.

@@ -37,6 +37,7 @@ SYMBOLS = (
     "mke_oc_em_plan_temp_bytes", "mke_oc_em_plan", "mke_oc_pass2", "mke_oc_steps",
     "mke_tuning_init", "mke_triple_score_fwd_bwd_t", "mke_rows_update_multi_t",
     "mke_align_topk_mean_temp_bytes", "mke_align_topk_mean", "mke_align_rank_ex",
+    "mke_tripleset_forget", "mke_tripleset_filter_bytes", "mke_epoch_positives",
 )
 ACT_NONE, ACT_TANH, ACT_SIGMOID = 0, 1, 2
 AE_MAX_LAYERS = 4
@@ -257,6 +258,7 @@ def lib():
         L.mke_oc_block_floats.restype = C.c_int64
         L.mke_oc_em_plan_temp_bytes.restype = C.c_int64
         L.mke_align_topk_mean_temp_bytes.restype = C.c_int64
+        L.mke_tripleset_filter_bytes.restype = C.c_int64
         _lib = L
         # MKE_OPTIONS="name=value,name=value": mke_set_option calls applied at load (performance knobs for experiments)
         for kv in filter(None, os.environ.get("MKE_OPTIONS", "").split(",")):
@@ -637,6 +639,38 @@ def tripleset_build(h, r, t, keys):
                                    C.c_int64(h.numel()), _dev(keys, torch.int64, "keys"), C.c_uint64(keys.numel()),
                                    _stream())
     _check(rc, "mke_tripleset_build")
+
+
+def tripleset_forget(keys):
+    """Drop the library's prefilter of the table at `keys` (a tensor or a raw address); no-op when it has none."""
+    addr = keys if isinstance(keys, int) else keys.data_ptr()
+    _check(lib().mke_tripleset_forget(C.c_void_p(addr)), "mke_tripleset_forget")
+
+
+def tripleset_filter_bytes(keys) -> int:
+    """Size of the prefilter the sampler uses for this table; 0 when it has none (the table is probed directly)."""
+    return int(lib().mke_tripleset_filter_bytes(_dev(keys, torch.int64, "keys"), C.c_uint64(keys.numel())))
+
+
+def epoch_positives(list1, list2, perm1, perm2, b1, b2, n_steps, list1_out, list2_out, pos):
+    """mke_epoch_positives: lists [n, 3] int32, perms int64 or None, pos = (pos_h, pos_r, pos_t) int32."""
+    i32, i64 = torch.int32, torch.int64
+    n1, n2 = list1.shape[0], list2.shape[0]
+    need = min(n_steps * b1, n1) + min(n_steps * b2, n2)
+    for x in pos:
+        if x.numel() < need:
+            raise MultiKEHipError(f"epoch buffers hold {x.numel()} positives, the layout needs {need}")
+    for pm, n in ((perm1, n1), (perm2, n2)):
+        if pm is not None and pm.numel() != n:
+            raise MultiKEHipError("a permutation must be as long as its list")
+    for o, l in ((list1_out, list1), (list2_out, list2)):
+        if o is not None and o.shape != l.shape:
+            raise MultiKEHipError("a shuffled list must have its list's shape")
+    rc = lib().mke_epoch_positives(_dev(list1, i32, "list1"), _dev(list2, i32, "list2"), C.c_int64(n1), C.c_int64(n2),
+                                   _dev(perm1, i64, "perm1"), _dev(perm2, i64, "perm2"), C.c_int64(b1), C.c_int64(b2),
+                                   C.c_int64(n_steps), _dev(list1_out, i32, "list1_out"), _dev(list2_out, i32, "list2_out"),
+                                   _dev(pos[0], i32, "pos_h"), _dev(pos[1], i32, "pos_r"), _dev(pos[2], i32, "pos_t"), _stream())
+    _check(rc, "mke_epoch_positives")
 
 
 def tripleset_query(h, r, t, keys, out):

@@ -10,9 +10,28 @@
 //
 // Shape: one group of 16 (neg_per_pos <= 15: four positives per wavefront), 32 (<= 32: two) or 64 lanes per positive, lane q of
 // the group = slot q of the round (neg_per_pos <= 64).
+//
+// Known-triple prefilter: almost every candidate is NOT a known triple, and the exact answer costs one random 8-byte
+// read into a table that is larger than an XCD's 4 MB L2 (8 MB per KG at 460 K triples).  In front of that probe
+// sits a one-hash Bloom filter of FILTER_BITS_PER_SLOT bits per table slot (bit = top bits of the same mix64 whose low
+// bits pick the slot): a clear bit answers "not known" from L2, a set bit falls through to the exact probe, so the
+// output is the unfiltered kernel's bit for bit.  The library owns the filters, one per (keys, capacity), and
+// mke_tripleset_build is the only writer of both (see the header for what keeps them in step).
+#include <mutex>
+#include <unordered_map>
+
 #include "mke_common.h"
 
 namespace mke {
+
+// 8 bits per slot = 1 bit per byte of table: capacity is in [2n, 4n) slots for n keys, so n/m is 1/16 .. 1/32 and
+// 1 - exp(-n/m) = 3 .. 6 % of the candidates still probe; 1 MB per KG at the C2 shape (2 MB of a 4 MB L2 for both).
+// Capped at 2^25 bits (4 MB) per set: past C2's size the filters no longer fit the L2 anyway, and a few MB that stay in the
+// Infinity Cache in front of a table of hundreds of MB (C5: 128 MB per KG, 13 % of the candidates still probe) serve better
+// than an L2-sized filter that lets half of them through.
+constexpr int FILTER_BITS_PER_SLOT_LOG2 = 3;
+constexpr int FILTER_MAX_BITS_LOG2 = 25;
+constexpr int FILTER_MIN_BITS_LOG2 = 10;
 
 struct SampleParams {
   const int32_t* __restrict__ ph;
@@ -23,6 +42,8 @@ struct SampleParams {
   const int32_t* __restrict__ pos_index;  // nullable: epoch position of positive i (else pos_offset + i)
   int npp, max_try;
   mke_kg_side side[2];
+  const uint32_t* __restrict__ filter[2];  // nullable, per side: bit array of the side's known-triple set
+  int filter_shift[2];                     // bit index = mix64(key) >> filter_shift
   uint32_t seed_lo, seed_hi, sid;
   int32_t* __restrict__ nh;
   int32_t* __restrict__ nr;
@@ -48,14 +69,22 @@ __host__ __device__ __forceinline__ uint32_t draw_next(uint32_t gi, uint32_t rou
   }
 }
 
-__device__ __forceinline__ bool set_contains(const uint64_t* __restrict__ keys, uint64_t cap, uint64_t key) {
-  uint64_t slot = mix64(key) & (cap - 1);
+__device__ __forceinline__ bool set_contains_hashed(const uint64_t* __restrict__ keys, uint64_t cap, uint64_t key, uint64_t hash) {
+  uint64_t slot = hash & (cap - 1);
   for (;;) {
     const uint64_t k = keys[slot];
     if (k == key) return true;
     if (k == MKE_EMPTY_KEY) return false;
     slot = (slot + 1) & (cap - 1);
   }
+}
+__device__ __forceinline__ bool set_contains(const uint64_t* __restrict__ keys, uint64_t cap, uint64_t key) {
+  return set_contains_hashed(keys, cap, key, mix64(key));
+}
+// false: the key is certainly not in the set the filter was built with; true: ask the table
+__device__ __forceinline__ bool filter_maybe(const uint32_t* __restrict__ filter, int shift, uint64_t hash) {
+  const uint64_t bit = hash >> shift;
+  return (filter[bit >> 5] >> (uint32_t)(bit & 31u)) & 1u;
 }
 
 // GS lanes per positive (GS = 32 when neg_per_pos <= 32: two positives per wavefront, else 64).  Everything that is
@@ -87,6 +116,8 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_neg_sample(const SampleParams p) 
   const mke_kg_side& sd = p.side[kg];
   const uint32_t sid = p.sid + (uint32_t)kg;
   const uint64_t* __restrict__ keys = sd.known_keys;
+  const uint32_t* __restrict__ filter = p.filter[kg];
+  const int fshift = p.filter_shift[kg];
   const uint32_t gi = p.pos_index ? (uint32_t)p.pos_index[ii] : (uint32_t)(ii + p.pos_offset);
   const int N = p.npp;
   const uint64_t gmask_all = GS == 64 ? ~0ull : (((1ull << (GS & 63)) - 1ull) << gbase);
@@ -166,7 +197,9 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_neg_sample(const SampleParams p) 
     const int nt = corrupt_head ? t : ent;
     bool keep = active;
     if (active && round < p.max_try - 1 && keys != nullptr) {
-      keep = !set_contains(keys, sd.known_capacity, triple_key((uint32_t)nh, (uint32_t)r, (uint32_t)nt));
+      const uint64_t key = triple_key((uint32_t)nh, (uint32_t)r, (uint32_t)nt);
+      const uint64_t hash = mix64(key);
+      if (filter == nullptr || filter_maybe(filter, fshift, hash)) keep = !set_contains_hashed(keys, sd.known_capacity, key, hash);
     }
     const uint64_t mask = (__ballot(keep) & gmask_all) >> gbase;  // this group's kept slots
     if (keep) {
@@ -180,11 +213,17 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_neg_sample(const SampleParams p) 
 
 __global__ __launch_bounds__(MKE_BLOCK) void k_tripleset_build(const int32_t* __restrict__ h, const int32_t* __restrict__ r,
                                                                const int32_t* __restrict__ t, int64_t n,
-                                                               uint64_t* __restrict__ keys, uint64_t cap) {
+                                                               uint64_t* __restrict__ keys, uint64_t cap,
+                                                               uint32_t* __restrict__ filter, int filter_shift) {
   const int64_t i = (int64_t)blockIdx.x * MKE_BLOCK + threadIdx.x;
   if (i >= n) return;
   const uint64_t key = triple_key((uint32_t)h[i], (uint32_t)r[i], (uint32_t)t[i]);
-  uint64_t slot = mix64(key) & (cap - 1);
+  const uint64_t hash = mix64(key);
+  if (filter) {
+    const uint64_t bit = hash >> filter_shift;
+    atomicOr(&filter[bit >> 5], 1u << (uint32_t)(bit & 31u));
+  }
+  uint64_t slot = hash & (cap - 1);
   for (;;) {
     const unsigned long long prev =
         atomicCAS((unsigned long long*)&keys[slot], (unsigned long long)MKE_EMPTY_KEY, (unsigned long long)key);
@@ -200,6 +239,89 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_tripleset_query(const int32_t* __
   const int64_t i = (int64_t)blockIdx.x * MKE_BLOCK + threadIdx.x;
   if (i >= n) return;
   out[i] = set_contains(keys, cap, triple_key((uint32_t)h[i], (uint32_t)r[i], (uint32_t)t[i])) ? 1 : 0;
+}
+
+// A new filter starts from what its table already holds (a table may have been filled before it had a filter).
+__global__ __launch_bounds__(MKE_BLOCK) void k_filter_from_table(const uint64_t* __restrict__ keys, uint64_t cap,
+                                                                 uint32_t* __restrict__ filter, int filter_shift) {
+  const uint64_t i = (uint64_t)blockIdx.x * MKE_BLOCK + threadIdx.x;
+  if (i >= cap) return;
+  const uint64_t key = keys[i];
+  if (key == MKE_EMPTY_KEY) return;
+  const uint64_t bit = mix64(key) >> filter_shift;
+  atomicOr(&filter[bit >> 5], 1u << (uint32_t)(bit & 31u));
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The filters: device buffers owned by the library, found by the address of the table they belong to.
+// ---------------------------------------------------------------------------------------------------------------
+struct TripleFilter {
+  uint64_t capacity;
+  uint32_t* bits;
+  int shift;      // 64 - log2(number of bits)
+};
+static std::mutex g_filter_mu;
+static std::unordered_map<const void*, TripleFilter> g_filters;
+
+static int filter_bits_log2(uint64_t capacity) {
+  int lg = 0;
+  while ((1ull << lg) < capacity) ++lg;
+  lg += FILTER_BITS_PER_SLOT_LOG2;
+  return lg < FILTER_MIN_BITS_LOG2 ? FILTER_MIN_BITS_LOG2 : (lg > FILTER_MAX_BITS_LOG2 ? FILTER_MAX_BITS_LOG2 : lg);
+}
+
+// The filter of (keys, capacity) for a launch that only reads it; {nullptr, 0} when the set has none.
+static TripleFilter filter_lookup(const uint64_t* keys, uint64_t capacity) {
+  std::lock_guard<std::mutex> lk(g_filter_mu);
+  const auto it = g_filters.find(keys);
+  if (it == g_filters.end() || it->second.capacity != capacity) return TripleFilter{0, nullptr, 0};
+  return it->second;
+}
+
+static void filter_forget(const void* keys) {
+  std::lock_guard<std::mutex> lk(g_filter_mu);
+  const auto it = g_filters.find(keys);
+  if (it == g_filters.end()) return;
+  (void)hipFree(it->second.bits);   // waits for the device: no launch that reads the bits is still running
+  g_filters.erase(it);
+}
+
+// The filter mke_tripleset_build is about to add to; created (zeroed, then filled from the table as it stands, both on
+// `st`) when the table has none.  An entry of another capacity at this address belongs to a set that is gone.
+static int filter_for_build(uint64_t* keys, uint64_t capacity, hipStream_t st, TripleFilter* out) {
+  std::lock_guard<std::mutex> lk(g_filter_mu);
+  auto it = g_filters.find(keys);
+  if (it != g_filters.end() && it->second.capacity != capacity) {
+    (void)hipFree(it->second.bits);
+    g_filters.erase(it);
+    it = g_filters.end();
+  }
+  if (it != g_filters.end()) { *out = it->second; return MKE_OK; }
+  const int lg = filter_bits_log2(capacity);
+  const size_t bytes = (size_t)1 << (lg - 3);
+  // the buffer lives on the table's device, whichever device is current
+  int cur = 0, dev = 0;
+  hipPointerAttribute_t attr;
+  if (hipGetDevice(&cur) != hipSuccess) { set_error("mke_tripleset_build: no device"); return MKE_E_NULL; }
+  dev = cur;
+  if (hipPointerGetAttributes(&attr, keys) == hipSuccess) dev = attr.device; else (void)hipGetLastError();
+  TripleFilter f{capacity, nullptr, 64 - lg};
+  if (dev != cur) (void)hipSetDevice(dev);
+  hipError_t e = hipMalloc((void**)&f.bits, bytes);
+  if (e == hipSuccess) e = hipMemsetAsync(f.bits, 0, bytes, st);
+  if (dev != cur) (void)hipSetDevice(cur);
+  if (e != hipSuccess) {
+    if (f.bits) (void)hipFree(f.bits);
+    set_error("mke_tripleset_build: filter allocation (%zu bytes): %s", bytes, hipGetErrorString(e));
+    return (int)e;
+  }
+  const uint64_t blocks = (capacity + MKE_BLOCK - 1) / MKE_BLOCK;
+  hipLaunchKernelGGL(k_filter_from_table, dim3((unsigned)blocks), dim3(MKE_BLOCK), 0, st, keys, capacity, f.bits, f.shift);
+  const int rc = check_launch("k_filter_from_table");
+  if (rc) { (void)hipFree(f.bits); return rc; }
+  g_filters.emplace(keys, f);
+  *out = f;
+  return MKE_OK;
 }
 
 }  // namespace mke
@@ -222,6 +344,11 @@ int launch_neg_sample(const int32_t* pos_h, const int32_t* pos_r, const int32_t*
   p.npp = neg_per_pos; p.max_try = max_try;
   p.side[0] = sides[0];
   p.side[1] = pos_kg ? sides[1] : sides[0];
+  for (int k = 0; k < 2; ++k) {       // a set without a filter (or with one of another capacity) is probed directly
+    const TripleFilter f = p.side[k].known_keys ? filter_lookup(p.side[k].known_keys, p.side[k].known_capacity) : TripleFilter{0, nullptr, 0};
+    p.filter[k] = f.bits;
+    p.filter_shift[k] = f.shift;
+  }
   p.seed_lo = seed_lo; p.seed_hi = seed_hi; p.sid = stream_id;
   p.nh = neg_h; p.nr = neg_r; p.nt = neg_t;
   // lanes per positive: 16 (four positives per wavefront; fast form only, which needs an idle lane: neg_per_pos <= 15), 32, 64
@@ -326,10 +453,23 @@ extern "C" int mke_tripleset_build(const int32_t* h, const int32_t* r, const int
     set_error("capacity must be a power of two > n");
     return MKE_E_SHAPE;
   }
+  TripleFilter f;
+  const int rc = filter_for_build(keys, capacity, (hipStream_t)stream, &f);
+  if (rc) return rc;
   const int64_t blocks = (n + MKE_BLOCK - 1) / MKE_BLOCK;
   hipLaunchKernelGGL(k_tripleset_build, dim3((unsigned)blocks), dim3(MKE_BLOCK), 0, (hipStream_t)stream, h, r, t, n,
-                     keys, capacity);
+                     keys, capacity, f.bits, f.shift);
   return check_launch("k_tripleset_build");
+}
+
+extern "C" int64_t mke_tripleset_filter_bytes(const uint64_t* keys, uint64_t capacity) {
+  const mke::TripleFilter f = keys ? mke::filter_lookup(keys, capacity) : mke::TripleFilter{0, nullptr, 0};
+  return f.bits ? (int64_t)1 << (64 - f.shift - 3) : 0;
+}
+
+extern "C" int mke_tripleset_forget(const uint64_t* keys) {
+  if (keys) mke::filter_forget(keys);
+  return MKE_OK;
 }
 
 extern "C" int mke_tripleset_query(const int32_t* h, const int32_t* r, const int32_t* t, int64_t n,

@@ -108,7 +108,7 @@ class RelationViewRunner:
         p, b = self.plan, self.bat
         b.side1.fill(p.sides[0])
         b.side2.fill(p.sides[1])
-        # positives are re-materialised (new tensors) by every shuffle
+        # the batcher's current epoch buffers (staging swaps them with the alternate set)
         p.pos_h, p.pos_r, p.pos_t = (_lib.ptr(x, torch.int32, "pos") for x in (b.pos_h, b.pos_r, b.pos_t))
         p.seed_lo, p.seed_hi = b.rng_seed
         p.stream_id = b.rng_stream

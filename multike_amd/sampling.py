@@ -39,10 +39,24 @@ class KnownTripleSet:
         while cap < 2 * n + 2:
             cap *= 2
         self.keys = torch.full((cap,), -1, dtype=torch.int64, device=h.device)
+        # The library keeps the sampler's prefilter of this table, found by the table's address (mke_tripleset_forget in
+        # include/multike_hip.h).  The table is new and empty: whatever an earlier table at this address left goes first;
+        # from here on every key enters through add(), which keeps table and filter in step.
+        self._addr = self.keys.data_ptr() if self.keys.is_cuda else None
+        if self._addr is not None:
+            _lib.tripleset_forget(self._addr)
         self.add(h, r, t)
 
     def add(self, h, r, t):
         _lib.tripleset_build(h.contiguous(), r.contiguous(), t.contiguous(), self.keys)
+
+    def __del__(self):
+        # the table's memory goes back to the allocator: the filter must not outlive it at this address
+        try:
+            if getattr(self, "_addr", None) is not None:
+                _lib.tripleset_forget(self._addr)
+        except Exception:       # interpreter shutdown: the library may be gone already
+            pass
 
     def contains(self, h, r, t) -> torch.Tensor:
         out = torch.empty(h.numel(), dtype=torch.uint8, device=h.device)
@@ -121,8 +135,12 @@ class RelationBatcher:
     triples1/triples2: array-like [n, 3] (h, r, t) of each KG's `local_relation_triples_list`.
     """
 
+    # The next epoch's permutation pair is drawn ahead of time on a side stream (the two randperm sorts depend on nothing the
+    # epoch trains).  Class default; the constructor's `prefetch_perms` overrides it per batcher.
+    PREFETCH_PERMS = True
+
     def __init__(self, triples1, triples2, side1: KGSide, side2: KGSide, batch_size: int, neg_per_pos: int,
-                 device="cuda", seed: int = 0):
+                 device="cuda", seed: int = 0, prefetch_perms: bool | None = None):
         self.device = torch.device(device)
         self.t1 = torch.as_tensor(int_triples(triples1), device=self.device)
         self.t2 = torch.as_tensor(int_triples(triples2), device=self.device)
@@ -136,7 +154,16 @@ class RelationBatcher:
         self.epoch = 0
         self._gen = torch.Generator(device=self.device)
         self._gen.manual_seed(self.seed)
+        self._native = self.device.type == "cuda"
+        self._prefetch = self._native and bool(self.PREFETCH_PERMS if prefetch_perms is None else prefetch_perms)
+        self._perm_stream = self._next_perms = None
         self._layout()
+        if self._native:
+            # persistent buffers (native plans and side streams keep their addresses): the epoch's positives, twice (current and
+            # staged), and each KG's list, twice (the shuffle reads one and writes the other)
+            n_pos = int(self.off[-1])
+            self.pos_h, self.pos_r, self.pos_t = (torch.empty(n_pos, dtype=torch.int32, device=self.device) for _ in range(3))
+            self._spare_lists = (torch.empty_like(self.t1), torch.empty_like(self.t2))
         self._materialise(None, None)
 
     def _layout(self):
@@ -148,7 +175,8 @@ class RelationBatcher:
         self.off = np.zeros(self.steps + 1, dtype=np.int64)
         self.off[1:] = np.cumsum(c1 + c2)
         self.cnt1 = c1
-        # gather map: epoch position -> (kg, index into that KG's (shuffled) list)
+        # gather map: epoch position -> (kg, index into that KG's (shuffled) list).  The torch chain's (CPU devices, and the
+        # chain as tools/boundary_ab.py switches it back on); mke_epoch_positives computes the same places from (b1, b2, n1, n2)
         src = np.empty(int(self.off[-1]), dtype=np.int64)
         for i in range(self.steps):
             o = self.off[i]
@@ -160,41 +188,71 @@ class RelationBatcher:
             kg[self.off[i] + c1[i]:self.off[i + 1]] = 1
         self.pos_kg = torch.as_tensor(kg, device=self.device)  # fixed across epochs: only the contents shuffle
 
-    def _materialise(self, perm1, perm2):
-        if self.device.type == "cuda":
-            # the lists are replaced below; if this epoch runs on another stream than the one they were allocated on
-            # (drivers run the relation group on a side stream), the allocator must not hand the old ones out again
-            # before this stream has read them
-            cur = torch.cuda.current_stream(self.device)
-            for t in (self.t1, self.t2):
-                t.record_stream(cur)
+    def _draw_perms(self):
+        """The generator's next pair: KG 1, then KG 2 (the order every epoch has drawn them in)."""
+        return (torch.randperm(self.n1, generator=self._gen, device=self.device),
+                torch.randperm(self.n2, generator=self._gen, device=self.device))
+
+    def _take_perms(self):
+        """The permutation pair of the next epoch, on the current stream.  With prefetch the pair was drawn when the previous one
+        was taken, on the side stream, and the pair after it is drawn now: the generator hands out the same sequence of pairs
+        as without, one epoch early.  The pair drawn at the last epoch boundary of a run is never used."""
+        if not self._prefetch:
+            return self._draw_perms()
+        cur = torch.cuda.current_stream(self.device)
+        if self._perm_stream is None:
+            self._perm_stream = torch.cuda.Stream(device=self.device)
+            self._next_perms = self._draw_perms()      # the first pair: nothing to overlap with, drawn in line
+        else:
+            cur.wait_stream(self._perm_stream)
+        perms = self._next_perms
+        for p in perms:
+            p.record_stream(cur)                       # allocated on the side stream, read by this stream's gather
+        with torch.cuda.stream(self._perm_stream):
+            self._next_perms = self._draw_perms()
+        return perms
+
+    def _materialise(self, perm1, perm2, staged: bool = False):
+        """New lists t[perm] and their epoch layout: into the current epoch buffers, or (staged) into the alternate ones."""
+        if self._native:
+            if staged and getattr(self, "_alt", None) is None:
+                self._alt = tuple(torch.empty_like(x) for x in (self.pos_h, self.pos_r, self.pos_t))
+            pos = self._alt if staged else (self.pos_h, self.pos_r, self.pos_t)
+            if perm1 is None:                           # the first epoch: the lists as given
+                _lib.epoch_positives(self.t1, self.t2, None, None, self.b1, self.b2, self.steps, None, None, pos)
+                return
+            out = self._spare_lists
+            _lib.epoch_positives(self.t1, self.t2, perm1, perm2, self.b1, self.b2, self.steps, out[0], out[1], pos)
+            if staged:
+                self._staged_lists = out
+            else:
+                self._spare_lists, (self.t1, self.t2) = (self.t1, self.t2), out
+            return
         t1 = self.t1 if perm1 is None else self.t1[perm1]
         t2 = self.t2 if perm2 is None else self.t2[perm2]
         allt = torch.cat([t1, t2], 0)[self._src]  # epoch order, step-contiguous
-        if getattr(self, "pos_h", None) is None:
-            self.pos_h = allt[:, 0].contiguous()
-            self.pos_r = allt[:, 1].contiguous()
-            self.pos_t = allt[:, 2].contiguous()
-        else:  # persistent epoch buffers: addresses stay valid across epochs (native plans, side streams)
-            self.pos_h.copy_(allt[:, 0])
-            self.pos_r.copy_(allt[:, 1])
-            self.pos_t.copy_(allt[:, 2])
-        self.t1, self.t2 = t1, t2
+        cols = tuple(allt[:, k].contiguous() for k in range(3))
+        if staged:
+            if getattr(self, "_alt", None) is None:
+                self._alt = cols
+            else:
+                for dst, src in zip(self._alt, cols):
+                    dst.copy_(src)
+            self._staged_lists = (t1, t2)
+        elif getattr(self, "pos_h", None) is None:
+            self.pos_h, self.pos_r, self.pos_t = cols
+            self.t1, self.t2 = t1, t2
+        else:  # persistent epoch buffers
+            for dst, src in zip((self.pos_h, self.pos_r, self.pos_t), cols):
+                dst.copy_(src)
+            self.t1, self.t2 = t1, t2
 
     # -- next-epoch staging: lets a caller permute (and sample) epoch e+1 while epoch e is still being trained ------
     def stage_next_epoch(self):
         """Draw the next epoch's permutation into the ALTERNATE epoch buffers (the current ones are untouched).
         Returns the staged (pos_h, pos_r, pos_t); `commit_staged()` makes them current."""
-        p1 = torch.randperm(self.n1, generator=self._gen, device=self.device)
-        p2 = torch.randperm(self.n2, generator=self._gen, device=self.device)
-        t1, t2 = self.t1[p1], self.t2[p2]
-        allt = torch.cat([t1, t2], 0)[self._src]
-        if getattr(self, "_alt", None) is None:
-            self._alt = tuple(allt[:, k].contiguous() for k in range(3))
-        else:
-            for k in range(3):
-                self._alt[k].copy_(allt[:, k])
-        self._staged_lists = (t1, t2)
+        p1, p2 = self._take_perms()
+        self._materialise(p1, p2, staged=True)
         return self._alt
 
     def commit_staged(self):
@@ -202,14 +260,15 @@ class RelationBatcher:
         cur = (self.pos_h, self.pos_r, self.pos_t)
         self.pos_h, self.pos_r, self.pos_t = self._alt
         self._alt = cur
+        if self._native:
+            self._spare_lists = (self.t1, self.t2)
         self.t1, self.t2 = self._staged_lists
         self._staged_lists = None
         self.epoch += 1
 
     def shuffle(self):
         """random.shuffle of both positive lists after an epoch (code/MultiKE_model.py:314-315)."""
-        p1 = torch.randperm(self.n1, generator=self._gen, device=self.device)
-        p2 = torch.randperm(self.n2, generator=self._gen, device=self.device)
+        p1, p2 = self._take_perms()
         self._materialise(p1, p2)
         self.epoch += 1
 

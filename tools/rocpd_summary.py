@@ -107,7 +107,44 @@ def pmc_table(db, needle="mke"):
     return "\n".join(out)
 
 
+def boundary_table(db, min_gap_us=200.0):
+    """The epoch boundaries of a bench.py headline run: every place where two consecutive k_triple_score launches are more than
+    `min_gap_us` apart (inside an epoch only the update launch sits between them), with the kernels dispatched in between summed
+    per name.  `idle` = the part of the gap in which no kernel ran (launch overhead, host work, the profiler's own cost)."""
+    c = sqlite3.connect(db)
+    tabs = [r[0] for r in c.execute("select name from sqlite_master where type='table'")]
+    kd = [t for t in tabs if t.startswith("rocpd_kernel_dispatch")][0]
+    ks = [t for t in tabs if t.startswith("rocpd_info_kernel_symbol")][0]
+    rows = list(c.execute(f"select s.kernel_name, d.start, d.end from {kd} d join {ks} s on d.kernel_id = s.id order by d.start"))
+    score = [i for i, r in enumerate(rows) if "k_triple_score" in r[0]]
+    steady = sorted((rows[b][1] - rows[a][1]) / 1e3 for a, b in zip(score, score[1:]) if b == a + 2)
+    out = [f"{len(score)} score launches; steady step (score start to score start, one update between): median "
+           f"{steady[len(steady) // 2]:.2f} us" if steady else f"{len(score)} score launches", "",
+           "| after score # | gap us | kernels in it | kernel time us | idle us | the kernels (launches x summed us) |", "|---|---|---|---|---|---|"]
+    gaps = []
+    for n, (a, b) in enumerate(zip(score, score[1:])):
+        gap = (rows[b][1] - rows[a][2]) / 1e3
+        if gap < min_gap_us:
+            continue
+        by = {}
+        for name, st, en in rows[a + 1:b]:
+            k = name.split("(")[0][:48]
+            v = by.setdefault(k, [0, 0.0])
+            v[0] += 1; v[1] += (en - st) / 1e3
+        busy = sum(v[1] for v in by.values())
+        gaps.append(gap)
+        top = sorted(by.items(), key=lambda kv: -kv[1][1])[:6]
+        out.append(f"| {n + 1} | {gap:.1f} | {b - a - 1} | {busy:.1f} | {gap - busy:.1f} | " + "; ".join(f"`{k}` {v[0]} x {v[1]:.1f}" for k, v in top) + " |")
+    if gaps:
+        g = sorted(gaps)
+        out += ["", f"{len(gaps)} boundaries: gap min {g[0]:.1f} / median {g[len(g) // 2]:.1f} / max {g[-1]:.1f} us"]
+    return "\n".join(out)
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 2 and sys.argv[2] == "--boundaries":    # rocpd_summary.py <db> --boundaries [min gap us]
+        print(boundary_table(sys.argv[1], float(sys.argv[3]) if len(sys.argv) > 3 else 200.0))
+        sys.exit(0)
     if len(sys.argv) > 2 and sys.argv[2] == "--pmc":           # rocpd_summary.py <db> --pmc [kernel-name substring]
         print(pmc_table(sys.argv[1], sys.argv[3] if len(sys.argv) > 3 else "mke"))
         sys.exit(0)
