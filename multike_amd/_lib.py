@@ -865,27 +865,6 @@ def oc_plan(pos_h, pos_t, codes, neg_per_pos: int, part_lo, n_parts: int, n_rank
     _check(rc, "mke_oc_plan")
 
 
-def oc_bases(step: OcStepStruct, send_block):
-    rc = lib().mke_oc_bases(C.byref(step), _dev(send_block, torch.float32, "send_block"), _stream())
-    _check(rc, "mke_oc_bases")
-
-
-def oc_count(step: OcStepStruct):
-    rc = lib().mke_oc_count(C.byref(step), _stream())
-    _check(rc, "mke_oc_count")
-
-
-def oc_score(step: OcStepStruct, v_all, block_floats: int, g_all, loss_partials):
-    rc = lib().mke_oc_score(C.byref(step), _dev(v_all, torch.float32, "v_all"), C.c_int64(block_floats),
-                            _dev(g_all, torch.float32, "g_all"), _dev(loss_partials, torch.float64, "loss_partials"), _stream())
-    _check(rc, "mke_oc_score")
-
-
-def oc_apply(step: OcStepStruct, gv):
-    rc = lib().mke_oc_apply(C.byref(step), _dev(gv, torch.float32, "gv"), _stream())
-    _check(rc, "mke_oc_apply")
-
-
 OC_BASES, OC_COUNT, OC_SCORE, OC_APPLY, OC_UPDATE, OC_PASS2 = 1, 2, 4, 8, 16, 32
 
 

@@ -1,7 +1,7 @@
-"""Entity-row sharded relation-view training, "owner computes" form (RCCL over xGMI on MI355X; SURVEY.md §8e).
+"""Entity-row sharded relation-view training, "owner computes" form (RCCL over xGMI on MI355X; SURVEY.md §8e, DESIGN.md §5.1).
 
 The reference has no multi-device code; this is new design.  One process per GPU.
-  * entity table + its Adagrad slot + gradient scratch are row-sharded by  id % world  (local row = id // world);
+  * entity table + its Adagrad slot are row-sharded by  id % world  (local row = id // world);
   * the relation table is replicated;
   * a global step is `world` x batch_size positives in the reference's epoch order; rank g is HOME of the g-th
     contiguous slice and samples its negatives (Philox stream indexed by the GLOBAL epoch position: the negatives of a
@@ -11,516 +11,47 @@ The reference has no multi-device code; this is new design.  One process per GPU
     (corrupted head: d = c^ + RT_p) — so the NEGATIVES go to the rows.  And the reference's sampler tosses ONE coin per round
     (code/base/batch.py:97-105): a positive's negatives almost always corrupt the same side, so only ONE of the two vectors
     travels for it (both for the few positives whose re-draw rounds fell on the other side); the positive's own term
-    d = HR_p - t^ (or h^ + RT_p) is scored like a negative by the owner of t (of h).  Per global step:
-        (once per epoch, prefetched on a side stream: every rank draws 1 / world of the epoch's negatives, packs them as
-         (entity, side) codes with the group's need flags, one all-gather of the codes)
-        owner of h_p builds HR_p, owner of t_p builds RT_p — the needed ones                                [mke_oc_bases]
-        ALL-GATHER of the blocks (~1 vector per positive)
-        reference counts of the own rows over the whole global step (needs only the codes)                 [mke_oc_count]
-        every rank scores, for ALL world x batch positives, the negatives whose corrupt entity it owns: corrupt-row
-        gradient applied locally (in place when referenced once, else scattered), partial dL/dHR_p, dL/dRT_p written into
-        the slot the vector came from; the positive's own term by the owner of its other entity            [mke_oc_score]
-        REDUCE-SCATTER of the gradient vectors (same layout): the owner of h_p / t_p receives the sum
-        head / tail rows' and relation rows' gradient from it                                              [mke_oc_apply]
-        ALL-REDUCE of the relation gradient;  one update of every touched shard row and relation row  [mke_rows_update_multi]
-    i.e. every row is updated once per step from the sum of all its contributions (dense-Adagrad-equivalent, SURVEY.md
-    §8e "semantics note").  Slots are assigned per epoch from the (replicated) epoch order, so capacity is known exactly
-    before the epoch starts: nothing can overflow mid-epoch.
+    d = HR_p - t^ (or h^ + RT_p) is scored like a negative by the owner of t (of h).
+Once per epoch (`EpochPlan`; prefetched on a side stream): every rank draws 1 / world of the epoch's negatives as (entity, side)
+codes with the group's need flags, one all-gather of the codes, then every travelling vector's slot and — entity-major form — the
+reference lists of this rank's rows (`EmPlan`).  Capacity is known exactly before the epoch starts: nothing overflows mid-epoch.
+Per global step, ENTITY-MAJOR form (the default of the HIP backend):
+    owner of h_p builds HR_p, owner of t_p builds RT_p — the needed ones                                          [BASES]
+    ALL-GATHER of the blocks (~1 vector per positive)
+    every rank scores, for ALL world x batch positives, the negatives (and positives' own terms) whose entity it owns: one
+    coefficient per (positive, owned negative) stored, partial dL/dHR_p, dL/dRT_p written into the vector's slot  [SCORE]
+    REDUCE-SCATTER of the gradient vectors (same layout): the owner of h_p / t_p receives the sum
+    every touched owned row finished in place from its reference list, in list order (no scratch, no atomics: the step is
+    bit-reproducible run to run); this rank's partial relation gradient stored                                    [PASS2]
+    ALL-REDUCE of the relation gradient;  update of the relation table                                            [UPDATE]
+The ATOMICS form (`entity_major=False` / MKE_OC_EM=0; what peer-direct and the tests' NumPy backend use): the bases launch also
+counts the references of the own rows [COUNT], SCORE adds the corrupt rows' gradients to a scratch (in place when a row is referenced
+once), the head / tail / relation rows' gradients follow the reduce-scatter [APPLY], UPDATE updates every touched shard and relation
+row.  Either way a row is updated once per step from the sum of all its contributions (dense-Adagrad-equivalent).
 Bytes per rank and step over the links: (G-1)/G * 2 * ~1 * P stride 4 against (G-1)/G * 2 * P (N + 2) stride 4 of a
 row exchange — 27x less at N = 25 / dim 75, 66x less at N = 64 / dim 256 (DESIGN.md §5 has the latency model).
 
 `chunks` > 1 splits the global step's positives into that many parts whose all-gather / reduce-scatter run on the
-communicator's own stream while the previous / next part is scored (split-batch pipelining; the single update at the end
-sees every part's gradients, so the result is the same function).
+communicator's own stream while the previous / next part is scored (split-batch pipelining; the single second pass / update
+at the end sees every part's gradients, so the result is the same function).
 
-The compute steps go through a backend object: `OcHipBackend` (the product, HIP kernels) — tests inject a CPU backend
-built on the oracle to exercise this logic under `gloo`.
+The compute steps go through a backend (multike_amd/oc_backend.py: `OcHipBackend`, the product; tests inject a CPU backend built
+on the oracle to exercise this logic under `gloo`), the collectives through a communicator (multike_amd/oc_comm.py).  A run of
+steps inside an epoch is ONE native call (`run` -> mke_oc_steps) when both allow it; `step` is the same schedule from Python.
 """
-from __future__ import annotations
-
 import math
-import ctypes as C
+import os
 from dataclasses import dataclass
+from enum import Enum
 
 import numpy as np
 import torch
-import torch.distributed as dist
 
 from . import _lib
-from .sampling import KGSide, KnownTripleSet, RelationBatcher, side_array
+from .oc_backend import APPLY, BASES, COUNT, PASS2, SCORE, UPDATE, OcHipBackend, OcStep     # noqa: F401 — this module is the import surface
+from .oc_comm import OcComm, OcGlooComm, OcHostStagedComm, OcRcclComm, default_comm         # noqa: F401
+from .sampling import KGSide, RelationBatcher
 from .tables import ADAGRAD_INIT_ACC, PLACEMENT_LOG, placed_rows
-
-
-@dataclass
-class OcStep:
-    """One part of a global step as the backends see it (tensors on the trainer's device)."""
-    pos_h: torch.Tensor
-    pos_r: torch.Tensor
-    pos_t: torch.Tensor
-    per: int
-    slot_h: torch.Tensor
-    slot_t: torch.Tensor
-    own_h: torch.Tensor
-    own_t: torch.Tensor
-    tag: int
-    codes: torch.Tensor = None      # the epoch's negative codes of every rank, [world][codes_per_rank]
-    code_off: tuple = ()            # per home rank: offset of its codes of this part inside `codes`
-    native: object = None           # backend-private cache (the ctypes mke_oc_step of the HIP backend)
-    pos_w: torch.Tensor = None      # per-positive weights of the part (weighted cross-KG loops), or None
-
-
-class OcHipBackend:
-    """Product backend: every compute step is a HIP kernel of libmultike_hip.so (mke_oc.hip, mke_update.hip)."""
-
-    device_type = "cuda"
-
-    def make_known(self, h, r, t):
-        return KnownTripleSet(h, r, t)
-
-    def sample_at(self, pos, pos_index, pos_kg, side1, side2, neg_per_pos, seed, stream_id, out):
-        _lib.neg_sample_at(pos, pos_index, pos_kg, side_array(side1, side2), neg_per_pos, 10, seed, stream_id, out)
-
-    def block_elems(self, capacity, stride):
-        return _lib.oc_block_floats(capacity, stride)
-
-    def pack_codes(self, pos_h, neg_h, neg_t, neg_per_pos, codes):
-        _lib.oc_pack_codes(pos_h, neg_h, neg_t, neg_per_pos, codes)
-
-    def plan(self, pos_h, pos_t, codes, neg_per_pos, part_lo, n_parts, n_ranks, rank, slot_h, slot_t, own_h, own_t, counts):
-        """slots, owned lists and per-(part, owner) counts of the whole epoch in ONE launch (mke_oc_plan)."""
-        _lib.oc_plan(pos_h, pos_t, codes, neg_per_pos, part_lo, n_parts, n_ranks, rank, slot_h, slot_t, own_h, own_t, counts)
-
-    def em_plan(self, tr, ph, pr, pt, codes, slot, bufs):
-        """mke_oc_em_plan: the epoch's references to this rank's rows sorted by (step, row, positive, kind), the touched rows of
-        every global step and their CSR offsets (entity-major second pass) — one native call, nothing synchronises."""
-        i32, i64 = torch.int32, torch.int64
-        a = _lib.OcEmPlanArgs()
-        a.pos_h, a.pos_r, a.pos_t = _lib.ptr(ph, i32, "pos"), _lib.ptr(pr, i32, "pos"), _lib.ptr(pt, i32, "pos")
-        a.codes, a.neg_per_pos = _lib.ptr(codes, i32, "codes"), tr.N
-        a.slot_h, a.slot_t = _lib.ptr(slot[0], i32, "slot"), _lib.ptr(slot[1], i32, "slot")
-        a.step_lo, a.n_steps, a.chunks = _lib.ptr(tr._step_lo, i64, "step_lo"), tr.steps, tr.chunks
-        a.n_all, a.max_step = tr._n_all, tr._max_step
-        a.n_ranks, a.rank, a.n_local, a.n_rel = tr.world, tr.rank, max(1, tr.n_local), tr.rel.shape[0]
-        a.keys, a.keys_alt, a.capacity = _lib.ptr(bufs["keys"], i64, "keys"), _lib.ptr(bufs["keys_alt"], i64, "keys"), bufs["capacity"]
-        a.vals_alt, a.wave_scratch = _lib.ptr(bufs["vals_alt"], i32, "vals_alt"), _lib.ptr(bufs["waves"], i32, "waves")
-        a.scratch8 = _lib.ptr(bufs["scratch8"], i64, "scratch8")
-        a.refs, a.rows, a.off = _lib.ptr(bufs["refs"], i32, "refs"), _lib.ptr(bufs["rows"], i32, "rows"), _lib.ptr(bufs["off"], i32, "off")
-        a.flags, a.scan = _lib.ptr(bufs["flags"], i32, "flags"), _lib.ptr(bufs["scan"], i32, "scan")
-        a.step_row0, a.n_refs = _lib.ptr(bufs["row0"], i64, "row0"), _lib.ptr(bufs["n_refs"], i64, "n_refs")
-        a.item_row, a.item_off, a.item_part = (_lib.ptr(bufs[k], i32, k) for k in ("item_row", "item_off", "item_part"))
-        a.long_row, a.long_part0 = _lib.ptr(bufs["long_row"], i32, "long_row"), _lib.ptr(bufs["long_part0"], i32, "long_part0")
-        a.step_item0, a.step_long0, a.step_part0 = (_lib.ptr(bufs["steps3"][k], i64, "steps3") for k in range(3))
-        a.temp, a.temp_bytes = _lib.ptr(bufs["temp"], torch.uint8, "temp"), bufs["temp"].numel()
-        _lib.oc_em_plan(a)
-
-    def em_temp_bytes(self, capacity):
-        return _lib.oc_em_plan_temp_bytes(capacity)
-
-    def _struct(self, tr: "OwnerComputesTrainer", st: OcStep):
-        f32, i32 = torch.float32, torch.int32
-        s = _lib.OcStepStruct()
-        s.ent, s.ent_acc = _lib.ptr(tr.ent, f32, "ent"), _lib.ptr(tr.ent_acc, f32, "acc")
-        s.ent_grad = _lib.ptr(tr.ent_grad, f32, "grad") if tr.ent_grad is not None else None      # entity-major: no entity scratch
-        s.ent_touched = _lib.ptr(tr.ent_touched, i32, "touched") if tr.ent_touched is not None else None
-        s.ref_count = _lib.ptr(tr.ref_count, i32, "ref_count") if tr.ref_count is not None else None
-        s.n_local = max(1, tr.n_local)     # as in the plan (em_plan): pass 2 finds relation row r at n_local + r
-        s.rel, s.rel_grad = _lib.ptr(tr.rel, f32, "rel"), _lib.ptr(tr.rel_grad, f32, "rel_grad")
-        s.rel_grad_copies = 1 if tr.rel_grad.dim() == 2 else tr.rel_grad.shape[0]     # privatised relation gradient (all-reduced whole)
-        s.rel_acc = _lib.ptr(tr.rel_acc, f32, "rel_acc")
-        s.rel_touched, s.n_rel = _lib.ptr(tr.rel_touched, i32, "rel_touched"), tr.rel.shape[0]
-        s.stride, s.dim, s.rank, s.n_ranks = tr.stride, tr.dim, tr.rank, tr.world
-        s.pos_h, s.pos_r, s.pos_t = (_lib.ptr(x, i32, "pos") for x in (st.pos_h, st.pos_r, st.pos_t))
-        s.n_pos, s.per = st.pos_h.numel(), st.per
-        s.slot_h, s.slot_t = _lib.ptr(st.slot_h, i32, "slot"), _lib.ptr(st.slot_t, i32, "slot")
-        s.own_h, s.n_own_h = _lib.ptr(st.own_h, i32, "own"), st.own_h.numel()
-        s.own_t, s.n_own_t = _lib.ptr(st.own_t, i32, "own"), st.own_t.numel()
-        s.neg_per_pos, s.capacity = tr.N, tr.C
-        s.codes = _lib.ptr(st.codes, i32, "codes")
-        for g, o in enumerate(st.code_off):
-            s.code_off[g] = int(o)
-        s.optimizer, s.lr, s.scale, s.tag = tr.OPTIMIZER, tr.lr, tr.scale, st.tag
-        s.pos_w = _lib.ptr(st.pos_w, f32, "pos_w") if st.pos_w is not None else None
-        if tr.hot_slot is not None:           # hub rows of the shard: private gradient copies behind the shard's own rows
-            s.hot.slot, s.hot.n_hot = _lib.ptr(tr.hot_slot, i32, "hot_slot"), tr.n_hot
-            s.hot.copies, s.hot.row0 = tr.HOT_COPIES, tr.ent_grad_rows
-        s.tuning = _lib.tuning_ptr(tr.tuning)
-        s.n_peers = 0
-        if tr.peer_direct and tr.world > 1:   # peer-mapped blocks (chunk 0: peer-direct runs unchunked)
-            gb = 2 * tr.C * tr.stride * 4
-            s.n_peers = tr.world
-            for g in range(tr.world):
-                s.peer_v[g] = tr._peer_send[g].data_ptr()
-                s.peer_g[g] = tr._peer_inbox[g].data_ptr() + tr.rank * gb
-        return s
-
-    def _cached(self, tr, st):
-        """The part's mke_oc_step is built once per epoch (st.native) and only re-tagged per step."""
-        s = st.native
-        if s is None:
-            s = st.native = self._struct(tr, st)
-        s.tag = st.tag
-        return s
-
-    def prepare_epoch(self, tr):
-        """One mke_oc_step per part of the epoch, from raw device addresses (the epoch buffers are persistent: positives,
-        slots, owned lists keep their addresses; only the owned-list offsets change from epoch to epoch) — no tensor
-        slicing and no struct building on the step path."""
-        i32 = torch.int32
-        b = tr.bat
-        if not tr._parts:
-            self._steps = []
-            return
-        oh, ot = _lib.ptr(tr._own[0], i32, "own"), _lib.ptr(tr._own[1], i32, "own")
-        em = tr._em if tr.em else None
-        key = (tr.C, b.pos_h.data_ptr(), tr._slot[0].data_ptr(), tr._slot[1].data_ptr(), oh, ot, tr._codes.data_ptr(), len(tr._parts),
-               tr._peer_send[0].data_ptr() if tr.peer_direct and tr.world > 1 else 0,
-               (em["refs"].data_ptr(), em["item_row"].data_ptr(), em["item_off"].data_ptr(), tr._em_coef.data_ptr(),
-                tr._em_partials.data_ptr()) if em else 0)
-        cache = self.__dict__.setdefault("_tables", {})
-        if key in cache:                                  # the two epoch buffer sets alternate: one table each
-            self._steps = cache[key]
-        else:                                             # first use of this buffer set, or a buffer was re-allocated
-            base = self._struct(tr, tr._build_part_step(0, 0))
-            ph, pr, pt = (_lib.ptr(x, i32, "pos") for x in (b.pos_h, b.pos_r, b.pos_t))
-            sh, stt = _lib.ptr(tr._slot[0], i32, "slot"), _lib.ptr(tr._slot[1], i32, "slot")
-            pw = getattr(b, "pos_w", None)
-            pw = _lib.ptr(pw, torch.float32, "pos_w") if pw is not None else None
-            arr = (_lib.OcStepStruct * len(tr._parts))()     # contiguous: mke_oc_steps walks it (the list below holds views)
-            out = []
-            for k, (_, lo, hi) in enumerate(tr._parts):
-                s = arr[k]
-                C.memmove(C.byref(s), C.byref(base), C.sizeof(s))
-                s.pos_h, s.pos_r, s.pos_t = ph + 4 * lo, pr + 4 * lo, pt + 4 * lo
-                s.slot_h, s.slot_t = sh + 4 * lo, stt + 4 * lo
-                s.pos_w = (pw + 4 * lo) if pw is not None else None
-                s.n_pos = hi - lo
-                s.per = max(1, -(-(hi - lo) // tr.world))
-                for g in range(tr.world):
-                    s.code_off[g] = (lo + g * int(s.per)) * tr.N      # codes are laid out by epoch position
-                if em:      # entity-major: the step's coefficient buffer, this part's first positive in it, the chunks' vector blocks
-                    step = tr._parts[k][0]
-                    s.em_coef, s.em_pos0 = tr._em_coef.data_ptr(), lo - int(b.off[step])
-                    s.em_refs = em["refs"].data_ptr()
-                    s.em_chunks, s.em_block_floats = len(tr._parts_of[step]), tr.block
-                    for c in range(int(s.em_chunks)):
-                        s.em_v[c], s.em_gv[c] = tr._addr[c][1], tr._addr[c][3]
-                out.append(s)
-            if len(cache) > 4:
-                cache.clear()
-            self._steps = cache[key] = out
-            out_arr = self.__dict__.setdefault("_arrays", {})
-            if len(out_arr) > 4:
-                out_arr.clear()
-            out_arr[key] = arr
-            self._ring = tr.loss_ring.data_ptr()
-            self._ring_stride = tr.loss_ring.shape[1] * 8
-        self._parts_arr = self._arrays[key]
-        cnth, cntt = (x.tolist() for x in tr._own_cnt)
-        for k, (s, (_, lo, _hi)) in enumerate(zip(self._steps, tr._parts)):     # a part's owned list starts at the part's own offset
-            s.own_h, s.n_own_h = oh + 4 * lo, cnth[k]
-            s.own_t, s.n_own_t = ot + 4 * lo, cntt[k]
-        if em:              # the work items / long rows of each global step: positions change from epoch to epoch
-            i0, l0, p0 = (em[k].tolist() for k in ("item0_host", "long0_host", "part0_host"))
-            rp, op, pp = em["item_row"].data_ptr(), em["item_off"].data_ptr(), em["item_part"].data_ptr()
-            lr, lp = em["long_row"].data_ptr(), em["long_part0"].data_ptr()
-            for s, (step, _, _) in zip(self._steps, tr._parts):
-                s.em_rows, s.em_off, s.em_n_rows = rp + 4 * i0[step], op + 4 * i0[step], i0[step + 1] - i0[step]
-                s.em_part = pp + 4 * i0[step]
-                s.em_long_rows, s.em_long_part0, s.em_n_long = lr + 4 * l0[step], lp + 4 * l0[step], l0[step + 1] - l0[step]
-                s.em_part0, s.em_partials = p0[step], tr._em_partials.data_ptr()
-        # the whole epoch's schedule for mke_oc_steps (one native call per run of steps)
-        lp = _lib.OcLoopStruct()
-        lp.parts, lp.n_steps, lp.chunks = C.addressof(self._parts_arr), tr.steps, tr.chunks
-        first = (C.c_int32 * (tr.steps + 1))()
-        k = 0
-        for st in range(tr.steps):
-            first[st] = k
-            k += len(tr._parts_of.get(st, ()))
-        first[tr.steps] = k
-        self._step_part0 = first
-        lp.step_part0 = C.addressof(first)
-        for c in range(tr.chunks):
-            lp.send[c], lp.v_all[c], lp.g_all[c], lp.gv[c] = tr._addr[c]
-        lp.block_floats = tr.block
-        lp.loss_ring, lp.loss_stride = self._ring, tr.loss_ring.shape[1]
-        self._loop = lp
-
-    def run_steps(self, tr, s0, s1, tag_base, comm_struct, comm_stream, overlap_rs=False):
-        """Global steps [s0, s1) of the current epoch in ONE native call (mke_oc_steps): kernels, collectives and — with several
-        parts per step — the two-stream pipeline are enqueued from C++."""
-        lp = self._loop
-        lp.tag_base = tag_base
-        lp.comm = C.addressof(comm_struct) if comm_struct is not None else None
-        lp.comm_stream = comm_stream
-        lp.overlap_rs = int(bool(overlap_rs))
-        _lib.oc_steps(lp, s0, s1)
-
-    def bases(self, tr, st, send):
-        _lib.oc_bases(self._cached(tr, st), send)
-
-    def count(self, tr, st):
-        _lib.oc_count(self._cached(tr, st))
-
-    def score(self, tr, st, v_all, g_all, loss_partials):
-        _lib.oc_score(self._cached(tr, st), v_all, tr.block, g_all, loss_partials)
-
-    def apply(self, tr, st, gv):
-        _lib.oc_apply(self._cached(tr, st), gv)
-
-    def update(self, tr, tag):
-        # relation table: EVERY row (touched = None) — after the all-reduce a row may carry a gradient no local triple touched
-        hot = None
-        if tr.hot_slot is not None:
-            hot = _lib.HotRowsStruct(_lib.ptr(tr.hot_slot, torch.int32, "hot_slot"), tr.n_hot, tr.HOT_COPIES, tr.ent_grad_rows)
-        _lib.rows_update_multi([(tr.rel, tr.rel_acc, tr.rel_grad, None, True),
-                                (tr.ent, tr.ent_acc, tr.ent_grad, tr.ent_touched, True, tr.ref_count, hot)],
-                               tag, tr.stride, tr.dim, tr.OPTIMIZER, tr.lr)
-
-    def run(self, tr, k, tag, phases, c, loss_slot):
-        """The phases of `phases` (OC_* bit mask) of part k (chunk buffers c) in ONE native call; buffers by raw address
-        (validated when they were allocated)."""
-        a = tr._addr[c]
-        s = self._steps[k]
-        s.tag = tag
-        _lib.oc_run(s, phases, a[0], a[1], tr.block, a[2], a[3], self._ring + loss_slot * self._ring_stride)
-
-
-BASES, COUNT, SCORE, APPLY, UPDATE, PASS2 = _lib.OC_BASES, _lib.OC_COUNT, _lib.OC_SCORE, _lib.OC_APPLY, _lib.OC_UPDATE, _lib.OC_PASS2
-
-
-class OcComm:
-    """The three collectives of the step on torch.distributed (RCCL over xGMI on MI355X; gloo in the CPU tests).
-    `async_op` returns a work handle whose wait() orders the CURRENT stream after the collective."""
-
-    def __init__(self, group=None):
-        self.group = group
-
-    def all_gather(self, out, mine, async_op=False):
-        return dist.all_gather_into_tensor(out, mine, group=self.group, async_op=async_op)
-
-    def reduce_scatter(self, out, inp, async_op=False):
-        return dist.reduce_scatter_tensor(out, inp, group=self.group, async_op=async_op)
-
-    def all_reduce(self, t, op=None):
-        dist.all_reduce(t, group=self.group) if op is None else dist.all_reduce(t, op=op, group=self.group)
-
-    def all_gather_list(self, parts, mine):
-        dist.all_gather(parts, mine, group=self.group)
-
-    def barrier(self, token):
-        """Stream-ordered cross-rank barrier (peer-direct mode): a one-element all-reduce — every rank's stream passes it only
-        after every rank's stream has reached it; the host is not blocked."""
-        dist.all_reduce(token, group=self.group)
-
-    def all_gather_object(self, obj):
-        out = [None] * dist.get_world_size(self.group)
-        dist.all_gather_object(out, obj, group=self.group)
-        return out
-
-    def for_plan(self):
-        """A communicator of its own for the once-per-epoch all-gather of the negative codes: that collective is issued from
-        the plan's side stream while the step collectives run on the main stream — on one communicator the steps would queue
-        behind it (a process group's collectives execute in issue order)."""
-        if not dist.is_initialized() or dist.get_world_size(self.group) == 1:
-            return self
-        return type(self)(dist.new_group(ranks=list(range(dist.get_world_size(self.group)))) if self.group is None else
-                          dist.new_group(ranks=dist.get_process_group_ranks(self.group)))
-
-
-class _EventWork:
-    """Handle of an asynchronous collective: wait() orders the CURRENT stream after it (no host wait)."""
-
-    def __init__(self, ev):
-        self.ev = ev
-
-    def wait(self):
-        torch.cuda.current_stream().wait_event(self.ev)
-
-
-class OcRcclComm(OcComm):
-    """The three collectives through RCCL directly (multike_amd/rccl.py), enqueued ON THE CALLER'S STREAM: stream order is the
-    dependency, no event and no second stream per collective (torch.distributed's two stream hops per collective cost ~26 us
-    of device time and ~30 us of host time each on this part: EXPERIMENTS R5.3).  async_op=True (the chunk-pipelined schedule)
-    goes to this communicator's own stream with two pooled events.  The default of the HIP trainers on an "nccl" process
-    group; MKE_OC_COMM=torch selects OcComm."""
-
-    def __init__(self, group=None):
-        super().__init__(group)
-        from .rccl import Communicator
-        self.c = Communicator(group)
-        self.c.self_check()                 # all three collectives give the right sums, or raise before any training step
-        self._side, self._events, self._k = None, None, 0
-
-    def _async(self, fn):
-        if self._side is None:
-            self._side = torch.cuda.Stream()
-            self._events = [torch.cuda.Event() for _ in range(64)]
-        cur = torch.cuda.current_stream()
-        e_in, e_out = self._events[self._k % 64], self._events[(self._k + 1) % 64]
-        self._k += 2
-        e_in.record(cur)
-        self._side.wait_event(e_in)
-        fn(self._side)
-        e_out.record(self._side)
-        return _EventWork(e_out)
-
-    def all_gather(self, out, mine, async_op=False):
-        o, m = out.view(-1), mine.reshape(-1)
-        if async_op:
-            return self._async(lambda st: self.c.all_gather(o, m, st))
-        self.c.all_gather(o, m)
-
-    def reduce_scatter(self, out, inp, async_op=False):
-        o, i = out.view(-1), inp.view(-1)
-        if async_op:
-            return self._async(lambda st: self.c.reduce_scatter(o, i, st))
-        self.c.reduce_scatter(o, i)
-
-    def all_reduce(self, t, op=None):
-        if op is not None:
-            return super().all_reduce(t, op)
-        self.c.all_reduce(t.view(-1))
-
-    def barrier(self, token):
-        self.c.all_reduce(token.view(-1))
-
-    def native(self, tr=None):
-        """mke_oc_comm over this communicator: RCCL's own entry points, called from the native step loop (mke_oc_steps)."""
-        if getattr(self, "_native", None) is None:
-            from . import rccl
-            L = rccl.lib()
-            cs = _lib.OcCommStruct()
-            cs.kind, cs.ctx = _lib.OC_COMM_NCCL, self.c._comm.value
-            cs.all_gather = C.cast(L.ncclAllGather, C.c_void_p).value
-            cs.reduce_scatter = C.cast(L.ncclReduceScatter, C.c_void_p).value
-            cs.all_reduce = C.cast(L.ncclAllReduce, C.c_void_p).value
-            cs.world, cs.rank = self.c.world, self.c.rank
-            self._native = cs
-        return self._native
-
-    def for_plan(self):
-        """A second RCCL communicator (concurrent with the step collectives), one per step communicator."""
-        if getattr(self, "_plan", None) is None:
-            self._plan = OcRcclComm(self.group)
-        return self._plan
-
-
-_DEFAULT_RCCL = None        # the process's step communicator over the world: every trainer of a model shares it
-
-
-def default_comm(device, world, force=False):
-    """The communicator a HIP trainer uses when none is given."""
-    import os
-    global _DEFAULT_RCCL
-    if device.type == "cuda" and dist.is_initialized() and dist.get_backend() == "nccl" and (world > 1 or force) \
-            and os.environ.get("MKE_OC_COMM", "rccl") != "torch":
-        if _DEFAULT_RCCL is None or (_DEFAULT_RCCL is not False and _DEFAULT_RCCL.c.world != dist.get_world_size()):
-            # every rank tries; the ranks then agree (one torch.distributed all-reduce) on whether ALL of them succeeded — a
-            # communicator that came up on some ranks only must not be used by any
-            try:
-                cand, err = OcRcclComm(), None
-            except Exception as e:      # noqa: BLE001 — reported below, the torch.distributed communicator takes over
-                cand, err = None, e
-            ok = torch.tensor([1 if cand is not None else 0], dtype=torch.int32, device=device)
-            dist.all_reduce(ok, op=dist.ReduceOp.MIN)
-            if int(ok) == 1:
-                _DEFAULT_RCCL = cand
-            else:
-                import warnings
-                warnings.warn(f"multike_amd: RCCL through ctypes did not come up on every rank ({err!r} on this one): using torch.distributed for the collectives")
-                _DEFAULT_RCCL = False
-        if _DEFAULT_RCCL is not False:
-            return _DEFAULT_RCCL
-    return OcComm() if (device.type == "cuda" or not dist.is_initialized()) else OcGlooComm()
-
-
-class OcGlooComm(OcComm):
-    """gloo has no reduce-scatter: all-reduce the whole buffer and keep this rank's block (CPU tests only)."""
-
-    def all_gather(self, out, mine, async_op=False):
-        w = dist.get_world_size(self.group)
-        dist.all_gather(list(out.view(w, -1).unbind(0)), mine.reshape(-1), group=self.group)
-
-    def reduce_scatter(self, out, inp, async_op=False):
-        w, r = dist.get_world_size(self.group), dist.get_rank(self.group)
-        tmp = inp.clone()
-        dist.all_reduce(tmp, group=self.group)
-        out.copy_(tmp.view(w, -1)[r].view_as(out))
-
-
-class OcHostStagedComm(OcGlooComm):
-    """Test vehicle: the same collectives on DEVICE tensors through gloo, staged over the host.  Lets two ranks that SHARE
-    one GPU run the device kernels with world_size 2 (RCCL refuses two ranks on one device)."""
-
-    def all_gather(self, out, mine, async_op=False):
-        o = torch.empty(out.shape, dtype=out.dtype)
-        super().all_gather(o, mine.cpu())
-        out.copy_(o)
-
-    def reduce_scatter(self, out, inp, async_op=False):
-        o = torch.empty(out.shape, dtype=out.dtype)
-        super().reduce_scatter(o, inp.cpu())
-        out.copy_(o)
-
-    def all_reduce(self, t, op=None):
-        c = t.cpu()
-        super().all_reduce(c, op)
-        t.copy_(c)
-
-    def all_gather_list(self, parts, mine):
-        cp = [torch.empty(p.shape, dtype=p.dtype) for p in parts]
-        dist.all_gather(cp, mine.cpu(), group=self.group)
-        for p, c in zip(parts, cp):
-            p.copy_(c)
-
-    def barrier(self, token):
-        torch.cuda.synchronize()           # gloo orders hosts, not streams
-        dist.barrier(group=self.group)
-
-    def native(self, tr):
-        """mke_oc_comm of kind CALLBACK: the native step loop calls back into these staged collectives (the buffers are found by
-        their device address among the trainer's exchange buffers; the callback works on the stream the loop hands it)."""
-        def find(addr, count):
-            for t in tr._exchange_tensors():
-                if t.data_ptr() == addr:
-                    return t.view(-1)[:count]
-            raise _lib.MultiKEHipError("native callback: unknown exchange buffer")
-
-        def on(stream):
-            # the stream the loop enqueues on, as a torch stream: handle 0 is torch's default stream (torch.cuda.ExternalStream(0)
-            # is NOT — it makes a stream of its own, and the staged copies then raced the kernels: caught at world 8)
-            return torch.cuda.ExternalStream(stream) if stream else torch.cuda.default_stream()
-
-        def move(fn, scale_in, scale_out):
-            def cb(ctx, send, recv, count, stream):
-                try:
-                    with torch.cuda.stream(on(stream)):
-                        fn(find(recv, count * scale_out), find(send, count * scale_in))
-                    return 0
-                except Exception:      # noqa: BLE001 — an exception must not unwind through the C frame
-                    import traceback
-                    traceback.print_exc()
-                    return 1
-            return _lib.OC_CB_MOVE(cb)
-
-        def reduce(ctx, buf, count, stream):
-            try:
-                with torch.cuda.stream(on(stream)):
-                    self.all_reduce(find(buf, count))
-                return 0
-            except Exception:          # noqa: BLE001
-                import traceback
-                traceback.print_exc()
-                return 1
-
-        G = dist.get_world_size(self.group)
-        keep = (move(self.all_gather, 1, G), move(self.reduce_scatter, G, 1), _lib.OC_CB_REDUCE(reduce))
-        cs = _lib.OcCommStruct()
-        cs.kind = _lib.OC_COMM_CALLBACK
-        cs.all_gather, cs.reduce_scatter, cs.all_reduce = (C.cast(f, C.c_void_p).value for f in keep)
-        cs.world, cs.rank = G, dist.get_rank(self.group)
-        cs._keep = keep                # the thunks live as long as the struct
-        return cs
 
 
 class TripleListBatcher:
@@ -608,6 +139,63 @@ def hub_rows_of_shard(triples, n_ent: int, global_batch: int, rank: int, world: 
     return np.sort(hot // world)
 
 
+
+class PlanStage(Enum):
+    SAMPLED = 1         # this rank's share of the codes is drawn; the all-gather has not been issued
+    GATHERED = 2        # every rank's codes are (being) gathered; slots and lists not yet computed
+    DONE = 3            # everything enqueued: `ready` marks the end
+
+
+@dataclass(slots=True)           # an undeclared attribute cannot be added
+class EmPlan:
+    """Entity-major reference lists of one epoch (mke_oc_em_plan's buffers; all allocated by the trainer's `_persist`).  Sort
+    scratch is shared by the two buffer sets, outputs are per set.  The host readbacks are set by `_finish_plan`."""
+    capacity: int                   # references the lists have room for
+    keys: torch.Tensor              # -- scratch
+    keys_alt: torch.Tensor
+    flags: torch.Tensor
+    scan: torch.Tensor
+    vals_alt: torch.Tensor
+    scratch8: torch.Tensor
+    waves: torch.Tensor
+    temp: torch.Tensor
+    refs: torch.Tensor              # -- outputs: (locator, coefficient index) per reference, in list order
+    rows: torch.Tensor              # touched rows of every step, and their CSR offsets into `refs`
+    off: torch.Tensor
+    step_row0: torch.Tensor         # [steps + 1] first touched row of every step
+    item_row: torch.Tensor          # work items of the second pass (rows, or 32-reference segments of long rows)
+    item_off: torch.Tensor
+    item_part: torch.Tensor
+    long_row: torch.Tensor          # long rows and their first partial slot
+    long_part0: torch.Tensor
+    steps3: torch.Tensor            # [3][steps + 1] first work item / long row / partial slot of every step
+    n_refs_dev: torch.Tensor        # [1] references this rank owns (may exceed `capacity`: the plan is then redone)
+    host: torch.Tensor = None       # pinned copy of step_row0 | steps3 | n_refs_dev (asynchronous; read by `_finish_plan`)
+    row0: torch.Tensor = None       # -- host readbacks, [steps + 1] each
+    item0: torch.Tensor = None
+    long0: torch.Tensor = None
+    part0: torch.Tensor = None
+    n_refs: int = None
+
+
+@dataclass(slots=True)           # an undeclared attribute cannot be added
+class EpochPlan:
+    """The plan of one epoch order in buffer set `bs`, filled stage by stage (`_plan_sample` -> `_plan_gather` -> `_plan_rest`)."""
+    bs: int
+    pos: tuple                      # (h, r, t) of the epoch, in epoch order
+    codes: torch.Tensor             # the epoch's negative codes in position order
+    stage: PlanStage = PlanStage.SAMPLED
+    codes_all: torch.Tensor = None  # G > 1: the all-gather's output (a view of `codes`) ...
+    mine: torch.Tensor = None       # ... and this rank's share, its input
+    slot: list = None               # [2] slot of every positive's HR / RT vector in its owner's block (-1: stays home)
+    own: list = None                # [2] this rank's owned positives per part, in slot order
+    cnt_host: torch.Tensor = None   # pinned [2][parts][G] vectors per (part, owner)
+    em: EmPlan = None
+    sampled: object = None          # events (HIP device only): share drawn / codes gathered / all of it enqueued
+    gathered: object = None
+    ready: object = None
+
+
 class OwnerComputesTrainer:
     # hub rows of the shard (mke_oc_step.hot): entities that are head or tail of >= HOT_MIN positives of an average GLOBAL step get
     # HOT_COPIES private copies of their gradient row for mke_oc_apply and the positives' own terms (the fused runner's rule,
@@ -629,7 +217,6 @@ class OwnerComputesTrainer:
         share their variables and have one optimizer each (code/MultiKE_model.py:17-31): shared tables and (zero-invariant)
         gradient / flag scratch, own Adagrad accumulators, own tag range; `ent0` / `rel0` are then unused."""
         self.scale = float(scale)
-        self._em_request = entity_major
         self.tuning = _lib.tuning(**tuning) if tuning else None     # this trainer's knobs (mke_oc_step.tuning), e.g. {"oc_score_quarter": 1}
         # ent_table / rel_table (multike_amd.tables.EmbeddingTable: this rank's shard of `n_ent` global rows, and the
         # replicated relation table): train THOSE — the trainer then shares them with whatever else holds them (other
@@ -644,14 +231,13 @@ class OwnerComputesTrainer:
             rel0 = np.empty((tables_of.rel.shape[0], tables_of.dim), dtype=np.float32)
         self.backend = backend or OcHipBackend()
         self.device = torch.device(device or ("cuda" if self.backend.device_type == "cuda" else "cpu"))
-        import os as _os
-        self.force_collectives = _os.environ.get("MKE_OC_FORCE_COLLECTIVES", "0") == "1"
+        # MKE_OC_FORCE_COLLECTIVES=1: a one-rank group takes the G > 1 step path — its three collectives issued for real on the
+        # one-rank communicator — so that the host cost of that path can be measured on one GPU (bench.py --force-sharded
+        # reports `host_us_per_step`)
+        self.force_collectives = os.environ.get("MKE_OC_FORCE_COLLECTIVES", "0") == "1"
         if comm is None:
             comm = default_comm(self.device, world, self.force_collectives)
-        self.comm = comm
-        # the epoch plan's collective (the ranks' shares of the epoch's negative codes) on a communicator of its own
-        # (round 5 put the epoch plan's collective on a communicator of its own, issued from the side stream: nothing ordered
-        # it against the step collectives across ranks — it now goes through `comm` at a fixed point of the step sequence)
+        self.comm = comm            # the steps' three collectives AND the epoch plan's one (`_plan_gather`)
         self.rank, self.world, self.lr = rank, world, float(lr)
         self.dim = ent0.shape[1]
         self.stride = _lib.stride_for(self.dim)
@@ -663,23 +249,15 @@ class OwnerComputesTrainer:
             raise _lib.MultiKEHipError("the sharded relation view packs entity ids into 29 bits")
         self.batch_size = int(batch_size)
         self.chunks = max(1, int(chunks))
-        # peer-direct (opt-in): no all-gather / reduce-scatter — every rank maps the other ranks' send blocks and gradient
-        # inboxes (IPC handles exchanged once) and mke_oc_score reads / writes them straight over xGMI; two stream-ordered
-        # barriers per step.  Correct by construction and tested with two ranks on one GPU; not measured on several.
         self.prefetch = bool(prefetch)
-        # MKE_OC_FORCE_COLLECTIVES=1: a one-rank group takes the G > 1 step path — its three collectives issued for real on the
-        # one-rank communicator — so that the host cost of that path (Python + torch.distributed per step) can be measured on
-        # one GPU (bench.py --force-sharded reports `host_us_per_step`)
-        self.peer_direct = bool(peer_direct) and world > 1
+        self.peer_direct = bool(peer_direct) and world > 1       # opt-in (`_step_peer_direct`); runs unchunked
         if self.peer_direct:
             self.chunks = 1
-        # ENTITY-MAJOR second pass (round 6): the score launch stores one coefficient per (positive, owned negative),
-        # mke_oc_pass2 finishes every touched owned row in place from the row's reference list of the epoch plan — no gradient
-        # scratch, flags, reference counts, hub-row copies or atomics on entity rows, results bit-reproducible run to run.  The
-        # default of the HIP backend (MKE_OC_EM=0 / entity_major=False: the atomics form of rounds 2-5); not with peer-direct.
-        em = self._em_request
+        # entity-major form (module docstring): the default of a backend that has the plan for it, float32 tables;
+        # MKE_OC_EM=0 / entity_major=False select the atomics form, peer-direct implies it
+        em = entity_major
         if em is None:
-            em = _os.environ.get("MKE_OC_EM", "1") != "0"
+            em = os.environ.get("MKE_OC_EM", "1") != "0"
         self.em = bool(em) and hasattr(self.backend, "em_plan") and not self.peer_direct and self.chunks <= _lib.OC_EM_MAX_CHUNKS \
             and dtype == torch.float32
         if self.em:
@@ -752,6 +330,7 @@ class OwnerComputesTrainer:
                                        int(global_batch) if global_batch else batch_size * world, neg_per_pos,
                                        device=dev, seed=seed)
         self.steps = self.bat.steps
+        self.ent_grad_full = None     # the gradient scratch with the hub rows' copies behind it, when this trainer allocated one
         self._declare_hot_rows(ent_table, tables_of)
         # trainers sharing the touched-flag arrays keep apart in tag space (a flag is `touched[row] == tag`)
         self._n_sharing = 0
@@ -762,13 +341,25 @@ class OwnerComputesTrainer:
             self.tag = int(tag_base)
         self.loss_ring = torch.zeros(max(1, self.steps) * self.chunks, _lib.LOSS_PARTIALS, dtype=torch.float64, device=dev)
         self.score_events = None  # set to a list to collect (start, end, triples) HIP events of the score kernel
-        self.C = 0
-        self._em_capacity = {}
         self._dtype = dtype
-        self._planned_epoch = -1
-        self._stepped = -1
-        self._parts = None
-        self._persistent = {}
+        self._persistent = {}         # epoch buffers by (name, buffer set): `_persist`
+        self._layout()
+        # -- the current epoch's plan (`_finish_plan`) --
+        self.C, self.block = 0, 0     # capacity of an exchange block in vectors per owner / its size in elements
+        self._send = self._v_all = self._g_all = self._gv = self._addr = None     # exchange buffers per chunk, and their addresses
+        self._inbox = self._peer_send = self._peer_inbox = self._bar = None       # peer-direct (`_map_peers`)
+        self._codes = self._slot = self._own = self._own_cnt = None
+        self.vectors_planned = 0
+        self._plan_bs = 0             # which of the two epoch buffer sets the current plan lives in
+        self._st_cache = {}           # OcStep per part, for backends that take tensors (`_part_step`)
+        self._em = None               # EmPlan of the current epoch (entity-major form)
+        self._em_capacity = {}        # buffer set -> capacity of its reference lists
+        self._em_partials = self._em_coef = None
+        # -- the next epoch's plan and the streams --
+        self._next_plan = None        # EpochPlan being prefetched
+        self._side = None             # the plans' side stream
+        self._comm_stream = None      # the native loop's communication stream
+        self._comm_native, self._comm_native_key = None, None     # mke_oc_comm of `comm`, per exchange-buffer generation
         self._plan_epoch()
 
     def _declare_hot_rows(self, ent_table, tables_of):
@@ -789,7 +380,7 @@ class OwnerComputesTrainer:
             return
         b, G = self.bat, self.world
         n_all = int(b.off[-1]) if self.steps else 0
-        if self.device.type == "cuda" and isinstance(self.backend, OcHipBackend) and n_all and self._dtype_is_f32():
+        if self.device.type == "cuda" and isinstance(self.backend, OcHipBackend) and n_all and self.ent.dtype == torch.float32:
             ids = torch.cat([b.pos_h[:n_all], b.pos_t[:n_all]]).long()
             deg = torch.bincount(ids, minlength=self.n_ent).float() / max(1, self.steps)      # references per global step
             hot = torch.nonzero(deg >= self.HOT_MIN).reshape(-1)
@@ -803,9 +394,6 @@ class OwnerComputesTrainer:
         rows = self.ent_grad_rows + self.HOT_COPIES * self.n_hot
         full = self._mk_rows(0.0, [self.ent, self.ent_acc]) if rows == self.ent.shape[0] else torch.zeros(rows, self.stride, dtype=self.ent.dtype, device=self.device)
         self.ent_grad_full, self.ent_grad = full, full[:self.ent.shape[0]]
-
-    def _dtype_is_f32(self):
-        return self.ent.dtype == torch.float32
 
     # ------------------------------------------------------------------------------------------------
     def parts_of_step(self, s: int):
@@ -825,7 +413,7 @@ class OwnerComputesTrainer:
 
     def _layout(self):
         """What depends only on the sizes of the epoch (fixed across epochs: a shuffle permutes contents, not the step /
-        part / slice boundaries): parts, every rank's slice of every part, this rank's epoch positions, part ids."""
+        part / slice boundaries): parts, every rank's slice of every part, this rank's epoch positions, part ids.  Once, at construction."""
         b, G, dev = self.bat, self.world, self.device
         parts = [(s, lo, hi) for s in range(self.steps) for (lo, hi) in self.parts_of_step(s)]
         self._parts = parts
@@ -856,35 +444,29 @@ class OwnerComputesTrainer:
     def _plan_gather(self, plan):
         """The ONE collective of an epoch plan: every rank's 1 / G of the epoch's negative codes, all-gathered on the step
         communicator, on the stream the steps run on, at a fixed point of the step sequence (`_gather_at`) — so the ranks issue
-        every collective of the job in one order (round 5 issued it from the side stream on a communicator of its own:
-        concurrent collectives on two communicators, with nothing ordering them across ranks)."""
-        if "mine" in plan and (self.world > 1 or self.force_collectives):
-            if "sampled" in plan:
-                torch.cuda.current_stream().wait_event(plan["sampled"])
-            self.comm.all_gather(plan["codes_all"], plan["mine"])
+        every collective of the job in one order."""
+        if plan.mine is not None and (self.world > 1 or self.force_collectives):
+            if plan.sampled is not None:
+                torch.cuda.current_stream().wait_event(plan.sampled)
+            self.comm.all_gather(plan.codes_all, plan.mine)
             if self.device.type == "cuda":
-                plan["gathered"] = torch.cuda.Event()
-                plan["gathered"].record()
-        plan["stage"] = "gathered"
+                plan.gathered = torch.cuda.Event()
+                plan.gathered.record()
+        plan.stage = PlanStage.GATHERED
 
     def _plan_sample(self, pos, rng_stream, bs):
-        """Device work only (no host synchronisation), into buffer set `bs`: the negatives of EVERY positive of the epoch
-        (one sampler launch — every rank draws all of them itself: the Philox stream is a function of the epoch position,
-        so the ranks agree without exchanging a byte) packed as codes; the slot of every positive's HR / RT vector in its
-        owner's block; the owned positives per part in slot order; per (part, owner) counts, copied to pinned host memory
-        asynchronously."""
+        """First stage of a plan, into buffer set `bs` (device work only, no host synchronisation): this rank draws the negatives
+        of ITS contiguous 1 / G of the epoch positions (the Philox stream is a function of the epoch position, so who draws a
+        positive's negatives does not matter) and packs them as codes; `_plan_gather` then gives every rank the whole epoch's
+        codes in position order.  (Rounds 2-4: every rank drew all of them — 63 us per step of rank compute at the C5 shape
+        with 8 ranks.)"""
         b, G, dev, N = self.bat, self.world, self.device, self.N
         i32 = dict(dtype=torch.int32, device=dev)
         ph, pr, pt = pos
-        n_all, parts, part_id = self._n_all, self._parts, self._part_id
-        plan = {"bs": bs}
-        # Every rank draws the negatives of ITS contiguous 1 / G of the epoch positions (the Philox stream is a function of
-        # the epoch position, so who draws a positive's negatives does not matter), packs them as codes, and ONE all-gather
-        # per epoch (`_plan_gather`: on the step communicator, at a fixed point of the step sequence) gives every rank the whole
-        # epoch's codes in position order.  (Rounds 2-4: every rank drew all of them — 63 us per step of rank compute at the
-        # C5 shape with 8 ranks.)
+        n_all = self._n_all
         n_per = -(-n_all // G) if n_all else 0            # positions per rank (the last rank's share may be shorter)
         codes = self._persist(("codes", bs), torch.zeros(0, **i32), max(1, G * n_per * N))
+        plan = EpochPlan(bs, pos, codes)
         if n_all and N:
             lo_r, hi_r = min(n_all, self.rank * n_per), min(n_all, (self.rank + 1) * n_per)
             mine = codes[self.rank * n_per * N:(self.rank + 1) * n_per * N] if G == 1 else \
@@ -903,29 +485,28 @@ class OwnerComputesTrainer:
                                            b.side1, b.side2, N, b.rng_seed, rng_stream, out)
                     self.backend.pack_codes(ph[a:e], out[0], out[2], N, mine[(a - lo_r) * N:(e - lo_r) * N])
             if G > 1 or self.force_collectives:      # (forced at one rank: an in-place all-gather of the whole array)
-                plan["codes_all"], plan["mine"] = codes[:G * n_per * N], mine[:n_per * N]
-        plan["codes"], plan["pos"], plan["stage"] = codes, pos, "sampled"
+                plan.codes_all, plan.mine = codes[:G * n_per * N], mine[:n_per * N]
         if dev.type == "cuda":
-            plan["sampled"] = torch.cuda.Event()
-            plan["sampled"].record()
+            plan.sampled = torch.cuda.Event()
+            plan.sampled.record()
         return plan
 
     def _plan_rest(self, plan):
         """What follows the codes' all-gather (device work only): slots, owned lists, counts, the entity-major reference lists."""
         b, G, dev, N = self.bat, self.world, self.device, self.N
         i32 = dict(dtype=torch.int32, device=dev)
-        ph, pr, pt = plan["pos"]
-        bs, codes = plan["bs"], plan["codes"]
+        ph, pr, pt = plan.pos
+        bs, codes = plan.bs, plan.codes
         n_all, parts, part_id = self._n_all, self._parts, self._part_id
-        if "gathered" in plan:
-            torch.cuda.current_stream().wait_event(plan["gathered"])
+        if plan.gathered is not None:
+            torch.cuda.current_stream().wait_event(plan.gathered)
         # slot of every positive's HR / RT vector in its owner's block (rank among the positives of its part that NEED that
         # vector — the group flags in the first code of every positive — and have the same owner, epoch order; -1 when not
         # needed), this rank's owned positives per part in slot order (part k's list starts at own[lo_k]), and the
         # per-(part, owner) counts.  HIP backend: one launch (mke_oc_plan); other backends (the CPU tests): torch.
         slot = [self._persist(("slot", x, bs), torch.zeros(0, **i32), max(1, n_all)) for x in range(2)]
         own = [self._persist(("own", x, bs), torch.zeros(0, **i32), max(1, n_all)) for x in range(2)]
-        plan["slot"], plan["own"] = slot, own
+        plan.slot, plan.own = slot, own
         if n_all:
             cnt = self._persist(("cnt", bs), torch.zeros(0, **i32), 2 * len(parts) * G)
             if hasattr(self.backend, "plan"):
@@ -956,42 +537,36 @@ class OwnerComputesTrainer:
                 host = torch.empty(c.shape, dtype=torch.int32, pin_memory=dev.type == "cuda")
                 self._persistent[("cnt_host", bs)] = host
             host.copy_(c, non_blocking=True)
-            plan["cnt_host"] = host
+            plan.cnt_host = host
         if self.em:
-            plan["em"] = self._compute_em_plan(ph, pr, pt, codes, slot, bs)
+            plan.em = self._compute_em_plan(ph, pr, pt, codes, slot, bs)
         if dev.type == "cuda":
-            plan["event"] = torch.cuda.Event()
-            plan["event"].record()
-        plan["stage"] = "done"
+            plan.ready = torch.cuda.Event()
+            plan.ready.record()
+        plan.stage = PlanStage.DONE
         return plan
 
     def _em_buffers(self, bs, capacity):
         """Scratch (shared by the two buffer sets: plans are computed one at a time on one stream) and outputs (per buffer set)
         of the entity-major plan at `capacity` references."""
         dev = self.device
-        i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
-        z32, z64 = torch.zeros(0, **i32), torch.zeros(0, **i64)
-        out = {"capacity": capacity}
-        out["keys"] = self._persist(("em_keys",), z64, capacity + 1)
-        out["keys_alt"] = self._persist(("em_keys_alt",), z64, capacity + 1)
-        out["flags"] = self._persist(("em_flags",), z32, capacity + 1)
-        out["scan"] = self._persist(("em_scan",), z32, capacity + 1)
-        out["vals_alt"] = self._persist(("em_vals_alt",), z32, capacity + 1)
-        out["scratch8"] = self._persist(("em_scratch8",), z64, capacity + 1)
-        out["waves"] = self._persist(("em_waves",), z32, 2 * (_lib.OC_EM_WAVES + 1))
-        out["temp"] = self._persist(("em_temp",), torch.zeros(0, dtype=torch.uint8, device=dev), self.backend.em_temp_bytes(capacity))
-        out["refs"] = self._persist(("em_refs", bs), z32, 2 * capacity)
-        out["rows"] = self._persist(("em_rows", bs), z32, capacity)
-        out["off"] = self._persist(("em_off", bs), z32, capacity + 1)
-        out["row0"] = self._persist(("em_row0", bs), z64, self.steps + 1)
-        # the work items of the second pass (rows, or 32-reference segments of long rows), the long rows and their partial slots
-        for k in ("item_row", "item_off", "item_part"):
-            out[k] = self._persist(("em_" + k, bs), z32, capacity + 1)
-        for k in ("long_row", "long_part0"):
-            out[k] = self._persist(("em_" + k, bs), z32, capacity // 32 + 2)
-        out["steps3"] = self._persist(("em_steps3", bs), z64, 3 * (self.steps + 1)).view(-1)[:3 * (self.steps + 1)].view(3, self.steps + 1)
-        out["n_refs"] = self._persist(("em_n_refs", bs), z64, 1)
-        return out
+        z32, z64 = (torch.zeros(0, dtype=t, device=dev) for t in (torch.int32, torch.int64))
+        p = self._persist
+        S1 = self.steps + 1
+        return EmPlan(
+            capacity=capacity,
+            keys=p(("em_keys",), z64, capacity + 1), keys_alt=p(("em_keys_alt",), z64, capacity + 1),
+            flags=p(("em_flags",), z32, capacity + 1), scan=p(("em_scan",), z32, capacity + 1),
+            vals_alt=p(("em_vals_alt",), z32, capacity + 1), scratch8=p(("em_scratch8",), z64, capacity + 1),
+            waves=p(("em_waves",), z32, 2 * (_lib.OC_EM_WAVES + 1)),
+            temp=p(("em_temp",), torch.zeros(0, dtype=torch.uint8, device=dev), self.backend.em_temp_bytes(capacity)),
+            refs=p(("em_refs", bs), z32, 2 * capacity), rows=p(("em_rows", bs), z32, capacity), off=p(("em_off", bs), z32, capacity + 1),
+            step_row0=p(("em_row0", bs), z64, S1),
+            item_row=p(("em_item_row", bs), z32, capacity + 1), item_off=p(("em_item_off", bs), z32, capacity + 1),
+            item_part=p(("em_item_part", bs), z32, capacity + 1),
+            long_row=p(("em_long_row", bs), z32, capacity // 32 + 2), long_part0=p(("em_long_part0", bs), z32, capacity // 32 + 2),
+            steps3=p(("em_steps3", bs), z64, 3 * S1).view(-1)[:3 * S1].view(3, S1),
+            n_refs_dev=p(("em_n_refs", bs), z64, 1))
 
     def _compute_em_plan(self, ph, pr, pt, codes, slot, bs, capacity=None):
         """The entity-major reference lists of the epoch in buffer set `bs` (device work only; the touched-row offsets of the
@@ -1006,33 +581,33 @@ class OwnerComputesTrainer:
                 # entities move only the five non-negative elements of a position; a rank that owns more re-plans once at the exact size
                 capacity = upper if G == 1 else min(upper, int(1.06 * self._n_all * (N + 3) / G) + 4096)
         self._em_capacity[bs] = capacity
-        bufs = self._em_buffers(bs, capacity)
-        self.backend.em_plan(self, ph, pr, pt, codes, slot, bufs)
+        em = self._em_buffers(bs, capacity)
+        self.backend.em_plan(self, ph, pr, pt, codes, slot, em)
         S1 = self.steps + 1
         host = self._persistent.get(("em_host", bs))
         if host is None or host.numel() != 4 * S1 + 1:
             host = self._persistent[("em_host", bs)] = torch.empty(4 * S1 + 1, dtype=torch.int64, pin_memory=self.device.type == "cuda")
-        host[:S1].copy_(bufs["row0"][:S1], non_blocking=True)
-        host[S1:4 * S1].copy_(bufs["steps3"].reshape(-1), non_blocking=True)
-        host[4 * S1:].copy_(bufs["n_refs"][:1], non_blocking=True)
-        bufs["host"] = host
-        return bufs
+        host[:S1].copy_(em.step_row0[:S1], non_blocking=True)
+        host[S1:4 * S1].copy_(em.steps3.reshape(-1), non_blocking=True)
+        host[4 * S1:].copy_(em.n_refs_dev[:1], non_blocking=True)
+        em.host = host
+        return em
 
     def _finish_plan(self, plan):
         """Make a computed plan the current one: wait for its counts (the only host synchronisation of an epoch), size the
         exchange blocks exactly, rebuild the native step descriptors."""
         G, dev = self.world, self.device
-        if "event" in plan:
-            plan["event"].synchronize()
+        if plan.ready is not None:
+            plan.ready.synchronize()
         parts = self._parts
-        self._codes, self._slot, self._own = plan["codes"], plan["slot"], plan["own"]
+        self._codes, self._slot, self._own = plan.codes, plan.slot, plan.own
         self._own_cnt = []                      # per part: how many HR / RT vectors of it this rank owns
         worst = 0
         self.vectors_planned = 0                # HR + RT vectors that travel in this epoch (all owners): ~1 per positive
         for x in range(2):
             mine = np.zeros(len(parts), dtype=np.int64)
             if self._n_all:
-                cnt = plan["cnt_host"][x].numpy().reshape(len(parts), G)
+                cnt = plan.cnt_host[x].numpy().reshape(len(parts), G)
                 worst = max(worst, int(cnt.max()))
                 self.vectors_planned += int(cnt.sum())
                 mine = cnt[:, self.rank].astype(np.int64)
@@ -1053,38 +628,32 @@ class OwnerComputesTrainer:
             self._addr = [tuple(t.data_ptr() for t in (self._send[c], self._v_all[c], self._g_all[c], self._gv[c]))
                           for c in range(self.chunks)]
         if self.em:
-            em = plan["em"]
+            em = plan.em
             S1 = self.steps + 1
-            n_refs = int(em["host"][4 * S1])
-            if n_refs > em["capacity"]:        # more references than the 1 / G estimate allowed for (skewed ownership): re-plan in line, exactly
-                b = self.bat
-                pos = (b.pos_h, b.pos_r, b.pos_t)
-                em = self._compute_em_plan(pos[0], pos[1], pos[2], plan["codes"], plan["slot"], plan["bs"], capacity=int(n_refs * 1.1) + 4096)
+            n_refs = int(em.host[4 * S1])
+            if n_refs > em.capacity:        # more references than the 1 / G estimate allowed for (skewed ownership): re-plan in line, exactly
+                em = plan.em = self._compute_em_plan(*plan.pos, plan.codes, plan.slot, plan.bs, capacity=int(n_refs * 1.1) + 4096)
                 if dev.type == "cuda":
                     torch.cuda.current_stream().synchronize()
-                n_refs = int(em["host"][4 * S1])
-            em["row0_host"] = em["host"][:S1].clone()
-            em["item0_host"], em["long0_host"], em["part0_host"] = (em["host"][(k + 1) * S1:(k + 2) * S1].clone() for k in range(3))
-            em["n_refs_host"] = n_refs
+                n_refs = int(em.host[4 * S1])
+            em.row0, em.item0, em.long0, em.part0 = (em.host[k * S1:(k + 1) * S1].clone() for k in range(4))
+            em.n_refs = n_refs
             # the long rows' partial sums of ONE step (stride + 16 floats per slot: the gradient vector and the coefficient sum)
-            need_parts = int((em["part0_host"][1:] - em["part0_host"][:-1]).max()) if self.steps else 0
+            need_parts = int((em.part0[1:] - em.part0[:-1]).max()) if self.steps else 0
             need_parts = max(1, need_parts) * (self.stride + 16)
-            if getattr(self, "_em_partials", None) is None or self._em_partials.numel() < need_parts:
+            if self._em_partials is None or self._em_partials.numel() < need_parts:
                 self._em_partials = torch.zeros(need_parts, dtype=torch.float32, device=dev)
             self._em = em
             need_coef = max(1, self._max_step * (self.N + 1))
-            if getattr(self, "_em_coef", None) is None or self._em_coef.numel() < need_coef:
+            if self._em_coef is None or self._em_coef.numel() < need_coef:
                 self._em_coef = torch.zeros(need_coef, dtype=torch.float32, device=dev)
-        self._planned_epoch = self.bat.epoch
-        self._plan_bs = plan["bs"]
+        self._plan_bs = plan.bs
         self._st_cache = {}
         if hasattr(self.backend, "prepare_epoch"):
             self.backend.prepare_epoch(self)
 
     def _plan_epoch(self):
         """Plan of the CURRENT epoch order, in line (construction, or an epoch boundary without a prefetched plan)."""
-        if getattr(self, "_parts", None) is None:
-            self._layout()
         b = self.bat
         self._finish_plan(self._compute_plan((b.pos_h, b.pos_r, b.pos_t), b.rng_stream, 0))
         self._next_plan = None
@@ -1094,7 +663,7 @@ class OwnerComputesTrainer:
         sampler, two sorts): by the time the epoch ends it is waiting in the other buffer set."""
         b = self.bat
         nxt = ((b.epoch + 1) * 2) & 0xFFFFFFFF
-        bs = 1 - getattr(self, "_plan_bs", 0)
+        bs = 1 - self._plan_bs
         split = self.world > 1 or self.force_collectives
         first = self._plan_sample if split else self._compute_plan               # G > 1: the collective waits for `_gather_at`
         if self.device.type != "cuda":
@@ -1106,7 +675,7 @@ class OwnerComputesTrainer:
 
     def _on_side(self, fn):
         """Run fn with the plan's side stream current (and pinned for the native calls), ordered after the current stream."""
-        if getattr(self, "_side", None) is None:
+        if self._side is None:
             self._side = torch.cuda.Stream(device=self.device)
         main = torch.cuda.current_stream()
         self._side.wait_stream(main)
@@ -1128,8 +697,8 @@ class OwnerComputesTrainer:
     def _plan_midpoint(self):
         """At step `_gather_at` of every epoch, on every rank: the prefetched plan's collective (main stream, step communicator),
         then the rest of the plan back on the side stream."""
-        plan = getattr(self, "_next_plan", None)
-        if plan is None or plan.get("stage") != "sampled":
+        plan = self._next_plan
+        if plan is None or plan.stage is not PlanStage.SAMPLED:
             return
         self._plan_gather(plan)
         if self.device.type != "cuda":
@@ -1139,11 +708,11 @@ class OwnerComputesTrainer:
 
     def _advance_epoch(self):
         """Epoch boundary: random.shuffle of both positive lists (code/MultiKE_model.py:314-315) + the new epoch's plan."""
-        if getattr(self, "_next_plan", None) is not None:
+        if self._next_plan is not None:
             self._plan_midpoint()                            # (an epoch of one step: its midpoint is the boundary itself)
             plan, self._next_plan = self._next_plan, None
-            if "event" in plan:
-                torch.cuda.current_stream().wait_event(plan["event"])
+            if plan.ready is not None:
+                torch.cuda.current_stream().wait_event(plan.ready)
             self.bat.commit_staged()
             self._finish_plan(plan)
         else:
@@ -1156,8 +725,8 @@ class OwnerComputesTrainer:
         sits at the end of an epoch): a plan of that epoch prefetched with the old candidates is dropped."""
         for side, nb in ((self.bat.side1, tables[0]), (self.bat.side2, tables[1])):
             side.set_neighbours(*(nb if nb is not None else (None, None)))
-        if getattr(self, "_next_plan", None) is not None:
-            if getattr(self, "_side", None) is not None:
+        if self._next_plan is not None:
+            if self._side is not None:
                 torch.cuda.current_stream().wait_stream(self._side)    # the dropped plan may still be writing its buffer set
             self._next_plan = None
 
@@ -1192,10 +761,9 @@ class OwnerComputesTrainer:
 
     def _part_step(self, k: int, tag: int) -> OcStep:
         st = self._st_cache.get(k)
-        if st is not None:
-            st.tag = tag
-            return st
-        st = self._st_cache[k] = self._build_part_step(k, tag)
+        if st is None:
+            st = self._st_cache[k] = self._build_part_step(k, tag)
+        st.tag = tag
         return st
 
     def _build_part_step(self, k: int, tag: int) -> OcStep:
@@ -1216,7 +784,6 @@ class OwnerComputesTrainer:
         """(usable, mke_oc_comm or None): the step loop can go through mke_oc_steps — HIP backend, a communicator with a native
         form (RCCL through ctypes, the tests' host-staged ranks, the tools' loop-back) or a single rank, no peer-direct, no
         per-launch event collection.  MKE_OC_NATIVE=0 keeps the Python loop."""
-        import os
         if not hasattr(self.backend, "run_steps") or self.peer_direct or self.score_events is not None or self.chunks > _lib.OC_EM_MAX_CHUNKS \
                 or os.environ.get("MKE_OC_NATIVE", "1") == "0":
             return False, None
@@ -1225,7 +792,7 @@ class OwnerComputesTrainer:
         if not hasattr(self.comm, "native"):
             return False, None
         key = (self.C, self._send[0].data_ptr())
-        if getattr(self, "_comm_native_key", None) != key:      # callbacks look the exchange buffers up by address
+        if self._comm_native_key != key:                     # callbacks look the exchange buffers up by address
             self._comm_native, self._comm_native_key = self.comm.native(self), key
         return True, self._comm_native
 
@@ -1240,7 +807,6 @@ class OwnerComputesTrainer:
         work items that do not need its result (at 8 ranks ~95 % of the rows: the corrupt entities) — two stream hops per step
         (~26 us), so only when the reduce-scatter is long: >= 16 MB received per rank (the C5 shape at 8 ranks: 40 MB = 122 us in the
         link model; C2: 12 MB = 48 us, not worth the hops).  MKE_OC_OVERLAP_RS=0 / 1 forces it."""
-        import os
         if not self.em or self.chunks != 1 or self.world < 2 and not self.force_collectives:
             return False
         env = os.environ.get("MKE_OC_OVERLAP_RS")
@@ -1261,152 +827,131 @@ class OwnerComputesTrainer:
                     self.step(i + k)
                 i += m
                 continue
+            # the epoch prologue of `_begin_step`, except that a run which would pass the gather point is cut there
             if s == 0 and i > 0:
                 self._advance_epoch()
             if s == 0 and self.prefetch:
-                self._prefetch_next_epoch()                  # the next epoch's plan overlaps this epoch's steps
+                self._prefetch_next_epoch()
             k = self._gather_at
             if s == k:
                 self._plan_midpoint()
-            elif s < k < s + m and getattr(self, "_next_plan", None) is not None and self._next_plan.get("stage") == "sampled":
+            elif s < k < s + m and self._next_plan is not None and self._next_plan.stage is PlanStage.SAMPLED:
                 m = k - s                                    # stop at the epoch's gather point: the collective goes between two steps
             ok, cs = self._native_loop()                     # the exchange buffers may have grown with the new epoch's plan
             comm_stream = None
             overlap = self._overlap_rs() if cs is not None else False
             if cs is not None and (self.chunks > 1 or overlap) and self.device.type == "cuda":
-                if getattr(self, "_comm_stream", None) is None:
+                if self._comm_stream is None:
                     self._comm_stream = torch.cuda.Stream(device=self.device)
                 comm_stream = self._comm_stream.cuda_stream
             self.backend.run_steps(self, s, s + m, self.tag, cs, comm_stream, overlap)
             self.tag += m
             i += m
-            self._stepped = i - 1
 
-    def step(self, i: int):
-        """Global step i (steps must be issued in order)."""
-        s = i % self.steps
+    def _begin_step(self, s: int, i: int):
+        """What precedes step s of an epoch (global step i), on every rank at the same point of the step sequence."""
         if s == 0 and i > 0:
             self._advance_epoch()
         if s == 0 and self.prefetch:
             self._prefetch_next_epoch()                      # the next epoch's plan overlaps this epoch's steps
         if s == self._gather_at:
-            self._plan_midpoint()
-        be, G, cm = self.backend, self.world, self.comm
-        ks = self._parts_of.get(s, [])
-        self.tag += 1
-        tag = self.tag
+            self._plan_midpoint()                            # ... and its one collective goes between two steps
+
+    def _score(self, k: int, tag: int, c: int, loss_slot: int, share: int):
+        """SCORE of part k, between two HIP events when `score_events` collects them (`share`: ranks the part's triples are spread over)."""
         ev = self.score_events
-        slot0 = s * self.chunks
-        if self.em:
-            self._step_em(s, ks, tag, slot0)
-            self._stepped = i
+        if ev is None:
+            self.backend.run(self, k, tag, SCORE, c, loss_slot)
             return
-        if G == 1 and not self.force_collectives:  # every row is local: no collective between the phases
-            last = len(ks) - 1
-            if last == 0 and ev is None:
-                be.run(self, ks[0], tag, BASES | COUNT | SCORE | APPLY | UPDATE, 0, slot0)
-            else:
-                for c, k in enumerate(ks):
-                    be.run(self, k, tag, BASES | COUNT, c, slot0 + c)       # counts of ALL parts before any is scored
-                for c, k in enumerate(ks):
-                    if ev is not None:
-                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        e0.record()
-                    be.run(self, k, tag, SCORE, c, slot0 + c)
-                    if ev is not None:
-                        e1.record()
-                        ev.append((e0, e1, (self._parts[k][2] - self._parts[k][1]) * (1 + self.N)))
-                for c, k in enumerate(ks):
-                    be.run(self, k, tag, APPLY | (UPDATE if c == last else 0), c, slot0 + c)
-            self._stepped = i
-            return
-        if self.peer_direct:
-            for k in ks:
-                be.run(self, k, tag, BASES | COUNT, 0, slot0)
-                cm.barrier(self._bar)                        # every rank's vectors are in its send block
-                be.run(self, k, tag, SCORE, 0, slot0)        # reads peers' blocks, writes its slice of peers' inboxes
-                cm.barrier(self._bar)                        # every writer's slice of every inbox is complete
-                be.run(self, k, tag, APPLY, 0, slot0)
-            cm.all_reduce(self.rel_grad)
-            if ks:
-                be.run(self, ks[-1], tag, UPDATE, 0, slot0)
-            self._stepped = i
-            return
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        self.backend.run(self, k, tag, SCORE, c, loss_slot)
+        e1.record()
+        ev.append((e0, e1, (self._parts[k][2] - self._parts[k][1]) * (1 + self.N) // share))
+
+    def _exchange(self, ks, tag, slot0, first_phases, share):
+        """bases -> ALL-GATHER -> score -> REDUCE-SCATTER of every part; with several parts the collectives are asynchronous and
+        part c is scored while part c + 1's all-gather / part c - 1's reduce-scatter are on the wire.  Returns the reduce-scatters'
+        handles (None: already in stream order) for the caller to wait on where its tail needs them."""
+        be, cm = self.backend, self.comm
         pipelined = len(ks) > 1 and self.device.type == "cuda"
-        works = {}
-        # ---- HR / RT vectors of every part, all-gathered (asynchronously when pipelining) -------------------------
-        # The reference counts over the WHOLE global step (all parts) are complete before any part is scored; they need
-        # only the epoch's codes and ride on blocks of the bases launch (one kernel boundary less per part, and nothing
-        # of theirs left behind the all-gather)
+        ag, rs = [], []
         for c, k in enumerate(ks):
-            be.run(self, k, tag, BASES | (COUNT if self.ref_count is not None else 0), c, slot0 + c)
-            works[("ag", c)] = cm.all_gather(self._v_all[c], self._send[c], async_op=pipelined)
-        # ---- score part c while part c+1's all-gather / part c-1's reduce-scatter are on the wire ------------------
+            be.run(self, k, tag, first_phases, c, slot0 + c)
+            ag.append(cm.all_gather(self._v_all[c], self._send[c], async_op=pipelined))
         for c, k in enumerate(ks):
-            if works.get(("ag", c)) is not None:
-                works[("ag", c)].wait()
-            if ev is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            be.run(self, k, tag, SCORE, c, slot0 + c)
-            if ev is not None:
-                e1.record()
-                ev.append((e0, e1, (self._parts[k][2] - self._parts[k][1]) * (1 + self.N) // G))
-            works[("rs", c)] = cm.reduce_scatter(self._gv[c], self._g_all[c], async_op=pipelined)
-        for c, k in enumerate(ks):
-            if works.get(("rs", c)) is not None:
-                works[("rs", c)].wait()
-            be.run(self, k, tag, APPLY, c, slot0 + c)
-        # ---- replicated relation table: all-reduce the (small) dense gradient; one update of everything ---------------
+            if ag[c] is not None:
+                ag[c].wait()
+            self._score(k, tag, c, slot0 + c, share)
+            rs.append(cm.reduce_scatter(self._gv[c], self._g_all[c], async_op=pipelined))
+        return rs
+
+    def _step_local(self, ks, tag, slot0):
+        """A one-rank step: every row is local, no collective between the phases — one native call when there is one part."""
+        be, last = self.backend, len(ks) - 1
+        if last == 0 and self.score_events is None:
+            be.run(self, ks[0], tag, BASES | SCORE | PASS2 | UPDATE if self.em else BASES | COUNT | SCORE | APPLY | UPDATE, 0, slot0)
+        elif self.em:
+            for c, k in enumerate(ks):
+                be.run(self, k, tag, BASES, c, slot0 + c)
+                self._score(k, tag, c, slot0 + c, 1)
+            be.run(self, ks[-1], tag, PASS2 | UPDATE, 0, slot0)
+        else:
+            for c, k in enumerate(ks):
+                be.run(self, k, tag, BASES | COUNT, c, slot0 + c)       # counts of ALL parts before any is scored
+            for c, k in enumerate(ks):
+                self._score(k, tag, c, slot0 + c, 1)
+            for c, k in enumerate(ks):
+                be.run(self, k, tag, APPLY | (UPDATE if c == last else 0), c, slot0 + c)
+
+    def _step_peer_direct(self, ks, tag, slot0):
+        """Atomics form without all-gather / reduce-scatter: every rank maps the other ranks' send blocks and gradient inboxes (IPC
+        handles exchanged once, `_map_peers`) and the score launch reads / writes them straight over xGMI; two stream-ordered
+        barriers per part.  Correct by construction and tested with two ranks on one GPU; not measured on several."""
+        be, cm = self.backend, self.comm
+        for k in ks:
+            be.run(self, k, tag, BASES | COUNT, 0, slot0)
+            cm.barrier(self._bar)                            # every rank's vectors are in its send block
+            be.run(self, k, tag, SCORE, 0, slot0)            # reads peers' blocks, writes its slice of peers' inboxes
+            cm.barrier(self._bar)                            # every writer's slice of every inbox is complete
+            be.run(self, k, tag, APPLY, 0, slot0)
         cm.all_reduce(self.rel_grad)
         if ks:
             be.run(self, ks[-1], tag, UPDATE, 0, slot0)
-        self._stepped = i
 
-    def _step_em(self, s, ks, tag, slot0):
-        """Global step s in the entity-major form: per part  bases -> ALL-GATHER -> score (one coefficient per owned negative,
-        the partial gradient vectors) -> REDUCE-SCATTER;  then ONE second pass over the touched owned rows of the whole step
-        (mke_oc_pass2: finishes the entity rows in place, stores this rank's partial relation gradient), the relation gradient's
-        ALL-REDUCE and the relation table's update."""
-        be, G, cm, ev = self.backend, self.world, self.comm, self.score_events
-        if not ks:
+    def step(self, i: int):
+        """Global step i (steps must be issued in order): the schedule of the module docstring, enqueued from Python."""
+        s = i % self.steps
+        self._begin_step(s, i)
+        be, cm = self.backend, self.comm
+        ks = self._parts_of.get(s, [])
+        self.tag += 1
+        tag, slot0 = self.tag, s * self.chunks
+        if self.em and not ks:
             return
-        last = len(ks) - 1
-
-        def score(c, k, share):
-            if ev is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            be.run(self, k, tag, SCORE, c, slot0 + c)
-            if ev is not None:
-                e1.record()
-                ev.append((e0, e1, (self._parts[k][2] - self._parts[k][1]) * (1 + self.N) // share))
-
-        if G == 1 and not self.force_collectives:        # every row is local: no collective between the phases
-            if last == 0 and ev is None:
-                be.run(self, ks[0], tag, BASES | SCORE | PASS2 | UPDATE, 0, slot0)
-                return
+        if self.world == 1 and not self.force_collectives:
+            self._step_local(ks, tag, slot0)
+        elif self.peer_direct:
+            self._step_peer_direct(ks, tag, slot0)
+        elif self.em:
+            # every part's vectors and gradient vectors in place, then ONE second pass over the touched owned rows of the whole step
+            for w in self._exchange(ks, tag, slot0, BASES, self.world):
+                if w is not None:
+                    w.wait()
+            be.run(self, ks[-1], tag, PASS2, 0, slot0)
+            cm.all_reduce(self.rel_grad)                     # this rank's partial relation gradient, stored by the second pass
+            be.run(self, ks[-1], tag, UPDATE, 0, slot0)
+        else:
+            # the reference counts over the WHOLE global step (all parts) are complete before any part is scored: they need only the
+            # epoch's codes and ride on blocks of the bases launch
+            rs = self._exchange(ks, tag, slot0, BASES | (COUNT if self.ref_count is not None else 0), self.world)
             for c, k in enumerate(ks):
-                be.run(self, k, tag, BASES, c, slot0 + c)
-                score(c, k, 1)
-            be.run(self, ks[-1], tag, PASS2 | UPDATE, 0, slot0)
-            return
-        pipelined = len(ks) > 1 and self.device.type == "cuda"
-        works = {}
-        for c, k in enumerate(ks):
-            be.run(self, k, tag, BASES, c, slot0 + c)
-            works[("ag", c)] = cm.all_gather(self._v_all[c], self._send[c], async_op=pipelined)
-        for c, k in enumerate(ks):
-            if works.get(("ag", c)) is not None:
-                works[("ag", c)].wait()
-            score(c, k, G)
-            works[("rs", c)] = cm.reduce_scatter(self._gv[c], self._g_all[c], async_op=pipelined)
-        for c in range(len(ks)):
-            if works.get(("rs", c)) is not None:
-                works[("rs", c)].wait()
-        be.run(self, ks[-1], tag, PASS2, 0, slot0)              # every part's vectors and gradient vectors are in place
-        cm.all_reduce(self.rel_grad)                            # this rank's partial relation gradient, stored by the second pass
-        be.run(self, ks[-1], tag, UPDATE, 0, slot0)
+                if rs[c] is not None:
+                    rs[c].wait()
+                be.run(self, k, tag, APPLY, c, slot0 + c)
+            cm.all_reduce(self.rel_grad)                     # replicated relation table: the (small) dense gradient; one update of everything
+            if ks:
+                be.run(self, ks[-1], tag, UPDATE, 0, slot0)
 
     # ------------------------------------------------------------------------------------------------
     def check(self) -> dict:
@@ -1416,16 +961,15 @@ class OwnerComputesTrainer:
                "entity_major": bool(self.em), "native_step_loop": bool(self._native_loop()[0]),
                "reduce_scatter_under_second_pass": bool(self._overlap_rs()), "communicator": type(self.comm).__name__}
         if self.em:
-            out["references_per_global_step"] = self._em["n_refs_host"] / max(1, self.steps)
-            out["long_rows_per_global_step"] = int(self._em["long0_host"][-1]) / max(1, self.steps)
+            out["references_per_global_step"] = self._em.n_refs / max(1, self.steps)
+            out["long_rows_per_global_step"] = int(self._em.long0[-1]) / max(1, self.steps)
         return out
 
     def scratch_clean(self) -> bool:
         """The zero invariants between steps: gradient scratch all zero, reference counts all zero (the entity-major form has
         no entity scratch and no counts: only the relation gradient)."""
         ok = float(self.rel_grad.abs().max()) == 0.0
-        g = getattr(self, "ent_grad_full", None)
-        g = g if g is not None else self.ent_grad
+        g = self.ent_grad_full if self.ent_grad_full is not None else self.ent_grad
         if g is not None:
             ok = ok and float(g.abs().max()) == 0.0
         if self.ref_count is not None:

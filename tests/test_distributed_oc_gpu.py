@@ -178,9 +178,9 @@ def test_entity_major_hub_entities_equal_dense_oracle():
     _, _, _, spe = _reference(1, 1, n_ent, dim, neg, b, zipf=1.2)
     steps = min(spe, 6)
     tr = _make(0, 1, n_ent=n_ent, dim=dim, neg=neg, b=b, zipf=1.2, em=True)
-    longest = int((tr._em["off"][1:tr._em["row0_host"][-1] + 1] - tr._em["off"][:tr._em["row0_host"][-1]]).max())
+    longest = int((tr._em.off[1:tr._em.row0[-1] + 1] - tr._em.off[:tr._em.row0[-1]]).max())
     assert longest > 64, longest                   # lists that span several 32-reference segments:
-    assert int(tr._em["long0_host"][-1]) > 0       # ... cut into work items of their own, partial sums, a combine launch
+    assert int(tr._em.long0[-1]) > 0       # ... cut into work items of their own, partial sums, a combine launch
     for i in range(steps):
         tr.step(i)
     e, r, losses, _ = _reference(1, steps, n_ent, dim, neg, b, zipf=1.2)
@@ -198,10 +198,10 @@ def test_entity_major_plan_grows_when_a_rank_owns_more_than_its_share():
     _, _, _, spe = _reference(1, 1, n_ent, dim, neg)
     steps = min(spe, 5)
     tr = _make(0, 1, n_ent=n_ent, dim=dim, neg=neg, em=True)
-    full = tr._em["capacity"]
+    full = tr._em.capacity
     tr._em_capacity = {0: 100, 1: 100}
     tr._plan_epoch()                                   # overflows, re-plans at the reported size
-    assert 100 < tr._em["capacity"] <= full and tr._em["n_refs_host"] <= tr._em["capacity"]
+    assert 100 < tr._em.capacity <= full and tr._em.n_refs <= tr._em.capacity
     tr.run(0, steps)
     e, r, losses, _ = _reference(1, steps, n_ent, dim, neg)
     np.testing.assert_allclose(tr.epoch_loss(), sum(losses), rtol=2e-6)
@@ -295,11 +295,11 @@ def test_epoch_plan_with_64_bit_keys_gives_the_same_lists(zipf):
         try:
             tr = _make(0, 1, neg=25, em=True, zipf=zipf, hot_min=None)
             em = tr._em
-            n = int(em["n_refs_host"])
+            n = int(em.n_refs)
             S1 = tr.steps + 1
-            items = int(em["host"][S1:2 * S1][-1])
-            lists = [em["refs"][:2 * n].clone(), em["item_row"][:items].clone(), em["item_off"][:items + 1].clone(), em["item_part"][:items].clone(),
-                     em["host"].clone()]
+            items = int(em.host[S1:2 * S1][-1])
+            lists = [em.refs[:2 * n].clone(), em.item_row[:items].clone(), em.item_off[:items + 1].clone(), em.item_part[:items].clone(),
+                     em.host.clone()]
             tr.run(0, tr.steps + 2)
             torch.cuda.synchronize()
             runs.append(lists + [tr.ent.clone(), tr.ent_acc.clone(), tr.rel.clone(), tr.loss_ring.clone()])

@@ -50,9 +50,6 @@ class LoopbackComm(OcComm):
         self.calls = 0
         self.events, self.k = None, 0
 
-    def for_plan(self):
-        return self
-
     def _run(self, fn, wire_bytes, async_op):
         self.calls += 1
         cur = torch.cuda.current_stream()
@@ -193,9 +190,9 @@ def main():
     phases = {}
     for name, e0, e1 in ev:
         phases.setdefault(name, []).append(e0.elapsed_time(e1) * 1e3)
-    out = {"tool": "oc_rank_compute", "config": a.config, "zipf": a.zipf, "rel_zipf": a.rel_zipf, "options": a.set, "world": G, "rank": 0, "entity_major": tr.em, "native_loop": bool(a.native), "hi_prio_stream": bool(a.hi_prio), "em_refs_per_step": (tr._em["n_refs_host"] / max(1, tr.steps)) if tr.em else None,
-           "em_rows_per_step": (int(tr._em["row0_host"][-1]) / max(1, tr.steps)) if tr.em else None,
-           "em_long_rows_per_step": (int(tr._em["long0_host"][-1]) / max(1, tr.steps)) if tr.em else None, "chunks": a.chunks, "global_batch": B * G,
+    out = {"tool": "oc_rank_compute", "config": a.config, "zipf": a.zipf, "rel_zipf": a.rel_zipf, "options": a.set, "world": G, "rank": 0, "entity_major": tr.em, "native_loop": bool(a.native), "hi_prio_stream": bool(a.hi_prio), "em_refs_per_step": (tr._em.n_refs / max(1, tr.steps)) if tr.em else None,
+           "em_rows_per_step": (int(tr._em.row0[-1]) / max(1, tr.steps)) if tr.em else None,
+           "em_long_rows_per_step": (int(tr._em.long0[-1]) / max(1, tr.steps)) if tr.em else None, "chunks": a.chunks, "global_batch": B * G,
            "scored_per_global_step": B * G * (1 + cfg["neg"]), "steps_per_epoch": tr.steps, "rows_owned": tr.n_local,
            "capacity_vectors": tr.C,
            "phase_us": {k: float(np.mean(v)) for k, v in phases.items()},

@@ -35,4 +35,4 @@ for _ in range(6):
 e1.record()
 torch.cuda.synchronize()
 print('{"tool": "plan_prof", "config": "%s", "world": %d, "plan_ms": %.3f, "steps_per_epoch": %d, "refs": %d, "capacity": %d}'
-      % (a.config, G, e0.elapsed_time(e1) / 6, tr.steps, tr._em["n_refs_host"], tr._em["capacity"]))
+      % (a.config, G, e0.elapsed_time(e1) / 6, tr.steps, tr._em.n_refs, tr._em.capacity))
