@@ -216,11 +216,9 @@ int launch_gemm_f32(const float* A, int64_t a_rs, int64_t a_cs, const float* B, 
   GemmParams p;
   if (!gemm_setup(p, A, a_rs, a_cs, B, b_rs, b_cs, C, ldc, M, N, K, splits, accumulate, tanh_sumsq_partials, epi_plain)) return MKE_OK;
   // tall and skinny with the fused epilogue: K split over the four wavefronts of a 16-row block (see k_gemm_tall)
-  if (tanh_sumsq_partials && a_cs == 1 && b_cs == 1 && N <= 80 && K <= 320 && M >= 1024 && (M + 15) / 16 <= MKE_LOSS_PARTIALS) {
-    const dim3 grid((M + 15) / 16);
-    if (K <= 80) hipLaunchKernelGGL((k_gemm_tall<5, 5>), grid, dim3(MKE_BLOCK), 0, st, p);
-    else if (K <= 160) hipLaunchKernelGGL((k_gemm_tall<5, 10>), grid, dim3(MKE_BLOCK), 0, st, p);
-    else hipLaunchKernelGGL((k_gemm_tall<5, 20>), grid, dim3(MKE_BLOCK), 0, st, p);
+  // caller: the space-mapping step's P = V M (K = N = dim <= 80); the attribute step's dense layer reaches here only past these limits
+  if (tanh_sumsq_partials && a_cs == 1 && b_cs == 1 && N <= 80 && K <= 80 && M >= 1024 && (M + 15) / 16 <= MKE_LOSS_PARTIALS) {
+    hipLaunchKernelGGL((k_gemm_tall<5, 5>), dim3((M + 15) / 16), dim3(MKE_BLOCK), 0, st, p);
     return check_launch("k_gemm_tall");
   }
   if (tanh_sumsq_partials && p.gx * p.gy > MKE_LOSS_PARTIALS) { set_error("gemm epilogue: more than %d blocks", MKE_LOSS_PARTIALS); return MKE_E_SHAPE; }
