@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MKE_VERSION 106 /* 0.1.6: + CSLS re-scoring and the euclidean metric of the alignment evaluator (mke_align_topk_mean, mke_align_topk_mean_temp_bytes, mke_align_rank_ex: additions only); 0.1.5: + entity-major second pass of the owner-computes step (mke_oc_step.em_*, mke_oc_em_plan, MKE_OC_PASS2: additions only), + mke_oc_steps / mke_oc_comm (the G > 1 step loop as ONE native call), per-plan tuning (mke_tuning); 0.1.4: mke_oc_* exchange ONE vector per positive (the side its negatives corrupt): group flags in the codes, slot -1, mke_oc_plan takes the codes, mke_oc_step.hot (hub rows of the shard), mke_attr_step_args.attr_grad_copies, + mke_probe_rows; 0.1.3: + hub rows (mke_hot_rows: mke_triple_score_fwd_bwd_xch, mke_update_table.hot, mke_relation_plan.hot; additions only); 0.1.2: + mke_oc_plan, mke_topk_long, options "attr_fused_bwd" / "oc_score_quarter" (additions only); 0.1.1: mke_align_rank gained `ties` */
+#define MKE_VERSION 107 /* 0.1.7: the score step takes ONE argument struct (+ mke_score_args, mke_triple_score_step) and this release REMOVES entry points, the first to do so: mke_triple_score_fwd_bwd_x, _xc, _xch, _t and _det are gone (mke_triple_score_fwd_bwd stays), callers of those fill a mke_score_args; 0.1.6: + CSLS re-scoring and the euclidean metric of the alignment evaluator (mke_align_topk_mean, mke_align_topk_mean_temp_bytes, mke_align_rank_ex: additions only); 0.1.5: + entity-major second pass of the owner-computes step (mke_oc_step.em_*, mke_oc_em_plan, MKE_OC_PASS2: additions only), + mke_oc_steps / mke_oc_comm (the G > 1 step loop as ONE native call), per-plan tuning (mke_tuning); 0.1.4: mke_oc_* exchange ONE vector per positive (the side its negatives corrupt): group flags in the codes, slot -1, mke_oc_plan takes the codes, mke_oc_step.hot (hub rows of the shard), mke_attr_step_args.attr_grad_copies, + mke_probe_rows; 0.1.3: + hub rows (mke_hot_rows: mke_triple_score_fwd_bwd_xch, mke_update_table.hot, mke_relation_plan.hot; additions only); 0.1.2: + mke_oc_plan, mke_topk_long, options "attr_fused_bwd" / "oc_score_quarter" (additions only); 0.1.1: mke_align_rank gained `ties` */
 
 /* error codes (negative = argument errors) */
 #define MKE_OK 0
@@ -59,8 +59,8 @@ int mke_version(void);
 const char* mke_last_error(void);
 
 /* Per-call tuning (version 105; performance only, never results): a field at MKE_TUNE_DEFAULT follows the process default
- * (mke_set_option).  Carried by pointer (NULL = all defaults) in mke_relation_plan, mke_attr_step_args and mke_oc_step, and
- * taken as an argument by the *_t entry points; the library reads it for the duration of that one call only. */
+ * (mke_set_option).  Carried by pointer (NULL = all defaults) in mke_relation_plan, mke_score_args, mke_attr_step_args and
+ * mke_oc_step, and taken as an argument by mke_rows_update_multi_t; the library reads it for the duration of that one call only. */
 #define MKE_TUNE_DEFAULT (-2)
 typedef struct mke_tuning {
   int score_splits, score_half_groups, score_offsets32, score_lane_ids, count_in_score, update_chunk, oc_score_quarter,
@@ -93,7 +93,7 @@ int mke_tuning_init(mke_tuning* t);   /* every field = MKE_TUNE_DEFAULT */
  *   "score_lane_ids"    : 1 (default) = the training kernel fetches a group's negative ids and reference counts once, one
  *                     negative per lane, and gathers accumulator rows only for rows it finishes in place; 0 = per round
  *   "count_in_score"    : 1 (default) = mke_relation_steps lets the NEXT step's reference counting ride in the score
- *                     launch (mke_triple_score_fwd_bwd_xc); 0 = in the update launch (mke_rows_update_multi_count)
+ *                     launch (mke_score_args.next_count); 0 = in the update launch (mke_rows_update_multi_count)
  * Returns the previous value through *old_value when it is not NULL. */
 int mke_set_option(const char* name, int value, int* old_value);
 
@@ -138,8 +138,13 @@ int mke_triple_score_fwd_bwd(
     double* loss_partials /* [MKE_LOSS_PARTIALS] */,
     void* stream);
 
-/* (1b) Exclusive-row fast path.  Most entity rows a step touches are the corrupted entity of exactly ONE negative
- *   (uniform sampling: ~70 % of the touched rows at the DBP-WD shape).  Such a row is read by one quarter-wave and
+/* (1b) The same step with its optional parts: mke_triple_score_step takes ONE argument struct (version 107; it replaces the
+ *   positional mke_triple_score_fwd_bwd_x / _xc / _xch / _t / _det, one entry point per combination of the parts below).  A
+ *   zero-initialised mke_score_args with the tables, the positives and the negatives filled is the forward pass of (1); the
+ *   positional mke_triple_score_fwd_bwd above is that struct filled from its arguments.
+ *
+ *   Exclusive-row fast path (ref_count != NULL).  Most entity rows a step touches are the corrupted entity of exactly ONE
+ *   negative (uniform sampling: ~70 % of the touched rows at the DBP-WD shape).  Such a row is read by one quarter-wave and
  *   receives one gradient contribution, so that quarter-wave can apply the Jacobian + optimizer update itself — the
  *   scatter (atomic read-modify-write of the gradient row) and the later visit by mke_rows_update (3 row reads, 3 row
  *   writes) collapse into 1 accumulator read + 2 row writes.  Result: identical to the two-kernel path (same formulas,
@@ -148,45 +153,21 @@ int mke_triple_score_fwd_bwd(
  *   mke_count_entity_refs: ref_count[e] += occurrences of e in (pos_h, pos_t, neg_h, neg_t), not counting a negative's
  *     entry that repeats its own positive's entity on that side (grouped negatives, neg_per_pos >= 1).  ref_count is
  *     int32 [n_ent], zero on entry by invariant.
- *   mke_triple_score_fwd_bwd_x: as (1), plus: a negative that differs from its positive in exactly one entity e with
+ *   ref_count given: as (1), plus: a negative that differs from its positive in exactly one entity e with
  *     ref_count[e] == 1 is applied in place on (ent_table, ent_acc) with (optimizer, lr) and ref_count[e] is reset to 0;
  *     every other row goes through grad_ent / touched_ent as in (1).  mke_rows_update* reset ref_count for the rows they
- *     visit when given the array (mke_update_table.ref_count / the ref_count argument), restoring the invariant. */
-/* Deterministic mode (parity / debugging; SURVEY.md §7 "hard parts"): the same step with every gradient-row contribution
- * STORED into a slot of its own instead of added atomically — slot ((g * (neg_per_pos + 1) + n) * 3 + c) for contribution c
- * (0 head, 1 relation, 2 tail row) of triple n of group g (n = neg_per_pos: the group's pre-reduced flush), key
- * (is_relation << 40) | row — then summed per row in slot order:
- *     fill stage_keys with 0x7F bytes -> mke_triple_score_fwd_bwd_det -> stable sort of the keys (-> sorted_keys, order)
- *     -> mke_stage_reduce -> mke_rows_update_multi as usual.
- * stage_rows: [stage_slots][stride] floats, stage_slots >= 3 * n_pos * (neg_per_pos + 1) (ungrouped: 3 * (n_pos + n_neg)).
- * Results are bit-identical from run to run; rows referenced once are still updated in place (one contribution: no order). */
-int mke_triple_score_fwd_bwd_det(
-    float* ent_table, int64_t n_ent, int ent_normalize, const float* rel_table, int64_t n_rel, int rel_normalize,
-    int stride, int dim, const int32_t* pos_h, const int32_t* pos_r, const int32_t* pos_t, const float* pos_w,
-    int64_t n_pos, const int32_t* neg_h, const int32_t* neg_r, const int32_t* neg_t, const float* neg_w, int64_t n_neg,
-    int neg_per_pos, float scale, float* grad_ent, float* grad_rel, int32_t* touched_ent, int32_t* touched_rel, int32_t tag,
-    int32_t* ref_count /*nullable*/, float* ent_acc, int optimizer, float lr, float* stage_rows, int64_t* stage_keys,
-    int64_t stage_slots, double* loss_partials, void* stream);
-int mke_stage_reduce(const float* stage_rows, const int64_t* sorted_keys, const int64_t* order, int64_t n_slots, int stride,
-                     float* grad_ent, float* grad_rel, int32_t* touched_ent, int32_t* touched_rel, int32_t tag, void* stream);
-int mke_count_entity_refs(const int32_t* pos_h, const int32_t* pos_t, int64_t n_pos, const int32_t* neg_h,
-                          const int32_t* neg_t, int64_t n_neg, int neg_per_pos, int32_t* ref_count, void* stream);
-int mke_triple_score_fwd_bwd_x(
-    float* ent_table, int64_t n_ent, int ent_normalize,
-    const float* rel_table, int64_t n_rel, int rel_normalize,
-    int stride, int dim,
-    const int32_t* pos_h, const int32_t* pos_r, const int32_t* pos_t, const float* pos_w /*nullable*/, int64_t n_pos,
-    const int32_t* neg_h, const int32_t* neg_r, const int32_t* neg_t, const float* neg_w /*nullable*/, int64_t n_neg,
-    int neg_per_pos, float scale,
-    float* grad_ent, float* grad_rel, int grad_rel_copies,
-    int32_t* touched_ent, int32_t* touched_rel, int32_t tag,
-    int32_t* ref_count, float* ent_acc /*nullable for SGD*/, int optimizer, float lr,
-    double* loss_partials, void* stream);
-
-/* The same, and the first blocks of the launch also count the entity references of the NEXT step into next_count->ref_count
- * (mke_count_entity_refs semantics; a different buffer than `ref_count`; NULL = plain mke_triple_score_fwd_bwd_x): the counting
- * finishes under the scoring blocks instead of paying a launch or a tail of its own.  mke_count_job: section (2). */
-struct mke_count_job;
+ *     visit when given the array (mke_update_table.ref_count / the ref_count argument), restoring the invariant.
+ *
+ *   Count rider (next_count != NULL): the first blocks of the launch also count the entity references of the NEXT step into
+ *   next_count->ref_count (mke_count_entity_refs semantics; a different buffer than `ref_count`): the counting finishes under
+ *   the scoring blocks instead of paying a launch or a tail of its own (the update launch can carry the same job:
+ *   mke_rows_update_multi_count, section (2)). */
+typedef struct mke_count_job {
+  const int32_t* pos_h; const int32_t* pos_t; int64_t n_pos;
+  const int32_t* neg_h; const int32_t* neg_t; int64_t n_neg;
+  int neg_per_pos;
+  int32_t* ref_count;
+} mke_count_job;
 /* Hub rows (version 103).  A KG's degree distribution is heavy-tailed (code/base/batch.py:45-54 feeds real triples): a few
  * hundred entities are head or tail of several positives of EVERY step, and the flushes of all those groups' shared-row
  * gradients serialise on the same few cache lines of the gradient scratch.  For the rows listed here the flush of group g
@@ -199,29 +180,41 @@ typedef struct mke_hot_rows {
   int32_t n_hot, copies;
   int64_t row0;          /* first copy row (>= n_ent) */
 } mke_hot_rows;
-int mke_triple_score_fwd_bwd_xc(
-    float* ent_table, int64_t n_ent, int ent_normalize,
-    const float* rel_table, int64_t n_rel, int rel_normalize,
-    int stride, int dim,
-    const int32_t* pos_h, const int32_t* pos_r, const int32_t* pos_t, const float* pos_w /*nullable*/, int64_t n_pos,
-    const int32_t* neg_h, const int32_t* neg_r, const int32_t* neg_t, const float* neg_w /*nullable*/, int64_t n_neg,
-    int neg_per_pos, float scale,
-    float* grad_ent, float* grad_rel, int grad_rel_copies,
-    int32_t* touched_ent, int32_t* touched_rel, int32_t tag,
-    int32_t* ref_count, float* ent_acc /*nullable for SGD*/, int optimizer, float lr,
-    const struct mke_count_job* next_count /*nullable*/, double* loss_partials, void* stream);
-/* The same with hub rows (hot == NULL or hot->n_hot == 0: identical to mke_triple_score_fwd_bwd_xc). */
-int mke_triple_score_fwd_bwd_xch(
-    float* ent_table, int64_t n_ent, int ent_normalize,
-    const float* rel_table, int64_t n_rel, int rel_normalize,
-    int stride, int dim,
-    const int32_t* pos_h, const int32_t* pos_r, const int32_t* pos_t, const float* pos_w /*nullable*/, int64_t n_pos,
-    const int32_t* neg_h, const int32_t* neg_r, const int32_t* neg_t, const float* neg_w /*nullable*/, int64_t n_neg,
-    int neg_per_pos, float scale,
-    float* grad_ent, float* grad_rel, int grad_rel_copies,
-    int32_t* touched_ent, int32_t* touched_rel, int32_t tag,
-    int32_t* ref_count, float* ent_acc /*nullable for SGD*/, int optimizer, float lr,
-    const struct mke_count_job* next_count /*nullable*/, const mke_hot_rows* hot /*nullable*/, double* loss_partials, void* stream);
+/* Deterministic mode (stage_keys != NULL; parity / debugging; SURVEY.md §7 "hard parts"): the same step with every gradient-row
+ * contribution STORED into a slot of its own instead of added atomically — slot ((g * (neg_per_pos + 1) + n) * 3 + c) for
+ * contribution c (0 head, 1 relation, 2 tail row) of triple n of group g (n = neg_per_pos: the group's pre-reduced flush), key
+ * (is_relation << 40) | row — then summed per row in slot order:
+ *     fill stage_keys with 0x7F bytes -> mke_triple_score_step -> stable sort of the keys (-> sorted_keys, order)
+ *     -> mke_stage_reduce -> mke_rows_update_multi as usual.
+ * stage_rows: [stage_slots][stride] floats, stage_slots >= 3 * n_pos * (neg_per_pos + 1) (ungrouped: 3 * (n_pos + n_neg)).
+ * Results are bit-identical from run to run; rows referenced once are still updated in place (one contribution: no order).
+ * grad_rel is then one copy (grad_rel_copies is not read) and hub rows are not used. */
+typedef struct mke_score_args {
+  /* tables (ent_table is written only on the exclusive-row path) */
+  float* ent_table; int64_t n_ent; int ent_normalize;
+  const float* rel_table; int64_t n_rel; int rel_normalize;
+  int stride, dim;
+  const int32_t* pos_h; const int32_t* pos_r; const int32_t* pos_t; const float* pos_w /*nullable*/; int64_t n_pos;
+  const int32_t* neg_h; const int32_t* neg_r; const int32_t* neg_t; const float* neg_w /*nullable*/; int64_t n_neg;
+  int neg_per_pos;
+  float scale;
+  /* gradient scratch: grad_ent == NULL = forward only */
+  float* grad_ent; float* grad_rel /*nullable iff grad_ent is*/; int grad_rel_copies;
+  int32_t* touched_ent; int32_t* touched_rel; int32_t tag;
+  /* exclusive-row path: ref_count == NULL = off */
+  int32_t* ref_count; float* ent_acc /*nullable for SGD*/; int optimizer; float lr;
+  const mke_count_job* next_count;   /* host pointer, NULL = no rider */
+  mke_hot_rows hot;                  /* slot == NULL (or n_hot == 0): none; needs grad_ent */
+  /* deterministic mode: stage_keys == NULL = atomics */
+  float* stage_rows; int64_t* stage_keys; int64_t stage_slots;
+  double* loss_partials;             /* [MKE_LOSS_PARTIALS] */
+  const mke_tuning* tuning;          /* host pointer, NULL = the enclosing call's knobs / the process defaults */
+} mke_score_args;
+int mke_triple_score_step(const mke_score_args* args, void* stream);
+int mke_stage_reduce(const float* stage_rows, const int64_t* sorted_keys, const int64_t* order, int64_t n_slots, int stride,
+                     float* grad_ent, float* grad_rel, int32_t* touched_ent, int32_t* touched_rel, int32_t tag, void* stream);
+int mke_count_entity_refs(const int32_t* pos_h, const int32_t* pos_t, int64_t n_pos, const int32_t* neg_h,
+                          const int32_t* neg_t, int64_t n_neg, int neg_per_pos, int32_t* ref_count, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * (2) Per-row optimizer step on the rows touched in this step: Jacobian of normalise-on-read, then
@@ -275,13 +268,7 @@ int mke_rows_update_multi(const mke_update_table* tables, int n_tables, int32_t 
 
 /* The same launch can also carry the reference counting of the NEXT step (mke_count_entity_refs semantics into
  * next_ref_count, a different buffer than the ones the tables reset): the counting blocks ride along with the update
- * blocks instead of paying their own kernel boundary.  count == NULL: plain mke_rows_update_multi. */
-typedef struct mke_count_job {
-  const int32_t* pos_h; const int32_t* pos_t; int64_t n_pos;
-  const int32_t* neg_h; const int32_t* neg_t; int64_t n_neg;
-  int neg_per_pos;
-  int32_t* ref_count;
-} mke_count_job;
+ * blocks instead of paying their own kernel boundary.  count == NULL: plain mke_rows_update_multi.  mke_count_job: section (1b). */
 int mke_rows_update_multi_count(const mke_update_table* tables, int n_tables, int32_t tag, int stride, int dim,
                                 int optimizer, float lr, const mke_count_job* count /*nullable*/, void* stream);
 
@@ -919,7 +906,7 @@ int mke_dense_layer_fwd(const float* x, int64_t ldx, const float* w, int64_t ldw
  *      g_all: [n_ranks][2 * capacity][stride] — every slot is overwritten each step; gv: this rank's block after the
  *      reduce-scatter.  ref_count (nullable): zero-invariant counters of the exclusive-row fast path (a corrupt row
  *      referenced once in the whole global step is updated in place by mke_oc_score).  Same arithmetic as
- *      mke_triple_score_fwd_bwd_x; both tables are read through l2_normalize (the relation view's tables).
+ *      mke_triple_score_step; both tables are read through l2_normalize (the relation view's tables).
  * ------------------------------------------------------------------------------------------------ */
 #define MKE_OC_MAX_RANKS 16
 #define MKE_OC_NEED_HR 0x40000000u
@@ -1080,15 +1067,8 @@ typedef struct mke_oc_loop {
 } mke_oc_loop;
 int mke_oc_steps(const mke_oc_loop* loop, int step_begin, int step_end, void* stream);
 
-/* The per-step entry points with their tuning as an argument (version 105): mke_triple_score_fwd_bwd_xch and
- * mke_rows_update_multi_count, `tuning` = NULL being exactly those. */
-int mke_triple_score_fwd_bwd_t(
-    float* ent_table, int64_t n_ent, int ent_normalize, const float* rel_table, int64_t n_rel, int rel_normalize,
-    int stride, int dim, const int32_t* pos_h, const int32_t* pos_r, const int32_t* pos_t, const float* pos_w,
-    int64_t n_pos, const int32_t* neg_h, const int32_t* neg_r, const int32_t* neg_t, const float* neg_w, int64_t n_neg,
-    int neg_per_pos, float scale, float* grad_ent, float* grad_rel, int grad_rel_copies, int32_t* touched_ent,
-    int32_t* touched_rel, int32_t tag, int32_t* ref_count, float* ent_acc, int optimizer, float lr,
-    const mke_count_job* next_count, const mke_hot_rows* hot, const mke_tuning* tuning, double* loss_partials, void* stream);
+/* mke_rows_update_multi_count with its tuning as an argument (version 105), `tuning` = NULL being exactly that.  (The score
+ * step carries its own in mke_score_args.tuning.) */
 int mke_rows_update_multi_t(const mke_update_table* tables, int n_tables, int32_t tag, int stride, int dim, int optimizer,
                             float lr, const mke_count_job* count, const mke_tuning* tuning, void* stream);
 

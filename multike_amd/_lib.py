@@ -24,8 +24,8 @@ _SUPPORTED_FPL = (1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 13, 16, 20)
 
 # every symbol include/multike_hip.h declares (tests/test_abi.py checks the .so exports each of them)
 SYMBOLS = (
-    "mke_version", "mke_last_error", "mke_set_option", "mke_triple_score_fwd_bwd", "mke_triple_score_fwd_bwd_x",
-    "mke_count_entity_refs", "mke_triple_score_fwd_bwd_xc", "mke_triple_score_fwd_bwd_xch", "mke_triple_score_fwd_bwd_det", "mke_stage_reduce", "mke_rows_update", "mke_rows_update_multi", "mke_rows_update_multi_count",
+    "mke_version", "mke_last_error", "mke_set_option", "mke_triple_score_fwd_bwd", "mke_triple_score_step",
+    "mke_count_entity_refs", "mke_stage_reduce", "mke_rows_update", "mke_rows_update_multi", "mke_rows_update_multi_count",
     "mke_neg_sample", "mke_tripleset_build", "mke_tripleset_query", "mke_gathered_logistic_fwd_bwd",
     "mke_gathered_alignment_fwd_bwd", "mke_align_fwd_bwd", "mke_gather_rows", "mke_relation_steps",
     "mke_rowset_build", "mke_rowset_remap", "mke_rows_gather_padded", "mke_rows_scatter_add",
@@ -35,7 +35,7 @@ SYMBOLS = (
     "mke_ae_scratch_floats", "mke_ae_train_steps", "mke_ae_step_phases", "mke_ae_encode", "mke_dense_layer_fwd",
     "mke_topk_long", "mke_probe_rows", "mke_oc_block_floats", "mke_oc_pack_codes", "mke_oc_plan", "mke_oc_bases", "mke_oc_count", "mke_oc_score", "mke_oc_apply", "mke_oc_run",
     "mke_oc_em_plan_temp_bytes", "mke_oc_em_plan", "mke_oc_pass2", "mke_oc_steps",
-    "mke_tuning_init", "mke_triple_score_fwd_bwd_t", "mke_rows_update_multi_t",
+    "mke_tuning_init", "mke_rows_update_multi_t",
     "mke_align_topk_mean_temp_bytes", "mke_align_topk_mean", "mke_align_rank_ex",
     "mke_tripleset_forget", "mke_tripleset_filter_bytes", "mke_epoch_positives",
 )
@@ -94,6 +94,21 @@ class MappingStepArgs(C.Structure):
 class HotRowsStruct(C.Structure):
     """mke_hot_rows"""
     _fields_ = [("slot", C.c_void_p), ("n_hot", C.c_int32), ("copies", C.c_int32), ("row0", C.c_int64)]
+
+
+class ScoreArgs(C.Structure):
+    """mke_score_args"""
+    _fields_ = [("ent_table", C.c_void_p), ("n_ent", C.c_int64), ("ent_normalize", C.c_int),
+                ("rel_table", C.c_void_p), ("n_rel", C.c_int64), ("rel_normalize", C.c_int), ("stride", C.c_int), ("dim", C.c_int),
+                ("pos_h", C.c_void_p), ("pos_r", C.c_void_p), ("pos_t", C.c_void_p), ("pos_w", C.c_void_p), ("n_pos", C.c_int64),
+                ("neg_h", C.c_void_p), ("neg_r", C.c_void_p), ("neg_t", C.c_void_p), ("neg_w", C.c_void_p), ("n_neg", C.c_int64),
+                ("neg_per_pos", C.c_int), ("scale", C.c_float),
+                ("grad_ent", C.c_void_p), ("grad_rel", C.c_void_p), ("grad_rel_copies", C.c_int),
+                ("touched_ent", C.c_void_p), ("touched_rel", C.c_void_p), ("tag", C.c_int32),
+                ("ref_count", C.c_void_p), ("ent_acc", C.c_void_p), ("optimizer", C.c_int), ("lr", C.c_float),
+                ("next_count", C.c_void_p), ("hot", HotRowsStruct),
+                ("stage_rows", C.c_void_p), ("stage_keys", C.c_void_p), ("stage_slots", C.c_int64),
+                ("loss_partials", C.c_void_p), ("tuning", C.c_void_p)]
 
 
 class OcStepStruct(C.Structure):
@@ -323,24 +338,6 @@ def set_option(name: str, value: int) -> int:
     return old.value
 
 
-def triple_score_fwd_bwd_det(ent, ent_normalize, rel, rel_normalize, dim, pos, pos_w, neg, neg_w, neg_per_pos, scale, grad_ent,
-                             grad_rel, touched_ent, touched_rel, tag, ref_count, ent_acc, optimizer, lr, stage_rows, stage_keys,
-                             loss_partials):
-    ph, pr, pt = pos
-    nh, nr, nt = neg if neg is not None else (None, None, None)
-    i32, f32 = torch.int32, torch.float32
-    rc = lib().mke_triple_score_fwd_bwd_det(
-        _dev(ent, f32, "ent"), C.c_int64(ent.shape[0]), C.c_int(int(ent_normalize)), _dev(rel, f32, "rel"), C.c_int64(rel.shape[0]),
-        C.c_int(int(rel_normalize)), C.c_int(ent.shape[1]), C.c_int(dim), _dev(ph, i32, "ph"), _dev(pr, i32, "pr"), _dev(pt, i32, "pt"),
-        _dev(pos_w, f32, "pos_w"), C.c_int64(ph.numel()), _dev(nh, i32, "nh"), _dev(nr, i32, "nr"), _dev(nt, i32, "nt"),
-        _dev(neg_w, f32, "neg_w"), C.c_int64(0 if nh is None else nh.numel()), C.c_int(neg_per_pos), C.c_float(scale),
-        _dev(grad_ent, f32, "grad_ent"), _dev(grad_rel, f32, "grad_rel"), _dev(touched_ent, i32, "touched"),
-        _dev(touched_rel, i32, "touched"), C.c_int32(tag), _dev(ref_count, i32, "ref_count"), _dev(ent_acc, f32, "acc"),
-        C.c_int(optimizer), C.c_float(lr), _dev(stage_rows, f32, "stage_rows"), _dev(stage_keys, torch.int64, "stage_keys"),
-        C.c_int64(stage_keys.numel()), _dev(loss_partials, torch.float64, "loss"), _stream())
-    _check(rc, "mke_triple_score_fwd_bwd_det")
-
-
 def stage_reduce(stage_rows, sorted_keys, order, grad_ent, grad_rel, touched_ent, touched_rel, tag):
     rc = lib().mke_stage_reduce(_dev(stage_rows, torch.float32, "stage_rows"), _dev(sorted_keys, torch.int64, "keys"),
                                 _dev(order, torch.int64, "order"), C.c_int64(sorted_keys.numel()), C.c_int(stage_rows.shape[1]),
@@ -356,33 +353,6 @@ def get_option(name: str) -> int:
     return old
 
 
-def triple_score_fwd_bwd(ent, ent_normalize, rel, rel_normalize, dim, pos, pos_w, neg, neg_w, neg_per_pos, scale,
-                         grad_ent, grad_rel, touched_ent, touched_rel, tag, loss_partials):
-    """mke_triple_score_fwd_bwd.  pos/neg = (h, r, t) int32 CUDA tensors (neg may be None).
-    grad_rel may be [K, n_rel, stride] (K privatised copies) or [n_rel, stride]."""
-    rel_copies = 1 if grad_rel is None or grad_rel.dim() == 2 else grad_rel.shape[0]
-    ph, pr, pt = pos
-    n_pos = ph.numel()
-    if neg is None:
-        nh = nr = nt = None
-        n_neg = 0
-    else:
-        nh, nr, nt = neg
-        n_neg = nh.numel()
-    rc = lib().mke_triple_score_fwd_bwd(
-        _dev(ent, torch.float32, "ent_table"), C.c_int64(ent.shape[0]), C.c_int(int(ent_normalize)),
-        _dev(rel, torch.float32, "rel_table"), C.c_int64(rel.shape[0]), C.c_int(int(rel_normalize)),
-        C.c_int(ent.shape[1]), C.c_int(dim),
-        _dev(ph, torch.int32, "pos_h"), _dev(pr, torch.int32, "pos_r"), _dev(pt, torch.int32, "pos_t"),
-        _dev(pos_w, torch.float32, "pos_w"), C.c_int64(n_pos),
-        _dev(nh, torch.int32, "neg_h"), _dev(nr, torch.int32, "neg_r"), _dev(nt, torch.int32, "neg_t"),
-        _dev(neg_w, torch.float32, "neg_w"), C.c_int64(n_neg), C.c_int(neg_per_pos), C.c_float(scale),
-        _dev(grad_ent, torch.float32, "grad_ent"), _dev(grad_rel, torch.float32, "grad_rel"), C.c_int(rel_copies),
-        _dev(touched_ent, torch.int32, "touched_ent"), _dev(touched_rel, torch.int32, "touched_rel"), C.c_int32(tag),
-        _dev(loss_partials, torch.float64, "loss_partials"), _stream())
-    _check(rc, "mke_triple_score_fwd_bwd")
-
-
 def count_entity_refs(pos_h, pos_t, neg_h, neg_t, neg_per_pos, ref_count):
     rc = lib().mke_count_entity_refs(_dev(pos_h, torch.int32, "pos_h"), _dev(pos_t, torch.int32, "pos_t"),
                                      C.c_int64(pos_h.numel()), _dev(neg_h, torch.int32, "neg_h"),
@@ -391,59 +361,58 @@ def count_entity_refs(pos_h, pos_t, neg_h, neg_t, neg_per_pos, ref_count):
     _check(rc, "mke_count_entity_refs")
 
 
+def _score_step(ent, ent_normalize, rel, rel_normalize, dim, pos, pos_w, neg, neg_w, neg_per_pos, scale, grad_ent, grad_rel,
+                touched_ent, touched_rel, tag, loss_partials, **more):
+    """mke_triple_score_step: one ScoreArgs filled from tensors (pos / neg = (h, r, t) int32 CUDA tensors, neg may be None;
+    grad_rel [K, n_rel, stride] = K privatised copies, or [n_rel, stride]).  `more`: the remaining fields, as values ready
+    for the struct."""
+    i32, f32 = torch.int32, torch.float32
+    a = ScoreArgs(**more)
+    a.ent_table, a.n_ent, a.ent_normalize = ptr(ent, f32, "ent_table"), ent.shape[0], int(ent_normalize)
+    a.rel_table, a.n_rel, a.rel_normalize = ptr(rel, f32, "rel_table"), rel.shape[0], int(rel_normalize)
+    a.stride, a.dim = ent.shape[1], dim
+    ph, pr, pt = pos
+    nh, nr, nt = neg if neg is not None else (None, None, None)
+    a.pos_h, a.pos_r, a.pos_t = ptr(ph, i32, "pos_h"), ptr(pr, i32, "pos_r"), ptr(pt, i32, "pos_t")
+    a.pos_w, a.n_pos = ptr(pos_w, f32, "pos_w"), ph.numel()
+    a.neg_h, a.neg_r, a.neg_t = ptr(nh, i32, "neg_h"), ptr(nr, i32, "neg_r"), ptr(nt, i32, "neg_t")
+    a.neg_w, a.n_neg = ptr(neg_w, f32, "neg_w"), 0 if nh is None else nh.numel()
+    a.neg_per_pos, a.scale = neg_per_pos, scale
+    a.grad_ent, a.grad_rel = ptr(grad_ent, f32, "grad_ent"), ptr(grad_rel, f32, "grad_rel")
+    a.grad_rel_copies = 1 if grad_rel is None or grad_rel.dim() == 2 else grad_rel.shape[0]
+    a.touched_ent, a.touched_rel, a.tag = ptr(touched_ent, i32, "touched_ent"), ptr(touched_rel, i32, "touched_rel"), tag
+    a.loss_partials = ptr(loss_partials, torch.float64, "loss_partials")
+    _check(lib().mke_triple_score_step(C.byref(a), _stream()), "mke_triple_score_step")
+
+
+def triple_score_fwd_bwd(ent, ent_normalize, rel, rel_normalize, dim, pos, pos_w, neg, neg_w, neg_per_pos, scale,
+                         grad_ent, grad_rel, touched_ent, touched_rel, tag, loss_partials):
+    """The fused relation-view step, forward (grad_ent None) or forward / backward (header section (1))."""
+    _score_step(ent, ent_normalize, rel, rel_normalize, dim, pos, pos_w, neg, neg_w, neg_per_pos, scale, grad_ent, grad_rel,
+                touched_ent, touched_rel, tag, loss_partials)
+
+
 def triple_score_fwd_bwd_x(ent, ent_normalize, rel, rel_normalize, dim, pos, pos_w, neg, neg_w, neg_per_pos, scale, grad_ent,
                            grad_rel, touched_ent, touched_rel, tag, ref_count, ent_acc, optimizer, lr, loss_partials, hot=None,
                            tuning=None):
-    """mke_triple_score_fwd_bwd_x: the fused step with the exclusive-row fast path (ref_count filled by
-    count_entity_refs for the same batch).  hot (HotRowsStruct of the entity table, `EmbeddingTable.hot_struct()`): the hub
-    rows' flushes go to their private copies (mke_triple_score_fwd_bwd_xch); the update must then get the same struct."""
-    ph, pr, pt = pos
-    nh, nr, nt = neg
-    rel_copies = 1 if grad_rel.dim() == 2 else grad_rel.shape[0]
-    if tuning is not None:       # this call's knobs (TuningStruct): mke_triple_score_fwd_bwd_t
-        rc = lib().mke_triple_score_fwd_bwd_t(
-            _dev(ent, torch.float32, "ent_table"), C.c_int64(ent.shape[0]), C.c_int(int(ent_normalize)),
-            _dev(rel, torch.float32, "rel_table"), C.c_int64(rel.shape[0]), C.c_int(int(rel_normalize)),
-            C.c_int(ent.shape[1]), C.c_int(dim),
-            _dev(ph, torch.int32, "pos_h"), _dev(pr, torch.int32, "pos_r"), _dev(pt, torch.int32, "pos_t"),
-            _dev(pos_w, torch.float32, "pos_w"), C.c_int64(ph.numel()),
-            _dev(nh, torch.int32, "neg_h"), _dev(nr, torch.int32, "neg_r"), _dev(nt, torch.int32, "neg_t"),
-            _dev(neg_w, torch.float32, "neg_w"), C.c_int64(nh.numel()), C.c_int(neg_per_pos), C.c_float(scale),
-            _dev(grad_ent, torch.float32, "grad_ent"), _dev(grad_rel, torch.float32, "grad_rel"), C.c_int(rel_copies),
-            _dev(touched_ent, torch.int32, "touched_ent"), _dev(touched_rel, torch.int32, "touched_rel"), C.c_int32(tag),
-            _dev(ref_count, torch.int32, "ref_count"), _dev(ent_acc, torch.float32, "ent_acc"), C.c_int(optimizer), C.c_float(lr),
-            None, (C.byref(hot) if hot is not None and hot.n_hot > 0 else None), C.byref(tuning),
-            _dev(loss_partials, torch.float64, "loss_partials"), _stream())
-        _check(rc, "mke_triple_score_fwd_bwd_t")
-        return
-    if hot is not None and hot.n_hot > 0:
-        rc = lib().mke_triple_score_fwd_bwd_xch(
-            _dev(ent, torch.float32, "ent_table"), C.c_int64(ent.shape[0]), C.c_int(int(ent_normalize)),
-            _dev(rel, torch.float32, "rel_table"), C.c_int64(rel.shape[0]), C.c_int(int(rel_normalize)),
-            C.c_int(ent.shape[1]), C.c_int(dim),
-            _dev(ph, torch.int32, "pos_h"), _dev(pr, torch.int32, "pos_r"), _dev(pt, torch.int32, "pos_t"),
-            _dev(pos_w, torch.float32, "pos_w"), C.c_int64(ph.numel()),
-            _dev(nh, torch.int32, "neg_h"), _dev(nr, torch.int32, "neg_r"), _dev(nt, torch.int32, "neg_t"),
-            _dev(neg_w, torch.float32, "neg_w"), C.c_int64(nh.numel()), C.c_int(neg_per_pos), C.c_float(scale),
-            _dev(grad_ent, torch.float32, "grad_ent"), _dev(grad_rel, torch.float32, "grad_rel"), C.c_int(rel_copies),
-            _dev(touched_ent, torch.int32, "touched_ent"), _dev(touched_rel, torch.int32, "touched_rel"), C.c_int32(tag),
-            _dev(ref_count, torch.int32, "ref_count"), _dev(ent_acc, torch.float32, "ent_acc"), C.c_int(optimizer), C.c_float(lr),
-            None, C.byref(hot), _dev(loss_partials, torch.float64, "loss_partials"), _stream())
-        _check(rc, "mke_triple_score_fwd_bwd_xch")
-        return
-    rc = lib().mke_triple_score_fwd_bwd_x(
-        _dev(ent, torch.float32, "ent_table"), C.c_int64(ent.shape[0]), C.c_int(int(ent_normalize)),
-        _dev(rel, torch.float32, "rel_table"), C.c_int64(rel.shape[0]), C.c_int(int(rel_normalize)),
-        C.c_int(ent.shape[1]), C.c_int(dim),
-        _dev(ph, torch.int32, "pos_h"), _dev(pr, torch.int32, "pos_r"), _dev(pt, torch.int32, "pos_t"),
-        _dev(pos_w, torch.float32, "pos_w"), C.c_int64(ph.numel()),
-        _dev(nh, torch.int32, "neg_h"), _dev(nr, torch.int32, "neg_r"), _dev(nt, torch.int32, "neg_t"),
-        _dev(neg_w, torch.float32, "neg_w"), C.c_int64(nh.numel()), C.c_int(neg_per_pos), C.c_float(scale),
-        _dev(grad_ent, torch.float32, "grad_ent"), _dev(grad_rel, torch.float32, "grad_rel"), C.c_int(rel_copies),
-        _dev(touched_ent, torch.int32, "touched_ent"), _dev(touched_rel, torch.int32, "touched_rel"), C.c_int32(tag),
-        _dev(ref_count, torch.int32, "ref_count"), _dev(ent_acc, torch.float32, "ent_acc"), C.c_int(optimizer), C.c_float(lr),
-        _dev(loss_partials, torch.float64, "loss_partials"), _stream())
-    _check(rc, "mke_triple_score_fwd_bwd_x")
+    """The fused step with the exclusive-row fast path (ref_count filled by count_entity_refs for the same batch).  hot
+    (HotRowsStruct of the entity table, `EmbeddingTable.hot_struct()`): the hub rows' flushes go to their private copies
+    (mke_score_args.hot); the update must then get the same struct.  tuning: this call's knobs (TuningStruct)."""
+    more = {"hot": hot} if hot is not None and hot.n_hot > 0 else {}
+    _score_step(ent, ent_normalize, rel, rel_normalize, dim, pos, pos_w, neg, neg_w, neg_per_pos, scale, grad_ent, grad_rel,
+                touched_ent, touched_rel, tag, loss_partials, ref_count=ptr(ref_count, torch.int32, "ref_count"),
+                ent_acc=ptr(ent_acc, torch.float32, "ent_acc"), optimizer=optimizer, lr=lr, tuning=tuning_ptr(tuning), **more)
+
+
+def triple_score_fwd_bwd_det(ent, ent_normalize, rel, rel_normalize, dim, pos, pos_w, neg, neg_w, neg_per_pos, scale, grad_ent,
+                             grad_rel, touched_ent, touched_rel, tag, ref_count, ent_acc, optimizer, lr, stage_rows, stage_keys,
+                             loss_partials):
+    """The same step in deterministic mode: contributions stored into stage_rows / stage_keys (then stage_reduce)."""
+    _score_step(ent, ent_normalize, rel, rel_normalize, dim, pos, pos_w, neg, neg_w, neg_per_pos, scale, grad_ent, grad_rel,
+                touched_ent, touched_rel, tag, loss_partials, ref_count=ptr(ref_count, torch.int32, "ref_count"),
+                ent_acc=ptr(ent_acc, torch.float32, "ent_acc"), optimizer=optimizer, lr=lr,
+                stage_rows=ptr(stage_rows, torch.float32, "stage_rows"), stage_keys=ptr(stage_keys, torch.int64, "stage_keys"),
+                stage_slots=stage_keys.numel())
 
 
 def rows_update(table, acc, grad, touched, tag, dim, normalize, optimizer, lr):

@@ -848,8 +848,6 @@ int launch_gemm_f32_pair(const float* A0, int64_t a0_rs, int64_t a0_cs, const fl
                          int64_t ldc0, int M0, int N0, int K0, int splits0, int acc0, const float* A1, int64_t a1_rs, int64_t a1_cs,
                          const float* B1, int64_t b1_rs, int64_t b1_cs, float* C1, int64_t ldc1, int M1, int N1, int K1, int splits1,
                          int acc1, hipStream_t st);
-int launch_rows_update_multi(const mke_update_table* tables, int n_tables, int32_t tag, int stride, int dim, int optimizer,
-                             float lr, hipStream_t st, const mke_count_job* count, const DenseJob* dense);
 
 
 static int conv_dispatch(const ConvParams& p, bool bwd, hipStream_t st) {

@@ -171,6 +171,10 @@ struct DenseJob {
   float* ws;
   int ws_n, ws_stride, ws_copies;
 };
+// mke_rows_update_multi* behind the C-ABI (mke_update.hip): the touched-row update of up to MKE_MAX_UPDATE_TABLES tables, with
+// optional rider blocks for the next step's reference counting and for a dense parameter update
+int launch_rows_update_multi(const mke_update_table* tables, int n_tables, int32_t tag, int stride, int dim, int optimizer,
+                             float lr, hipStream_t st, const mke_count_job* count = nullptr, const DenseJob* dense = nullptr);
 __device__ __forceinline__ void dense_update_range(const DenseJob& j, int64_t block, int64_t n_blocks) {
   for (int64_t i = block * MKE_BLOCK + threadIdx.x; i < j.n; i += n_blocks * MKE_BLOCK) {
     float gv = j.g[i];

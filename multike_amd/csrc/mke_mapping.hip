@@ -17,8 +17,6 @@ namespace mke {
 
 int launch_gemm_f32(const float* A, int64_t a_rs, int64_t a_cs, const float* B, int64_t b_rs, int64_t b_cs, float* C, int64_t ldc,
                     int M, int N, int K, int splits, int accumulate, hipStream_t st, double* tanh_sumsq_partials, int epi_plain);
-int launch_rows_update_multi(const mke_update_table* tables, int n_tables, int32_t tag, int stride, int dim, int optimizer,
-                             float lr, hipStream_t st, const mke_count_job* count, const DenseJob* dense);
 
 __device__ __forceinline__ double partials_total(const double* __restrict__ partials, double* s_w, double* s_tot) {
   double v = 0.0;

@@ -790,11 +790,6 @@ extern "C" int mke_oc_apply(const mke_oc_step* s, const float* gv, void* stream)
   return check_launch("k_oc_apply");
 }
 
-namespace mke {
-int launch_rows_update_multi(const mke_update_table* tables, int n_tables, int32_t tag, int stride, int dim, int optimizer,
-                             float lr, hipStream_t st, const mke_count_job* count, const struct DenseJob* dense);
-}
-
 // Several phases of one part's step in ONE call (host overhead: the step is 5 launches of 5-50 us each): bit 0 bases, 1 count,
 // 2 score, 3 apply, 4 the row update (relation table: every row; shard: touched rows).  What lies between two collectives
 // goes into one call: single rank: 31;  G > 1: 1 | all-gather | 6 | reduce-scatter | 8 | all-reduce | 16.

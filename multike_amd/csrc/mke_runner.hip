@@ -8,9 +8,23 @@ namespace mke {
 #define RUN_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_error("mke_relation_steps: %s: %s", #x, hipGetErrorString(e_)); rc = (int)e_; goto done; } } while (0)
 #define RUN_MKE(x) do { rc = (x); if (rc) goto done; } while (0)
 
+// What changes from step to step in the score launch's arguments (the rest is filled once per plan: mke_relation_steps)
+static void score_step_args(const mke_relation_plan* pl, int s, int64_t no /* offset of its negatives in neg_* */, int32_t* refc, mke_score_args* sa) {
+  const int N = pl->neg_per_pos;
+  const int64_t lo = pl->step_off[s], hi = pl->step_off[s + 1];
+  sa->pos_h = pl->pos_h + lo; sa->pos_r = pl->pos_r + lo; sa->pos_t = pl->pos_t + lo; sa->pos_w = pl->pos_w ? pl->pos_w + lo : nullptr;
+  sa->n_pos = hi - lo;
+  sa->neg_h = N ? pl->neg_h + no : nullptr; sa->neg_r = N ? pl->neg_r + no : nullptr; sa->neg_t = N ? pl->neg_t + no : nullptr;
+  sa->n_neg = (hi - lo) * N;
+  sa->tag = pl->tag_base + s;
+  sa->ref_count = refc;
+  sa->loss_partials = pl->loss_partials + (int64_t)(s % pl->loss_ring) * MKE_LOSS_PARTIALS;
+}
+
 // Overlapped schedule: a second stream runs the work that does not depend on the tables — reference counting of step
 // s+1 and negative sampling of chunk c+1 — while the main stream scores and updates step s.
-static int run_overlapped(const mke_relation_plan* pl, int step_begin, int step_end, hipStream_t mainS, const mke_update_table* ut_in) {
+static int run_overlapped(const mke_relation_plan* pl, int step_begin, int step_end, hipStream_t mainS, const mke_update_table* ut_in,
+                          mke_score_args sa) {
   int rc = MKE_OK;
   const int N = pl->neg_per_pos, SC = pl->sample_chunk;
   hipStream_t side = nullptr;
@@ -71,15 +85,10 @@ static int run_overlapped(const mke_relation_plan* pl, int step_begin, int step_
     const int b = s & 1, c = s / SC;
     if (s == chunk_lo(c)) RUN_HIP(hipStreamWaitEvent(mainS, evS[c & 1], 0));
     RUN_HIP(hipStreamWaitEvent(mainS, evC[b], 0));
-    const int64_t lo = pl->step_off[s], hi = pl->step_off[s + 1], no = neg_off(s);
     const int32_t tag = pl->tag_base + s;
     int32_t* refc = pl->ent_ref_count + (int64_t)b * pl->n_ent;
-    RUN_MKE(mke_triple_score_fwd_bwd_x(pl->ent_table, pl->n_ent, pl->ent_normalize, pl->rel_table, pl->n_rel, pl->rel_normalize,
-                                       pl->stride, pl->dim, pl->pos_h + lo, pl->pos_r + lo, pl->pos_t + lo, pl->pos_w ? pl->pos_w + lo : nullptr, hi - lo,
-                                       pl->neg_h + no, pl->neg_r + no, pl->neg_t + no, nullptr, (hi - lo) * N, N, pl->scale,
-                                       pl->ent_grad, pl->rel_grad, pl->rel_grad_copies, pl->ent_touched, pl->rel_touched, tag, refc,
-                                       pl->ent_acc, pl->optimizer, pl->lr,
-                                       pl->loss_partials + (int64_t)(s % pl->loss_ring) * MKE_LOSS_PARTIALS, mainS));
+    score_step_args(pl, s, neg_off(s), refc, &sa);
+    RUN_MKE(mke_triple_score_step(&sa, mainS));
     ut[1].ref_count = refc;
     RUN_MKE(mke_rows_update_multi(ut, 2, tag, pl->stride, pl->dim, pl->optimizer, pl->lr, mainS));
     RUN_HIP(hipEventRecord(evU[b], mainS));
@@ -121,13 +130,20 @@ extern "C" int mke_relation_steps(const mke_relation_plan* pl, int step_begin, i
   ut[1].table = pl->ent_table; ut[1].acc = pl->ent_acc; ut[1].grad = pl->ent_grad; ut[1].touched = pl->ent_touched;
   ut[1].n_rows = pl->n_ent; ut[1].normalize = pl->ent_normalize; ut[1].grad_copies = 1; ut[1].ref_count = nullptr;
   ut[1].hot = pl->hot;     // hub rows of the entity table (slot == NULL: none)
-  const mke_hot_rows* hot = (pl->hot.slot && pl->hot.n_hot > 0) ? &pl->hot : nullptr;
+  mke_score_args sa = {};  // the score launch: per step only score_step_args changes (tuning: this call's scope, above)
+  sa.ent_table = pl->ent_table; sa.n_ent = pl->n_ent; sa.ent_normalize = pl->ent_normalize;
+  sa.rel_table = pl->rel_table; sa.n_rel = pl->n_rel; sa.rel_normalize = pl->rel_normalize; sa.stride = pl->stride; sa.dim = pl->dim;
+  sa.neg_per_pos = N; sa.scale = pl->scale;
+  sa.grad_ent = pl->ent_grad; sa.grad_rel = pl->rel_grad; sa.grad_rel_copies = pl->rel_grad_copies;
+  sa.touched_ent = pl->ent_touched; sa.touched_rel = pl->rel_touched;
+  sa.ent_acc = pl->ent_acc; sa.optimizer = pl->optimizer; sa.lr = pl->lr;
 
   if (pl->overlap) {
     if (N <= 0 || !pl->ent_ref_count) { set_error("overlap mode needs negatives and the reference-count scratch"); return MKE_E_SHAPE; }
     if (step_begin == step_end) return MKE_OK;
-    return run_overlapped(pl, step_begin, step_end, (hipStream_t)stream, ut);
+    return run_overlapped(pl, step_begin, step_end, (hipStream_t)stream, ut, sa);   // no count rider, no hub rows in the score launch
   }
+  sa.hot = pl->hot;
 
   int64_t chunk_lo = 0;  // first positive (epoch position) whose negatives sit at neg_*[0]
   int chunk_end = step_begin;  // steps < chunk_end are sampled
@@ -171,13 +187,9 @@ extern "C" int mke_relation_steps(const mke_relation_plan* pl, int step_begin, i
       counted_ahead = true;
     }
     const bool in_score = tune_count_in_score() != 0;
-    rc = mke_triple_score_fwd_bwd_xch(pl->ent_table, pl->n_ent, pl->ent_normalize, pl->rel_table, pl->n_rel, pl->rel_normalize,
-                                     pl->stride, pl->dim, pl->pos_h + lo, pl->pos_r + lo, pl->pos_t + lo, pl->pos_w ? pl->pos_w + lo : nullptr, hi - lo,
-                                     N ? pl->neg_h + no : nullptr, N ? pl->neg_r + no : nullptr, N ? pl->neg_t + no : nullptr,
-                                     nullptr, (hi - lo) * N, N, pl->scale, pl->ent_grad, pl->rel_grad, pl->rel_grad_copies,
-                                     pl->ent_touched, pl->rel_touched, tag, refc, pl->ent_acc, pl->optimizer, pl->lr,
-                                     in_score ? cjp : nullptr, hot,
-                                     pl->loss_partials + (int64_t)(s % pl->loss_ring) * MKE_LOSS_PARTIALS, stream);
+    score_step_args(pl, s, no, refc, &sa);
+    sa.next_count = in_score ? cjp : nullptr;
+    rc = mke_triple_score_step(&sa, stream);
     if (rc) return rc;
     ut[1].ref_count = refc;
     if (in_score) cjp = nullptr;

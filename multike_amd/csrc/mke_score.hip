@@ -497,22 +497,38 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_count_refs(const int32_t* __restr
 
 }  // namespace mke
 
-static int score_impl(
-    const float* ent_table, int64_t n_ent, int ent_normalize, const float* rel_table, int64_t n_rel,
-    int rel_normalize, int stride, int dim, const int32_t* pos_h, const int32_t* pos_r, const int32_t* pos_t,
-    const float* pos_w, int64_t n_pos, const int32_t* neg_h, const int32_t* neg_r, const int32_t* neg_t,
-    const float* neg_w, int64_t n_neg, int neg_per_pos, float scale, float* grad_ent, float* grad_rel,
-    int grad_rel_copies, int32_t* touched_ent, int32_t* touched_rel, int32_t tag, double* loss_partials, void* stream,
-    int32_t* ref_count, float* ent_w, float* ent_acc, int optimizer, float lr, float* stage_rows = nullptr,
-    int64_t* stage_keys = nullptr, int64_t stage_slots = 0, const mke_count_job* next_count = nullptr,
-    const mke_hot_rows* hot = nullptr) {
+namespace mke {
+// The 12 instantiations of one row width, and the run-time flags that select each:
+//   det (deterministic staging)            x {X, !X}          DET is its own instantiation (see k_triple_score), never O32 / LID
+//   x && o32 (the training step, < 4 GB)   x {LID on, off}    32-bit row offsets exist only with the exclusive-row path
+//   otherwise                              x {X, !X}
+// each for QPG = 2 (two groups per wavefront) and 4.
+template <int FPL, int U, int QPG>
+static void launch_score(bool det, bool x, bool o32, bool lid, hipStream_t st, const ScoreParams& p) {
+#define MKE_SCORE_LAUNCH(...) hipLaunchKernelGGL((k_triple_score<FPL, U, __VA_ARGS__>), dim3(MKE_LOSS_PARTIALS), dim3(MKE_BLOCK), 0, st, p)
+  if (det) { if (x) MKE_SCORE_LAUNCH(true, QPG, true); else MKE_SCORE_LAUNCH(false, QPG, true); }
+  else if (x && o32) { if (lid) MKE_SCORE_LAUNCH(true, QPG, false, true, true); else MKE_SCORE_LAUNCH(true, QPG, false, true); }
+  else { if (x) MKE_SCORE_LAUNCH(true, QPG); else MKE_SCORE_LAUNCH(false, QPG); }
+#undef MKE_SCORE_LAUNCH
+}
+}  // namespace mke
+
+static int score_impl(const mke_score_args& a, void* stream) {
   using namespace mke;
-  if (!ent_table || !rel_table || !loss_partials) { set_error("mke_triple_score_fwd_bwd: NULL table/loss"); return MKE_E_NULL; }
-  if (n_pos < 0 || n_neg < 0 || n_ent <= 0 || n_rel <= 0) { set_error("negative count"); return MKE_E_SHAPE; }
-  if (n_pos > 0 && (!pos_h || !pos_r || !pos_t)) { set_error("NULL positive index stream"); return MKE_E_NULL; }
-  if (n_neg > 0 && (!neg_h || !neg_r || !neg_t)) { set_error("NULL negative index stream"); return MKE_E_NULL; }
-  if (stride <= 0 || stride % 16 != 0 || dim <= 0 || dim > stride || stride > MKE_MAX_STRIDE) {
-    set_error("bad stride/dim: stride=%d dim=%d (stride %% 16 == 0, dim <= stride <= %d)", stride, dim, MKE_MAX_STRIDE);
+  TuningScope scope(a.tuning);      // this call's knobs (NULL: the enclosing call's / the process defaults)
+  const int64_t n_pos = a.n_pos, n_neg = a.n_neg;
+  const int stride = a.stride, neg_per_pos = a.neg_per_pos;
+  const bool det = a.stage_keys != nullptr;
+  if (a.optimizer != MKE_OPT_ADAGRAD && a.optimizer != MKE_OPT_SGD) { set_error("unsupported optimizer %d", a.optimizer); return MKE_E_UNSUPPORTED; }
+  if (a.ref_count && a.optimizer == MKE_OPT_ADAGRAD && !a.ent_acc) { set_error("exclusive-row path with Adagrad needs ent_acc"); return MKE_E_NULL; }
+  if (a.ref_count && !a.grad_ent) { set_error("exclusive-row path needs the gradient scratch (it is a training step)"); return MKE_E_NULL; }
+  if (det && !a.stage_rows) { set_error("deterministic mode: NULL staging buffers"); return MKE_E_NULL; }
+  if (!a.ent_table || !a.rel_table || !a.loss_partials) { set_error("mke_triple_score_step: NULL table/loss"); return MKE_E_NULL; }
+  if (n_pos < 0 || n_neg < 0 || a.n_ent <= 0 || a.n_rel <= 0) { set_error("negative count"); return MKE_E_SHAPE; }
+  if (n_pos > 0 && (!a.pos_h || !a.pos_r || !a.pos_t)) { set_error("NULL positive index stream"); return MKE_E_NULL; }
+  if (n_neg > 0 && (!a.neg_h || !a.neg_r || !a.neg_t)) { set_error("NULL negative index stream"); return MKE_E_NULL; }
+  if (stride <= 0 || stride % 16 != 0 || a.dim <= 0 || a.dim > stride || stride > MKE_MAX_STRIDE) {
+    set_error("bad stride/dim: stride=%d dim=%d (stride %% 16 == 0, dim <= stride <= %d)", stride, a.dim, MKE_MAX_STRIDE);
     return MKE_E_SHAPE;
   }
   if (neg_per_pos < 0 || (neg_per_pos > 0 && n_neg != n_pos * (int64_t)neg_per_pos)) {
@@ -520,15 +536,16 @@ static int score_impl(
               (long long)n_pos, neg_per_pos);
     return MKE_E_SHAPE;
   }
-  if ((grad_ent == nullptr) != (grad_rel == nullptr)) { set_error("grad_ent and grad_rel must both be given or both NULL"); return MKE_E_NULL; }
-  if (grad_ent && (!touched_ent || !touched_rel)) { set_error("NULL touched array"); return MKE_E_NULL; }
-  if (grad_ent && (grad_rel_copies < 1 || grad_rel_copies > 64)) { set_error("grad_rel_copies must be in [1,64]"); return MKE_E_SHAPE; }
+  if ((a.grad_ent == nullptr) != (a.grad_rel == nullptr)) { set_error("grad_ent and grad_rel must both be given or both NULL"); return MKE_E_NULL; }
+  if (a.grad_ent && (!a.touched_ent || !a.touched_rel)) { set_error("NULL touched array"); return MKE_E_NULL; }
+  const int grad_rel_copies = det ? 1 : a.grad_rel_copies;   // deterministic mode: one flush slot per group
+  if (a.grad_ent && (grad_rel_copies < 1 || grad_rel_copies > 64)) { set_error("grad_rel_copies must be in [1,64]"); return MKE_E_SHAPE; }
 
   ScoreParams p;
-  p.ent = ent_table; p.rel = rel_table; p.ent_norm = ent_normalize; p.rel_norm = rel_normalize;
-  p.stride = stride; p.dim = dim;
-  p.ph = pos_h; p.pr = pos_r; p.pt = pos_t; p.pw = pos_w; p.n_pos = n_pos;
-  p.nh = neg_h; p.nr = neg_r; p.nt = neg_t; p.nw = neg_w; p.n_neg = n_neg;
+  p.ent = a.ent_table; p.rel = a.rel_table; p.ent_norm = a.ent_normalize; p.rel_norm = a.rel_normalize;
+  p.stride = stride; p.dim = a.dim;
+  p.ph = a.pos_h; p.pr = a.pos_r; p.pt = a.pos_t; p.pw = a.pos_w; p.n_pos = n_pos;
+  p.nh = a.neg_h; p.nr = a.neg_r; p.nt = a.neg_t; p.nw = a.neg_w; p.n_neg = n_neg;
   p.npp = neg_per_pos;
   const int64_t total_waves = (int64_t)MKE_LOSS_PARTIALS * (MKE_BLOCK / 64);
   int splits = 1;
@@ -541,42 +558,43 @@ static int score_impl(
     if (s > neg_per_pos) s = neg_per_pos;
     splits = (int)s;
   }
-  if (stage_keys) {  // deterministic mode: one flush per group (its slot), every contribution has a slot of its own
+  if (det) {  // deterministic mode: one flush per group (its slot), every contribution has a slot of its own
     splits = 1;
     const int64_t need = (neg_per_pos > 0 ? n_pos * (neg_per_pos + 1) : n_pos + n_neg) * 3;
-    if (!stage_rows || !grad_ent || need > stage_slots) { set_error("deterministic mode: %lld staging slots needed, %lld given", (long long)need, (long long)stage_slots); return MKE_E_SHAPE; }
+    if (!a.grad_ent || need > a.stage_slots) { set_error("deterministic mode: %lld staging slots needed, %lld given", (long long)need, (long long)a.stage_slots); return MKE_E_SHAPE; }
   }
-  p.stage_rows = stage_rows; p.stage_keys = stage_keys;
+  p.stage_rows = a.stage_rows; p.stage_keys = a.stage_keys;
   p.hot_slot = nullptr; p.n_hot = 0; p.hot_copies = 1; p.hot_row0 = 0;
-  if (hot && hot->slot && hot->n_hot > 0 && grad_ent && !stage_keys) {
-    if (hot->copies < 1 || hot->row0 < n_ent || (hot->row0 + (int64_t)hot->copies * hot->n_hot) * stride >= (1ll << 31)) {
+  const mke_hot_rows& hot = a.hot;
+  if (hot.slot && hot.n_hot > 0 && a.grad_ent && !det) {
+    if (hot.copies < 1 || hot.row0 < a.n_ent || (hot.row0 + (int64_t)hot.copies * hot.n_hot) * stride >= (1ll << 31)) {
       set_error("hub rows: copies >= 1, row0 >= n_ent and the copy rows inside 2^31 floats of the scratch");
       return MKE_E_SHAPE;
     }
-    p.hot_slot = hot->slot; p.n_hot = hot->n_hot; p.hot_copies = hot->copies; p.hot_row0 = (int32_t)hot->row0;
+    p.hot_slot = hot.slot; p.n_hot = hot.n_hot; p.hot_copies = hot.copies; p.hot_row0 = (int32_t)hot.row0;
   }
   p.cj = mke_count_job{};
   p.count_blocks = 0;
-  if (next_count && next_count->n_pos + next_count->n_neg > 0) {
-    if (!next_count->ref_count || !next_count->pos_h || !next_count->pos_t || (next_count->n_neg > 0 && (!next_count->neg_h || !next_count->neg_t))) { set_error("count job: NULL pointer"); return MKE_E_NULL; }
-    int64_t cb = (next_count->n_pos + next_count->n_neg + 4 * MKE_BLOCK - 1) / (4 * MKE_BLOCK);
-    p.cj = *next_count;
+  if (const mke_count_job* nc = a.next_count; nc && nc->n_pos + nc->n_neg > 0) {
+    if (!nc->ref_count || !nc->pos_h || !nc->pos_t || (nc->n_neg > 0 && (!nc->neg_h || !nc->neg_t))) { set_error("count job: NULL pointer"); return MKE_E_NULL; }
+    int64_t cb = (nc->n_pos + nc->n_neg + 4 * MKE_BLOCK - 1) / (4 * MKE_BLOCK);
+    p.cj = *nc;
     if (p.cj.neg_per_pos < 1) p.cj.neg_per_pos = 1;
     p.count_blocks = (int)std::min<int64_t>(cb, MKE_LOSS_PARTIALS / 4);
   }
   p.splits = splits;
-  p.scale = scale;
-  p.gent = grad_ent; p.grel = grad_rel; p.grel_copies = grad_rel_copies < 1 ? 1 : grad_rel_copies;
-  p.grel_copy_elems = n_rel * (int64_t)stride;
-  p.tent = touched_ent; p.trel = touched_rel; p.tag = tag;
-  p.lossp = loss_partials;
-  const bool excl = ref_count != nullptr && grad_ent != nullptr && neg_per_pos > 0;
-  p.refcount = excl ? ref_count : nullptr; p.ent_w = ent_w; p.ent_acc = ent_acc; p.optimizer = optimizer; p.lr = lr;
-  hipStream_t st = (hipStream_t)stream;
+  p.scale = a.scale;
+  p.gent = a.grad_ent; p.grel = a.grad_rel; p.grel_copies = grad_rel_copies < 1 ? 1 : grad_rel_copies;
+  p.grel_copy_elems = a.n_rel * (int64_t)stride;
+  p.tent = a.touched_ent; p.trel = a.touched_rel; p.tag = a.tag;
+  p.lossp = a.loss_partials;
+  const bool excl = a.ref_count != nullptr && neg_per_pos > 0;   // (a training step: checked above)
+  p.refcount = excl ? a.ref_count : nullptr; p.ent_w = a.ent_table;
+  p.ent_acc = a.optimizer == MKE_OPT_ADAGRAD ? a.ent_acc : nullptr; p.optimizer = a.optimizer; p.lr = a.lr;
   const int fpl = stride / 16;
   // every row address of the launch fits 32 bits of byte offset (entity table = accumulator = gradient scratch in size)
-  const int64_t grad_rows = p.hot_slot ? (int64_t)p.hot_row0 + (int64_t)p.hot_copies * p.n_hot : n_ent;
-  const bool o32 = tune_score_o32() && grad_rows * (int64_t)stride < (1ll << 30) && n_rel * (int64_t)stride < (1ll << 30);
+  const int64_t grad_rows = p.hot_slot ? (int64_t)p.hot_row0 + (int64_t)p.hot_copies * p.n_hot : a.n_ent;
+  const bool o32 = tune_score_o32() && grad_rows * (int64_t)stride < (1ll << 30) && a.n_rel * (int64_t)stride < (1ll << 30);
   MKE_DISPATCH_FPL(fpl, {
     // corrupt rows in flight per quarter-wave.  2, not 4, at FPL <= 5: with the accumulator rows of the exclusive-row path
     // U = 4 costs 144-153 registers = 3 waves per SIMD, U = 2 119 = 4 waves per SIMD, and the extra wave hides more
@@ -591,105 +609,34 @@ static int score_impl(
     const int half_max = tune_score_half_max() >= 0 ? tune_score_half_max() : (FPL <= 8 ? 64 : 31);
     const bool half = neg_per_pos > 0 && neg_per_pos <= half_max && splits == 1;
     if (n_pos * (int64_t)splits > 0xFFFFFFFFll || n_pos + n_neg > 0xFFFFFFFFll) { set_error("more than 2^32 work items in one launch"); return MKE_E_RANGE; }
-    if (stage_keys) {
-      // deterministic mode: staging stores instead of atomics
-      if (half) {
-        if (excl) hipLaunchKernelGGL((k_triple_score<FPL, U, true, 2, true>), dim3(MKE_LOSS_PARTIALS), dim3(MKE_BLOCK), 0, st, p);
-        else hipLaunchKernelGGL((k_triple_score<FPL, U, false, 2, true>), dim3(MKE_LOSS_PARTIALS), dim3(MKE_BLOCK), 0, st, p);
-      } else {
-        if (excl) hipLaunchKernelGGL((k_triple_score<FPL, U, true, 4, true>), dim3(MKE_LOSS_PARTIALS), dim3(MKE_BLOCK), 0, st, p);
-        else hipLaunchKernelGGL((k_triple_score<FPL, U, false, 4, true>), dim3(MKE_LOSS_PARTIALS), dim3(MKE_BLOCK), 0, st, p);
-      }
-    } else if (excl && o32) {   // the training step on tables below 4 GB: 32-bit row offsets (row_at)
-      if (half && tune_score_lane_ids()) hipLaunchKernelGGL((k_triple_score<FPL, U, true, 2, false, true, true>), dim3(MKE_LOSS_PARTIALS), dim3(MKE_BLOCK), 0, st, p);
-      else if (half) hipLaunchKernelGGL((k_triple_score<FPL, U, true, 2, false, true>), dim3(MKE_LOSS_PARTIALS), dim3(MKE_BLOCK), 0, st, p);
-      else if (tune_score_lane_ids()) hipLaunchKernelGGL((k_triple_score<FPL, U, true, 4, false, true, true>), dim3(MKE_LOSS_PARTIALS), dim3(MKE_BLOCK), 0, st, p);
-      else hipLaunchKernelGGL((k_triple_score<FPL, U, true, 4, false, true>), dim3(MKE_LOSS_PARTIALS), dim3(MKE_BLOCK), 0, st, p);
-    } else if (half) {
-      if (excl) hipLaunchKernelGGL((k_triple_score<FPL, U, true, 2>), dim3(MKE_LOSS_PARTIALS), dim3(MKE_BLOCK), 0, st, p);
-      else hipLaunchKernelGGL((k_triple_score<FPL, U, false, 2>), dim3(MKE_LOSS_PARTIALS), dim3(MKE_BLOCK), 0, st, p);
-    } else {
-      if (excl) hipLaunchKernelGGL((k_triple_score<FPL, U, true, 4>), dim3(MKE_LOSS_PARTIALS), dim3(MKE_BLOCK), 0, st, p);
-      else hipLaunchKernelGGL((k_triple_score<FPL, U, false, 4>), dim3(MKE_LOSS_PARTIALS), dim3(MKE_BLOCK), 0, st, p);
-    }
+    const bool lid = tune_score_lane_ids() != 0;
+    if (half) launch_score<FPL, U, 2>(det, excl, o32, lid, (hipStream_t)stream, p);
+    else launch_score<FPL, U, 4>(det, excl, o32, lid, (hipStream_t)stream, p);
   });
   return check_launch("k_triple_score");
 }
 
+// the positional forward / backward of section (1): no exclusive-row path, no riders
 extern "C" int mke_triple_score_fwd_bwd(
     const float* ent_table, int64_t n_ent, int ent_normalize, const float* rel_table, int64_t n_rel,
     int rel_normalize, int stride, int dim, const int32_t* pos_h, const int32_t* pos_r, const int32_t* pos_t,
     const float* pos_w, int64_t n_pos, const int32_t* neg_h, const int32_t* neg_r, const int32_t* neg_t,
     const float* neg_w, int64_t n_neg, int neg_per_pos, float scale, float* grad_ent, float* grad_rel,
     int grad_rel_copies, int32_t* touched_ent, int32_t* touched_rel, int32_t tag, double* loss_partials, void* stream) {
-  return score_impl(ent_table, n_ent, ent_normalize, rel_table, n_rel, rel_normalize, stride, dim, pos_h, pos_r, pos_t, pos_w,
-                    n_pos, neg_h, neg_r, neg_t, neg_w, n_neg, neg_per_pos, scale, grad_ent, grad_rel, grad_rel_copies,
-                    touched_ent, touched_rel, tag, loss_partials, stream, nullptr, nullptr, nullptr, 0, 0.f);
+  mke_score_args a = {};
+  a.ent_table = const_cast<float*>(ent_table); a.n_ent = n_ent; a.ent_normalize = ent_normalize;   // not written: ref_count stays NULL
+  a.rel_table = rel_table; a.n_rel = n_rel; a.rel_normalize = rel_normalize; a.stride = stride; a.dim = dim;
+  a.pos_h = pos_h; a.pos_r = pos_r; a.pos_t = pos_t; a.pos_w = pos_w; a.n_pos = n_pos;
+  a.neg_h = neg_h; a.neg_r = neg_r; a.neg_t = neg_t; a.neg_w = neg_w; a.n_neg = n_neg; a.neg_per_pos = neg_per_pos;
+  a.scale = scale; a.grad_ent = grad_ent; a.grad_rel = grad_rel; a.grad_rel_copies = grad_rel_copies;
+  a.touched_ent = touched_ent; a.touched_rel = touched_rel; a.tag = tag; a.optimizer = MKE_OPT_ADAGRAD;
+  a.loss_partials = loss_partials;
+  return score_impl(a, stream);
 }
 
-extern "C" int mke_triple_score_fwd_bwd_xc(
-    float* ent_table, int64_t n_ent, int ent_normalize, const float* rel_table, int64_t n_rel, int rel_normalize,
-    int stride, int dim, const int32_t* pos_h, const int32_t* pos_r, const int32_t* pos_t, const float* pos_w,
-    int64_t n_pos, const int32_t* neg_h, const int32_t* neg_r, const int32_t* neg_t, const float* neg_w, int64_t n_neg,
-    int neg_per_pos, float scale, float* grad_ent, float* grad_rel, int grad_rel_copies, int32_t* touched_ent,
-    int32_t* touched_rel, int32_t tag, int32_t* ref_count, float* ent_acc, int optimizer, float lr,
-    const mke_count_job* next_count, double* loss_partials, void* stream) {
-  using namespace mke;
-  if (optimizer != MKE_OPT_ADAGRAD && optimizer != MKE_OPT_SGD) { set_error("unsupported optimizer %d", optimizer); return MKE_E_UNSUPPORTED; }
-  if (ref_count && optimizer == MKE_OPT_ADAGRAD && !ent_acc) { set_error("exclusive-row path with Adagrad needs ent_acc"); return MKE_E_NULL; }
-  if (ref_count && !grad_ent) { set_error("exclusive-row path needs the gradient scratch (it is a training step)"); return MKE_E_NULL; }
-  return score_impl(ent_table, n_ent, ent_normalize, rel_table, n_rel, rel_normalize, stride, dim, pos_h, pos_r, pos_t, pos_w,
-                    n_pos, neg_h, neg_r, neg_t, neg_w, n_neg, neg_per_pos, scale, grad_ent, grad_rel, grad_rel_copies,
-                    touched_ent, touched_rel, tag, loss_partials, stream, ref_count, ent_table,
-                    optimizer == MKE_OPT_ADAGRAD ? ent_acc : nullptr, optimizer, lr, nullptr, nullptr, 0, next_count);
-}
-
-extern "C" int mke_triple_score_fwd_bwd_xch(
-    float* ent_table, int64_t n_ent, int ent_normalize, const float* rel_table, int64_t n_rel, int rel_normalize,
-    int stride, int dim, const int32_t* pos_h, const int32_t* pos_r, const int32_t* pos_t, const float* pos_w,
-    int64_t n_pos, const int32_t* neg_h, const int32_t* neg_r, const int32_t* neg_t, const float* neg_w, int64_t n_neg,
-    int neg_per_pos, float scale, float* grad_ent, float* grad_rel, int grad_rel_copies, int32_t* touched_ent,
-    int32_t* touched_rel, int32_t tag, int32_t* ref_count, float* ent_acc, int optimizer, float lr,
-    const mke_count_job* next_count, const mke_hot_rows* hot, double* loss_partials, void* stream) {
-  using namespace mke;
-  if (optimizer != MKE_OPT_ADAGRAD && optimizer != MKE_OPT_SGD) { set_error("unsupported optimizer %d", optimizer); return MKE_E_UNSUPPORTED; }
-  if (ref_count && optimizer == MKE_OPT_ADAGRAD && !ent_acc) { set_error("exclusive-row path with Adagrad needs ent_acc"); return MKE_E_NULL; }
-  if (ref_count && !grad_ent) { set_error("exclusive-row path needs the gradient scratch (it is a training step)"); return MKE_E_NULL; }
-  return score_impl(ent_table, n_ent, ent_normalize, rel_table, n_rel, rel_normalize, stride, dim, pos_h, pos_r, pos_t, pos_w,
-                    n_pos, neg_h, neg_r, neg_t, neg_w, n_neg, neg_per_pos, scale, grad_ent, grad_rel, grad_rel_copies,
-                    touched_ent, touched_rel, tag, loss_partials, stream, ref_count, ent_table,
-                    optimizer == MKE_OPT_ADAGRAD ? ent_acc : nullptr, optimizer, lr, nullptr, nullptr, 0, next_count, hot);
-}
-
-extern "C" int mke_triple_score_fwd_bwd_t(
-    float* ent_table, int64_t n_ent, int ent_normalize, const float* rel_table, int64_t n_rel, int rel_normalize,
-    int stride, int dim, const int32_t* pos_h, const int32_t* pos_r, const int32_t* pos_t, const float* pos_w,
-    int64_t n_pos, const int32_t* neg_h, const int32_t* neg_r, const int32_t* neg_t, const float* neg_w, int64_t n_neg,
-    int neg_per_pos, float scale, float* grad_ent, float* grad_rel, int grad_rel_copies, int32_t* touched_ent,
-    int32_t* touched_rel, int32_t tag, int32_t* ref_count, float* ent_acc, int optimizer, float lr,
-    const mke_count_job* next_count, const mke_hot_rows* hot, const mke_tuning* tuning, double* loss_partials, void* stream) {
-  mke::TuningScope scope(tuning);      // this call's knobs (NULL: the process defaults)
-  return mke_triple_score_fwd_bwd_xch(ent_table, n_ent, ent_normalize, rel_table, n_rel, rel_normalize, stride, dim, pos_h, pos_r, pos_t,
-                                      pos_w, n_pos, neg_h, neg_r, neg_t, neg_w, n_neg, neg_per_pos, scale, grad_ent, grad_rel,
-                                      grad_rel_copies, touched_ent, touched_rel, tag, ref_count, ent_acc, optimizer, lr, next_count, hot,
-                                      loss_partials, stream);
-}
-
-extern "C" int mke_triple_score_fwd_bwd_x(
-    float* ent_table, int64_t n_ent, int ent_normalize, const float* rel_table, int64_t n_rel, int rel_normalize,
-    int stride, int dim, const int32_t* pos_h, const int32_t* pos_r, const int32_t* pos_t, const float* pos_w,
-    int64_t n_pos, const int32_t* neg_h, const int32_t* neg_r, const int32_t* neg_t, const float* neg_w, int64_t n_neg,
-    int neg_per_pos, float scale, float* grad_ent, float* grad_rel, int grad_rel_copies, int32_t* touched_ent,
-    int32_t* touched_rel, int32_t tag, int32_t* ref_count, float* ent_acc, int optimizer, float lr, double* loss_partials,
-    void* stream) {
-  using namespace mke;
-  if (optimizer != MKE_OPT_ADAGRAD && optimizer != MKE_OPT_SGD) { set_error("unsupported optimizer %d", optimizer); return MKE_E_UNSUPPORTED; }
-  if (ref_count && optimizer == MKE_OPT_ADAGRAD && !ent_acc) { set_error("exclusive-row path with Adagrad needs ent_acc"); return MKE_E_NULL; }
-  if (ref_count && !grad_ent) { set_error("exclusive-row path needs the gradient scratch (it is a training step)"); return MKE_E_NULL; }
-  return score_impl(ent_table, n_ent, ent_normalize, rel_table, n_rel, rel_normalize, stride, dim, pos_h, pos_r, pos_t, pos_w,
-                    n_pos, neg_h, neg_r, neg_t, neg_w, n_neg, neg_per_pos, scale, grad_ent, grad_rel, grad_rel_copies,
-                    touched_ent, touched_rel, tag, loss_partials, stream, ref_count, ent_table,
-                    optimizer == MKE_OPT_ADAGRAD ? ent_acc : nullptr, optimizer, lr);
+extern "C" int mke_triple_score_step(const mke_score_args* args, void* stream) {
+  if (!args) { mke::set_error("mke_triple_score_step: NULL args"); return MKE_E_NULL; }
+  return score_impl(*args, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -725,23 +672,6 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_stage_reduce(const float* __restr
   }
 }
 }  // namespace mke
-
-extern "C" int mke_triple_score_fwd_bwd_det(
-    float* ent_table, int64_t n_ent, int ent_normalize, const float* rel_table, int64_t n_rel, int rel_normalize,
-    int stride, int dim, const int32_t* pos_h, const int32_t* pos_r, const int32_t* pos_t, const float* pos_w,
-    int64_t n_pos, const int32_t* neg_h, const int32_t* neg_r, const int32_t* neg_t, const float* neg_w, int64_t n_neg,
-    int neg_per_pos, float scale, float* grad_ent, float* grad_rel, int32_t* touched_ent, int32_t* touched_rel, int32_t tag,
-    int32_t* ref_count, float* ent_acc, int optimizer, float lr, float* stage_rows, int64_t* stage_keys, int64_t stage_slots,
-    double* loss_partials, void* stream) {
-  using namespace mke;
-  if (optimizer != MKE_OPT_ADAGRAD && optimizer != MKE_OPT_SGD) { set_error("unsupported optimizer %d", optimizer); return MKE_E_UNSUPPORTED; }
-  if (ref_count && optimizer == MKE_OPT_ADAGRAD && !ent_acc) { set_error("exclusive-row path with Adagrad needs ent_acc"); return MKE_E_NULL; }
-  if (!stage_rows || !stage_keys) { set_error("mke_triple_score_fwd_bwd_det: NULL staging buffers"); return MKE_E_NULL; }
-  return score_impl(ent_table, n_ent, ent_normalize, rel_table, n_rel, rel_normalize, stride, dim, pos_h, pos_r, pos_t, pos_w,
-                    n_pos, neg_h, neg_r, neg_t, neg_w, n_neg, neg_per_pos, scale, grad_ent, grad_rel, 1, touched_ent, touched_rel, tag,
-                    loss_partials, stream, ref_count, ent_table, optimizer == MKE_OPT_ADAGRAD ? ent_acc : nullptr, optimizer, lr,
-                    stage_rows, stage_keys, stage_slots);
-}
 
 extern "C" int mke_stage_reduce(const float* stage_rows, const int64_t* sorted_keys, const int64_t* order, int64_t n_slots, int stride,
                                 float* grad_ent, float* grad_rel, int32_t* touched_ent, int32_t* touched_rel, int32_t tag,

@@ -329,7 +329,7 @@ static inline int chunk_for(int64_t n_rows) {
 }
 
 int launch_rows_update_multi(const mke_update_table* tables, int n_tables, int32_t tag, int stride, int dim, int optimizer,
-                             float lr, hipStream_t st, const mke_count_job* count = nullptr, const DenseJob* dense = nullptr) {
+                             float lr, hipStream_t st, const mke_count_job* count, const DenseJob* dense) {
   MultiUpdateParams mp;
   mp.n_tables = n_tables;
   mp.count_blocks = 0;

@@ -144,7 +144,7 @@ class EmbeddingTable:
 
     def set_hot_rows(self, rows, copies: int = 16):
         """Declare the hub rows of this table (ids, at most a few thousand): their gradient flushes are privatised `copies`
-        ways (mke_triple_score_fwd_bwd_xch / mke_update_table.hot).  Must be called before the scratch is first used, or
+        ways (mke_score_args.hot / mke_update_table.hot).  Must be called before the scratch is first used, or
         while it is all zero (between steps): the scratch is re-allocated with the copy rows behind the table's own."""
         rows = np.unique(np.asarray(rows, dtype=np.int64))
         if self.grad_copies != 1:
@@ -295,8 +295,8 @@ class StepEngine:
     def _relation_step_deterministic(self, ent, rel, opt_name, pos, neg, neg_per_pos, lr, pos_w, neg_w, scale, optimizer,
                                      exclusive_rows):
         """`mke_set_option("deterministic", 1)`: every gradient-row contribution is stored into a slot of its own
-        (mke_triple_score_fwd_bwd_det), a stable sort of the slot keys brings a row's contributions together in slot
-        order, mke_stage_reduce sums them front to back: bit-identical results from run to run, and hub rows whose
+        (mke_triple_score_step with mke_score_args.stage_keys), a stable sort of the slot keys brings a row's contributions
+        together in slot order, mke_stage_reduce sums them front to back: bit-identical results from run to run, and hub rows whose
         gradient is a cancelling sum of hundreds of terms are summed in ONE order (the atomic path's order changes from
         run to run).  Rows referenced once are still finished in place (one contribution: no order to fix)."""
         tag, lp = self._next()

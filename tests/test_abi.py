@@ -48,7 +48,8 @@ def test_struct_layouts_match_header():
     for cname, st in (("mke_kg_side", _lib.KGSideStruct), ("mke_update_table", _lib.UpdateTableStruct),
                       ("mke_relation_plan", _lib.RelationPlanStruct), ("mke_oc_step", _lib.OcStepStruct),
                       ("mke_ae_plan", _lib.AEPlanStruct), ("mke_oc_em_plan_args", _lib.OcEmPlanArgs), ("mke_oc_comm", _lib.OcCommStruct),
-                      ("mke_oc_loop", _lib.OcLoopStruct), ("mke_tuning", _lib.TuningStruct), ("mke_attr_step_args", _lib.AttrStepArgs)):
+                      ("mke_oc_loop", _lib.OcLoopStruct), ("mke_tuning", _lib.TuningStruct), ("mke_attr_step_args", _lib.AttrStepArgs),
+                      ("mke_score_args", _lib.ScoreArgs)):
         body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cname, cname), h, flags=re.S).group(1)
         body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
         names = []
@@ -143,3 +144,48 @@ def test_round6_entry_points_validate_without_gpu(lib):
     arr[1].hot.row0 = 2                       # copies inside the table's own rows
     rc = lib.mke_rows_update_multi(arr, C.c_int(2), C.c_int32(1), C.c_int(80), C.c_int(75), C.c_int(0), C.c_float(0.1), null)
     assert rc == -2 and b"hub rows" in lib.mke_last_error()
+
+
+def test_score_step_validates_without_gpu(lib):
+    """mke_triple_score_step rejects bad arguments before any launch.  The codes are the ones the positional variants it
+    replaced (ABI 106: _x, _xch, _det, plain) returned for the same arguments, recorded from a build of that version; the one
+    difference: ref_count without grad_ent in deterministic mode was -2 from the staging check and is -1 from the common one."""
+    from multike_amd import _lib
+    one = 16
+
+    def rc(**fields):
+        a = _lib.ScoreArgs(ent_table=one, n_ent=10, ent_normalize=1, rel_table=one, n_rel=3, rel_normalize=1, stride=80, dim=75,
+                           pos_h=one, pos_r=one, pos_t=one, n_pos=2, neg_h=one, neg_r=one, neg_t=one, n_neg=4, neg_per_pos=2,
+                           scale=1.0, grad_ent=one, grad_rel=one, grad_rel_copies=1, touched_ent=one, touched_rel=one, tag=1,
+                           ent_acc=one, optimizer=_lib.OPT_ADAGRAD, lr=0.1, loss_partials=one)
+        for k, v in fields.items():
+            setattr(a, k, v)
+        return lib.mke_triple_score_step(C.byref(a), None)
+
+    det = dict(stage_rows=one, stage_keys=one, stage_slots=1000)      # 2 groups of 1 + 2 triples, 3 rows each: 18 slots needed
+    assert lib.mke_triple_score_step(None, None) == -1 and b"NULL args" in lib.mke_last_error()
+    assert rc(ent_table=None) == -1 and b"NULL table/loss" in lib.mke_last_error()
+    assert rc(rel_table=None) == -1
+    assert rc(loss_partials=None) == -1
+    assert rc(stride=75) == -2 and b"stride" in lib.mke_last_error()
+    assert rc(n_neg=5) == -2 and b"grouped negatives" in lib.mke_last_error()
+    assert rc(grad_rel=None) == -1 and b"both" in lib.mke_last_error()
+    assert rc(grad_rel_copies=65) == -2 and b"grad_rel_copies" in lib.mke_last_error()
+    assert rc(optimizer=7) == -3 and b"optimizer" in lib.mke_last_error()
+    assert rc(ref_count=one, ent_acc=None) == -1 and b"ent_acc" in lib.mke_last_error()
+    assert rc(ref_count=one, grad_ent=None, grad_rel=None) == -1 and b"gradient scratch" in lib.mke_last_error()
+    assert rc(ref_count=one, grad_ent=None, grad_rel=None, **det) == -1       # was -2 (see above)
+    assert rc(**dict(det, stage_rows=None)) == -1 and b"staging" in lib.mke_last_error()
+    assert rc(**dict(det, stage_slots=17)) == -2 and b"18 staging slots needed, 17 given" in lib.mke_last_error()
+    assert rc(hot=_lib.HotRowsStruct(one, 2, 4, 5)) == -2 and b"hub rows" in lib.mke_last_error()      # row0 5 < n_ent 10
+    class CountJob(C.Structure):     # mke_count_job (the Python side never fills one: the native step loop does)
+        _fields_ = [("pos_h", C.c_void_p), ("pos_t", C.c_void_p), ("n_pos", C.c_int64), ("neg_h", C.c_void_p), ("neg_t", C.c_void_p),
+                    ("n_neg", C.c_int64), ("neg_per_pos", C.c_int), ("ref_count", C.c_void_p)]
+
+    cj = CountJob(pos_h=one, pos_t=one, n_pos=2, neg_h=one, neg_t=one, n_neg=4, neg_per_pos=2, ref_count=None)
+    assert rc(next_count=C.addressof(cj)) == -1 and b"count job" in lib.mke_last_error()
+    # the positional wrapper that stays goes through the same checks
+    p, null = C.c_void_p(one), C.c_void_p(0)
+    assert lib.mke_triple_score_fwd_bwd(p, C.c_int64(10), C.c_int(1), p, C.c_int64(3), C.c_int(1), C.c_int(75), C.c_int(75), p, p, p, null,
+                                        C.c_int64(2), p, p, p, null, C.c_int64(4), C.c_int(2), C.c_float(1.0), p, p, C.c_int(1), p, p,
+                                        C.c_int32(1), p, null) == -2 and b"stride" in lib.mke_last_error()

@@ -31,7 +31,7 @@ def test_new_symbols_exported_and_listed(lib):
         assert s in _lib.SYMBOLS
         getattr(raw, s)
     h = open(os.path.join(ROOT, "include", "multike_hip.h")).read()
-    assert int(re.search(r"#define MKE_VERSION (\d+)", h).group(1)) == 106 == lib.mke_version()
+    assert int(re.search(r"#define MKE_VERSION (\d+)", h).group(1)) == 107 == lib.mke_version()
 
 
 def _c_layout(struct, fields, tmp_path):
