@@ -816,6 +816,81 @@ typedef struct mke_align_args {
 int mke_align_rank_ex(const mke_align_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * (9c) Stable (Gale-Shapley) alignment on the device, still without the n1 x n2 matrix (additions only; version unchanged).
+ *
+ * replaces: code/base/alignment.py:82-128 stable_alignment, :131-138 arg_sort (both directions), :166-219 galeshapley.
+ *
+ * The result is the suitor-optimal stable matching of the instance in which every suitor (row of a) keeps only its `cut`
+ * best reviewers (rows of b): deferred acceptance run to its fixed point.  Whenever the reference's galeshapley(.., cut)
+ * matches every suitor within its `cut` rounds this is its result.  Ties: a suitor prefers the lower column, a reviewer the
+ * lower row.
+ *
+ *   mke_stable_lists (replaces arg_sort, :131-138, and the matrix of :84-85): out_val / out_col [n_a][cut] = per row of a the
+ *     `cut` largest s_ij over the n_b rows of b, s as in mke_align_rank_ex (METRIC, then CSLS when csls_row / csls_col are
+ *     set), ordered by value descending, then column ascending.  A NaN similarity never enters a list; a list with fewer than
+ *     `cut` entries is padded with column -1 (value -inf).  1 <= cut <= n_b.
+ *       cut <= 128 and whole_rows == 0 (sweep path): no similarity row is written.  A per-row threshold is taken from a
+ *         strided sample of columns, one sweep appends the re-scored similarities at or above it to per-segment candidate
+ *         lists (packed ordered(s) << 32 | 0xFFFFFFFF - j), an exact selection sorts them.  flags[i] = 1 for a row whose
+ *         threshold left fewer than `cut` candidates or whose segment overflowed: its list is NOT valid and the caller
+ *         redoes those rows with whole_rows = 1; flags[i] = 0 otherwise.  n_b <= 1024 sweeps without a threshold (never
+ *         flags).  sample_cols: 0 = automatic; > 0 forces a threshold from about that many sampled columns (tests, tuning).
+ *       cut > 128, whole_rows != 0, or sim_mat != NULL (whole-row path): rounds of rows bounded to 2^26 floats: mke_sim_sample,
+ *         the re-scoring in place, mke_topk_long, a gather + sort of each list.  flags[i] = 0 for every row.
+ *       sim_mat != NULL: [n_a][ld_sim] similarities given by the caller (code/base/alignment.py:82 sim_mat=...), used as they
+ *         are; a, b, kpad, metric, sq_*, csls_* are ignored.
+ *     temp: mke_stable_lists_temp_bytes bytes, independent of n_a * n_b.
+ *   mke_stable_lists_temp_bytes(n_a, n_b, kpad, cut, whole_rows): scratch bytes, or a negative MKE_E_*.
+ *
+ *   mke_stable_rounds (replaces galeshapley's loop, :202-218): enqueues rounds first_round .. first_round + n_rounds - 1 and
+ *     never synchronises.  State, zeroed by the caller before round 0: ptr[n_a] (position in the row's list, `cut` once the
+ *     list is exhausted), holder[n_b] (ordered(value) << 32 | 0xFFFFFFFF - row of the best proposal so far, 0 = free),
+ *     proposals[n_proposals].  In a round every suitor that is not the holder of the column at its ptr advances (from round 1
+ *     on) and, while it has candidates, proposes with one 64-bit atomic max; proposals[round] = proposals of that round.  A
+ *     round whose predecessor made none returns at once, so the caller reads proposals[last round of a batch] and stops at 0.
+ *     first_round + n_rounds > n_proposals: MKE_E_RANGE.  A column outside [0, n_b) ends a list.
+ *   mke_stable_finish (replaces :123-127): match[i] = the column that holds suitor i, or -1; counts[0] = matched suitors,
+ *     counts[1] = suitors with match[i] == i.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct mke_stable_lists_args {
+  const float* a; int lda;          /* [n_a][lda] suitors */
+  const float* b; int ldb;          /* [n_b][ldb] reviewers */
+  int kpad;
+  int64_t n_a, n_b;
+  int metric;
+  const float* sq_a;                /* [n_a], euclidean only (nullable otherwise) */
+  const float* sq_b;                /* [n_b], euclidean only */
+  const float* csls_row;            /* [n_a] r_T, or NULL: no CSLS */
+  const float* csls_col;            /* [n_b] r_S, or NULL (NULL exactly when csls_row is) */
+  const float* sim_mat;             /* nullable: [n_a][ld_sim] similarities given by the caller */
+  int64_t ld_sim;
+  int cut;
+  int whole_rows;                   /* != 0: the whole-row path whatever `cut` */
+  int sample_cols;                  /* 0 = automatic */
+  float* out_val;                   /* [n_a][cut] */
+  int32_t* out_col;                 /* [n_a][cut] */
+  int32_t* flags;                   /* [n_a] 1 = redo this row with whole_rows */
+  void* temp; int64_t temp_bytes;   /* >= mke_stable_lists_temp_bytes(n_a, n_b, kpad, cut, whole_rows != 0 || sim_mat != NULL) */
+} mke_stable_lists_args;
+int64_t mke_stable_lists_temp_bytes(int64_t n_a, int64_t n_b, int kpad, int cut, int whole_rows);
+int mke_stable_lists(const mke_stable_lists_args* args, void* stream);
+
+typedef struct mke_stable_match_args {
+  int64_t n_a, n_b;
+  int cut;
+  const float* val;                 /* [n_a][cut] lists of mke_stable_lists */
+  const int32_t* col;               /* [n_a][cut] */
+  int32_t* ptr;                     /* [n_a] */
+  uint64_t* holder;                 /* [n_b] */
+  int32_t* proposals;               /* [n_proposals] */
+  int64_t n_proposals;
+  int32_t* match;                   /* [n_a], mke_stable_finish only */
+  int32_t* counts;                  /* [2], mke_stable_finish only */
+} mke_stable_match_args;
+int mke_stable_rounds(const mke_stable_match_args* args, int64_t first_round, int n_rounds, void* stream);
+int mke_stable_finish(const mke_stable_match_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * (10) Small dense f32 GEMM on the matrix cores (v_mfma_f32_32x32x2_f32, exact f32) with arbitrary operand strides:
  *        C[M][N] (=|+=) A[M][K] . B[K][N],  A(i,k) = A[i*a_row_stride + k*a_col_stride], likewise B.
  *      splits > 1: split-K, partial products are added atomically (accumulate must be 1; C zeroed or holding the

@@ -11,6 +11,7 @@ import time
 import numpy as np
 
 from .base import evaluation as eva
+from .base.alignment import stable_alignment
 from .base.batch import neighbour_table
 from .MultiKE_model import MultiKE
 from .utils import task_divide
@@ -78,6 +79,7 @@ def test(model, embed_choice='avg', w=(1, 1, 1)):
     print(embed_choice, 'test results:')
     _, mrr_12 = eva.valid(embeds1, embeds2, None, model.args.top_k, model.args.test_threads_num, normalize=True,
                           csls_k=_csls_k(model))
+    _stable(model, embeds1, embeds2)
     return mrr_12
 
 
@@ -85,6 +87,14 @@ def _csls_k(model):
     """Hyper-parameter `csls` (OpenEA's key; 0 = off): CSLS re-scoring of the test-time evaluations only — validation and
     early stopping stay plain."""
     return int(getattr(model.args, "csls", 0) or 0)
+
+
+def _stable(model, embeds1, embeds2):
+    """Hyper-parameter `stable_cut` (0 = off): after the greedy lines of a test, the one-to-one stable alignment of the same
+    rows (code/base/alignment.py:82-128) over every suitor's `stable_cut` best targets, CSLS re-scored as the test is."""
+    cut = int(getattr(model.args, "stable_cut", 0) or 0)
+    if cut > 0:
+        stable_alignment(embeds1, embeds2, 'inner', True, _csls_k(model), model.args.test_threads_num, cut=cut)
 
 
 def _unit_rows(x):
@@ -111,7 +121,7 @@ def wva(embeds1, embeds2, embeds3):
             _compute_weight(embeds3, embeds1, embeds2))
 
 
-def _wva_eval(model, ents1, ents2, label, keys=None, csls_k=0):
+def _wva_eval(model, ents1, ents2, label, keys=None, csls_k=0, stable=False):
     tabs = (model.name_embeds, model.rv_ent_embeds, model.av_ent_embeds)
     if keys is not None and getattr(model, "device", None) is not None and all(hasattr(t, "lookup") for t in tabs):
         ids1, ids2 = _device_ids(model, keys[0], lambda: ents1), _device_ids(model, keys[1], lambda: ents2)
@@ -128,6 +138,8 @@ def _wva_eval(model, ents1, ents2, label, keys=None, csls_k=0):
     embeds2 = sum(float(w) * v for w, v in zip(wsum, v2))
     print(label)
     _, mrr_12 = eva.valid(embeds1, embeds2, None, model.args.top_k, model.args.test_threads_num, normalize=True, csls_k=csls_k)
+    if stable:
+        _stable(model, embeds1, embeds2)
     return mrr_12
 
 
@@ -140,7 +152,7 @@ def valid_WVA(model):
 def test_WVA(model):
     """code/MultiKE_Late.py:138-173."""
     return _wva_eval(model, model.kgs.test_entities1, model.kgs.test_entities2, 'wvag test results:', keys=("test1", "test2"),
-                     csls_k=_csls_k(model))
+                     csls_k=_csls_k(model), stable=True)
 
 
 class _ScheduledMultiKE(MultiKE):

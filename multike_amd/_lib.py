@@ -37,6 +37,7 @@ SYMBOLS = (
     "mke_oc_em_plan_temp_bytes", "mke_oc_em_plan", "mke_oc_pass2", "mke_oc_steps",
     "mke_tuning_init", "mke_rows_update_multi_t",
     "mke_align_topk_mean_temp_bytes", "mke_align_topk_mean", "mke_align_rank_ex",
+    "mke_stable_lists_temp_bytes", "mke_stable_lists", "mke_stable_rounds", "mke_stable_finish",
     "mke_tripleset_forget", "mke_tripleset_filter_bytes", "mke_epoch_positives",
 )
 ACT_NONE, ACT_TANH, ACT_SIGMOID = 0, 1, 2
@@ -273,6 +274,7 @@ def lib():
         L.mke_oc_block_floats.restype = C.c_int64
         L.mke_oc_em_plan_temp_bytes.restype = C.c_int64
         L.mke_align_topk_mean_temp_bytes.restype = C.c_int64
+        L.mke_stable_lists_temp_bytes.restype = C.c_int64
         L.mke_tripleset_filter_bytes.restype = C.c_int64
         _lib = L
         # MKE_OPTIONS="name=value,name=value": mke_set_option calls applied at load (performance knobs for experiments)
@@ -966,6 +968,84 @@ def align_rank_ex(emb1, emb2, kpad, rank, ties, best, metric=METRIC_INNER, sq1=N
                      _dev(csls_row, torch.float32, "csls_row"), _dev(csls_col, torch.float32, "csls_col"),
                      _dev(rank, torch.int32, "rank"), _dev(ties, torch.int32, "ties"), _dev(best, torch.int64, "best"))
     _check(lib().mke_align_rank_ex(C.byref(args), _stream()), "mke_align_rank_ex")
+
+
+class StableListsArgs(C.Structure):
+    """mke_stable_lists_args"""
+    _fields_ = [("a", C.c_void_p), ("lda", C.c_int), ("b", C.c_void_p), ("ldb", C.c_int), ("kpad", C.c_int),
+                ("n_a", C.c_int64), ("n_b", C.c_int64), ("metric", C.c_int), ("sq_a", C.c_void_p), ("sq_b", C.c_void_p),
+                ("csls_row", C.c_void_p), ("csls_col", C.c_void_p), ("sim_mat", C.c_void_p), ("ld_sim", C.c_int64),
+                ("cut", C.c_int), ("whole_rows", C.c_int), ("sample_cols", C.c_int), ("out_val", C.c_void_p),
+                ("out_col", C.c_void_p), ("flags", C.c_void_p), ("temp", C.c_void_p), ("temp_bytes", C.c_int64)]
+
+
+class StableMatchArgs(C.Structure):
+    """mke_stable_match_args"""
+    _fields_ = [("n_a", C.c_int64), ("n_b", C.c_int64), ("cut", C.c_int), ("val", C.c_void_p), ("col", C.c_void_p),
+                ("ptr", C.c_void_p), ("holder", C.c_void_p), ("proposals", C.c_void_p), ("n_proposals", C.c_int64),
+                ("match", C.c_void_p), ("counts", C.c_void_p)]
+
+
+def stable_lists_temp_bytes(n_a: int, n_b: int, kpad: int, cut: int, whole_rows: bool = False) -> int:
+    """mke_stable_lists_temp_bytes; raises on the arguments mke_stable_lists would reject."""
+    r = int(lib().mke_stable_lists_temp_bytes(C.c_int64(n_a), C.c_int64(n_b), C.c_int(kpad), C.c_int(cut), C.c_int(int(whole_rows))))
+    _check(r if r < 0 else 0, "mke_stable_lists_temp_bytes")
+    return r
+
+
+def stable_lists(a, b, kpad, cut, metric=METRIC_INNER, sq_a=None, sq_b=None, csls_row=None, csls_col=None, sim_mat=None,
+                 whole_rows=False, sample_cols=0):
+    """mke_stable_lists -> (val float32 [n_a, cut], col int32 [n_a, cut], flags int32 [n_a]): per row of a its `cut` best
+    columns of b (value descending, column ascending; short lists padded with column -1).  Rows with flags == 1 are NOT
+    valid: the caller redoes them with whole_rows = True (base.alignment.candidate_lists does).  With `sim_mat` (float32
+    [n_a, >= n_b] on the device) the operands are ignored and the caller's similarities are used."""
+    if sim_mat is not None:
+        n_a, n_b, dev = sim_mat.shape[0], sim_mat.shape[1], sim_mat.device
+        if sim_mat.stride(1) != 1 and sim_mat.numel() > 0:
+            raise MultiKEHipError("stable_lists: sim_mat must be row-major")
+        whole_rows = True
+    else:
+        n_a, n_b, dev = a.shape[0], b.shape[0], a.device
+    need = stable_lists_temp_bytes(n_a, n_b, kpad if sim_mat is None else 16, cut, whole_rows)
+    val = torch.empty(n_a, cut, dtype=torch.float32, device=dev)
+    col = torch.empty(n_a, cut, dtype=torch.int32, device=dev)
+    flags = torch.zeros(n_a, dtype=torch.int32, device=dev)
+    temp = torch.empty(max(need, 8) // 8, dtype=torch.int64, device=dev)
+    args = StableListsArgs()
+    if sim_mat is None:
+        args.a, args.lda, args.b, args.ldb = _dev(a, torch.float32, "a"), a.shape[1], _dev(b, torch.float32, "b"), b.shape[1]
+        args.kpad, args.metric = kpad, metric
+        args.sq_a, args.sq_b = _dev(sq_a, torch.float32, "sq_a"), _dev(sq_b, torch.float32, "sq_b")
+        args.csls_row, args.csls_col = _dev(csls_row, torch.float32, "csls_row"), _dev(csls_col, torch.float32, "csls_col")
+    else:
+        if not sim_mat.is_cuda or sim_mat.dtype != torch.float32:
+            raise MultiKEHipError("stable_lists: sim_mat must be a float32 CUDA/HIP tensor (no CPU path exists)")
+        args.sim_mat, args.ld_sim = C.c_void_p(sim_mat.data_ptr()), sim_mat.stride(0) if n_a > 1 else max(n_b, 1)
+    args.n_a, args.n_b, args.cut, args.whole_rows, args.sample_cols = n_a, n_b, cut, int(bool(whole_rows)), sample_cols
+    args.out_val, args.out_col = _dev(val, torch.float32, "out_val"), _dev(col, torch.int32, "out_col")
+    args.flags, args.temp, args.temp_bytes = _dev(flags, torch.int32, "flags"), _dev(temp, torch.int64, "temp"), temp.numel() * 8
+    _check(lib().mke_stable_lists(C.byref(args), _stream()), "mke_stable_lists")
+    return val, col, flags
+
+
+def stable_match_args(val, col, n_b, ptr, holder, proposals, match=None, counts=None) -> StableMatchArgs:
+    """mke_stable_match_args over the lists val / col [n_a, cut] and the state ptr [n_a] int32, holder [n_b] int64,
+    proposals [n] int32 (all zeroed before round 0); match [n_a] int32 and counts [2] int32 for stable_finish."""
+    n_a, cut = col.shape
+    return StableMatchArgs(n_a, n_b, cut, _dev(val, torch.float32, "val"), _dev(col, torch.int32, "col"),
+                           _dev(ptr, torch.int32, "ptr"), _dev(holder, torch.int64, "holder"),
+                           _dev(proposals, torch.int32, "proposals"), proposals.numel() if proposals is not None else 0,
+                           _dev(match, torch.int32, "match"), _dev(counts, torch.int32, "counts"))
+
+
+def stable_rounds(args: StableMatchArgs, first_round: int, n_rounds: int):
+    """mke_stable_rounds: enqueue rounds first_round .. first_round + n_rounds - 1 (no synchronisation)."""
+    _check(lib().mke_stable_rounds(C.byref(args), C.c_int64(first_round), C.c_int(n_rounds), _stream()), "mke_stable_rounds")
+
+
+def stable_finish(args: StableMatchArgs):
+    """mke_stable_finish: match[i] = the column holding suitor i or -1; counts = (matched, matched to its own index)."""
+    _check(lib().mke_stable_finish(C.byref(args), _stream()), "mke_stable_finish")
 
 
 def gemm_f32(lhs, rhs, out, transpose_a=False, transpose_b=False, splits=1, accumulate=False):

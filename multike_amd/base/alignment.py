@@ -1,6 +1,7 @@
 """base/alignment.py surface of the reference (code/base/alignment.py:8-79): `greedy_alignment` — Hits@k / MR / MRR of
 the gold counterpart under the (normalised) inner-product similarity — on the f32 matrix cores via `mke_align_rank`; the
-euclidean metric and CSLS re-scoring via `mke_align_topk_mean` + `mke_align_rank_ex`.
+euclidean metric and CSLS re-scoring via `mke_align_topk_mean` + `mke_align_rank_ex`; `stable_alignment` (:82-128) — the
+one-to-one Gale-Shapley matching — via `mke_stable_lists` + `mke_stable_rounds` + `mke_stable_finish`.
 The n1 x n2 similarity matrix is never materialised (the reference holds 60K x 60K fp32 = 14 GB and argsorts its rows
 in `nums_threads` worker processes)."""
 from __future__ import annotations
@@ -166,6 +167,84 @@ def greedy_alignment(embed1, embed2, top_k, nums_threads, metric, normalize, csl
     cost = time.time() - t
     print_results(top_k, hits, mr, mrr, cost, accurate, csls_k)
     return alignment_rest, hits[0], mr, mrr
+
+
+STABLE_ROUND_BATCH = 32      # rounds enqueued between two reads of the proposal counter
+
+
+def candidate_lists(a, b, kpad, cut, metric_code=_lib.METRIC_INNER, sq_a=None, sq_b=None, csls=None, sim_mat=None, sample_cols=0):
+    """(val float32 [n1, cut], col int32 [n1, cut], redone): per row its `cut` best columns under the re-scored similarity,
+    value descending then column ascending, short lists padded with column -1 (what code/base/alignment.py:131-138 `arg_sort`
+    keeps of a row that `galeshapley(.., cut)` can ever look at).  Rows the sweep path flagged (threshold estimate too tight,
+    or a candidate segment overflowed) are redone here through the whole-row path; `redone` is how many."""
+    r_t, r_s = csls if csls is not None else (None, None)
+    if sim_mat is not None:
+        val, col, _ = _lib.stable_lists(None, None, 0, cut, sim_mat=sim_mat)
+        return val, col, 0
+    val, col, flags = _lib.stable_lists(a, b, kpad, cut, metric_code, sq_a, sq_b, r_t, r_s, sample_cols=sample_cols)
+    idx = torch.nonzero(flags, as_tuple=False).flatten()      # one read-back: the rows to redo (usually none)
+    if idx.numel():
+        pick = lambda t: None if t is None else t[idx].contiguous()
+        v2, c2, _ = _lib.stable_lists(a[idx].contiguous(), b, kpad, cut, metric_code, pick(sq_a), sq_b, pick(r_t), r_s,
+                                      whole_rows=True)
+        val[idx], col[idx] = v2, c2
+    return val, col, int(idx.numel())
+
+
+def stable_matching(val, col, n2, batch=STABLE_ROUND_BATCH):
+    """(match int32 [n1] on the device, matched, matched golds, rounds): deferred acceptance to its fixed point over the lists
+    (code/base/alignment.py:166-219 `galeshapley` without its round limit): suitors = rows, reviewers = the n2 columns."""
+    n1, dev = col.shape[0], col.device
+    ptr = torch.zeros(n1, dtype=torch.int32, device=dev)
+    holder = torch.zeros(n2, dtype=torch.int64, device=dev)
+    proposals = torch.zeros(1024, dtype=torch.int32, device=dev)
+    match = torch.empty(n1, dtype=torch.int32, device=dev)
+    counts = torch.zeros(2, dtype=torch.int32, device=dev)
+    rounds = 0
+    while n1 > 0:
+        if rounds + batch > proposals.numel():                # a chain longer than the counter array: extend it
+            proposals = torch.cat([proposals, torch.zeros_like(proposals)])
+        args = _lib.stable_match_args(val, col, n2, ptr, holder, proposals)
+        _lib.stable_rounds(args, rounds, batch)
+        rounds += batch
+        if int(proposals[rounds - 1]) == 0:                   # the only synchronisation: one int per batch of rounds
+            break
+    _lib.stable_finish(_lib.stable_match_args(val, col, n2, ptr, holder, proposals, match, counts))
+    matched, gold = (int(x) for x in counts.cpu().tolist())
+    used = int((proposals[:max(rounds, 1)] > 0).sum()) if n1 > 0 else 0
+    return match, matched, gold, used
+
+
+def stable_alignment(embed1, embed2, metric, normalize, csls_k, nums_threads, cut=100, sim_mat=None):
+    """code/base/alignment.py:82-128.  Returns (match, precision): match int64 [n1] on the host, match[i] = the row of embed2
+    matched to row i of embed1 or -1 (the reference returns None); precision = matched golds / matched suitors * 100 (:123-128).
+    The result is the suitor-optimal stable matching with every suitor's list truncated to its `cut` best columns, run to its
+    fixed point — the reference's result whenever its galeshapley matches every suitor within `cut` rounds.  Ties: a suitor
+    prefers the lower column, a reviewer the lower row.  `nums_threads` is accepted and ignored.  `sim_mat`: a float32
+    [n1, n2] similarity matrix on the device given by the caller, used in place of sim(embed1, embed2, ...)."""
+    _check_metric(metric, normalize)
+    csls_k = int(csls_k or 0)
+    t = time.time()
+    if sim_mat is not None:
+        if not isinstance(sim_mat, torch.Tensor):
+            sim_mat = torch.as_tensor(np.asarray(sim_mat), dtype=torch.float32).to("cuda")
+        sim_mat = sim_mat.float().contiguous()
+        n1, n2 = sim_mat.shape
+        val, col, _ = candidate_lists(None, None, 0, max(1, min(int(cut), n2)), sim_mat=sim_mat)
+    else:
+        a, b, kpad, code, sq1, sq2 = prepare_operands(embed1, embed2, metric, normalize, "cuda")
+        n1, n2 = a.shape[0], b.shape[0]
+        csls = csls_means(a, b, kpad, code, sq1, sq2, csls_k) if csls_k > 0 else None
+        val, col, _ = candidate_lists(a, b, kpad, max(1, min(int(cut), n2)), code, sq1, sq2, csls)
+    torch.cuda.synchronize()
+    print("generating candidate lists costs time {:.3f} s ".format(time.time() - t))
+    t = time.time()
+    match, matched, gold, _ = stable_matching(val, col, n2)
+    match = match.cpu().numpy().astype(np.int64)
+    precision = gold / matched * 100 if matched else 0.0
+    cost = time.time() - t
+    print("stable alignment precision = {:.3f}%, time = {:.3f} s ".format(precision, cost))
+    return match, precision
 
 
 def print_results(top_k, hits, mr, mrr, cost, accurate, csls_k=0):

@@ -20,6 +20,7 @@
 //   k_align_rank_ex the fold of k_align_rank (greater / ties counters, best column with the lowest column winning a tie) with
 //                   every similarity passed through METRIC and, with CSLS, the re-scoring.  The gold is the diagonal MFMA
 //                   product through the SAME epilogue, so a row never counts itself and ties are exact comparisons.
+#include "mke_rescore.h"
 #include "mke_simtile.h"
 
 #include <math.h>
@@ -30,19 +31,6 @@ namespace mke {
 #define CSLS_FAST_K 32       // k <= CSLS_FAST_K: the partial sweep; above: whole rows through mke_sim_sample + k_topk_mean
 #define CSLS_MAX_CHUNKS 64
 #define CSLS_SORT_LDS 4096   // k_topk_mean sorts up to this many values in LDS, more in the caller's scratch
-
-template <int MET>
-__device__ __forceinline__ float metric_value(float dot, float sqi, float sqj) {
-  if (MET == MKE_METRIC_EUCLIDEAN) return 1.0f - sqrtf(fmaxf(sqi + sqj - 2.0f * dot, 0.0f));
-  return dot;
-}
-
-__device__ __forceinline__ unsigned csls_key(float v) {  // order-preserving integer image (+0 and -0 one key)
-  unsigned u = __float_as_uint(v);
-  if (u == 0x80000000u) u = 0u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float csls_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
 
 __device__ __forceinline__ void wave_sync_lds() {
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -249,13 +237,6 @@ struct AlignRankExParams {
   unsigned long long* __restrict__ best;
 };
 
-template <int MET, bool CSLS>
-__device__ __forceinline__ float rescore(float dot, float sqi, float sqj, float rt, float rs) {
-  float v = metric_value<MET>(dot, sqi, sqj);
-  if (CSLS) v = (2.0f * v - rt) - rs;
-  return v;
-}
-
 template <int KS, int MET, bool CSLS>
 __global__ __launch_bounds__(MKE_BLOCK) void k_align_rank_ex(const AlignRankExParams p) {
   constexpr bool EUC = MET == MKE_METRIC_EUCLIDEAN;
@@ -344,29 +325,6 @@ static int sweep_chunks(int64_t rows, int ntiles, int target, int cap) {
   if (chunks < 1) chunks = 1;
   const int per = (ntiles + chunks - 1) / chunks;
   return (ntiles + per - 1) / per;  // no empty chunk
-}
-
-static bool kpad_ok(int kpad) {
-  switch (kpad) {
-    case 16: case 32: case 48: case 64: case 80: case 96: case 112: case 128: case 160: case 192: case 208: case 256: case 320:
-      return true;
-    default:
-      return false;
-  }
-}
-
-// rows of the large-k path per round: the similarity rows of one round stay under 2^26 floats (256 MB)
-static int64_t fallback_rows(int64_t n_a, int64_t n_b) {
-  int64_t r = ((int64_t)1 << 26) / n_b;
-  r = r / SIMT_BM * SIMT_BM;
-  if (r < SIMT_BM) r = SIMT_BM;
-  return r < n_a ? r : n_a;
-}
-
-static int64_t pow2_at_least(int64_t x) {
-  int64_t p = 1;
-  while (p < x) p <<= 1;
-  return p;
 }
 
 }  // namespace mke

@@ -66,6 +66,9 @@ class _ShardedMixin:
         assert args.alignment_module == 'swapping'
         if args.optimizer != "Adagrad":
             raise _lib.MultiKEHipError("the multi-GPU drivers are built for the reference's default optimizer (Adagrad)")
+        if int(getattr(args, "stable_cut", 0) or 0) > 0:
+            raise _lib.MultiKEHipError("stable_cut > 0: the stable (Gale-Shapley) alignment is not sharded over ranks; "
+                                       "run the single-GPU driver (python -m multike_amd.run) or set stable_cut=0")
         self.kgs = kgs = data.kgs
         self.kg1, self.kg2 = kgs.kg1, kgs.kg2
         self.rank, self.world = rank, world

@@ -44,6 +44,8 @@ def default_args(**over):
         start_valid=100, eval_freq=10, stop_metric="mrr", top_k=[1, 5, 10, 50], is_save=True,
         # CSLS re-scoring of the final tests (OpenEA's key `csls`; 0 = off, the reference's evaluation)
         csls=0,
+        # one-to-one (Gale-Shapley) alignment of the final tests over every suitor's `stable_cut` best targets (0 = off)
+        stable_cut=0,
         # view combination and predicate soft alignment
         orthogonal_weight=2, cv_name_weight=1, cv_weight=1, start_predicate_soft_alignment=10, predicate_soft_sim=0.85,
         predicate_init_sim=0.90)
