@@ -14,14 +14,13 @@
 //                   tau rises to the k-th.  k values per (row, chunk) go out.  LDS: 32 KB of buffers + the sweep's tiles
 //                   (43 KB at kpad 80: two blocks per CU on the 160 KB of gfx950).
 //   k_topk_mean     per row of a list of values (the chunk partials, or a whole similarity row in the large-k path): exact
-//                   k-th largest by a byte-wise radix select, the values above it sorted descending (bitonic), summed in
+//                   k-th largest by radix_select_kth, the values above it sorted descending (sort_desc), summed in
 //                   float64 in descending order with the ties of the k-th last, divided by k, rounded to f32 — a unique,
 //                   run-to-run identical mean of the exact top-k multiset.
 //   k_align_rank_ex the fold of k_align_rank (greater / ties counters, best column with the lowest column winning a tie) with
 //                   every similarity passed through METRIC and, with CSLS, the re-scoring.  The gold is the diagonal MFMA
 //                   product through the SAME epilogue, so a row never counts itself and ties are exact comparisons.
 #include "mke_rescore.h"
-#include "mke_simtile.h"
 
 #include <math.h>
 
@@ -84,7 +83,7 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_topk_partial(const TopkPartialPar
   int cnt[16];
 #pragma unroll
   for (int reg = 0; reg < 16; ++reg) {
-    const int r = strip0 + (reg & 3) + 8 * (reg >> 2) + 4 * half;
+    const int r = simt_row(reg, half, strip0);
     tau[reg] = -INFINITY;
     cnt[reg] = 0;
     sqi[reg] = (MET == MKE_METRIC_EUCLIDEAN && r < p.n_a) ? p.sq_a[r] : 0.f;
@@ -104,7 +103,7 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_topk_partial(const TopkPartialPar
       if (m == 0) continue;  // wave-uniform
       const unsigned mh = half ? (unsigned)(m >> 32) : (unsigned)m;  // the 32 lanes of a half hold 32 columns of ONE row
       const int nh = __popc(mh);
-      float* buf = s_buf[wv * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * half];
+      float* buf = s_buf[simt_row(reg, half, wv * 32)];
       if (cnt[reg] + nh > CSLS_BUF) {  // uniform in the half: cnt > CSLS_BUF - 32 >= k, keep the k largest
         tau[reg] = csls_compact(buf, cnt[reg], k, l31);
         cnt[reg] = k;  // k + nh <= 64: the hits still fit (they beat the old tau; extra ones go at the next compaction)
@@ -116,7 +115,7 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_topk_partial(const TopkPartialPar
   wave_sync_lds();
 #pragma unroll
   for (int reg = 0; reg < 16; ++reg) {
-    const int rr = (reg & 3) + 8 * (reg >> 2) + 4 * half;
+    const int rr = simt_row(reg, half);
     float* buf = s_buf[wv * 32 + rr];
     if (cnt[reg] > k) csls_compact(buf, cnt[reg], k, l31);
     const int row = strip0 + rr;
@@ -145,76 +144,35 @@ __device__ __forceinline__ float mean_value(const TopkMeanParams& p, const float
 }
 
 __global__ __launch_bounds__(MKE_BLOCK) void k_topk_mean(const TopkMeanParams p) {
-  static_assert(MKE_BLOCK == 256, "one histogram bin per thread");
   __shared__ int s_hist[MKE_BLOCK / 64][256];
   __shared__ int s_wave[MKE_BLOCK / 64];
   __shared__ unsigned s_prefix;
   __shared__ int s_need, s_gt;
   __shared__ unsigned s_sort[CSLS_SORT_LDS];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int tid = threadIdx.x;
   const int64_t row = blockIdx.x;
   const float* __restrict__ v = p.vals + row * p.ld;
   const float sqi = p.metric == MKE_METRIC_EUCLIDEAN ? p.sq_a[row] : 0.f;
-  if (tid == 0) { s_prefix = 0u; s_need = p.k; s_gt = 0; }
-  __syncthreads();
-  for (int hi = 32; hi > 0; hi -= 8) {  // the k-th largest key, most significant byte first (as k_topk_long)
-    const int shift = hi - 8;
-#pragma unroll
-    for (int q = 0; q < MKE_BLOCK / 64; ++q) s_hist[q][tid] = 0;
-    __syncthreads();
-    const unsigned pre = s_prefix;
-    const int need = s_need;
-    for (int i = tid; i < p.m; i += MKE_BLOCK) {
-      const unsigned kx = csls_key(mean_value(p, v, sqi, i));
-      if (hi >= 32 || (kx >> hi) == (pre >> hi)) atomicAdd(&s_hist[wv][(kx >> shift) & 255u], 1);
-    }
-    __syncthreads();
-    const int dgt = 255 - tid;
-    const int h = s_hist[0][dgt] + s_hist[1][dgt] + s_hist[2][dgt] + s_hist[3][dgt];
-    int incl = h;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int o = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += o;
-    }
-    if (lane == 63) s_wave[wv] = incl;
-    __syncthreads();
-    for (int q = 0; q < wv; ++q) incl += s_wave[q];
-    if (incl >= need && incl - h < need) {
-      s_prefix = pre | ((unsigned)dgt << shift);
-      s_need = need - (incl - h);
-    }
-    __syncthreads();
-  }
-  const unsigned kth = s_prefix;
-  const int ties = s_need;  // copies of the k-th value in the top k; the other k - ties values are above it
+  if (tid == 0) s_gt = 0;
+  int ties;  // copies of the k-th value in the top k; the other k - ties values are above it
+  const unsigned kth = radix_select_kth(s_hist, s_wave, &s_prefix, &s_need, p.m, p.k, &ties,
+                                        [&](int i) { return float_key(mean_value(p, v, sqi, i)); });
   const int gt = p.k - ties;
   int np2 = 1;
   while (np2 < gt) np2 <<= 1;
   unsigned* buf = p.k <= CSLS_SORT_LDS ? s_sort : p.sort_tmp + row * p.sort_ld;
   for (int i = tid; i < p.m; i += MKE_BLOCK) {
-    const unsigned kx = csls_key(mean_value(p, v, sqi, i));
+    const unsigned kx = float_key(mean_value(p, v, sqi, i));
     if (kx > kth) buf[atomicAdd(&s_gt, 1)] = kx;
   }
   __syncthreads();
   for (int i = gt + tid; i < np2; i += MKE_BLOCK) buf[i] = 0u;  // below every float key: sorts last
   __syncthreads();
-  for (int size = 2; size <= np2; size <<= 1) {  // bitonic sort, descending
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int i = tid; i < np2 / 2; i += MKE_BLOCK) {
-        const int lo = 2 * i - (i & (stride - 1));
-        const int hi2 = lo + stride;
-        const bool desc = (lo & size) == 0;
-        const unsigned x = buf[lo], y = buf[hi2];
-        if ((x < y) == desc) { buf[lo] = y; buf[hi2] = x; }
-      }
-      __syncthreads();
-    }
-  }
+  sort_desc(buf, np2);
   if (tid == 0) {
     double s = 0.0;
-    for (int i = 0; i < gt; ++i) s += (double)csls_unkey(buf[i]);
-    const double kv = (double)csls_unkey(kth);
+    for (int i = 0; i < gt; ++i) s += (double)key_float(buf[i]);
+    const double kv = (double)key_float(kth);
     for (int i = 0; i < ties; ++i) s += kv;
     p.out[row] = (float)(s / (double)p.k);
   }
@@ -248,7 +206,7 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_align_rank_ex(const AlignRankExPa
   float gold[16], sqi[16], rti[16];
 #pragma unroll
   for (int reg = 0; reg < 16; ++reg) {
-    const int r = strip0 + (reg & 3) + 8 * (reg >> 2) + 4 * half;
+    const int r = simt_row(reg, half, strip0);
     sqi[reg] = (EUC && r < p.n1) ? p.sq1[r] : 0.f;
     rti[reg] = (CSLS && r < p.n1) ? p.csls_row[r] : 0.f;
   }
@@ -263,12 +221,12 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_align_rank_ex(const AlignRankExPa
     const float rsj = (CSLS && ok) ? p.csls_col[r] : 0.f;
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg) {
-      const int m = (reg & 3) + 8 * (reg >> 2) + 4 * half;
+      const int m = simt_row(reg, half);
       if (m == l31) s_gold[wv][m] = rescore<MET, CSLS>(d[reg], sqi[reg], sqj, rti[reg], rsj);
     }
     __syncthreads();
 #pragma unroll
-    for (int reg = 0; reg < 16; ++reg) gold[reg] = s_gold[wv][(reg & 3) + 8 * (reg >> 2) + 4 * half];
+    for (int reg = 0; reg < 16; ++reg) gold[reg] = s_gold[wv][simt_row(reg, half)];
   }
   int cnt[16], eq[16];
   float bestv[16];
@@ -302,30 +260,20 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_align_rank_ex(const AlignRankExPa
       const int oc = __shfl_xor(bc, off, 64);
       if (ov > bv || (ov == bv && oc < bc)) { bv = ov; bc = oc; }
     }
-    const int row = strip0 + (reg & 3) + 8 * (reg >> 2) + 4 * half;
+    const int row = simt_row(reg, half, strip0);
     if (l31 == 0 && row < p.n1 && t0 < t1) {
       atomicAdd(&p.rank[row], c);
       atomicAdd(&p.ties[row], ce);
     }
     if (l31 == 0 && row < p.n1 && t0 < t1 && bc != 0x7FFFFFFF) {  // bc unset: every similarity of the chunk was NaN
-      unsigned u = __float_as_uint(bv);
-      u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-      const unsigned long long key = ((unsigned long long)u << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)bc);
+      const unsigned long long key = best_key(bv, bc);
       atomicMax(&p.best[row], key);
     }
   }
 }
 
-// (row blocks, column chunks) of a sweep: enough items to fill the chip several times over, a chunk at least 16 tiles
-static int sweep_chunks(int64_t rows, int ntiles, int target, int cap) {
-  const int row_blocks = (int)((rows + SIMT_BM - 1) / SIMT_BM);
-  int chunks = (target + row_blocks - 1) / row_blocks;
-  if (chunks > (ntiles + 15) / 16) chunks = (ntiles + 15) / 16;
-  if (chunks > cap) chunks = cap;
-  if (chunks < 1) chunks = 1;
-  const int per = (ntiles + chunks - 1) / chunks;
-  return (ntiles + per - 1) / per;  // no empty chunk
-}
+// column chunks of k_topk_partial: the scratch query and the launch agree on them
+static SimtSplit topk_partial_split(int64_t n_a, int64_t n_b, int kpad) { return simt_split(n_a, n_b, kpad, 6144, 16, CSLS_MAX_CHUNKS); }
 
 }  // namespace mke
 
@@ -339,9 +287,7 @@ static int topk_mean_temp(int64_t n_a, int64_t n_b, int kpad, int k, int64_t* by
   if (n_a == 0) return MKE_OK;
   int64_t floats;
   if (k <= CSLS_FAST_K) {
-    const int bn = SIMT_BN_FOR(kpad / 16);
-    const int chunks = sweep_chunks(n_a, (int)((n_b + bn - 1) / bn), 6144, CSLS_MAX_CHUNKS);
-    floats = n_a * chunks * k;  // < 2^31 * 64 * 32: the kernels index it with int64 offsets
+    floats = n_a * topk_partial_split(n_a, n_b, kpad).chunks * k;  // < 2^31 * 64 * 32: the kernels index it with int64 offsets
   } else {
     const int64_t r = fallback_rows(n_a, n_b);
     floats = r * n_b + (k > CSLS_SORT_LDS ? r * pow2_at_least(k) : 0);
@@ -369,7 +315,7 @@ extern "C" int mke_align_topk_mean(const mke_topk_mean_args* args, void* stream)
   if (!g.a || !g.b || !g.out || (need > 0 && !g.temp)) { set_error("mke_align_topk_mean: NULL pointer"); return MKE_E_NULL; }
   if (g.metric == MKE_METRIC_EUCLIDEAN && (!g.sq_a || !g.sq_b)) { set_error("mke_align_topk_mean: euclidean needs sq_a and sq_b"); return MKE_E_NULL; }
   if (g.lda < g.kpad || g.ldb < g.kpad || g.lda % 4 != 0 || g.ldb % 4 != 0) { set_error("mke_align_topk_mean: lda, ldb must be multiples of 4 >= kpad"); return MKE_E_SHAPE; }
-  if (!kpad_ok(g.kpad)) { set_error("mke_align_topk_mean: unsupported kpad %d", g.kpad); return MKE_E_UNSUPPORTED; }
+  if (!simt_kpad_ok(g.kpad)) { set_error("mke_align_topk_mean: unsupported kpad %d", g.kpad); return MKE_E_UNSUPPORTED; }
   if (g.temp_bytes < need) { set_error("mke_align_topk_mean: temp below mke_align_topk_mean_temp_bytes (%lld)", (long long)need); return MKE_E_SHAPE; }
   hipStream_t st = (hipStream_t)stream;
   TopkMeanParams mp;
@@ -378,22 +324,15 @@ extern "C" int mke_align_topk_mean(const mke_topk_mean_args* args, void* stream)
     TopkPartialParams p;
     p.a = g.a; p.lda = g.lda; p.b = g.b; p.ldb = g.ldb; p.n_a = (int)g.n_a; p.n_b = (int)g.n_b; p.sq_a = g.sq_a; p.sq_b = g.sq_b;
     p.k = g.k;
-    const int bn = SIMT_BN_FOR(g.kpad / 16);
-    const int ntiles = (int)((g.n_b + bn - 1) / bn);
-    p.chunks = sweep_chunks(g.n_a, ntiles, 6144, CSLS_MAX_CHUNKS);
-    p.tiles_per_chunk = (ntiles + p.chunks - 1) / p.chunks;
+    const SimtSplit sp = topk_partial_split(g.n_a, g.n_b, g.kpad);
+    p.chunks = sp.chunks; p.tiles_per_chunk = sp.tiles_per_chunk;
     p.part = (float*)g.temp;
     dim3 grid((unsigned)((g.n_a + SIMT_BM - 1) / SIMT_BM), (unsigned)p.chunks);
-#define TP_CASE(K)                                                                                              \
-  case K:                                                                                                       \
-    if (g.metric == MKE_METRIC_EUCLIDEAN) hipLaunchKernelGGL((k_topk_partial<K / 16, MKE_METRIC_EUCLIDEAN>), grid, dim3(MKE_BLOCK), 0, st, p); \
-    else hipLaunchKernelGGL((k_topk_partial<K / 16, MKE_METRIC_INNER>), grid, dim3(MKE_BLOCK), 0, st, p);       \
-    break;
-    switch (g.kpad) {
-      TP_CASE(16) TP_CASE(32) TP_CASE(48) TP_CASE(64) TP_CASE(80) TP_CASE(96) TP_CASE(112) TP_CASE(128) TP_CASE(160)
-      TP_CASE(192) TP_CASE(208) TP_CASE(256) TP_CASE(320)
-    }
-#undef TP_CASE
+    simt_for_kpad(g.kpad, [&](auto ks) {
+      for_rescore(g.metric == MKE_METRIC_EUCLIDEAN, false, [&](auto met, auto) {  // the partials take the metric only
+        hipLaunchKernelGGL((k_topk_partial<decltype(ks)::value, decltype(met)::value>), grid, dim3(MKE_BLOCK), 0, st, p);
+      });
+    });
     const int e = check_launch("k_topk_partial");
     if (e) return e;
     mp.vals = p.part; mp.ld = (int64_t)p.chunks * g.k; mp.m = p.chunks * g.k;
@@ -434,29 +373,20 @@ extern "C" int mke_align_rank_ex(const mke_align_args* args, void* stream) {
     return MKE_E_SHAPE;
   }
   if (g.n2 < g.n1) { set_error("mke_align_rank_ex: gold column = row index needs n2 >= n1"); return MKE_E_SHAPE; }
-  if (!kpad_ok(g.kpad)) { set_error("mke_align_rank_ex: unsupported kpad %d", g.kpad); return MKE_E_UNSUPPORTED; }
+  if (!simt_kpad_ok(g.kpad)) { set_error("mke_align_rank_ex: unsupported kpad %d", g.kpad); return MKE_E_UNSUPPORTED; }
   AlignRankExParams p;
   p.emb1 = g.emb1; p.ld1 = g.ld1; p.emb2 = g.emb2; p.ld2 = g.ld2; p.n1 = (int)g.n1; p.n2 = (int)g.n2;
   p.sq1 = g.sq1; p.sq2 = g.sq2; p.csls_row = g.csls_row; p.csls_col = g.csls_col;
   p.rank = g.rank; p.ties = g.ties; p.best = (unsigned long long*)g.best;
-  const int bn = SIMT_BN_FOR(g.kpad / 16);
-  const int ntiles = (int)((g.n2 + bn - 1) / bn);
-  const int chunks = sweep_chunks(g.n1, ntiles, 6144, 1 << 16);
-  p.tiles_per_chunk = (ntiles + chunks - 1) / chunks;
-  dim3 grid((unsigned)((g.n1 + SIMT_BM - 1) / SIMT_BM), (unsigned)chunks);
+  const SimtSplit sp = simt_split(g.n1, g.n2, g.kpad, 6144, 16, 1 << 16);
+  p.tiles_per_chunk = sp.tiles_per_chunk;
+  dim3 grid((unsigned)((g.n1 + SIMT_BM - 1) / SIMT_BM), (unsigned)sp.chunks);
   hipStream_t st = (hipStream_t)stream;
-  const bool csls = g.csls_row != nullptr, euc = g.metric == MKE_METRIC_EUCLIDEAN;
-#define RX_CASE(K)                                                                                                             \
-  case K:                                                                                                                      \
-    if (euc && csls) hipLaunchKernelGGL((k_align_rank_ex<K / 16, MKE_METRIC_EUCLIDEAN, true>), grid, dim3(MKE_BLOCK), 0, st, p);  \
-    else if (euc) hipLaunchKernelGGL((k_align_rank_ex<K / 16, MKE_METRIC_EUCLIDEAN, false>), grid, dim3(MKE_BLOCK), 0, st, p);  \
-    else if (csls) hipLaunchKernelGGL((k_align_rank_ex<K / 16, MKE_METRIC_INNER, true>), grid, dim3(MKE_BLOCK), 0, st, p);      \
-    else hipLaunchKernelGGL((k_align_rank_ex<K / 16, MKE_METRIC_INNER, false>), grid, dim3(MKE_BLOCK), 0, st, p);               \
-    break;
-  switch (g.kpad) {
-    RX_CASE(16) RX_CASE(32) RX_CASE(48) RX_CASE(64) RX_CASE(80) RX_CASE(96) RX_CASE(112) RX_CASE(128) RX_CASE(160)
-    RX_CASE(192) RX_CASE(208) RX_CASE(256) RX_CASE(320)
-  }
-#undef RX_CASE
+  simt_for_kpad(g.kpad, [&](auto ks) {
+    for_rescore(g.metric == MKE_METRIC_EUCLIDEAN, g.csls_row != nullptr, [&](auto met, auto csls) {
+      hipLaunchKernelGGL((k_align_rank_ex<decltype(ks)::value, decltype(met)::value, decltype(csls)::value>), grid, dim3(MKE_BLOCK), 0,
+                         st, p);
+    });
+  });
   return check_launch("k_align_rank_ex");
 }

@@ -12,7 +12,10 @@
 //
 // The gold similarity is taken from the SAME MFMA computation (the diagonal tile), so `sim > gold` is an exact
 // comparison of identically rounded numbers and a row never counts itself.
+#include "mke_select.h"
 #include "mke_simtile.h"
+
+#include <limits.h>
 
 namespace mke {
 
@@ -47,12 +50,12 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_align_rank(const AlignRankParams 
     const f32x16 d = simt_fragment_product<KS>(a, b);
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg) {
-      const int m = (reg & 3) + 8 * (reg >> 2) + 4 * half;
+      const int m = simt_row(reg, half);
       if (m == l31) s_gold[wv][m] = d[reg];
     }
     __syncthreads();
 #pragma unroll
-    for (int reg = 0; reg < 16; ++reg) gold[reg] = s_gold[wv][(reg & 3) + 8 * (reg >> 2) + 4 * half];
+    for (int reg = 0; reg < 16; ++reg) gold[reg] = s_gold[wv][simt_row(reg, half)];
   }
   int cnt[16];
   int eq[TIES ? 16 : 1];
@@ -87,14 +90,11 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_align_rank(const AlignRankParams 
       const int oc = __shfl_xor(bc, off, 64);
       if (ov > bv || (ov == bv && oc < bc)) { bv = ov; bc = oc; }
     }
-    const int row = strip0 + (reg & 3) + 8 * (reg >> 2) + 4 * half;
+    const int row = simt_row(reg, half, strip0);
     if (l31 == 0 && row < p.n1 && t0 < t1) {
       atomicAdd(&p.rank[row], c);
       if (TIES) atomicAdd(&p.ties[row], ce);
-      // order-preserving key: similarity (monotone uint) in the high word, lowest column wins ties
-      unsigned u = __float_as_uint(bv);
-      u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-      const unsigned long long key = ((unsigned long long)u << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)bc);
+      const unsigned long long key = best_key(bv, bc);
       atomicMax(&p.best[row], key);
     }
   }
@@ -116,28 +116,16 @@ extern "C" int mke_align_rank(const float* emb1, int ld1, const float* emb2, int
   AlignRankParams p;
   p.emb1 = emb1; p.ld1 = ld1; p.emb2 = emb2; p.ld2 = ld2; p.n1 = (int)n1; p.n2 = (int)n2; p.rank = rank; p.ties = ties;
   p.best = (unsigned long long*)best;
-  const int bn = SIMT_BN_FOR(kpad / 16);
-  const int ntiles = (int)((n2 + bn - 1) / bn);
-  const int row_blocks = (int)((n1 + SIMT_BM - 1) / SIMT_BM);
   // enough (row block, column chunk) items to fill the chip several times over; a chunk is at least 16 tiles
-  int chunks = (6144 + row_blocks - 1) / row_blocks;
-  if (chunks > (ntiles + 15) / 16) chunks = (ntiles + 15) / 16;
-  if (chunks < 1) chunks = 1;
-  p.tiles_per_chunk = (ntiles + chunks - 1) / chunks;
-  dim3 grid((unsigned)row_blocks, (unsigned)((ntiles + p.tiles_per_chunk - 1) / p.tiles_per_chunk));
+  const SimtSplit sp = simt_split(n1, n2, kpad, 6144, 16, INT_MAX);
+  p.tiles_per_chunk = sp.tiles_per_chunk;
+  dim3 grid((unsigned)((n1 + SIMT_BM - 1) / SIMT_BM), (unsigned)sp.chunks);
   hipStream_t st = (hipStream_t)stream;
-#define EV_CASE(K)                                                                \
-  case K:                                                                         \
-    if (ties) hipLaunchKernelGGL((k_align_rank<K / 16, true>), grid, dim3(MKE_BLOCK), 0, st, p);   \
-    else hipLaunchKernelGGL((k_align_rank<K / 16, false>), grid, dim3(MKE_BLOCK), 0, st, p);       \
-    break;
-  switch (kpad) {
-    EV_CASE(16) EV_CASE(32) EV_CASE(48) EV_CASE(64) EV_CASE(80) EV_CASE(96) EV_CASE(112) EV_CASE(128) EV_CASE(160)
-    EV_CASE(192) EV_CASE(208) EV_CASE(256) EV_CASE(320)
-    default:
-      set_error("unsupported kpad %d", kpad);
-      return MKE_E_UNSUPPORTED;
-  }
-#undef EV_CASE
+  const bool found = simt_for_kpad(kpad, [&](auto ks) {
+    constexpr int KS = decltype(ks)::value;
+    if (ties) hipLaunchKernelGGL((k_align_rank<KS, true>), grid, dim3(MKE_BLOCK), 0, st, p);
+    else hipLaunchKernelGGL((k_align_rank<KS, false>), grid, dim3(MKE_BLOCK), 0, st, p);
+  });
+  if (!found) { set_error("unsupported kpad %d", kpad); return MKE_E_UNSUPPORTED; }
   return check_launch("k_align_rank");
 }

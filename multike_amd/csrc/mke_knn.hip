@@ -14,14 +14,17 @@
 //                  The columns are split over gridDim.y segments (a row-owner block sweeping all columns alone would
 //                  leave a 2x tail: 782 blocks on 768 slots); segment s of a row has its own counter and seg_cap slots.
 //   k_topk_rows    exact k-th largest of a short list held in LDS (<= 4096 values: the candidates of a row, or a row of
-//                  sample similarities when only the threshold is wanted): 4-pass byte-wise radix select on the
-//                  order-preserving integer image of the floats, then an ordered compaction (block scan) of the values
-//                  above the k-th plus the first ties — the output is deterministic and in candidate (= column) order.
+//                  sample similarities when only the threshold is wanted): radix select (radix_digit_step of mke_select.h)
+//                  on the order-preserving integer image of the floats (float_key), then an ordered compaction (block scan)
+//                  of the values above the k-th plus the first ties — the output is deterministic and in candidate (= column) order.
 //
 // The threshold of a row is the m-th largest of its similarities to a fixed column sample (caller: a small library GEMM
 // + k_topk_rows), chosen so that ~1.4 k columns pass; a row whose estimate came out too tight (< k hits) or whose
 // segment overflowed is flagged and redone by the caller at full width.  The result is the exact top-k set.
+#include "mke_select.h"
 #include "mke_simtile.h"
+
+#include <limits.h>
 
 namespace mke {
 
@@ -56,7 +59,7 @@ __global__ __launch_bounds__(MKE_BLOCK, KS <= 5 ? 3 : 1) void k_sim_select(const
   int cnt[16];
 #pragma unroll
   for (int reg = 0; reg < 16; ++reg) {
-    const int r = strip0 + (reg & 3) + 8 * (reg >> 2) + 4 * half;
+    const int r = simt_row(reg, half, strip0);
     tauR[reg] = r < p.row_hi ? p.tau[r - p.row_lo] : 3.0e38f;
     cnt[reg] = 0;
   }
@@ -83,7 +86,7 @@ __global__ __launch_bounds__(MKE_BLOCK, KS <= 5 ? 3 : 1) void k_sim_select(const
         mke_candidate c;
         c.idx = col;
         c.sim = acc[reg];
-        *reinterpret_cast<mke_candidate*>(cand_b + (base0_b + (unsigned)((reg & 3) + 8 * (reg >> 2)) * row_stride_b + (unsigned)pos * 8u)) = c;
+        *reinterpret_cast<mke_candidate*>(cand_b + (base0_b + (unsigned)simt_row(reg, 0) * row_stride_b + (unsigned)pos * 8u)) = c;
       }
       cnt[reg] += __popc(mh);
     }
@@ -91,7 +94,7 @@ __global__ __launch_bounds__(MKE_BLOCK, KS <= 5 ? 3 : 1) void k_sim_select(const
   if (l31 == 0) {
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg) {
-      const int r = strip0 + (reg & 3) + 8 * (reg >> 2) + 4 * half;
+      const int r = simt_row(reg, half, strip0);
       if (r < p.row_hi) p.seg_count[(int64_t)(r - p.row_lo) * p.n_seg + seg] = cnt[reg];
     }
   }
@@ -128,20 +131,10 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_sim_sample(const SimSampleParams 
   simt_sweep<KS>(a, p.samp, p.ld_s, p.n_samp, t0, t1, [&](const f32x16& acc, int col, bool col_ok) {
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg) {
-      const int dr = (reg & 3) + 8 * (reg >> 2);
+      const int dr = simt_row(reg, 0);
       if (col_ok && strip0 + 4 * half + dr < p.row_hi) o[(int64_t)dr * p.n_samp + col] = acc[reg];
     }
   });
-}
-
-// order-preserving integer image of a float: larger float <=> larger unsigned
-__device__ __forceinline__ unsigned float_key(float v) {
-  unsigned u = __float_as_uint(v);
-  if (u == 0x80000000u) u = 0u;  // -0 and +0 compare equal as floats: one key
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_float(unsigned k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
 }
 
 struct TopkParams {
@@ -160,7 +153,6 @@ struct TopkParams {
 // twice the resident blocks of this latency-bound kernel (0.31 -> 0.17 ms per 16384 x 4096 threshold block)
 template <bool WITH_IDX>
 __global__ __launch_bounds__(MKE_BLOCK) void k_topk_rows(const TopkParams p) {
-  static_assert(MKE_BLOCK == 256, "one histogram bin per thread");
   __shared__ unsigned s_key[KNN_MAX_LIST];
   __shared__ int s_idx[WITH_IDX ? KNN_MAX_LIST : 1];
   __shared__ int s_hist[MKE_BLOCK / 64][256];
@@ -232,7 +224,7 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_topk_rows(const TopkParams p) {
   if (tid == 0) { s_prefix = hi >= 32 ? 0u : (kmax >> hi) << hi; s_need = p.k; }
   __syncthreads();
   // radix select on the undecided bits, most significant digit first; a private histogram per wavefront (4x fewer
-  // collisions), bins summed and scanned from the top by all 256 threads
+  // collisions)
   while (hi > 0) {
     const int w = min(8, hi), shift = hi - w;
 #pragma unroll
@@ -245,24 +237,8 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_topk_rows(const TopkParams p) {
       if (hi >= 32 || (kx >> hi) == (pre >> hi)) atomicAdd(&s_hist[wv][(kx >> shift) & ((1u << w) - 1u)], 1);
     }
     __syncthreads();
-    // thread t owns digit 255 - t: inclusive scan from the largest digit down
-    const int dgt = 255 - tid;
-    const int h = s_hist[0][dgt] + s_hist[1][dgt] + s_hist[2][dgt] + s_hist[3][dgt];
-    int incl = h;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int o = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += o;
-    }
-    if (lane == 63) s_wave[wv] = incl;
-    __syncthreads();
-    for (int q = 0; q < wv; ++q) incl += s_wave[q];
-    if (incl >= need && incl - h < need) {  // exactly one thread: the digit where the count from the top reaches `need`
-      s_prefix = pre | ((unsigned)dgt << shift);
-      s_need = need - (incl - h);
-    }
+    radix_digit_step(s_hist, s_wave, &s_prefix, &s_need, pre, need, shift);
     hi = shift;
-    __syncthreads();
   }
   const unsigned kth = s_prefix;
   const int ties = s_need;  // how many of the keys equal to kth belong to the top k
@@ -306,11 +282,10 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_topk_rows(const TopkParams p) {
 
 // Exact top k of LONG rows (whole similarity rows: a short KG, or a row of the main pass whose threshold estimate was off —
 // up to n = 100K+ values, far beyond the 4096 keys k_topk_rows holds in LDS).  One block per row; the row stays in global
-// memory (L2) and is streamed five times: four byte-wise radix-select passes (private histogram per wavefront, the 256
-// threads scan the bins from the top) fix the k-th largest key and how many of its ties belong to the top k, a fifth pass
-// compacts the columns above it plus the first ties in COLUMN order (block scan per 256-column chunk) — the output is a
-// deterministic function of the row.  Replaces torch.topk (a library call: its first use in a run cost a 170 ms
-// compilation / initialisation on a fresh box).
+// memory (L2) and is streamed five times: the four byte-wise passes of radix_select_kth (mke_select.h) fix the k-th largest
+// key and how many of its ties belong to the top k, a fifth pass compacts the columns above it plus the first ties in COLUMN
+// order (block scan per 256-column chunk) — the output is a deterministic function of the row.  Replaces torch.topk (a library
+// call: its first use in a run cost a 170 ms compilation / initialisation on a fresh box).
 struct TopkLongParams {
   const float* __restrict__ vals;   // [rows][ld]
   int64_t ld;
@@ -320,46 +295,14 @@ struct TopkLongParams {
 };
 
 __global__ __launch_bounds__(MKE_BLOCK) void k_topk_long(const TopkLongParams p) {
-  static_assert(MKE_BLOCK == 256, "one histogram bin per thread");
   __shared__ int s_hist[MKE_BLOCK / 64][256];
   __shared__ int s_wave[MKE_BLOCK / 64];
   __shared__ unsigned s_prefix;
   __shared__ int s_need;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const float* __restrict__ v = p.vals + (int64_t)blockIdx.x * p.ld;
-  if (tid == 0) { s_prefix = 0u; s_need = p.k; }
-  __syncthreads();
-  for (int hi = 32; hi > 0; hi -= 8) {
-    const int shift = hi - 8;
-#pragma unroll
-    for (int q = 0; q < MKE_BLOCK / 64; ++q) s_hist[q][tid] = 0;
-    __syncthreads();
-    const unsigned pre = s_prefix;
-    const int need = s_need;
-    for (int i = tid; i < p.n; i += MKE_BLOCK) {
-      const unsigned kx = float_key(v[i]);
-      if (hi >= 32 || (kx >> hi) == (pre >> hi)) atomicAdd(&s_hist[wv][(kx >> shift) & 255u], 1);
-    }
-    __syncthreads();
-    const int dgt = 255 - tid;                       // thread t owns digit 255 - t: inclusive scan from the largest digit down
-    const int h = s_hist[0][dgt] + s_hist[1][dgt] + s_hist[2][dgt] + s_hist[3][dgt];
-    int incl = h;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int o = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += o;
-    }
-    if (lane == 63) s_wave[wv] = incl;
-    __syncthreads();
-    for (int q = 0; q < wv; ++q) incl += s_wave[q];
-    if (incl >= need && incl - h < need) {           // exactly one thread: the digit where the count from the top reaches `need`
-      s_prefix = pre | ((unsigned)dgt << shift);
-      s_need = need - (incl - h);
-    }
-    __syncthreads();
-  }
-  const unsigned kth = s_prefix;
-  const int ties = s_need;                           // how many of the keys equal to kth belong to the top k
+  int ties;                                          // how many of the keys equal to kth belong to the top k
+  const unsigned kth = radix_select_kth(s_hist, s_wave, &s_prefix, &s_need, p.n, p.k, &ties, [&](int i) { return float_key(v[i]); });
   int32_t* __restrict__ o = p.out_idx + (int64_t)blockIdx.x * p.k;
   int gt_run = 0, eq_run = 0;                        // block-uniform running counts of the chunks before this one
   for (int base = 0; base < p.n; base += MKE_BLOCK) {
@@ -397,24 +340,14 @@ extern "C" int mke_sim_select(const float* emb, int ld, int kpad, int64_t n_cols
   SimSelectParams p;
   p.emb = emb; p.ld = ld; p.n_cols = (int)n_cols; p.row_lo = (int)row_lo; p.row_hi = (int)row_hi; p.tau = tau;
   p.n_seg = n_seg; p.seg_cap = seg_cap;
-  const int bn = SIMT_BN_FOR(kpad / 16);
-  const int ntiles = (int)((n_cols + bn - 1) / bn);
-  p.tiles_per_seg = (ntiles + n_seg - 1) / n_seg;
+  p.tiles_per_seg = simt_split_fixed(n_cols, kpad, n_seg).tiles_per_chunk;  // all n_seg segments are launched, empty ones too
   p.cand = cand; p.seg_count = seg_count;
   dim3 grid((unsigned)((row_hi - row_lo + SIMT_BM - 1) / SIMT_BM), (unsigned)n_seg);
   hipStream_t st = (hipStream_t)stream;
-#define KNN_CASE(K)                                                                 \
-  case K:                                                                           \
-    hipLaunchKernelGGL((k_sim_select<K / 16>), grid, dim3(MKE_BLOCK), 0, st, p);     \
-    break;
-  switch (kpad) {
-    KNN_CASE(16) KNN_CASE(32) KNN_CASE(48) KNN_CASE(64) KNN_CASE(80) KNN_CASE(96) KNN_CASE(112) KNN_CASE(128) KNN_CASE(160)
-    KNN_CASE(192) KNN_CASE(208) KNN_CASE(256) KNN_CASE(320)
-    default:
-      set_error("mke_sim_select: unsupported kpad %d", kpad);
-      return MKE_E_UNSUPPORTED;
-  }
-#undef KNN_CASE
+  const bool found = simt_for_kpad(kpad, [&](auto ks) {
+    hipLaunchKernelGGL((k_sim_select<decltype(ks)::value>), grid, dim3(MKE_BLOCK), 0, st, p);
+  });
+  if (!found) { set_error("mke_sim_select: unsupported kpad %d", kpad); return MKE_E_UNSUPPORTED; }
   return check_launch("k_sim_select");
 }
 
@@ -427,27 +360,14 @@ extern "C" int mke_sim_sample(const float* emb, int ld, int kpad, int64_t n_rows
   if (kpad <= 0 || kpad % 16 != 0 || kpad > MKE_MAX_STRIDE || ld < kpad || ld_samp < kpad || ld % 4 != 0 || ld_samp % 4 != 0) { set_error("mke_sim_sample: kpad must be a multiple of 16 <= %d and <= ld, ld_samp (multiples of 4)", MKE_MAX_STRIDE); return MKE_E_SHAPE; }
   SimSampleParams p;
   p.emb = emb; p.ld = ld; p.row_lo = (int)row_lo; p.row_hi = (int)row_hi; p.samp = samp; p.ld_s = ld_samp; p.n_samp = n_samp; p.out = out;
-  const int bn = SIMT_BN_FOR(kpad / 16);
-  const int ntiles = (n_samp + bn - 1) / bn;
-  const int row_blocks = (int)((row_hi - row_lo + SIMT_BM - 1) / SIMT_BM);
-  int chunks = (4096 + row_blocks - 1) / row_blocks;
-  if (chunks > (ntiles + 7) / 8) chunks = (ntiles + 7) / 8;
-  if (chunks < 1) chunks = 1;
-  p.tiles_per_chunk = (ntiles + chunks - 1) / chunks;
-  dim3 grid((unsigned)row_blocks, (unsigned)((ntiles + p.tiles_per_chunk - 1) / p.tiles_per_chunk));
+  const SimtSplit sp = simt_split(row_hi - row_lo, n_samp, kpad, 4096, 8, INT_MAX);
+  p.tiles_per_chunk = sp.tiles_per_chunk;
+  dim3 grid((unsigned)((row_hi - row_lo + SIMT_BM - 1) / SIMT_BM), (unsigned)sp.chunks);
   hipStream_t st = (hipStream_t)stream;
-#define KNN_CASE(K)                                                                 \
-  case K:                                                                           \
-    hipLaunchKernelGGL((k_sim_sample<K / 16>), grid, dim3(MKE_BLOCK), 0, st, p);     \
-    break;
-  switch (kpad) {
-    KNN_CASE(16) KNN_CASE(32) KNN_CASE(48) KNN_CASE(64) KNN_CASE(80) KNN_CASE(96) KNN_CASE(112) KNN_CASE(128) KNN_CASE(160)
-    KNN_CASE(192) KNN_CASE(208) KNN_CASE(256) KNN_CASE(320)
-    default:
-      set_error("mke_sim_sample: unsupported kpad %d", kpad);
-      return MKE_E_UNSUPPORTED;
-  }
-#undef KNN_CASE
+  const bool found = simt_for_kpad(kpad, [&](auto ks) {
+    hipLaunchKernelGGL((k_sim_sample<decltype(ks)::value>), grid, dim3(MKE_BLOCK), 0, st, p);
+  });
+  if (!found) { set_error("mke_sim_sample: unsupported kpad %d", kpad); return MKE_E_UNSUPPORTED; }
   return check_launch("k_sim_sample");
 }
 

@@ -1,7 +1,9 @@
-// mke_rescore.h — what the evaluator's sweeps share (mke_csls.hip, mke_stable.hip): the metric / CSLS epilogue of one
-// similarity, the order-preserving integer image of a float, and the bounds of the whole-row rounds.
+// mke_rescore.h — what the evaluator's re-scoring sweeps share (k_align_rank_ex and k_topk_partial of mke_csls.hip,
+// k_stable_select of mke_stable.hip): the metric / CSLS epilogue of one similarity, its dispatch on the host, and the bounds
+// of the whole-row rounds.
 #pragma once
-#include "mke_common.h"
+#include "mke_select.h"
+#include "mke_simtile.h"
 
 #include <math.h>
 
@@ -20,20 +22,15 @@ __device__ __forceinline__ float rescore(float dot, float sqi, float sqj, float 
   return v;
 }
 
-__device__ __forceinline__ unsigned csls_key(float v) {  // order-preserving integer image (+0 and -0 one key)
-  unsigned u = __float_as_uint(v);
-  if (u == 0x80000000u) u = 0u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float csls_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
-
-static inline bool kpad_ok(int kpad) {
-  switch (kpad) {
-    case 16: case 32: case 48: case 64: case 80: case 96: case 112: case 128: case 160: case 192: case 208: case 256: case 320:
-      return true;
-    default:
-      return false;
-  }
+// (euclidean, CSLS) as compile-time constants: f(std::integral_constant<int, MKE_METRIC_*>{}, std::bool_constant<CSLS>{})
+template <class F>
+static inline void for_rescore(bool euc, bool csls, F&& f) {
+  using Euc = std::integral_constant<int, MKE_METRIC_EUCLIDEAN>;
+  using Inner = std::integral_constant<int, MKE_METRIC_INNER>;
+  if (euc && csls) f(Euc{}, std::true_type{});
+  else if (euc) f(Euc{}, std::false_type{});
+  else if (csls) f(Inner{}, std::true_type{});
+  else f(Inner{}, std::false_type{});
 }
 
 // rows of a whole-row round: the similarity rows of one round stay under 2^26 floats (256 MB)

@@ -1,6 +1,9 @@
-// mke_simtile.h — the f32 MFMA sweep shared by the k-NN refresh (mke_knn.hip) and the alignment evaluator (mke_eval.hip):
-// similarities of a block's 128 rows against a range of 64-column tiles, handed tile by tile to an epilogue that folds
-// them into whatever the caller wants (candidate lists, rank counters) — the similarity matrix itself never exists.
+// mke_simtile.h — the f32 MFMA sweep behind every similarity the project reports, and what its clients need besides it.
+// Clients: k_align_rank (mke_eval.hip), k_align_rank_ex and k_topk_partial (mke_csls.hip), k_sim_select and k_sim_sample
+// (mke_knn.hip), k_stable_select (mke_stable.hip).  The sweep: similarities of a block's 128 rows against a range of
+// 64-column tiles, handed tile by tile to an epilogue that folds them into whatever the client wants (candidate lists, rank
+// counters, top-k buffers) — the similarity matrix itself never exists.  Besides it: the accumulator row map (simt_row),
+// the one list of supported widths (simt_for_kpad) and the column split of a launch (simt_split, simt_split_fixed).
 //
 // A block = 4 wavefronts x one 32-row strip.  The strip is the MFMA A operand and stays in VGPRs for the whole sweep; the
 // columns are rows of a row-major [n][ld] matrix, so a 64-column tile is 64 consecutive rows = one contiguous copy, staged
@@ -13,12 +16,58 @@
 #pragma once
 #include "mke_common.h"
 
+#include <type_traits>
+
 namespace mke {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #define SIMT_BM 128                              // rows per block
 #define SIMT_BN_FOR(KS) ((KS) <= 13 ? 64 : 32)   // columns per tile: BN x (kpad + 4) floats must stay under 64 KB
+
+// C/D map of v_mfma_f32_32x32x2_f32: accumulator register `reg` of a lane holds column lane & 31 of this row of the 32 x 32
+// product (half = lane >> 5); row0 = the row of the product's first, added first so that the sum associates as the kernels
+// always wrote it
+__host__ __device__ constexpr int simt_row(int reg, int half, int row0 = 0) { return row0 + (reg & 3) + 8 * (reg >> 2) + 4 * half; }
+
+// The supported widths — the only place that lists them.  Calls f(std::integral_constant<int, kpad / 16>{}) and returns true,
+// or returns false: no instantiation for this kpad.
+template <class F>
+static inline bool simt_for_kpad(int kpad, F&& f) {
+  switch (kpad) {
+#define SIMT_WIDTH(K) case K: f(std::integral_constant<int, K / 16>{}); return true;
+    SIMT_WIDTH(16) SIMT_WIDTH(32) SIMT_WIDTH(48) SIMT_WIDTH(64) SIMT_WIDTH(80) SIMT_WIDTH(96) SIMT_WIDTH(112) SIMT_WIDTH(128)
+    SIMT_WIDTH(160) SIMT_WIDTH(192) SIMT_WIDTH(208) SIMT_WIDTH(256) SIMT_WIDTH(320)
+#undef SIMT_WIDTH
+    default: return false;
+  }
+}
+static inline bool simt_kpad_ok(int kpad) { return simt_for_kpad(kpad, [](auto) {}); }
+
+// Column split of a launch: gridDim.y chunks of tiles_per_chunk tiles each, none of them empty.
+struct SimtSplit {
+  int chunks, tiles_per_chunk;
+};
+// `parts` equal parts of the n_cols columns' tiles.  .chunks counts the parts that hold a tile; a caller whose grid keeps `parts`
+// (mke_sim_select: the caller owns the segment layout) launches the empty ones too.
+static inline SimtSplit simt_split_fixed(int64_t n_cols, int kpad, int parts) {
+  const int bn = SIMT_BN_FOR(kpad / 16);
+  const int ntiles = (int)((n_cols + bn - 1) / bn);
+  const int per = (ntiles + parts - 1) / parts;
+  return {(ntiles + per - 1) / per, per};
+}
+// Enough (row block, column chunk) items to fill the chip several times over (`target`), a chunk at least min_tiles tiles, at
+// most `cap` chunks.
+static inline SimtSplit simt_split(int64_t rows, int64_t n_cols, int kpad, int target, int min_tiles, int cap) {
+  const int bn = SIMT_BN_FOR(kpad / 16);
+  const int ntiles = (int)((n_cols + bn - 1) / bn);
+  const int row_blocks = (int)((rows + SIMT_BM - 1) / SIMT_BM);
+  int chunks = (target + row_blocks - 1) / row_blocks;
+  if (chunks > (ntiles + min_tiles - 1) / min_tiles) chunks = (ntiles + min_tiles - 1) / min_tiles;
+  if (chunks > cap) chunks = cap;
+  if (chunks < 1) chunks = 1;
+  return simt_split_fixed(n_cols, kpad, chunks);
+}
 
 // MFMA A/B operand fragment of one row: frag[s * 8 + j] = row[16 s + 8 half + j]
 template <int KS>
@@ -33,7 +82,7 @@ __device__ __forceinline__ void simt_load_fragment(const float* __restrict__ row
   }
 }
 
-// 32 x 32 similarities of two fragments (C/D map: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5))
+// 32 x 32 similarities of two fragments (C/D map: col = lane & 31, row = simt_row(reg, lane >> 5))
 template <int KS>
 __device__ __forceinline__ f32x16 simt_fragment_product(const float (&a)[KS * 8], const float (&b)[KS * 8]) {
   f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};

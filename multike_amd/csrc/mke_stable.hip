@@ -12,16 +12,16 @@
 //   tau             per row the m-th largest re-scored similarity to a strided sample of <= 4096 columns (mke_sim_sample on
 //                   b with a row stride, k_stable_rescore, mke_topk_rows), m chosen so that about 2 cut + 32 columns pass.
 //                   n_b <= STABLE_LIST_CAP: no sample, tau = -inf (every column is a candidate).
-//   k_stable_select the sweep of mke_simtile.h; the epilogue appends (ordered(s) << 32 | 0xFFFFFFFF - column) of every
+//   k_stable_select the sweep of mke_simtile.h; the epilogue appends (float_key(s) << 32 | 0xFFFFFFFF - column) of every
 //                   s >= tau to the row's candidate list of this column segment: a ballot per accumulator register gives
 //                   each hit its slot, no atomics.  8 segments x 128 slots per row.
-//   k_stable_pick   one block per row: the candidates (<= 1024 packed keys) sorted descending in LDS (bitonic) — value
+//   k_stable_pick   one block per row: the candidates (<= 1024 packed keys) sorted descending in LDS (sort_desc) — value
 //                   descending, then column ascending, in one compare — and the first `cut` written out.  A row with
 //                   fewer than `cut` candidates under a threshold, or with an overflowed segment, is flagged; the caller
 //                   redoes flagged rows through the whole-row path.
 // cut > STABLE_FAST_CUT, flagged rows, or a similarity matrix given by the caller — rounds of whole rows (<= 2^26 floats):
 //   mke_sim_sample -> k_stable_rescore (in place; NaN becomes the negative quiet NaN, which orders below -inf in the integer
-//   image) -> mke_topk_long -> k_stable_gather (packed keys of the selected columns, bitonic sort, NaN dropped).
+//   image) -> mke_topk_long -> k_stable_gather (packed keys of the selected columns, sort_desc, NaN dropped).
 //
 // Deferred acceptance (mke_stable_rounds / mke_stable_finish): one thread per suitor and round; the only atomics are the
 // 64-bit max on holder[column] and the round's proposal counter.  holder only grows, so the outcome does not depend on the
@@ -34,7 +34,6 @@
 //   k_stable_pick                         28 VGPRs, 8,232 B of LDS per block;  k_stable_gather  17 VGPRs, 32,768 B of LDS
 //   (k_topk_partial<5, inner>, the LDS form of profiles/r07_csls.md: 220 + 32 registers and 75,776 B at k = 10, values only.)
 #include "mke_rescore.h"
-#include "mke_simtile.h"
 
 namespace mke {
 
@@ -82,7 +81,7 @@ __global__ __launch_bounds__(MKE_BLOCK, KS <= 5 ? 2 : 1) void k_stable_select(co
   int cnt[16];
 #pragma unroll
   for (int reg = 0; reg < 16; ++reg) {
-    const int r = strip0 + (reg & 3) + 8 * (reg >> 2) + 4 * half;
+    const int r = simt_row(reg, half, strip0);
     const bool ok = r < p.row_hi;
     tauR[reg] = ok ? (p.tau ? p.tau[r] : -INFINITY) : __builtin_nanf("");  // rows past the end take nothing (v >= NaN is false)
     sqi[reg] = (EUC && ok) ? p.sq_a[r] : 0.f;
@@ -112,8 +111,8 @@ __global__ __launch_bounds__(MKE_BLOCK, KS <= 5 ? 2 : 1) void k_stable_select(co
       const unsigned mh = half ? (unsigned)(m >> 32) : (unsigned)m;  // the 32 lanes of a half hold 32 columns of ONE row
       const int pos = cnt[reg] + __popc(mh & lt);
       if (hit && pos < STABLE_SEG_CAP) {
-        const unsigned long long key = ((unsigned long long)csls_key(v) << 32) | (unsigned long long)low;
-        *reinterpret_cast<unsigned long long*>(cand_b + (base0_b + (unsigned)((reg & 3) + 8 * (reg >> 2)) * row_stride_b + (unsigned)pos * 8u)) = key;
+        const unsigned long long key = ((unsigned long long)float_key(v) << 32) | (unsigned long long)low;
+        *reinterpret_cast<unsigned long long*>(cand_b + (base0_b + (unsigned)simt_row(reg, 0) * row_stride_b + (unsigned)pos * 8u)) = key;
       }
       cnt[reg] += __popc(mh);
     }
@@ -121,32 +120,15 @@ __global__ __launch_bounds__(MKE_BLOCK, KS <= 5 ? 2 : 1) void k_stable_select(co
   if (l31 == 0) {
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg) {
-      const int r = strip0 + (reg & 3) + 8 * (reg >> 2) + 4 * half;
+      const int r = simt_row(reg, half, strip0);
       if (r < p.row_hi) p.seg_count[(int64_t)(r - p.row_lo) * p.n_seg + seg] = cnt[reg];
     }
   }
 }
 
-// bitonic sort of np2 (a power of two) 64-bit keys, descending, by the whole block
-__device__ __forceinline__ void sort_desc(unsigned long long* buf, int np2) {
-  const int tid = threadIdx.x;
-  for (int size = 2; size <= np2; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int i = tid; i < np2 / 2; i += MKE_BLOCK) {
-        const int lo = 2 * i - (i & (stride - 1));
-        const int hi = lo + stride;
-        const bool desc = (lo & size) == 0;
-        const unsigned long long x = buf[lo], y = buf[hi];
-        if ((x < y) == desc) { buf[lo] = y; buf[hi] = x; }
-      }
-      __syncthreads();
-    }
-  }
-}
-
 __device__ __forceinline__ void write_entry(unsigned long long key, float* val, int32_t* col) {
-  if (key == 0ull) { *val = -INFINITY; *col = -1; return; }  // padding (no real key is 0: ordered(s) of a non-NaN s is not)
-  *val = csls_unkey((unsigned)(key >> 32));
+  if (key == 0ull) { *val = -INFINITY; *col = -1; return; }  // padding (no real key is 0: float_key(s) of a non-NaN s is not)
+  *val = key_float((unsigned)(key >> 32));
   *col = (int32_t)(0xFFFFFFFFu - (unsigned)key);
 }
 
@@ -228,7 +210,7 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_stable_rescore(const StableRescor
     if (euc && csls) v = rescore<MKE_METRIC_EUCLIDEAN, true>(v, sqi, p.sq_b[col], rti, p.csls_col[col]);
     else if (euc) v = rescore<MKE_METRIC_EUCLIDEAN, false>(v, sqi, p.sq_b[col], 0.f, 0.f);
     else if (csls) v = rescore<MKE_METRIC_INNER, true>(v, 0.f, 0.f, rti, p.csls_col[col]);
-    if (v != v) v = __uint_as_float(0xFFC00000u);  // orders below -inf in float_key / csls_key: selected last, dropped by the gather
+    if (v != v) v = __uint_as_float(0xFFC00000u);  // orders below -inf in float_key: selected last, dropped by the gather
     d[j] = v;
   }
 }
@@ -256,7 +238,7 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_stable_gather(const StableGatherP
     if (j < p.cut) {
       const int c = sel[j];
       const float x = v[c];
-      if (x == x) key = ((unsigned long long)csls_key(x) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)c);
+      if (x == x) key = ((unsigned long long)float_key(x) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)c);
     }
     buf[j] = key;
   }
@@ -313,7 +295,7 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_stable_round(const StableMatchPar
     }
   }
   if (propose) {
-    const unsigned long long key = ((unsigned long long)csls_key(p.val[(int64_t)i * p.cut + pos]) << 32) |
+    const unsigned long long key = ((unsigned long long)float_key(p.val[(int64_t)i * p.cut + pos]) << 32) |
                                    (unsigned long long)(0xFFFFFFFFu - (unsigned)i);
     atomicMax(&p.holder[c], key);
   }
@@ -419,7 +401,7 @@ extern "C" int mke_stable_lists(const mke_stable_lists_args* args, void* stream)
     if (!g.a || !g.b) { set_error("mke_stable_lists: NULL pointer"); return MKE_E_NULL; }
     if (g.metric == MKE_METRIC_EUCLIDEAN && (!g.sq_a || !g.sq_b)) { set_error("mke_stable_lists: euclidean needs sq_a and sq_b"); return MKE_E_NULL; }
     if (g.lda < g.kpad || g.ldb < g.kpad || g.lda % 4 != 0 || g.ldb % 4 != 0) { set_error("mke_stable_lists: lda, ldb must be multiples of 4 >= kpad"); return MKE_E_SHAPE; }
-    if (!kpad_ok(g.kpad)) { set_error("mke_stable_lists: unsupported kpad %d", g.kpad); return MKE_E_UNSUPPORTED; }
+    if (!simt_kpad_ok(g.kpad)) { set_error("mke_stable_lists: unsupported kpad %d", g.kpad); return MKE_E_UNSUPPORTED; }
   }
   if (g.temp_bytes < pl.bytes) { set_error("mke_stable_lists: temp below mke_stable_lists_temp_bytes (%lld)", (long long)pl.bytes); return MKE_E_SHAPE; }
   hipStream_t st = (hipStream_t)stream;
@@ -487,10 +469,9 @@ extern "C" int mke_stable_lists(const mke_stable_lists_args* args, void* stream)
   StableSelectParams sp;
   sp.a = g.a; sp.lda = g.lda; sp.b = g.b; sp.ldb = g.ldb; sp.n_b = (int)g.n_b; sp.sq_a = g.sq_a; sp.sq_b = g.sq_b;
   sp.csls_row = g.csls_row; sp.csls_col = g.csls_col; sp.tau = thresholded ? tau : nullptr;
-  const int bn = SIMT_BN_FOR(g.kpad / 16);
-  const int ntiles = (int)((g.n_b + bn - 1) / bn);
-  sp.tiles_per_seg = (ntiles + STABLE_SEGS - 1) / STABLE_SEGS;
-  sp.n_seg = (ntiles + sp.tiles_per_seg - 1) / sp.tiles_per_seg;  // no empty segment
+  const SimtSplit segs = simt_split_fixed(g.n_b, g.kpad, STABLE_SEGS);
+  sp.tiles_per_seg = segs.tiles_per_chunk;
+  sp.n_seg = segs.chunks;  // no empty segment
   sp.cand = (unsigned long long*)(temp + pl.off_work);
   sp.seg_count = (int32_t*)(temp + pl.off_cnt);
   StablePickParams pp;
@@ -499,18 +480,12 @@ extern "C" int mke_stable_lists(const mke_stable_lists_args* args, void* stream)
     const int64_t hi = lo + pl.rows < g.n_a ? lo + pl.rows : g.n_a;
     sp.row_lo = (int)lo; sp.row_hi = (int)hi;
     dim3 grid((unsigned)((hi - lo + SIMT_BM - 1) / SIMT_BM), (unsigned)sp.n_seg);
-#define ST_CASE(K)                                                                                                             \
-  case K:                                                                                                                      \
-    if (euc && csls) hipLaunchKernelGGL((k_stable_select<K / 16, MKE_METRIC_EUCLIDEAN, true>), grid, dim3(MKE_BLOCK), 0, st, sp);  \
-    else if (euc) hipLaunchKernelGGL((k_stable_select<K / 16, MKE_METRIC_EUCLIDEAN, false>), grid, dim3(MKE_BLOCK), 0, st, sp);  \
-    else if (csls) hipLaunchKernelGGL((k_stable_select<K / 16, MKE_METRIC_INNER, true>), grid, dim3(MKE_BLOCK), 0, st, sp);      \
-    else hipLaunchKernelGGL((k_stable_select<K / 16, MKE_METRIC_INNER, false>), grid, dim3(MKE_BLOCK), 0, st, sp);               \
-    break;
-    switch (g.kpad) {
-      ST_CASE(16) ST_CASE(32) ST_CASE(48) ST_CASE(64) ST_CASE(80) ST_CASE(96) ST_CASE(112) ST_CASE(128) ST_CASE(160)
-      ST_CASE(192) ST_CASE(208) ST_CASE(256) ST_CASE(320)
-    }
-#undef ST_CASE
+    simt_for_kpad(g.kpad, [&](auto ks) {
+      for_rescore(euc, csls, [&](auto met, auto cs) {
+        hipLaunchKernelGGL((k_stable_select<decltype(ks)::value, decltype(met)::value, decltype(cs)::value>), grid, dim3(MKE_BLOCK), 0,
+                           st, sp);
+      });
+    });
     int e = check_launch("k_stable_select");
     if (e) return e;
     pp.out_val = g.out_val + lo * g.cut; pp.out_col = g.out_col + lo * g.cut; pp.flags = g.flags + lo;

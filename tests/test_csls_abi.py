@@ -132,6 +132,31 @@ def test_topk_mean_argument_errors(lib):
         _lib.align_topk_mean_temp_bytes(10, 10, 16, 9)
 
 
+UNSUPPORTED_KPADS = (144, 176, 224, 240, 272, 288, 304)  # the multiples of 16 up to MKE_MAX_STRIDE without an instantiation
+
+
+def test_sweep_entry_points_refuse_a_width_without_instantiation(lib):
+    """Every sweep launcher whose "no instantiation" path had no test (mke_align_rank, mke_sim_select, mke_sim_sample,
+    mke_align_topk_mean on both of its paths) returns MKE_E_UNSUPPORTED with its own message once every other argument has
+    passed its checks; none returns 0 without having launched.  Codes and texts as recorded from the build before the
+    launch ladders became one width dispatcher (mke_align_rank's message carries no prefix)."""
+    fake = C.c_void_p(0x1000)
+    err = lambda: lib.mke_last_error().decode()
+    for kpad in UNSUPPORTED_KPADS:
+        ld = C.c_int(kpad)
+        rc = lib.mke_align_rank(fake, ld, fake, ld, C.c_int(kpad), C.c_int64(100), C.c_int64(120), fake, fake, fake, None)
+        assert (rc, err()) == (-3, f"unsupported kpad {kpad}")
+        rc = lib.mke_sim_select(fake, ld, C.c_int(kpad), C.c_int64(120), C.c_int64(0), C.c_int64(100), fake, C.c_int(4),
+                                C.c_int(64), fake, fake, None)
+        assert (rc, err()) == (-3, f"mke_sim_select: unsupported kpad {kpad}")
+        rc = lib.mke_sim_sample(fake, ld, C.c_int(kpad), C.c_int64(120), C.c_int64(0), C.c_int64(100), fake, ld, C.c_int(50),
+                                fake, None)
+        assert (rc, err()) == (-3, f"mke_sim_sample: unsupported kpad {kpad}")
+        for k in (10, 100):                                       # the partial sweep, and whole rows through mke_sim_sample
+            rc = lib.mke_align_topk_mean(C.byref(_mean_args(kpad=kpad, lda=kpad, ldb=kpad, k=k)), None)
+            assert (rc, err()) == (-3, f"mke_align_topk_mean: unsupported kpad {kpad}")
+
+
 def test_greedy_alignment_rejects_other_metrics():
     from multike_amd import _lib
     from multike_amd.base.alignment import greedy_alignment
