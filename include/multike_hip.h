@@ -1003,7 +1003,10 @@ typedef struct mke_oc_step {
    * peer_g[o] = this rank's slice [2 * capacity][stride] of rank o's gradient inbox — both mapped into this process
    * (hipIpc): mke_oc_score reads the vectors and writes its partial gradient vectors straight over xGMI, mke_oc_apply sums
    * the n_ranks slices of its own inbox in rank order.  The caller places a cross-GPU barrier after mke_oc_bases and after
-   * mke_oc_score. */
+   * mke_oc_score.  With em_coef != NULL (the entity-major form, peer-direct): mke_oc_score also stores every vector it has
+   * loaded into the LOCAL mirror its `v_all` argument names ([n_ranks][block_floats], the all-gathered layout), mke_oc_gv_sum
+   * (MKE_OC_GVSUM) sums the inbox into a local block [2 * capacity][stride] in the same rank order, and em_v[0] / em_gv[0]
+   * point at those two local buffers: mke_oc_pass2 never reads over the links. */
   int n_peers; const float* peer_v[MKE_OC_MAX_RANKS]; float* peer_g[MKE_OC_MAX_RANKS];
   const float* pos_w;   /* nullable: [n_pos] weights of the positives (the weighted cross-KG loops, code/losses.py:44-50) */
   /* version 104: hub rows of this rank's shard (mke_hot_rows over LOCAL rows; slot == NULL: none) — rows that are head / tail of
@@ -1011,7 +1014,8 @@ typedef struct mke_oc_step {
    * has hot.row0 + hot.copies * hot.n_hot rows, hot.row0 >= n_local), they are not reference-counted and never finished in
    * place; mke_oc_run's update adds the copies */
   mke_hot_rows hot;
-  /* version 105: ENTITY-MAJOR second pass (em_coef != NULL selects it; new design).  mke_oc_score then writes
+  /* version 105 (with n_peers != 0 too, without a version change: no field moved): ENTITY-MAJOR second pass (em_coef != NULL
+   * selects it; new design).  mke_oc_score then writes
    * no row gradient at all: per (positive, owned negative) — and for the positive's own term — it stores ONE coefficient,
    * em_coef[(em_pos0 + i) * (neg_per_pos + 1) + n] (n == neg_per_pos: the own term), and mke_oc_pass2 finishes every touched
    * owned row of the GLOBAL STEP in place from the row's reference list (mke_oc_em_plan, sorted by row: a fixed summation
@@ -1020,7 +1024,8 @@ typedef struct mke_oc_step {
    * atomics on entity rows, and the entity table takes no part in mke_oc_apply / the update launch.
    * em_refs: pairs (locator, coefficient index) of the whole epoch; em_rows / em_off: the work items of THIS step (a touched owned
    * row, or one 32-reference segment of a long row's list) and their offsets into em_refs (em_off[em_n_rows] valid); em_v[c] / em_gv[c]: chunk c's all-gathered vectors [n_ranks][block] and
-   * reduce-scattered gradient block (the step's parts, at most MKE_OC_EM_MAX_CHUNKS). */
+   * reduce-scattered gradient block (the step's parts, at most MKE_OC_EM_MAX_CHUNKS).  Peer-direct (n_peers != 0; one part): the
+   * local mirror mke_oc_score filled and the local block mke_oc_gv_sum summed — the same two layouts. */
   float* em_coef; int64_t em_pos0;
   const uint32_t* em_refs; const int32_t* em_rows; const int32_t* em_off; int64_t em_n_rows;
   int em_chunks; int64_t em_block_floats; const float* em_v[4]; const float* em_gv[4];
@@ -1055,9 +1060,17 @@ int mke_oc_plan(const int32_t* pos_h, const int32_t* pos_t, const int32_t* codes
                 int32_t* counts, void* stream);
 int mke_oc_bases(const mke_oc_step* step, float* send_block, void* stream);
 int mke_oc_count(const mke_oc_step* step, void* stream);
+/* v_all / g_all: the all-gathered vectors and the gradient-vector slots (ignored in peer-direct mode, where peer_v / peer_g
+ * take their place) — EXCEPT a peer-direct entity-major step (n_peers != 0 and em_coef != NULL): there v_all is the local
+ * mirror [n_ranks][block_floats] that the launch WRITES (through a cast: the qualifier is kept for the callers of the other
+ * forms); NULL is MKE_E_NULL. */
 int mke_oc_score(const mke_oc_step* step, const float* v_all, int64_t block_floats, float* g_all,
                  double* loss_partials /* [MKE_LOSS_PARTIALS] */, void* stream);
 int mke_oc_apply(const mke_oc_step* step, const float* gv, void* stream);
+/* peer-direct entity-major step only (else MKE_E_UNSUPPORTED): gv[slot] = sum over writers w = 0 .. n_ranks - 1, in that order,
+ * of inbox[w][slot], for this rank's owned slots [0, n_own_h) and [capacity, capacity + n_own_t); inbox: [n_ranks][2 *
+ * capacity][stride] (what the peers' mke_oc_score wrote through peer_g), gv: [2 * capacity][stride], both local. */
+int mke_oc_gv_sum(const mke_oc_step* step, const float* inbox, float* gv, void* stream);
 /* the phases selected by the bit mask, in the order above, in one call (what lies between two collectives);
  * MKE_OC_BASES | MKE_OC_COUNT is ONE launch (the counting needs only the codes: it runs on rider blocks beside the bases): */
 #define MKE_OC_BASES 1
@@ -1066,6 +1079,8 @@ int mke_oc_apply(const mke_oc_step* step, const float* gv, void* stream);
 #define MKE_OC_APPLY 8      /* atomics form only: with em_coef != NULL mke_oc_apply / mke_oc_run return MKE_E_UNSUPPORTED */
 #define MKE_OC_UPDATE 16   /* mke_rows_update_multi: relation table (every row) + the shard's touched rows (entity-major: relation table only) */
 #define MKE_OC_PASS2 32    /* entity-major second pass over the touched owned rows of the global step (after the LAST part's reduce-scatter) */
+#define MKE_OC_GVSUM 64    /* peer-direct entity-major: mke_oc_gv_sum(step, g_all = this rank's inbox, gv = the local block), run before
+                            * MKE_OC_PASS2; `gv` is written through a cast */
 int mke_oc_run(const mke_oc_step* step, int phases, float* send_block, const float* v_all, int64_t block_floats, float* g_all,
                const float* gv, double* loss_partials, void* stream);
 

@@ -34,7 +34,7 @@ SYMBOLS = (
     "mke_sample_distinct", "mke_neg_sample_at", "mke_rows_update_dense", "mke_dense_update_opt", "mke_align_steps", "mke_sim_select", "mke_sim_sample", "mke_topk_rows", "mke_topk_candidates", "mke_mapping_scratch_floats", "mke_mapping_step", "mke_mapping_step_phases", "mke_mapping_steps",
     "mke_ae_scratch_floats", "mke_ae_train_steps", "mke_ae_step_phases", "mke_ae_encode", "mke_dense_layer_fwd",
     "mke_topk_long", "mke_probe_rows", "mke_oc_block_floats", "mke_oc_pack_codes", "mke_oc_plan", "mke_oc_bases", "mke_oc_count", "mke_oc_score", "mke_oc_apply", "mke_oc_run",
-    "mke_oc_em_plan_temp_bytes", "mke_oc_em_plan", "mke_oc_pass2", "mke_oc_steps",
+    "mke_oc_em_plan_temp_bytes", "mke_oc_em_plan", "mke_oc_pass2", "mke_oc_steps", "mke_oc_gv_sum",
     "mke_tuning_init", "mke_rows_update_multi_t",
     "mke_align_topk_mean_temp_bytes", "mke_align_topk_mean", "mke_align_rank_ex",
     "mke_stable_lists_temp_bytes", "mke_stable_lists", "mke_stable_rounds", "mke_stable_finish",
@@ -837,6 +837,7 @@ def oc_plan(pos_h, pos_t, codes, neg_per_pos: int, part_lo, n_parts: int, n_rank
 
 
 OC_BASES, OC_COUNT, OC_SCORE, OC_APPLY, OC_UPDATE, OC_PASS2 = 1, 2, 4, 8, 16, 32
+OC_GVSUM = 64       # peer-direct entity-major: the inbox (mke_oc_run's g_all) summed into the local block (gv), before OC_PASS2
 
 
 def oc_em_plan_temp_bytes(capacity: int) -> int:
@@ -858,6 +859,13 @@ def oc_steps(loop: OcLoopStruct, step_begin: int, step_end: int):
 
 def oc_pass2(step: OcStepStruct):
     _check(lib().mke_oc_pass2(C.byref(step), _stream()), "mke_oc_pass2")
+
+
+def oc_gv_sum(step: OcStepStruct, inbox, gv):
+    """mke_oc_gv_sum: the writers' slices of this rank's gradient inbox summed, in rank order, into the local block `gv`
+    (peer-direct entity-major steps only)."""
+    rc = lib().mke_oc_gv_sum(C.byref(step), _dev(inbox, torch.float32, "inbox"), _dev(gv, torch.float32, "gv"), _stream())
+    _check(rc, "mke_oc_gv_sum")
 
 
 def oc_run(step: OcStepStruct, phases: int, send, v_all, block_floats: int, g_all, gv, loss_partials):

@@ -204,8 +204,21 @@ __device__ __forceinline__ float oc_positive_term(const mke_oc_step& s, int STRI
 // One wavefront per positive of the global step.  Lane l holds the code of negative l (neg_per_pos <= 64); the negatives
 // this rank owns are dealt round-robin to the four quarter-waves (the (4 round + q)-th set bit of the ballot), U of them
 // in flight per quarter.
-template <int FPL, int U, bool P2, bool EM = false>
+//
+// Peer-direct entity-major form (MIR): the vectors come from the owners' send blocks over the links, and the second pass wants
+// them again ~(N + 1) / G times each — so the wavefront that has just loaded a positive's HR / RT stores it into this rank's LOCAL
+// mirror [G][block_floats] (p.v_all, unused as a source in peer mode) at the address the all-gathered copy would have.  Every
+// rank visits every positive of the global step: after the launch the mirror IS the all-gathered buffer, one writer per slot.
+// MIR is a compile-time constant carried by the first template argument, FPLX = floats per lane (stride / 16 <= 20) | OC_MIRROR:
+// a template parameter of its own would rename the symbol of every existing instantiation, and a shared device-function body
+// under two thin kernels came out scheduled differently in 104 of the 135 kernels (profiles/r15_peer_em.md).  This way the
+// collective entity-major and the atomics instantiations keep their symbols and their instruction streams.
+#define OC_MIRROR 64
+template <int FPLX, int U, bool P2, bool EM = false>
 __global__ __launch_bounds__(MKE_BLOCK) void k_oc_score(const OcParams p) {
+  constexpr int FPL = FPLX & (OC_MIRROR - 1);
+  constexpr bool MIR = (FPLX & OC_MIRROR) != 0;
+  static_assert(EM || !MIR, "the mirror belongs to the entity-major form");
   constexpr int STRIDE = FPL * 16;   // == s.stride (the dispatch picks FPL from it): row offsets by shift-add, not a 64-bit multiply
   const mke_oc_step& s = p.s;
   const int lane = threadIdx.x & 63, j = lane & 15, q = lane >> 4;
@@ -234,6 +247,19 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_oc_score(const OcParams p) {
     for (int k = 0; k < FPL; ++k) HR[k] = RT[k] = gHR[k] = gRT[k] = 0.f;
     if (sh >= 0) load_row<FPL>(vh, 0, STRIDE, j, HR);
     if (st >= 0) load_row<FPL>(vt, 0, STRIDE, j, RT);
+    if constexpr (MIR) {   // the four quarters hold the same vectors: quarter 0 mirrors HR, quarter 1 RT
+      float* const mir = const_cast<float*>(p.v_all);
+      if (q == 0 && sh >= 0) {
+        float* o = mir + (int64_t)oc_mod(dv, ph) * p.block_floats + (int64_t)sh * STRIDE + j;
+#pragma unroll
+        for (int k = 0; k < FPL; ++k) o[k * 16] = HR[k];
+      }
+      if (q == 1 && st >= 0) {
+        float* o = mir + (int64_t)oc_mod(dv, pt) * p.block_floats + (C + st) * STRIDE + j;
+#pragma unroll
+        for (int k = 0; k < FPL; ++k) o[k * 16] = RT[k];
+      }
+    }
     const uint64_t mask = __ballot(mine);
     const int total = __popcll(mask);
     float* const coefp = EM ? s.em_coef + (s.em_pos0 + i) * (N + 1) : nullptr;   // this positive's coefficients (entity-major)
@@ -368,9 +394,12 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_oc_score(const OcParams p) {
 // with all 25 negatives each (profiles/r04_oc_rank_compute.md).  Here a quarter owns its positive outright: its 16 lanes fetch the
 // codes 16 at a time, the owned ones are visited one after the other (the four quarters of a wavefront iterate together until the
 // busiest is done), the partial gradient vectors need no cross-quarter reduction.  Same arithmetic, same slots, same in-place /
-// scatter rule per corrupt row as k_oc_score.
-template <int FPL, bool P2, bool EM = false>
+// scatter rule per corrupt row as k_oc_score; FPLX as there (| OC_MIRROR: the quarter mirrors its positive's vector(s)).
+template <int FPLX, bool P2, bool EM = false>
 __global__ __launch_bounds__(MKE_BLOCK) void k_oc_score_q(const OcParams p) {
+  constexpr int FPL = FPLX & (OC_MIRROR - 1);
+  constexpr bool MIR = (FPLX & OC_MIRROR) != 0;
+  static_assert(EM || !MIR, "the mirror belongs to the entity-major form");
   constexpr int STRIDE = FPL * 16;
   const mke_oc_step& s = p.s;
   const int lane = threadIdx.x & 63, j = lane & 15, q = lane >> 4;
@@ -395,6 +424,19 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_oc_score_q(const OcParams p) {
     for (int k = 0; k < FPL; ++k) HR[k] = RT[k] = gHR[k] = gRT[k] = 0.f;
     if (sh >= 0) load_row<FPL>(vh, 0, STRIDE, j, HR);
     if (st >= 0) load_row<FPL>(vt, 0, STRIDE, j, RT);
+    if constexpr (MIR) {   // (sh, st are -1 for a quarter without a positive)
+      float* const mir = const_cast<float*>(p.v_all);
+      if (sh >= 0) {
+        float* o = mir + (int64_t)oc_mod(dv, ph) * p.block_floats + (int64_t)sh * STRIDE + j;
+#pragma unroll
+        for (int k = 0; k < FPL; ++k) o[k * 16] = HR[k];
+      }
+      if (st >= 0) {
+        float* o = mir + (int64_t)oc_mod(dv, pt) * p.block_floats + (C + st) * STRIDE + j;
+#pragma unroll
+        for (int k = 0; k < FPL; ++k) o[k * 16] = RT[k];
+      }
+    }
     // the positive itself: with HR on the wire the owner of t scores it, else the owner of h
     if (act && oc_mod(dv, sh >= 0 ? pt : ph) == s.rank) {
       const float pw = s.pos_w ? s.pos_w[i] : 1.0f;
@@ -540,6 +582,31 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_oc_apply(const OcParams p) {
   }
 }
 
+// Peer-direct entity-major: a quarter-wave per owned slot (HR slots [0, n_own_h), RT slots [capacity, capacity + n_own_t)) sums the
+// n_ranks writers' slices of this rank's inbox (p.g_all: [n_ranks][2 C][stride]) into the local block the second pass reads
+// (p.send: [2 C][stride]) — slice 0, then += slice 1, ...: k_oc_apply's order.  One writer per slot, a fixed order: the step stays
+// bit-reproducible.  (The reduce-scatter's job, done by the rank that receives.)
+template <int FPL>
+__global__ __launch_bounds__(MKE_BLOCK) void k_oc_gv_sum(const OcParams p) {
+  const mke_oc_step& s = p.s;
+  const int j = threadIdx.x & 15;
+  const int64_t sub = ((int64_t)blockIdx.x * MKE_BLOCK + threadIdx.x) >> 4;
+  if (sub >= s.n_own_h + s.n_own_t) return;
+  const int64_t slot = sub < s.n_own_h ? sub : s.capacity + (sub - s.n_own_h);
+  const int64_t gb = 2 * s.capacity * (int64_t)s.stride;
+  float v[FPL];
+  load_row<FPL>(p.g_all, slot, s.stride, j, v);
+  for (int r = 1; r < s.n_ranks; ++r) {
+    float w[FPL];
+    load_row<FPL>(p.g_all + r * gb, slot, s.stride, j, w);
+#pragma unroll
+    for (int c = 0; c < FPL; ++c) v[c] += w[c];
+  }
+  float* o = p.send + slot * (int64_t)s.stride + j;
+#pragma unroll
+  for (int c = 0; c < FPL; ++c) o[c * 16] = v[c];
+}
+
 // ---- per-epoch plan: the slot of every positive's HR / RT vector in its owner's block -------------------------------------
 // Part k of the epoch = epoch positions [part_lo[k], part_lo[k + 1]).  Inside a part, the positives whose head (tail) is
 // owned by rank g = id % G AND whose negatives need HR (RT) — the flag bits of the group's first code, codes laid out by
@@ -653,7 +720,6 @@ static int oc_check(const mke_oc_step* s, const char* who) {
   if (s->optimizer != MKE_OPT_ADAGRAD && s->optimizer != MKE_OPT_SGD) { set_error("%s: Adagrad or SGD", who); return MKE_E_UNSUPPORTED; }
   if (s->hot.slot && (s->hot.n_hot < 1 || s->hot.copies < 1 || s->hot.copies > 64 || s->hot.row0 < s->n_local)) { set_error("%s: bad hub-row declaration", who); return MKE_E_SHAPE; }
   if (s->em_coef) {   // entity-major second pass
-    if (s->n_peers) { set_error("%s: the entity-major pass does not run peer-direct", who); return MKE_E_UNSUPPORTED; }
     if (s->em_pos0 < 0 || s->em_n_rows < 0 || s->em_chunks < 1 || s->em_chunks > MKE_OC_EM_MAX_CHUNKS) { set_error("%s: bad em_pos0 / em_n_rows / em_chunks (1..%d)", who, MKE_OC_EM_MAX_CHUNKS); return MKE_E_SHAPE; }
     if ((s->em_pos0 + s->n_pos) * (s->neg_per_pos + 1) > 0x7FFFFFFFll) { set_error("%s: the step's coefficients exceed 2^31", who); return MKE_E_RANGE; }
     if (s->capacity >= (1 << 23)) { set_error("%s: entity-major locators hold slots below 2^23", who); return MKE_E_RANGE; }
@@ -746,6 +812,8 @@ extern "C" int mke_oc_score(const mke_oc_step* s, const float* v_all, int64_t bl
   int rc = oc_check(s, "mke_oc_score");
   if (rc) return rc;
   const bool em = s->em_coef != nullptr;
+  const bool mir = em && s->n_peers;   // peer-direct entity-major: v_all is the local mirror the launch fills
+  if (mir && !v_all) { set_error("mke_oc_score: a peer-direct entity-major step needs the local vector mirror (v_all)"); return MKE_E_NULL; }
   if ((!s->n_peers && (!v_all || !g_all)) || !loss_partials || !s->rel_grad || !s->rel_touched || (!em && (!s->ent_grad || !s->ent_touched))) { set_error("mke_oc_score: NULL pointer"); return MKE_E_NULL; }
   if (!em && s->ref_count && s->optimizer == MKE_OPT_ADAGRAD && !s->ent_acc) { set_error("mke_oc_score: the exclusive-row path with Adagrad needs ent_acc"); return MKE_E_NULL; }
   OcParams p{};
@@ -761,14 +829,16 @@ extern "C" int mke_oc_score(const mke_oc_step* s, const float* v_all, int64_t bl
   hipStream_t st = (hipStream_t)stream;
   if (quarter) {
     MKE_DISPATCH_FPL(fpl, {
-      if (em) { if (pow2) hipLaunchKernelGGL((k_oc_score_q<FPL, true, true>), grid, blk, 0, st, p); else hipLaunchKernelGGL((k_oc_score_q<FPL, false, true>), grid, blk, 0, st, p); }
+      if (mir) { if (pow2) hipLaunchKernelGGL((k_oc_score_q<FPL | OC_MIRROR, true, true>), grid, blk, 0, st, p); else hipLaunchKernelGGL((k_oc_score_q<FPL | OC_MIRROR, false, true>), grid, blk, 0, st, p); }
+      else if (em) { if (pow2) hipLaunchKernelGGL((k_oc_score_q<FPL, true, true>), grid, blk, 0, st, p); else hipLaunchKernelGGL((k_oc_score_q<FPL, false, true>), grid, blk, 0, st, p); }
       else { if (pow2) hipLaunchKernelGGL((k_oc_score_q<FPL, true>), grid, blk, 0, st, p); else hipLaunchKernelGGL((k_oc_score_q<FPL, false>), grid, blk, 0, st, p); }
     });
     return check_launch("k_oc_score_q");
   }
   MKE_DISPATCH_FPL(fpl, {
     constexpr int U = FPL <= 5 ? 2 : 1;
-    if (em) { if (pow2) hipLaunchKernelGGL((k_oc_score<FPL, U, true, true>), grid, blk, 0, st, p); else hipLaunchKernelGGL((k_oc_score<FPL, U, false, true>), grid, blk, 0, st, p); }
+    if (mir) { if (pow2) hipLaunchKernelGGL((k_oc_score<FPL | OC_MIRROR, U, true, true>), grid, blk, 0, st, p); else hipLaunchKernelGGL((k_oc_score<FPL | OC_MIRROR, U, false, true>), grid, blk, 0, st, p); }
+    else if (em) { if (pow2) hipLaunchKernelGGL((k_oc_score<FPL, U, true, true>), grid, blk, 0, st, p); else hipLaunchKernelGGL((k_oc_score<FPL, U, false, true>), grid, blk, 0, st, p); }
     else { if (pow2) hipLaunchKernelGGL((k_oc_score<FPL, U, true>), grid, blk, 0, st, p); else hipLaunchKernelGGL((k_oc_score<FPL, U, false>), grid, blk, 0, st, p); }
   });
   return check_launch("k_oc_score");
@@ -790,9 +860,26 @@ extern "C" int mke_oc_apply(const mke_oc_step* s, const float* gv, void* stream)
   return check_launch("k_oc_apply");
 }
 
+extern "C" int mke_oc_gv_sum(const mke_oc_step* s, const float* inbox, float* gv, void* stream) {
+  using namespace mke;
+  int rc = oc_check(s, "mke_oc_gv_sum");
+  if (rc) return rc;
+  if (!s->n_peers || !s->em_coef) { set_error("mke_oc_gv_sum: only a peer-direct entity-major step (n_peers != 0, em_coef != NULL) sums its inbox"); return MKE_E_UNSUPPORTED; }
+  if (!inbox || !gv) { set_error("mke_oc_gv_sum: NULL inbox / output block"); return MKE_E_NULL; }
+  const int64_t subs = s->n_own_h + s->n_own_t;
+  if (subs == 0) return MKE_OK;
+  OcParams p{};
+  p.s = *s; p.g_all = const_cast<float*>(inbox); p.send = gv;
+  const int fpl = s->stride / 16;
+  const dim3 grid((unsigned)((subs + MKE_SUBS_PER_BLOCK - 1) / MKE_SUBS_PER_BLOCK));
+  MKE_DISPATCH_FPL(fpl, { hipLaunchKernelGGL((k_oc_gv_sum<FPL>), grid, dim3(MKE_BLOCK), 0, (hipStream_t)stream, p); });
+  return check_launch("k_oc_gv_sum");
+}
+
 // Several phases of one part's step in ONE call (host overhead: the step is 5 launches of 5-50 us each): bit 0 bases, 1 count,
 // 2 score, 3 apply, 4 the row update (relation table: every row; shard: touched rows).  What lies between two collectives
-// goes into one call: single rank: 31;  G > 1: 1 | all-gather | 6 | reduce-scatter | 8 | all-reduce | 16.
+// goes into one call: single rank: 31;  G > 1: 1 | all-gather | 6 | reduce-scatter | 8 | all-reduce | 16.  Bit 5 the entity-major
+// second pass; bit 6 (MKE_OC_GVSUM, peer-direct entity-major, before the second pass) sums the inbox `g_all` into the block `gv`.
 extern "C" int mke_oc_run(const mke_oc_step* s, int phases, float* send_block, const float* v_all, int64_t block_floats, float* g_all,
                           const float* gv, double* loss_partials, void* stream) {
   mke::TuningScope scope((s && s->tuning) ? s->tuning : nullptr);   // the step's knobs for the duration of this call
@@ -808,6 +895,7 @@ extern "C" int mke_oc_run(const mke_oc_step* s, int phases, float* send_block, c
   if ((phases & MKE_OC_COUNT) && !both && (rc = mke_oc_count(s, stream))) return rc;
   if ((phases & MKE_OC_SCORE) && (rc = mke_oc_score(s, v_all, block_floats, g_all, loss_partials, stream))) return rc;
   if ((phases & MKE_OC_APPLY) && (rc = mke_oc_apply(s, gv, stream))) return rc;
+  if ((phases & MKE_OC_GVSUM) && (rc = mke_oc_gv_sum(s, g_all, const_cast<float*>(gv), stream))) return rc;
   if ((phases & MKE_OC_PASS2) && (rc = mke_oc_pass2(s, stream))) return rc;
   if (phases & MKE_OC_UPDATE) {
     if ((rc = oc_check(s, "mke_oc_run"))) return rc;

@@ -664,7 +664,7 @@ extern "C" int mke_oc_pass2(const mke_oc_step* s, void* stream) {
   if (!s) { set_error("mke_oc_pass2: NULL step"); return MKE_E_NULL; }
   if (!s->em_coef) { set_error("mke_oc_pass2: the step is not entity-major (em_coef == NULL)"); return MKE_E_UNSUPPORTED; }
   if (s->stride <= 0 || s->stride % 16 != 0 || s->dim <= 0 || s->dim > s->stride || s->stride > MKE_MAX_STRIDE) { set_error("mke_oc_pass2: bad stride/dim"); return MKE_E_SHAPE; }
-  if (s->em_n_rows < 0 || s->em_chunks < 1 || s->em_chunks > MKE_OC_EM_MAX_CHUNKS || s->n_peers) { set_error("mke_oc_pass2: bad em_n_rows / em_chunks, or peer-direct"); return MKE_E_SHAPE; }
+  if (s->em_n_rows < 0 || s->em_chunks < 1 || s->em_chunks > MKE_OC_EM_MAX_CHUNKS) { set_error("mke_oc_pass2: bad em_n_rows / em_chunks"); return MKE_E_SHAPE; }
   if (s->em_n_rows == 0) return MKE_OK;
   if (!s->em_refs || !s->em_rows || !s->em_off || !s->ent || !s->rel_grad) { set_error("mke_oc_pass2: NULL reference lists / table"); return MKE_E_NULL; }
   for (int c = 0; c < s->em_chunks; ++c)

@@ -24,7 +24,7 @@ Per global step, ENTITY-MAJOR form (the default of the HIP backend):
     every touched owned row finished in place from its reference list, in list order (no scratch, no atomics: the step is
     bit-reproducible run to run); this rank's partial relation gradient stored                                    [PASS2]
     ALL-REDUCE of the relation gradient;  update of the relation table                                            [UPDATE]
-The ATOMICS form (`entity_major=False` / MKE_OC_EM=0; what peer-direct and the tests' NumPy backend use): the bases launch also
+The ATOMICS form (`entity_major=False` / MKE_OC_EM=0; what peer-direct takes unless asked otherwise, and the tests' NumPy backend): the bases launch also
 counts the references of the own rows [COUNT], SCORE adds the corrupt rows' gradients to a scratch (in place when a row is referenced
 once), the head / tail / relation rows' gradients follow the reduce-scatter [APPLY], UPDATE updates every touched shard and relation
 row.  Either way a row is updated once per step from the sum of all its contributions (dense-Adagrad-equivalent).
@@ -48,7 +48,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .oc_backend import APPLY, BASES, COUNT, PASS2, SCORE, UPDATE, OcHipBackend, OcStep     # noqa: F401 — this module is the import surface
+from .oc_backend import APPLY, BASES, COUNT, GVSUM, PASS2, SCORE, UPDATE, OcHipBackend, OcStep     # noqa: F401 — this module is the import surface
 from .oc_comm import OcComm, OcGlooComm, OcHostStagedComm, OcRcclComm, default_comm         # noqa: F401
 from .sampling import KGSide, RelationBatcher
 from .tables import ADAGRAD_INIT_ACC, PLACEMENT_LOG, placed_rows
@@ -254,12 +254,14 @@ class OwnerComputesTrainer:
         if self.peer_direct:
             self.chunks = 1
         # entity-major form (module docstring): the default of a backend that has the plan for it, float32 tables;
-        # MKE_OC_EM=0 / entity_major=False select the atomics form, peer-direct implies it
+        # MKE_OC_EM=0 / entity_major=False select the atomics form.  Peer-direct keeps the atomics form unless the entity-major one
+        # is asked for by name: entity_major=True, or MKE_SHARD_PEER_EM=1 where the caller left the choice open (`_step_peer_em`)
         em = entity_major
         if em is None:
             em = os.environ.get("MKE_OC_EM", "1") != "0"
-        self.em = bool(em) and hasattr(self.backend, "em_plan") and not self.peer_direct and self.chunks <= _lib.OC_EM_MAX_CHUNKS \
-            and dtype == torch.float32
+            if self.peer_direct:
+                em = em and os.environ.get("MKE_SHARD_PEER_EM", "0") == "1"
+        self.em = bool(em) and hasattr(self.backend, "em_plan") and self.chunks <= _lib.OC_EM_MAX_CHUNKS and dtype == torch.float32
         if self.em:
             exclusive_rows = False
         dev, st = self.device, self.stride
@@ -732,12 +734,20 @@ class OwnerComputesTrainer:
 
     def _map_peers(self, gb):
         """Exchange IPC handles of this rank's send block and gradient inbox ([world][2 C][stride]: one slice per writer) and
-        map every peer's (torch's CUDA-IPC tensor reductions: hipIpcGetMemHandle / hipIpcOpenMemHandle underneath)."""
+        map every peer's (torch's CUDA-IPC tensor reductions: hipIpcGetMemHandle / hipIpcOpenMemHandle underneath).
+        Entity-major form: `_v_all[0]` stays the LOCAL [world][block] buffer — the mirror the score launch fills with every vector
+        it reads — and `_gv[0]` the LOCAL [2 C][stride] block the inbox is summed into (GVSUM); the second pass reads those two
+        (`_addr` -> em_v[0] / em_gv[0] in `prepare_epoch`), only the send block and the inbox are shared."""
         from torch.multiprocessing.reductions import reduce_tensor
         G = self.world
+        if self._peer_send is not None and self.device.type == "cuda":
+            # re-mapping (the capacity grew): the exchange below is a host rendezvous, so once every rank's device is idle here no
+            # kernel anywhere still reads or writes the blocks that are about to be released
+            torch.cuda.synchronize()
         self._inbox = torch.zeros(G * gb, dtype=self._dtype, device=self.device)
-        self._gv = [self._inbox]
-        self._v_all = [self._send[0]]                      # unused in peer mode (kept non-null for the address table)
+        if not self.em:
+            self._gv = [self._inbox]
+            self._v_all = [self._send[0]]                  # unused in peer mode (kept non-null for the address table)
         self._g_all = [self._inbox]
         mine = (reduce_tensor(self._send[0]), reduce_tensor(self._inbox))
         every = self.comm.all_gather_object(mine)
@@ -807,8 +817,8 @@ class OwnerComputesTrainer:
         work items that do not need its result (at 8 ranks ~95 % of the rows: the corrupt entities) — two stream hops per step
         (~26 us), so only when the reduce-scatter is long: >= 16 MB received per rank (the C5 shape at 8 ranks: 40 MB = 122 us in the
         link model; C2: 12 MB = 48 us, not worth the hops).  MKE_OC_OVERLAP_RS=0 / 1 forces it."""
-        if not self.em or self.chunks != 1 or self.world < 2 and not self.force_collectives:
-            return False
+        if not self.em or self.peer_direct or self.chunks != 1 or self.world < 2 and not self.force_collectives:
+            return False                                     # (peer-direct has no reduce-scatter to hide)
         env = os.environ.get("MKE_OC_OVERLAP_RS")
         if env is not None:
             return env == "1"
@@ -919,6 +929,27 @@ class OwnerComputesTrainer:
         if ks:
             be.run(self, ks[-1], tag, UPDATE, 0, slot0)
 
+    def _step_peer_em(self, ks, tag, slot0):
+        """Entity-major form without all-gather / reduce-scatter (unchunked: one part).  The score launch reads the vectors from
+        the owners' send blocks, MIRRORS them into this rank's local [world][block] buffer and writes its partial gradient
+        vectors into its slice of the owners' inboxes; after the second barrier every rank sums its own inbox in rank order into
+        a local block and runs the second pass on the two local buffers — the collective form's second pass, unchanged.
+        The buffers may be reused by the next step without a further barrier: a peer reads this rank's send block and writes
+        this rank's inbox only inside its SCORE, i.e. between the step's two barriers; this rank rewrites its send block (next
+        BASES) and rereads its inbox (next GVSUM) only after the all-reduce of the relation gradient below, the step's third
+        rendezvous, which no rank passes before every rank has left SCORE; and the next step's writes into this rank's inbox wait
+        at that step's first barrier, which this rank enters after its GVSUM | PASS2.  Mirror, summed block and coefficients are
+        local.  Correct by construction and tested with two and three ranks on one GPU; never run on several."""
+        be, cm = self.backend, self.comm
+        k = ks[-1]                                           # (peer-direct runs unchunked: the step's only part)
+        be.run(self, k, tag, BASES, 0, slot0)
+        cm.barrier(self._bar)                                # every rank's vectors are in its send block
+        be.run(self, k, tag, SCORE, 0, slot0)                # reads peers' blocks (and mirrors them), writes its slice of peers' inboxes
+        cm.barrier(self._bar)                                # every writer's slice of every inbox is complete
+        be.run(self, k, tag, GVSUM | PASS2, 0, slot0)
+        cm.all_reduce(self.rel_grad)                         # this rank's partial relation gradient, stored by the second pass
+        be.run(self, k, tag, UPDATE, 0, slot0)
+
     def step(self, i: int):
         """Global step i (steps must be issued in order): the schedule of the module docstring, enqueued from Python."""
         s = i % self.steps
@@ -931,6 +962,8 @@ class OwnerComputesTrainer:
             return
         if self.world == 1 and not self.force_collectives:
             self._step_local(ks, tag, slot0)
+        elif self.peer_direct and self.em:
+            self._step_peer_em(ks, tag, slot0)
         elif self.peer_direct:
             self._step_peer_direct(ks, tag, slot0)
         elif self.em:
@@ -958,7 +991,7 @@ class OwnerComputesTrainer:
         """Capacity is fixed per epoch from the data before the epoch runs (`_plan_epoch`): nothing to flag."""
         out = {"capacity_vectors_per_owner": self.C, "block_bytes": self.block * 4, "chunks": self.chunks,
                "vectors_per_positive": self.vectors_planned / max(1, self._n_all),
-               "entity_major": bool(self.em), "native_step_loop": bool(self._native_loop()[0]),
+               "entity_major": bool(self.em), "peer_direct": bool(self.peer_direct), "native_step_loop": bool(self._native_loop()[0]),
                "reduce_scatter_under_second_pass": bool(self._overlap_rs()), "communicator": type(self.comm).__name__}
         if self.em:
             out["references_per_global_step"] = self._em.n_refs / max(1, self.steps)

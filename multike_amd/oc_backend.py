@@ -16,6 +16,7 @@ from . import _lib
 from .sampling import KnownTripleSet, side_array
 
 BASES, COUNT, SCORE, APPLY, UPDATE, PASS2 = _lib.OC_BASES, _lib.OC_COUNT, _lib.OC_SCORE, _lib.OC_APPLY, _lib.OC_UPDATE, _lib.OC_PASS2
+GVSUM = _lib.OC_GVSUM
 
 
 @dataclass
@@ -121,7 +122,9 @@ class OcHipBackend:
             s.hot.copies, s.hot.row0 = tr.HOT_COPIES, tr.ent_grad_rows
         s.tuning = _lib.tuning_ptr(tr.tuning)
         s.n_peers = 0
-        if tr.peer_direct and tr.world > 1:   # peer-mapped blocks (chunk 0: peer-direct runs unchunked)
+        # peer-mapped blocks (chunk 0: peer-direct runs unchunked); with the entity-major form `prepare_epoch` points em_v[0] /
+        # em_gv[0] at the LOCAL mirror and summed block (`_addr`), never at a peer's memory
+        if tr.peer_direct and tr.world > 1:
             gb = 2 * tr.C * tr.stride * 4
             s.n_peers = tr.world
             for g in range(tr.world):
@@ -141,9 +144,9 @@ class OcHipBackend:
         oh, ot = _lib.ptr(tr._own[0], i32, "own"), _lib.ptr(tr._own[1], i32, "own")
         em = tr._em if tr.em else None
         key = (tr.C, b.pos_h.data_ptr(), tr._slot[0].data_ptr(), tr._slot[1].data_ptr(), oh, ot, tr._codes.data_ptr(), len(tr._parts),
-               tr._peer_send[0].data_ptr() if tr.peer_direct and tr.world > 1 else 0,
+               tuple(t.data_ptr() for t in (*tr._peer_send, *tr._peer_inbox)) if tr.peer_direct and tr.world > 1 else 0,
                (em.refs.data_ptr(), em.item_row.data_ptr(), em.item_off.data_ptr(), tr._em_coef.data_ptr(),
-                tr._em_partials.data_ptr()) if em else 0)
+                tr._em_partials.data_ptr(), tr._addr[0][1], tr._addr[0][3]) if em else 0)
         if key not in self._cache:                        # first use of this buffer set, or a buffer was re-allocated
             base = self._struct(tr, tr._build_part_step(0, 0))
             ph, pr, pt = (_lib.ptr(x, i32, "pos") for x in (b.pos_h, b.pos_r, b.pos_t))

@@ -13,7 +13,8 @@ full tables.  Any mismatch raises on every rank (exit code != 0): a wrong transp
   3. all_gather of padded shards (checkpoint / evaluator / k-NN refresh), all_gather_object
   4. owner-computes relation steps at world N == the same global batches at world 1 (loss and the full entity table)
   5. sharded attribute view, common space, space mapping: two steps each == world 1
-  6. (--peer, informational) peer-direct IPC mapping of the other ranks' blocks: reported, not fatal (opt-in path, MKE_SHARD_PEER=1)
+  6. (--peer, informational) peer-direct IPC mapping of the other ranks' blocks, atomics form (`peer_direct`, MKE_SHARD_PEER=1) and
+     entity-major form (`peer_direct_em`, + MKE_SHARD_PEER_EM=1): reported, not fatal (opt-in paths)
 
 Rank 0 prints one JSON line {"selftest": "ok", ...} at the end."""
 import json
@@ -166,16 +167,19 @@ def main():
         report[f"epoch_{k}_max_abs_diff"] = err
     # ---- 6. peer-direct mapping (informational) -----------------------------------------------------------------------
     if world > 1 and "--peer" in sys.argv:       # opt-in: a rank that fails alone here could leave the others in a collective
-        try:
-            tr = OwnerComputesTrainer(kgs, ent0, rel0, P, N, rank, world, seed=7, lr=0.01, comm=oc, peer_direct=True)
-            for i in range(2):
-                tr.step(i)
-            lp = tr.epoch_loss()
-            report["peer_direct"] = "ok" if np.isfinite(lp) else "non-finite loss"
-        except Exception as e:  # noqa: BLE001 — reported, not fatal: the path is opt-in
-            report["peer_direct"] = f"unavailable: {type(e).__name__}: {str(e)[:120]}"
-        oks = oc.all_gather_object(report["peer_direct"])
-        report["peer_direct"] = oks if len(set(oks)) > 1 else oks[0]
+        # the atomics form, then the entity-major form (MKE_SHARD_PEER_EM=1 in the bench) of the same transport
+        for key, em in (("peer_direct", None), ("peer_direct_em", True)):
+            try:
+                tr = OwnerComputesTrainer(kgs, ent0, rel0, P, N, rank, world, seed=7, lr=0.01, comm=oc, peer_direct=True, entity_major=em)
+                for i in range(2):
+                    tr.step(i)
+                lp = tr.epoch_loss()
+                report[key] = ("ok" if bool(tr.em) == bool(em) else "ok, but not the form asked for") if np.isfinite(lp) else "non-finite loss"
+                del tr
+            except Exception as e:  # noqa: BLE001 — reported, not fatal: the path is opt-in
+                report[key] = f"unavailable: {type(e).__name__}: {str(e)[:120]}"
+            oks = oc.all_gather_object(report[key])
+            report[key] = oks if len(set(oks)) > 1 else oks[0]
     torch.cuda.synchronize()
     report["seconds"] = round(time.time() - t0, 1)
     report["selftest"] = "ok"
