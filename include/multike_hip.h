@@ -1040,6 +1040,14 @@ typedef struct mke_oc_step {
    * wire); 2 those with one (after the reduce-scatter), followed by the long rows' combine launch. */
   int em_mode;
   const mke_tuning* tuning;   /* version 105: host pointer, NULL = the process defaults */
+  /* owned code lists (appended, no field moved: the version stays; section 13b): own_off != NULL makes mke_oc_score (and through
+   * it mke_oc_run / mke_oc_steps) of an ENTITY-MAJOR step visit, for positive i of this part, the records [own_off[i],
+   * own_off[i + 1]) of own_rec (3 ints each: epoch position, n, code; ascending n) instead of scanning the positive's neg_per_pos
+   * codes for the ones this rank owns.  own_off is ADDRESSED PER PART — the caller passes mke_oc_owned_index's array advanced to
+   * the part's first positive — own_rec is the list's base; `codes` may then be NULL.  em_coef, the gradient-vector slots and the
+   * loss partials are bit-identical to the code scan.  Both transports take it (collectives, peer-direct: the same kernels with
+   * the mirror store).  Without em_coef (the atomics form, whose mke_oc_count reads all-gathered codes): MKE_E_UNSUPPORTED. */
+  const int32_t* own_rec; const int32_t* own_off;
 } mke_oc_step;
 #define MKE_OC_EM_MAX_CHUNKS 4
 #define MKE_OC_EM_WAVES 32768
@@ -1118,11 +1126,47 @@ typedef struct mke_oc_em_plan_args {
   int32_t* item_row; int32_t* item_off; int32_t* item_part; int32_t* long_row; int32_t* long_part0;
   int64_t* step_item0; int64_t* step_long0; int64_t* step_part0;
   void* temp; int64_t temp_bytes;
+  /* the negatives from this rank's OWNED list (appended; section 13b) — own_off != NULL: the negative elements are records
+   * [0, own_off[n_all]) of own_rec (mke_oc_owned_index's outputs, (position, n) order) instead of the owned ones among `codes`
+   * (which may then be NULL); own_cap = records own_rec has room for (the wavefront ranges are cut over own_cap + 5 n_all elements;
+   * the count itself stays on the device).  The five other elements of every position are enumerated as before.  Every output is
+   * bit-identical to the plan from the all-gathered codes of the same epoch. */
+  const int32_t* own_rec; const int32_t* own_off; int64_t own_cap;
 } mke_oc_em_plan_args;
 int64_t mke_oc_em_plan_temp_bytes(int64_t capacity);   /* covers the sort of capacity + 1 keys and every scan of the plan */
 int mke_oc_em_plan(const mke_oc_em_plan_args* args, void* stream);
 /* the second pass of the step `step` describes (its em_* fields; launched once per global step) */
 int mke_oc_pass2(const mke_oc_step* step, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * (13b) Owner-bucketed negative codes (mke_oc_own.hip; new design, no reference counterpart — the reference is single-device).
+ *      Instead of all-gathering every rank's codes (4 n_all N bytes received per rank and epoch, every rank then walking all of
+ *      them for the 1 / n_ranks it owns), every home rank buckets its codes by the OWNER of the corrupt entity and the buckets
+ *      are exchanged all-to-all: a rank receives only the negatives it owns (~12 n_all N / n_ranks bytes), already in (epoch
+ *      position, n) order — home ranks hold contiguous position ranges, so the buckets concatenated in source-rank order are in
+ *      position order.  RECORD (12 bytes, array of structures, in `send`, `recv` and `own_rec` alike): three int32
+ *          [0] epoch position (0 .. 2^31 - 1)   [1] n, the negative's index in its group (0 .. 63)
+ *          [2] the code WITHOUT the flag bits: (corrupt entity << 1) | corrupted-head, entity < 2^29.
+ *
+ * mke_oc_bucket_codes: codes = this rank's share [n_mine][neg_per_pos] as mke_oc_pack_codes wrote it, pos0 = epoch position of
+ *      its first positive (pos0 + n_mine <= 2^31, n_mine * neg_per_pos < 2^31).  need[i] = the MKE_OC_NEED_* flags of position
+ *      pos0 + i alone (bits 30 / 31; MKE_OC_NEED_HR when neg_per_pos == 0) — the layout mke_oc_plan reads from codes[i *
+ *      neg_per_pos]: mke_oc_plan with neg_per_pos = 1 on the all-gathered flags gives the slots unchanged.  send[d][k] (n_ranks x
+ *      cap records) = the k-th negative, in (position, n) order, whose owner (code >> 1) % n_ranks is d; counts[d] = how many
+ *      there ARE — it may exceed cap: then only the first cap are stored, nothing is written past cap, and the caller buckets
+ *      again with more room (the convention of mke_oc_em_plan's n_refs).  The order holds by construction: a count per wavefront
+ *      range, a prefix sum per destination, a fill by ballot rank — no atomics.  scratch: n_ranks * MKE_OC_BUCKET_WAVES ints.
+ * mke_oc_owned_index: recv = the n_ranks x cap records addressed to this rank (source-rank order: the all-to-all's output),
+ *      counts[s] = records source s addressed to it (DEVICE array; clamped to cap).  own_rec (room for n_ranks * cap records) =
+ *      the received records packed, own_off[p] .. own_off[p + 1] = the records of epoch position p (n_all + 1 ints; positions
+ *      without an owned negative get empty ranges; own_off[n_all] = records owned).
+ * The entity-major plan takes the list through mke_oc_em_plan_args.own_rec / own_off / own_cap, the score launch through
+ * mke_oc_step.own_rec / own_off. */
+#define MKE_OC_BUCKET_WAVES 8192
+int mke_oc_bucket_codes(const int32_t* codes, int64_t n_mine, int neg_per_pos, int64_t pos0, int n_ranks, int64_t cap,
+                        int32_t* need, int32_t* send, int32_t* counts, int32_t* scratch, void* stream);
+int mke_oc_owned_index(const int32_t* recv, const int32_t* counts, int n_ranks, int64_t cap, int64_t n_all,
+                       int32_t* own_rec, int32_t* own_off, void* stream);
 
 /* The step loop of the owner-computes relation view as ONE native call (version 105; new design — the single-device
  * counterpart is mke_relation_steps; semantics: code/MultiKE_model.py:304-322, one optimizer step per global batch, in epoch

@@ -35,6 +35,7 @@ SYMBOLS = (
     "mke_ae_scratch_floats", "mke_ae_train_steps", "mke_ae_step_phases", "mke_ae_encode", "mke_dense_layer_fwd",
     "mke_topk_long", "mke_probe_rows", "mke_oc_block_floats", "mke_oc_pack_codes", "mke_oc_plan", "mke_oc_bases", "mke_oc_count", "mke_oc_score", "mke_oc_apply", "mke_oc_run",
     "mke_oc_em_plan_temp_bytes", "mke_oc_em_plan", "mke_oc_pass2", "mke_oc_steps", "mke_oc_gv_sum",
+    "mke_oc_bucket_codes", "mke_oc_owned_index",
     "mke_tuning_init", "mke_rows_update_multi_t",
     "mke_align_topk_mean_temp_bytes", "mke_align_topk_mean", "mke_align_rank_ex",
     "mke_stable_lists_temp_bytes", "mke_stable_lists", "mke_stable_rounds", "mke_stable_finish",
@@ -130,7 +131,9 @@ class OcStepStruct(C.Structure):
                 ("em_n_rows", C.c_int64), ("em_chunks", C.c_int), ("em_block_floats", C.c_int64), ("em_v", C.c_void_p * 4),
                 ("em_gv", C.c_void_p * 4),
                 ("em_part", C.c_void_p), ("em_long_rows", C.c_void_p), ("em_long_part0", C.c_void_p), ("em_n_long", C.c_int64),
-                ("em_part0", C.c_int64), ("em_partials", C.c_void_p), ("em_mode", C.c_int), ("tuning", C.c_void_p)]
+                ("em_part0", C.c_int64), ("em_partials", C.c_void_p), ("em_mode", C.c_int), ("tuning", C.c_void_p),
+                # owned code lists (mke_oc_owned_index) in place of the code scan; own_off advanced to the part's first positive
+                ("own_rec", C.c_void_p), ("own_off", C.c_void_p)]
 
 
 TUNE_DEFAULT = -2
@@ -173,7 +176,8 @@ class OcEmPlanArgs(C.Structure):
                 ("step_row0", C.c_void_p), ("n_refs", C.c_void_p),
                 ("item_row", C.c_void_p), ("item_off", C.c_void_p), ("item_part", C.c_void_p), ("long_row", C.c_void_p), ("long_part0", C.c_void_p),
                 ("step_item0", C.c_void_p), ("step_long0", C.c_void_p), ("step_part0", C.c_void_p),
-                ("temp", C.c_void_p), ("temp_bytes", C.c_int64)]
+                ("temp", C.c_void_p), ("temp_bytes", C.c_int64),
+                ("own_rec", C.c_void_p), ("own_off", C.c_void_p), ("own_cap", C.c_int64)]
 
 
 OC_COMM_NCCL, OC_COMM_CALLBACK, OC_COMM_LOOPBACK = 0, 1, 2
@@ -838,6 +842,32 @@ def oc_plan(pos_h, pos_t, codes, neg_per_pos: int, part_lo, n_parts: int, n_rank
 
 OC_BASES, OC_COUNT, OC_SCORE, OC_APPLY, OC_UPDATE, OC_PASS2 = 1, 2, 4, 8, 16, 32
 OC_GVSUM = 64       # peer-direct entity-major: the inbox (mke_oc_run's g_all) summed into the local block (gv), before OC_PASS2
+
+
+OC_BUCKET_WAVES = 8192
+OC_REC_INTS = 3     # an owned-code record: (epoch position, n, code without flags), int32 each
+
+
+def oc_bucket_codes(codes, n_mine: int, neg_per_pos: int, pos0: int, n_ranks: int, cap: int, need, send, counts, scratch):
+    """mke_oc_bucket_codes: this rank's share of the epoch's codes bucketed by the owner of the corrupt entity ((position, n) order
+    inside each destination, true counts), and the positions' need flags alone."""
+    i32 = torch.int32
+    if scratch.numel() < n_ranks * OC_BUCKET_WAVES or counts.numel() < n_ranks or need.numel() < n_mine or send.numel() < OC_REC_INTS * n_ranks * cap:
+        raise MultiKEHipError("mke_oc_bucket_codes: need / send / counts / scratch too small")
+    rc = lib().mke_oc_bucket_codes(_dev(codes, i32, "codes"), C.c_int64(n_mine), C.c_int(neg_per_pos), C.c_int64(pos0), C.c_int(n_ranks),
+                                   C.c_int64(cap), _dev(need, i32, "need"), _dev(send, i32, "send"), _dev(counts, i32, "counts"),
+                                   _dev(scratch, i32, "scratch"), _stream())
+    _check(rc, "mke_oc_bucket_codes")
+
+
+def oc_owned_index(recv, counts, n_ranks: int, cap: int, n_all: int, own_rec, own_off):
+    """mke_oc_owned_index: the records addressed to this rank packed in (position, n) order, and their offsets per epoch position."""
+    i32 = torch.int32
+    if own_rec.numel() < OC_REC_INTS * n_ranks * cap or own_off.numel() < n_all + 1 or recv.numel() < OC_REC_INTS * n_ranks * cap or counts.numel() < n_ranks:
+        raise MultiKEHipError("mke_oc_owned_index: recv / counts / own_rec / own_off too small")
+    rc = lib().mke_oc_owned_index(_dev(recv, i32, "recv"), _dev(counts, i32, "counts"), C.c_int(n_ranks), C.c_int64(cap), C.c_int64(n_all),
+                                  _dev(own_rec, i32, "own_rec"), _dev(own_off, i32, "own_off"), _stream())
+    _check(rc, "mke_oc_owned_index")
 
 
 def oc_em_plan_temp_bytes(capacity: int) -> int:

@@ -36,6 +36,13 @@ __device__ __forceinline__ float sub16_sum(float v) {
   return v;
 }
 
+// id / G and id % G for the (non-negative) entity ids of the row-sharded tables: a shift and a mask when the world size is a power
+// of two (2, 4, 8 GPUs), else an UNSIGNED 32-bit division (mke_oc.hip has the measurements)
+struct OcDiv { uint32_t g; int shift; };
+__device__ __forceinline__ OcDiv oc_divisor(int g) { OcDiv d; d.g = (uint32_t)g; d.shift = (g & (g - 1)) == 0 ? __builtin_ctz((unsigned)g) : -1; return d; }
+__device__ __forceinline__ int oc_div(const OcDiv& d, int x) { return d.shift >= 0 ? (int)((uint32_t)x >> d.shift) : (int)((uint32_t)x / d.g); }
+__device__ __forceinline__ int oc_mod(const OcDiv& d, int x) { return d.shift >= 0 ? (int)((uint32_t)x & (d.g - 1u)) : (int)((uint32_t)x % d.g); }
+
 template <int FPL>
 __device__ __forceinline__ void load_row(const float* __restrict__ base, int64_t row, int stride, int j,
                                          float (&v)[FPL]) {

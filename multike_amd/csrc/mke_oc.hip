@@ -51,11 +51,8 @@ __device__ __forceinline__ const int32_t* oc_codes(const OcParams& p, int g) { r
 // id / G and id % G for the (non-negative) entity ids: a shift and a mask when the world size is a power of two (2, 4, 8 GPUs),
 // else an UNSIGNED 32-bit division.  The plain `int / int` of a run-time divisor is ~30 vector instructions on this part and the
 // 64-bit `i / per` ~150; SQ counters of k_oc_score_q as rank 0 of 8 showed the launch bound by instruction issue (1,660 vector
-// instructions per wavefront x 10 wavefronts per SIMD: EXPERIMENTS R5.26), a quarter of them these divisions.
-struct OcDiv { uint32_t g; int shift; };
-__device__ __forceinline__ OcDiv oc_divisor(int g) { OcDiv d; d.g = (uint32_t)g; d.shift = (g & (g - 1)) == 0 ? __builtin_ctz((unsigned)g) : -1; return d; }
-__device__ __forceinline__ int oc_div(const OcDiv& d, int x) { return d.shift >= 0 ? (int)((uint32_t)x >> d.shift) : (int)((uint32_t)x / d.g); }
-__device__ __forceinline__ int oc_mod(const OcDiv& d, int x) { return d.shift >= 0 ? (int)((uint32_t)x & (d.g - 1u)) : (int)((uint32_t)x % d.g); }
+// instructions per wavefront x 10 wavefronts per SIMD: EXPERIMENTS R5.26), a quarter of them these divisions.  (OcDiv, oc_divisor,
+// oc_div, oc_mod: mke_common.h — the owner-bucketed codes of mke_oc_own.hip use them too.)
 // the score kernels take the power-of-two case as a template parameter (with the run-time test the compiler computes BOTH forms and
 // selects: nothing saved)
 template <bool P2> struct OcDivP { uint32_t g; int shift; };
@@ -213,12 +210,21 @@ __device__ __forceinline__ float oc_positive_term(const mke_oc_step& s, int STRI
 // a template parameter of its own would rename the symbol of every existing instantiation, and a shared device-function body
 // under two thin kernels came out scheduled differently in 104 of the 135 kernels (profiles/r15_peer_em.md).  This way the
 // collective entity-major and the atomics instantiations keep their symbols and their instruction streams.
+//
+// Owned lists (OWN, FPLX | OC_OWNED — the same encoding, for the same reason): the codes were bucketed by owner before they were
+// exchanged (mke_oc_own.hip), so this rank holds only the negatives whose corrupt entity it owns, as records (position, n, code) in
+// (position, n) order with the per-positive offsets s.own_off.  The wavefront of positive i loads records [own_off[i], own_off[i + 1])
+// — lane l the l-th — instead of all N codes and the ownership test; the k-th owned negative still goes to quarter k % 4, its
+// coefficient to em_coef[... + n]: the sums, the slots and the loss partials are those of the code scan, bit for bit.
 #define OC_MIRROR 64
+#define OC_OWNED 128
 template <int FPLX, int U, bool P2, bool EM = false>
 __global__ __launch_bounds__(MKE_BLOCK) void k_oc_score(const OcParams p) {
   constexpr int FPL = FPLX & (OC_MIRROR - 1);
   constexpr bool MIR = (FPLX & OC_MIRROR) != 0;
+  constexpr bool OWN = (FPLX & OC_OWNED) != 0;
   static_assert(EM || !MIR, "the mirror belongs to the entity-major form");
+  static_assert(EM || !OWN, "owned lists belong to the entity-major form");
   constexpr int STRIDE = FPL * 16;   // == s.stride (the dispatch picks FPL from it): row offsets by shift-add, not a 64-bit multiply
   const mke_oc_step& s = p.s;
   const int lane = threadIdx.x & 63, j = lane & 15, q = lane >> 4;
@@ -237,9 +243,20 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_oc_score(const OcParams p) {
     const float* vt = (s.n_peers ? s.peer_v[oc_mod(dv, pt)] : p.v_all + (int64_t)oc_mod(dv, pt) * p.block_floats) + (C + max(st, 0)) * STRIDE;
     // codes first (one negative per lane), then the owned rows' reference counts together with the positive's vector(s): a
     // round below is one round trip, and the accumulator row is gathered only for rows that are finished in place
-    int code = 0;
-    if (lane < N) code = oc_code(oc_codes(p, home)[(i - (int64_t)home * s.per) * N + lane]);
-    const bool mine = lane < N && oc_mod(dv, code >> 1) == s.rank;
+    int code = 0, nn = lane;
+    bool mine;
+    if constexpr (OWN) {   // this positive's owned negatives, ascending n: lane l takes the l-th (at most N <= 64 of them)
+      const int lo = s.own_off[i];
+      mine = lane < s.own_off[i + 1] - lo;
+      if (mine) {
+        const int32_t* rec = s.own_rec + 3 * (int64_t)(lo + lane);
+        nn = rec[1];
+        code = rec[2];
+      }
+    } else {
+      if (lane < N) code = oc_code(oc_codes(p, home)[(i - (int64_t)home * s.per) * N + lane]);
+      mine = lane < N && oc_mod(dv, code >> 1) == s.rank;
+    }
     int rcl = 0;
     if constexpr (!EM) rcl = (mine && s.ref_count) ? (oc_is_hot(s, oc_div(dv, code >> 1)) ? 2 : s.ref_count[oc_div(dv, code >> 1)]) : 0;   // a hub row is never finished in place
     float HR[FPL], RT[FPL], gHR[FPL], gRT[FPL];
@@ -284,7 +301,7 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_oc_score(const OcParams p) {
         const int src = live[u] ? __builtin_ctzll(rest) : 0;
         const int cd = __shfl(code, src, 64);
         cnt[u] = EM ? 0 : __shfl(rcl, src, 64);
-        nidx[u] = src;
+        nidx[u] = OWN ? __shfl(nn, src, 64) : src;
         sideH[u] = cd & 1;
         e[u] = oc_div(dv, cd >> 1);
         rest &= rest - 1; rest &= rest - 1; rest &= rest - 1; rest &= rest - 1;
@@ -395,11 +412,17 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_oc_score(const OcParams p) {
 // codes 16 at a time, the owned ones are visited one after the other (the four quarters of a wavefront iterate together until the
 // busiest is done), the partial gradient vectors need no cross-quarter reduction.  Same arithmetic, same slots, same in-place /
 // scatter rule per corrupt row as k_oc_score; FPLX as there (| OC_MIRROR: the quarter mirrors its positive's vector(s)).
+// OWN (FPLX | OC_OWNED): the quarter walks its positive's owned records 16 at a time, in list order — ascending n, the order the
+// code scan visits them in.  The walk has a loop of its own with the entity-major arithmetic restated: taking the records inside the
+// scan's loop (constexpr branches on the code source) kept every existing instruction but re-allocated the registers of all 52
+// existing entity-major quarter instantiations, and the owned ones came out no smaller (profiles/r16_owner_codes.md).
 template <int FPLX, bool P2, bool EM = false>
 __global__ __launch_bounds__(MKE_BLOCK) void k_oc_score_q(const OcParams p) {
   constexpr int FPL = FPLX & (OC_MIRROR - 1);
   constexpr bool MIR = (FPLX & OC_MIRROR) != 0;
+  constexpr bool OWN = (FPLX & OC_OWNED) != 0;
   static_assert(EM || !MIR, "the mirror belongs to the entity-major form");
+  static_assert(EM || !OWN, "owned lists belong to the entity-major form");
   constexpr int STRIDE = FPL * 16;
   const mke_oc_step& s = p.s;
   const int lane = threadIdx.x & 63, j = lane & 15, q = lane >> 4;
@@ -442,9 +465,57 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_oc_score_q(const OcParams p) {
       const float pw = s.pos_w ? s.pos_w[i] : 1.0f;
       loss += oc_positive_term<FPL, EM>(s, STRIDE, j, sh >= 0, oc_div(dv, sh >= 0 ? pt : ph), pw, i, HR, RT, gHR, gRT);
     }
-    const int32_t* cp = oc_codes(p, home) + (i - (int64_t)home * s.per) * N;
+    const int32_t* cp = oc_codes(p, home) + (i - (int64_t)home * s.per) * N;      // (not read with OWN)
     float* const coefp = EM ? s.em_coef + (s.em_pos0 + i) * (N + 1) : nullptr;   // this positive's coefficients (entity-major)
-    for (int c0 = 0; c0 < N; c0 += 16) {                      // the group's codes, 16 per quarter at a time
+    if constexpr (OWN) {
+      const int lo = act ? s.own_off[i] : 0, cnt = act ? s.own_off[i + 1] - lo : 0;
+      for (int c0 = 0; __ballot(c0 < cnt); c0 += 16) {        // wave-uniform trip count: the quarters walk their lists together
+        int code = 0, nn = 0;
+        if (c0 + j < cnt) {
+          const int32_t* rec = s.own_rec + 3 * (int64_t)(lo + c0 + j);
+          nn = rec[1];
+          code = rec[2];
+        }
+        const int m = min(16, cnt - c0);                       // <= 0 for a quarter that is done
+#pragma unroll 1
+        for (int t = 0; __ballot(t < m); ++t) {                // one negative at a time, as the code scan: the registers of one row
+          const bool live = t < m;
+          const int src = 16 * q + (live ? t : 0);
+          const int cd = __shfl(code, src, 64);
+          const int nx = __shfl(nn, src, 64);
+          if (!live) continue;
+          const bool sideH = cd & 1;
+          const int e = oc_div(dv, cd >> 1);
+          float Cr[FPL];
+          load_row<FPL>(s.ent, e, STRIDE, j, Cr);
+          float ss = 0.f;
+#pragma unroll
+          for (int k = 0; k < FPL; ++k) ss = fmaf(Cr[k], Cr[k], ss);
+          const float cinv = rsqrtf(fmaxf(sub16_sum(ss), MKE_L2_EPS));
+          float d[FPL];
+          float y = 0.f;
+          const float sc = sideH ? cinv : -cinv;
+#pragma unroll
+          for (int k = 0; k < FPL; ++k) {
+            d[k] = fmaf(sc, Cr[k], sideH ? RT[k] : HR[k]);
+            y = fmaf(d[k], d[k], y);
+          }
+          y = sub16_sum(y);
+          const float t_ = __expf(-y);
+          const float s1 = 1.0f + t_;
+          loss += __logf(s1);
+          const float c = -2.0f * s.scale * t_ * __builtin_amdgcn_rcpf(s1);
+          const float cHR = sideH ? 0.f : c, cRT = sideH ? c : 0.f;
+#pragma unroll
+          for (int k = 0; k < FPL; ++k) {
+            gHR[k] = fmaf(cHR, d[k], gHR[k]);
+            gRT[k] = fmaf(cRT, d[k], gRT[k]);
+          }
+          if (j == 0) coefp[nx] = c;
+        }
+      }
+    }
+    for (int c0 = 0; !OWN && c0 < N; c0 += 16) {             // the group's codes, 16 per quarter at a time
       int code = 0;
       const bool has = act && c0 + j < N;
       if (has) code = oc_code(cp[c0 + j]);
@@ -711,7 +782,10 @@ static int oc_check(const mke_oc_step* s, const char* who) {
   if (s->n_own_h < 0 || s->n_own_t < 0 || s->n_own_h > s->capacity || s->n_own_t > s->capacity) { set_error("%s: owned vectors exceed the capacity", who); return MKE_E_SHAPE; }
   if (s->rel_grad_copies < 1 || s->rel_grad_copies > 64) { set_error("%s: rel_grad_copies must be in [1,64]", who); return MKE_E_SHAPE; }
   if (s->n_pos > 0 && (!s->pos_h || !s->pos_r || !s->pos_t || !s->slot_h || !s->slot_t)) { set_error("%s: NULL positive / slot stream", who); return MKE_E_NULL; }
-  if (s->n_pos * s->neg_per_pos > 0 && !s->codes) { set_error("%s: NULL negative codes", who); return MKE_E_NULL; }
+  if (s->own_off) {   // owned lists in place of the all-gathered codes
+    if (!s->em_coef) { set_error("%s: owned code lists (own_off) are built for the entity-major form only (em_coef != NULL): the atomics form counts its references over the all-gathered codes", who); return MKE_E_UNSUPPORTED; }
+    if (s->n_pos * s->neg_per_pos > 0 && !s->own_rec) { set_error("%s: own_off without own_rec", who); return MKE_E_NULL; }
+  } else if (s->n_pos * s->neg_per_pos > 0 && !s->codes) { set_error("%s: NULL negative codes", who); return MKE_E_NULL; }
   if (s->n_peers != 0 && s->n_peers != s->n_ranks) { set_error("%s: n_peers must be 0 or n_ranks", who); return MKE_E_SHAPE; }
   for (int g = 0; g < s->n_peers; ++g)
     if (!s->peer_v[g] || !s->peer_g[g]) { set_error("%s: NULL peer block %d", who, g); return MKE_E_NULL; }
@@ -813,6 +887,7 @@ extern "C" int mke_oc_score(const mke_oc_step* s, const float* v_all, int64_t bl
   if (rc) return rc;
   const bool em = s->em_coef != nullptr;
   const bool mir = em && s->n_peers;   // peer-direct entity-major: v_all is the local mirror the launch fills
+  const bool own = em && s->own_off;   // owned code lists in place of the code scan (either transport)
   if (mir && !v_all) { set_error("mke_oc_score: a peer-direct entity-major step needs the local vector mirror (v_all)"); return MKE_E_NULL; }
   if ((!s->n_peers && (!v_all || !g_all)) || !loss_partials || !s->rel_grad || !s->rel_touched || (!em && (!s->ent_grad || !s->ent_touched))) { set_error("mke_oc_score: NULL pointer"); return MKE_E_NULL; }
   if (!em && s->ref_count && s->optimizer == MKE_OPT_ADAGRAD && !s->ent_acc) { set_error("mke_oc_score: the exclusive-row path with Adagrad needs ent_acc"); return MKE_E_NULL; }
@@ -829,7 +904,9 @@ extern "C" int mke_oc_score(const mke_oc_step* s, const float* v_all, int64_t bl
   hipStream_t st = (hipStream_t)stream;
   if (quarter) {
     MKE_DISPATCH_FPL(fpl, {
-      if (mir) { if (pow2) hipLaunchKernelGGL((k_oc_score_q<FPL | OC_MIRROR, true, true>), grid, blk, 0, st, p); else hipLaunchKernelGGL((k_oc_score_q<FPL | OC_MIRROR, false, true>), grid, blk, 0, st, p); }
+      if (own && mir) { if (pow2) hipLaunchKernelGGL((k_oc_score_q<FPL | OC_MIRROR | OC_OWNED, true, true>), grid, blk, 0, st, p); else hipLaunchKernelGGL((k_oc_score_q<FPL | OC_MIRROR | OC_OWNED, false, true>), grid, blk, 0, st, p); }
+      else if (own) { if (pow2) hipLaunchKernelGGL((k_oc_score_q<FPL | OC_OWNED, true, true>), grid, blk, 0, st, p); else hipLaunchKernelGGL((k_oc_score_q<FPL | OC_OWNED, false, true>), grid, blk, 0, st, p); }
+      else if (mir) { if (pow2) hipLaunchKernelGGL((k_oc_score_q<FPL | OC_MIRROR, true, true>), grid, blk, 0, st, p); else hipLaunchKernelGGL((k_oc_score_q<FPL | OC_MIRROR, false, true>), grid, blk, 0, st, p); }
       else if (em) { if (pow2) hipLaunchKernelGGL((k_oc_score_q<FPL, true, true>), grid, blk, 0, st, p); else hipLaunchKernelGGL((k_oc_score_q<FPL, false, true>), grid, blk, 0, st, p); }
       else { if (pow2) hipLaunchKernelGGL((k_oc_score_q<FPL, true>), grid, blk, 0, st, p); else hipLaunchKernelGGL((k_oc_score_q<FPL, false>), grid, blk, 0, st, p); }
     });
@@ -837,7 +914,9 @@ extern "C" int mke_oc_score(const mke_oc_step* s, const float* v_all, int64_t bl
   }
   MKE_DISPATCH_FPL(fpl, {
     constexpr int U = FPL <= 5 ? 2 : 1;
-    if (mir) { if (pow2) hipLaunchKernelGGL((k_oc_score<FPL | OC_MIRROR, U, true, true>), grid, blk, 0, st, p); else hipLaunchKernelGGL((k_oc_score<FPL | OC_MIRROR, U, false, true>), grid, blk, 0, st, p); }
+    if (own && mir) { if (pow2) hipLaunchKernelGGL((k_oc_score<FPL | OC_MIRROR | OC_OWNED, U, true, true>), grid, blk, 0, st, p); else hipLaunchKernelGGL((k_oc_score<FPL | OC_MIRROR | OC_OWNED, U, false, true>), grid, blk, 0, st, p); }
+    else if (own) { if (pow2) hipLaunchKernelGGL((k_oc_score<FPL | OC_OWNED, U, true, true>), grid, blk, 0, st, p); else hipLaunchKernelGGL((k_oc_score<FPL | OC_OWNED, U, false, true>), grid, blk, 0, st, p); }
+    else if (mir) { if (pow2) hipLaunchKernelGGL((k_oc_score<FPL | OC_MIRROR, U, true, true>), grid, blk, 0, st, p); else hipLaunchKernelGGL((k_oc_score<FPL | OC_MIRROR, U, false, true>), grid, blk, 0, st, p); }
     else if (em) { if (pow2) hipLaunchKernelGGL((k_oc_score<FPL, U, true, true>), grid, blk, 0, st, p); else hipLaunchKernelGGL((k_oc_score<FPL, U, false, true>), grid, blk, 0, st, p); }
     else { if (pow2) hipLaunchKernelGGL((k_oc_score<FPL, U, true>), grid, blk, 0, st, p); else hipLaunchKernelGGL((k_oc_score<FPL, U, false>), grid, blk, 0, st, p); }
   });

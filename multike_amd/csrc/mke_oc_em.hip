@@ -42,7 +42,8 @@ struct EmPlanParams {
   mke_oc_em_plan_args a;
   uint32_t ep;          // elements per positive: neg_per_pos + 5
   int64_t n_codes;      // n_all * neg_per_pos: elements [0, n_codes) are the negatives in code order, [n_codes, n_codes + 5 n_all) the
-                        // five other elements of every position
+                        // five other elements of every position.  From an owned list (a.own_off): own_cap — the records the list has
+                        // room for; those past its count own_off[n_all] are nobody's
   uint64_t n_magic;     // ceil(2^40 / neg_per_pos), or 0 when it is not exact over [0, n_codes) (em_locate divides then)
   int64_t total;        // n_codes + 5 n_all
   int g_shift;          // log2(n_ranks) when it is a power of two, else -1
@@ -69,25 +70,37 @@ __device__ __forceinline__ int em_step_of(const int64_t* __restrict__ step_lo, i
 // The loads of an element are unconditional (clamped indices) and independent of each other, so that the EM_U elements a lane
 // handles per round are in flight together: with one dependent load per round the walks ran at the latency of a round trip per
 // 64 elements and wavefront (2.8 + 4.5 ms per epoch at the C5 shape with 8 ranks).
-struct EmElem { int ent; int kind; int64_t p; int code, sh, st, ph, pt; };
+struct EmElem { int ent; int kind; int64_t p; int code, sh, st, ph, pt; int n; };
 // Element t of the epoch: t < n_codes — negative t % N of position t / N, ONE load (its code; the position and the positive's slots
 // are looked up only for the eighth this rank owns); then five elements per position — own term, the head / tail rows' gradient
 // vectors, the relation row's two — from the position's slots and ids.  (Round 6 first enumerated position-major, N + 5 elements
 // per position with the five loads for every element: 62 + 148 us per epoch share at C2 with 8 ranks for the two walks.)  A
 // STABLE sort by (step, row) of the owned elements in THIS order leaves every row's references in a fixed order — its negatives by
 // (positive, n), then the other kinds by (positive, kind) — the summation order of the second pass.
-__device__ __forceinline__ EmElem em_elem_of(const EmPlanParams& pp, int64_t t) {
+// OWN (the negatives come from this rank's owned list, mke_oc_owned_index): element t < n_codes is record t of the list — already
+// (position, n, code), in the order the owned negatives have among all codes — or nobody's beyond the list's count n_own.
+template <bool OWN>
+__device__ __forceinline__ EmElem em_elem_of(const EmPlanParams& pp, int64_t t, int64_t n_own) {
   const mke_oc_em_plan_args& a = pp.a;
   EmElem e;
   e.sh = e.st = e.ph = e.pt = 0;
   e.p = -1;
+  e.n = 0;
   const bool in = t < pp.total;
   const int64_t tc = in ? t : 0;
   // the code load is unconditional (clamped) so that the EM_U elements of a lane are in flight together
-  e.code = pp.n_codes > 0 ? a.codes[tc < pp.n_codes ? tc : pp.n_codes - 1] : 0;
+  if constexpr (OWN) {
+    e.code = 0;
+    if (n_own > 0) {                               // uniform
+      const int32_t* rec = a.own_rec + 3 * (tc < n_own ? tc : n_own - 1);
+      e.p = rec[0]; e.n = rec[1]; e.code = rec[2];
+    }
+  } else {
+    e.code = pp.n_codes > 0 ? a.codes[tc < pp.n_codes ? tc : pp.n_codes - 1] : 0;
+  }
   if (tc < pp.n_codes) {
     e.kind = -1;                                   // a negative: its n = t - p N when the position is looked up (em_locate)
-    e.ent = (e.code & 0x3FFFFFFF) >> 1;
+    e.ent = (!OWN || tc < n_own) ? (e.code & 0x3FFFFFFF) >> 1 : -1;
   } else {
     const int64_t q = tc - pp.n_codes;
     const int64_t p = q / 5;
@@ -104,15 +117,22 @@ __device__ __forceinline__ EmElem em_elem_of(const EmPlanParams& pp, int64_t t) 
   return e;
 }
 // an OWNED negative's position, index in its group, and the positive's slots / ids
+template <bool OWN>
 __device__ __forceinline__ void em_locate(const EmPlanParams& pp, int64_t t, EmElem& e) {
   if (e.kind >= 0) return;
   const mke_oc_em_plan_args& a = pp.a;
   const int N = a.neg_per_pos;
-  // p = t / N as bits 40.. of the 128-bit product t * n_magic (a 64-bit product wraps from position 2^24 on)
-  const uint64_t tu = (uint64_t)t;
-  const int64_t p = pp.n_magic ? (int64_t)((__umul64hi(tu, pp.n_magic) << 24) | ((tu * pp.n_magic) >> 40)) : t / N;
-  e.p = p;
-  e.kind = (int)(t - p * N);
+  int64_t p;
+  if constexpr (OWN) {
+    p = e.p;                                       // the record carries both
+    e.kind = e.n;
+  } else {
+    // p = t / N as bits 40.. of the 128-bit product t * n_magic (a 64-bit product wraps from position 2^24 on)
+    const uint64_t tu = (uint64_t)t;
+    p = pp.n_magic ? (int64_t)((__umul64hi(tu, pp.n_magic) << 24) | ((tu * pp.n_magic) >> 40)) : t / N;
+    e.p = p;
+    e.kind = (int)(t - p * N);
+  }
   e.sh = a.slot_h[p]; e.st = a.slot_t[p]; e.ph = a.pos_h[p]; e.pt = a.pos_t[p];
 }
 __device__ __forceinline__ bool em_owned(const EmPlanParams& pp, const EmElem& e) {
@@ -126,8 +146,10 @@ __device__ __forceinline__ bool em_owned(const EmPlanParams& pp, const EmElem& e
 // A wavefront per contiguous range of elements, in two launches with a prefix sum between them: count the owned ones; append
 // (key, descriptor) at the range's offset + ballot rank — no cursor atomic (a returning atomic on one address costs ~12 ns:
 // one per 64 elements was 5.2 ms of a 6.2 ms plan at the C2 shape with 8 ranks), and the list comes out in element order.
+template <bool OWN>
 __global__ __launch_bounds__(MKE_BLOCK) void k_em_count(const EmPlanParams pp) {
   const int64_t total = pp.total;
+  const int64_t n_own = OWN ? (int64_t)pp.a.own_off[pp.a.n_all] : 0;
   const int lane = threadIdx.x & 63;
   const int64_t wave = ((int64_t)blockIdx.x * MKE_BLOCK + threadIdx.x) >> 6;
   if (wave >= pp.n_waves) return;
@@ -136,7 +158,7 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_em_count(const EmPlanParams pp) {
   for (int64_t t = t0 + lane; t - lane < t1; t += 64 * EM_U) {
     EmElem e[EM_U];
 #pragma unroll
-    for (int u = 0; u < EM_U; ++u) e[u] = em_elem_of(pp, t + 64 * u < t1 ? t + 64 * u : total);
+    for (int u = 0; u < EM_U; ++u) e[u] = em_elem_of<OWN>(pp, t + 64 * u < t1 ? t + 64 * u : total, n_own);
 #pragma unroll
     for (int u = 0; u < EM_U; ++u) cnt += em_owned(pp, e[u]) ? 1 : 0;
   }
@@ -184,13 +206,13 @@ __device__ __forceinline__ void em_wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <typename KEY>
-__device__ __forceinline__ void em_emit(const EmPlanParams& pp, int64_t t, int64_t k, int& s_hint, KEY* __restrict__ keys, uint32_t* __restrict__ vals,
+template <typename KEY, bool OWN>
+__device__ __forceinline__ void em_emit(const EmPlanParams& pp, int64_t t, int64_t n_own, int64_t k, int& s_hint, KEY* __restrict__ keys, uint32_t* __restrict__ vals,
                                         uint2* __restrict__ refs_unsorted) {
   const mke_oc_em_plan_args& a = pp.a;
   const int G = a.n_ranks;
-  EmElem e = em_elem_of(pp, t);
-  em_locate(pp, t, e);
+  EmElem e = em_elem_of<OWN>(pp, t, n_own);
+  em_locate<OWN>(pp, t, e);
   int s = s_hint;                                           // a step at or before the element's, or anything after the seam
   if (a.step_lo[s] > e.p) s = em_step_of(a.step_lo, a.n_steps, e.p);
   while (s + 1 < a.n_steps && a.step_lo[s + 1] <= e.p) ++s;
@@ -201,9 +223,10 @@ __device__ __forceinline__ void em_emit(const EmPlanParams& pp, int64_t t, int64
   if (k < a.capacity) { keys[k] = (KEY)srow; vals[k] = (uint32_t)k; refs_unsorted[k] = em_ref_of(pp, e, s, e.p - a.step_lo[s]); }
 }
 
-template <typename KEY>
+template <typename KEY, bool OWN>
 __global__ __launch_bounds__(MKE_BLOCK) void k_em_fill(const EmPlanParams pp, KEY* __restrict__ keys, uint32_t* __restrict__ vals, uint2* __restrict__ refs_unsorted) {
   const mke_oc_em_plan_args& a = pp.a;
+  const int64_t n_own = OWN ? (int64_t)a.own_off[a.n_all] : 0;
   __shared__ int64_t s_q[MKE_BLOCK / 64][128];              // per wavefront: owned element indices waiting for their turn
   const int64_t total = pp.total;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -219,7 +242,7 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_em_fill(const EmPlanParams pp, KE
   for (int64_t t = t0 + lane; t - lane < t1; t += 64 * EM_U) {     // wave-uniform trip count (ballots inside)
     EmElem e[EM_U];
 #pragma unroll
-    for (int u = 0; u < EM_U; ++u) e[u] = em_elem_of(pp, t + 64 * u < t1 ? t + 64 * u : total);
+    for (int u = 0; u < EM_U; ++u) e[u] = em_elem_of<OWN>(pp, t + 64 * u < t1 ? t + 64 * u : total, n_own);
 #pragma unroll
     for (int u = 0; u < EM_U; ++u) {
       const bool mine = em_owned(pp, e[u]);
@@ -230,7 +253,7 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_em_fill(const EmPlanParams pp, KE
         em_wave_lds_sync();
         const int64_t tq = q[lane];
         const int64_t spill = lane + 64 < qn ? q[lane + 64] : 0;
-        em_emit<KEY>(pp, tq, base + lane, s_hint, keys, vals, refs_unsorted);
+        em_emit<KEY, OWN>(pp, tq, n_own, base + lane, s_hint, keys, vals, refs_unsorted);
         em_wave_lds_sync();
         if (lane + 64 < qn) q[lane] = spill;              // at most 63 stay behind
         base += 64;
@@ -241,7 +264,7 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_em_fill(const EmPlanParams pp, KE
   }
   if (qn > 0) {
     em_wave_lds_sync();
-    if (lane < qn) em_emit<KEY>(pp, q[lane], base + lane, s_hint, keys, vals, refs_unsorted);
+    if (lane < qn) em_emit<KEY, OWN>(pp, q[lane], n_own, base + lane, s_hint, keys, vals, refs_unsorted);
   }
 }
 
@@ -363,15 +386,18 @@ static int em_plan_sorted(const EmPlanParams& pp, int key_bits, hipStream_t st) 
   uint2* refs_unsorted = reinterpret_cast<uint2*>(a.scratch8);     // the references at their unsorted positions (gathered after the sort)
   hipError_t e;
   if ((e = hipMemsetAsync(keys, 0xFF, (size_t)(a.capacity + 1) * sizeof(KEY), st)) != hipSuccess) { set_error("mke_oc_em_plan: %s", hipGetErrorString(e)); return (int)e; }
-  const int64_t total = a.n_all * (int64_t)pp.ep;
+  const int64_t total = pp.total;
+  const bool own = a.own_off != nullptr;
   const dim3 wgrid((unsigned)((pp.n_waves * 64 + MKE_BLOCK - 1) / MKE_BLOCK));
   size_t tb = (size_t)a.temp_bytes;
   if (total > 0) {
-    hipLaunchKernelGGL(k_em_count, wgrid, dim3(MKE_BLOCK), 0, st, pp);
+    if (own) hipLaunchKernelGGL(k_em_count<true>, wgrid, dim3(MKE_BLOCK), 0, st, pp);
+    else hipLaunchKernelGGL(k_em_count<false>, wgrid, dim3(MKE_BLOCK), 0, st, pp);
     int rc = check_launch("k_em_count");
     if (rc) return rc;
     if ((e = hipcub::DeviceScan::ExclusiveSum(a.temp, tb, pp.wave_cnt, pp.wave_off, pp.n_waves + 1, st)) != hipSuccess) { set_error("mke_oc_em_plan: scan: %s", hipGetErrorString(e)); return (int)e; }
-    hipLaunchKernelGGL((k_em_fill<KEY>), wgrid, dim3(MKE_BLOCK), 0, st, pp, keys, vals, refs_unsorted);
+    if (own) hipLaunchKernelGGL((k_em_fill<KEY, true>), wgrid, dim3(MKE_BLOCK), 0, st, pp, keys, vals, refs_unsorted);
+    else hipLaunchKernelGGL((k_em_fill<KEY, false>), wgrid, dim3(MKE_BLOCK), 0, st, pp, keys, vals, refs_unsorted);
     if ((rc = check_launch("k_em_fill"))) return rc;
   } else if ((e = hipMemsetAsync(a.n_refs, 0, sizeof(int64_t), st)) != hipSuccess) { set_error("mke_oc_em_plan: %s", hipGetErrorString(e)); return (int)e; }
   const int n = (int)(a.capacity + 1);
@@ -631,21 +657,23 @@ extern "C" int mke_oc_em_plan(const mke_oc_em_plan_args* args, void* stream) {
   if (a.capacity < 1 || a.capacity >= 0x7FFFFFFFll) { set_error("mke_oc_em_plan: capacity must be in [1, 2^31)"); return MKE_E_RANGE; }
   if (!a.keys || !a.keys_alt || !a.vals_alt || !a.scratch8 || !a.wave_scratch || !a.refs || !a.rows || !a.off || !a.flags || !a.scan || !a.step_row0 || !a.n_refs || !a.temp ||
       !a.item_row || !a.item_off || !a.item_part || !a.long_row || !a.long_part0 || !a.step_item0 || !a.step_long0 || !a.step_part0) { set_error("mke_oc_em_plan: NULL output / scratch"); return MKE_E_NULL; }
-  if (a.n_all > 0 && (!a.pos_h || !a.pos_r || !a.pos_t || !a.slot_h || !a.slot_t || !a.step_lo || (a.neg_per_pos > 0 && !a.codes))) { set_error("mke_oc_em_plan: NULL input"); return MKE_E_NULL; }
+  const bool own = a.own_off != nullptr;      // the negatives from this rank's owned list instead of the all-gathered codes
+  if (own && (a.own_cap < 0 || a.own_cap >= 0x7FFFFFFFll || (a.own_cap > 0 && !a.own_rec))) { set_error("mke_oc_em_plan: owned list: own_cap in [0, 2^31) and own_rec"); return MKE_E_SHAPE; }
+  if (a.n_all > 0 && (!a.pos_h || !a.pos_r || !a.pos_t || !a.slot_h || !a.slot_t || !a.step_lo || (a.neg_per_pos > 0 && !a.codes && !own))) { set_error("mke_oc_em_plan: NULL input"); return MKE_E_NULL; }
   if (a.temp_bytes < mke_oc_em_plan_temp_bytes(a.capacity)) { set_error("mke_oc_em_plan: temp storage below mke_oc_em_plan_temp_bytes"); return MKE_E_SHAPE; }
   if (a.max_step >= (1ll << 25) || a.max_step * (a.neg_per_pos + 1) > 0x7FFFFFFFll) { set_error("mke_oc_em_plan: a global step holds at most 2^25 positives"); return MKE_E_RANGE; }
   EmPlanParams pp;
   pp.a = a;
   pp.ep = (uint32_t)a.neg_per_pos + 5u;
-  pp.n_codes = a.n_all * (int64_t)a.neg_per_pos;
+  pp.n_codes = own ? (a.neg_per_pos > 0 ? a.own_cap : 0) : a.n_all * (int64_t)a.neg_per_pos;
   pp.n_magic = a.neg_per_pos > 0 ? ((1ull << 40) + a.neg_per_pos - 1) / a.neg_per_pos : 0;
   // with n_magic N = 2^40 + err, floor(t n_magic / 2^40) = floor(t / N) whenever t err < 2^40: checked for the largest t
   const uint64_t err = pp.n_magic * (uint64_t)a.neg_per_pos - (1ull << 40);
-  if (pp.n_magic && err && (uint64_t)(pp.n_codes - 1) >= ((1ull << 40) - 1) / err) pp.n_magic = 0;
+  if (pp.n_magic && err && pp.n_codes > 0 && (uint64_t)(pp.n_codes - 1) >= ((1ull << 40) - 1) / err) pp.n_magic = 0;
   pp.total = pp.n_codes + 5 * a.n_all;
   pp.g_shift = (a.n_ranks & (a.n_ranks - 1)) == 0 ? __builtin_ctz((unsigned)a.n_ranks) : -1;
   pp.rows_tot = a.n_local + a.n_rel;
-  const int64_t total = a.n_all * (int64_t)pp.ep;
+  const int64_t total = pp.total;
   int64_t nw = (total + 511) / 512;                       // >= 8 rounds of 64 elements per wavefront
   if (nw > MKE_OC_EM_WAVES) nw = MKE_OC_EM_WAVES;
   if (nw < 1) nw = 1;

@@ -15,6 +15,10 @@ The reference has no multi-device code; this is new design.  One process per GPU
 Once per epoch (`EpochPlan`; prefetched on a side stream): every rank draws 1 / world of the epoch's negatives as (entity, side)
 codes with the group's need flags, one all-gather of the codes, then every travelling vector's slot and — entity-major form — the
 reference lists of this rank's rows (`EmPlan`).  Capacity is known exactly before the epoch starts: nothing overflows mid-epoch.
+`codes="owner"` (MKE_OC_CODES=owner; entity-major form only, opt-in): the home rank buckets its codes by the OWNER of the corrupt
+entity and the buckets are exchanged all-to-all instead — a rank receives only the negatives it owns, in (position, n) order
+(`_bucket` / `_plan_gather` / `_owned_lists`), the reference lists are built from that list and the score launch walks it per positive
+instead of scanning every code.  Same lists, same sums, bit for bit.
 Per global step, ENTITY-MAJOR form (the default of the HIP backend):
     owner of h_p builds HR_p, owner of t_p builds RT_p — the needed ones                                          [BASES]
     ALL-GATHER of the blocks (~1 vector per positive)
@@ -191,6 +195,18 @@ class EpochPlan:
     own: list = None                # [2] this rank's owned positives per part, in slot order
     cnt_host: torch.Tensor = None   # pinned [2][parts][G] vectors per (part, owner)
     em: EmPlan = None
+    # -- owner-bucketed codes (`codes="owner"`): this rank's share of the codes, the buckets and what comes back
+    mine_codes: torch.Tensor = None     # this rank's share [n_per][N] as packed (kept: an overflowing bucket is filled again)
+    own_cap: int = 0                    # records per (source, destination) pair of the exchange
+    need_mine: torch.Tensor = None      # [n_per] need flags of this rank's positions ...
+    need_all: torch.Tensor = None       # ... and of every position after the all-gather ([G n_per]: mke_oc_plan reads it with N = 1)
+    cnt_mine: torch.Tensor = None       # [G] records this rank addresses to every owner (true counts: may exceed own_cap) ...
+    cnt_all: torch.Tensor = None        # ... and the whole [G][G] table (source, destination)
+    send: torch.Tensor = None           # [G][own_cap] records
+    recv: torch.Tensor = None
+    own_rec: torch.Tensor = None        # this rank's owned negatives, packed, in (position, n) order
+    own_off: torch.Tensor = None        # [n_all + 1] their offsets per epoch position
+    own_cnt_host: torch.Tensor = None   # pinned copy of cnt_all (asynchronous; read by `_finish_plan`)
     sampled: object = None          # events (HIP device only): share drawn / codes gathered / all of it enqueued
     gathered: object = None
     ready: object = None
@@ -209,13 +225,15 @@ class OwnerComputesTrainer:
                  exclusive_rows: bool = True, chunks: int = 1, peer_direct: bool = False, prefetch: bool = True,
                  batcher=None, scale: float = 1.0, tables_of: "OwnerComputesTrainer" = None, ent_table=None, rel_table=None,
                  opt_name: str = "relation", n_ent: int = None, tag_base: int = None, global_batch: int = None,
-                 entity_major: bool = None, tuning: dict = None):
+                 entity_major: bool = None, tuning: dict = None, codes: str = None):
         """batcher: an epoch source other than the two KGs' shuffled triples (`TripleListBatcher`: the cross-KG inference
         loops — positives only, `neg_per_pos` 0, `kgs` unused and `batch_size` the GLOBAL step size the batcher was built
         with); scale: the loss factor (2 for code/MultiKE_model.py:349-369); tables_of: another trainer of the same
         (rank, world, device, dtype) whose entity shard and relation table this one trains too — the graphs of one view
         share their variables and have one optimizer each (code/MultiKE_model.py:17-31): shared tables and (zero-invariant)
-        gradient / flag scratch, own Adagrad accumulators, own tag range; `ent0` / `rel0` are then unused."""
+        gradient / flag scratch, own Adagrad accumulators, own tag range; `ent0` / `rel0` are then unused.
+        codes: "gather" (every rank receives every code of the epoch) or "owner" (bucketed by owner and exchanged all-to-all: a rank
+        receives the negatives it owns — entity-major form only); None reads MKE_OC_CODES, default "gather"."""
         self.scale = float(scale)
         self.tuning = _lib.tuning(**tuning) if tuning else None     # this trainer's knobs (mke_oc_step.tuning), e.g. {"oc_score_quarter": 1}
         # ent_table / rel_table (multike_amd.tables.EmbeddingTable: this rank's shard of `n_ent` global rows, and the
@@ -264,6 +282,14 @@ class OwnerComputesTrainer:
         self.em = bool(em) and hasattr(self.backend, "em_plan") and self.chunks <= _lib.OC_EM_MAX_CHUNKS and dtype == torch.float32
         if self.em:
             exclusive_rows = False
+        form = codes if codes is not None else os.environ.get("MKE_OC_CODES", "gather")
+        if form not in ("gather", "owner"):
+            raise _lib.MultiKEHipError(f'codes / MKE_OC_CODES: "gather" or "owner", got {form!r}')
+        if form == "owner" and not self.em:
+            raise _lib.MultiKEHipError('codes="owner" (MKE_OC_CODES=owner) is built for the entity-major form only: entity_major=False / '
+                                       'MKE_OC_EM=0 (the atomics form, and a backend without the entity-major plan) counts its references '
+                                       'over the all-gathered codes — use codes="gather" with it')
+        self.codes_form = form
         dev, st = self.device, self.stride
         i32 = dict(dtype=torch.int32, device=dev)
         # --- row-sharded entity state ---------------------------------------------------------------
@@ -351,6 +377,10 @@ class OwnerComputesTrainer:
         self._send = self._v_all = self._g_all = self._gv = self._addr = None     # exchange buffers per chunk, and their addresses
         self._inbox = self._peer_send = self._peer_inbox = self._bar = None       # peer-direct (`_map_peers`)
         self._codes = self._slot = self._own = self._own_cnt = None
+        self._own_rec = self._own_off = None     # owned code lists of the current epoch (`codes="owner"`), else None
+        self._own_cap = 0             # records per (source, destination) pair of the code exchange (0: not sized yet)
+        self.owner_replans = 0        # epochs whose buckets overflowed the capacity and were exchanged again
+        self._code_bytes = 0          # code bytes this rank received for the current epoch's plan
         self.vectors_planned = 0
         self._plan_bs = 0             # which of the two epoch buffer sets the current plan lives in
         self._st_cache = {}           # OcStep per part, for backends that take tensors (`_part_step`)
@@ -447,7 +477,20 @@ class OwnerComputesTrainer:
         """The ONE collective of an epoch plan: every rank's 1 / G of the epoch's negative codes, all-gathered on the step
         communicator, on the stream the steps run on, at a fixed point of the step sequence (`_gather_at`) — so the ranks issue
         every collective of the job in one order."""
-        if plan.mine is not None and (self.world > 1 or self.force_collectives):
+        if plan.send is not None:
+            # owner-bucketed codes: three collectives at the same point — the positions' need flags (all-gather), every rank's counts
+            # per destination (all-gather: every rank holds the whole table and takes the same overflow decision), the buckets
+            # (equal-split all-to-all).  One rank without forced collectives: its one bucket is what it would receive.
+            if self.world > 1 or self.force_collectives:
+                if plan.sampled is not None:
+                    torch.cuda.current_stream().wait_event(plan.sampled)
+                self.comm.all_gather(plan.need_all, plan.need_mine)
+                self.comm.all_gather(plan.cnt_all, plan.cnt_mine)
+                self.comm.all_to_all(plan.recv, plan.send)
+                if self.device.type == "cuda":
+                    plan.gathered = torch.cuda.Event()
+                    plan.gathered.record()
+        elif plan.mine is not None and (self.world > 1 or self.force_collectives):
             if plan.sampled is not None:
                 torch.cuda.current_stream().wait_event(plan.sampled)
             self.comm.all_gather(plan.codes_all, plan.mine)
@@ -455,6 +498,73 @@ class OwnerComputesTrainer:
                 plan.gathered = torch.cuda.Event()
                 plan.gathered.record()
         plan.stage = PlanStage.GATHERED
+
+    def _bucket(self, plan):
+        """Owner form, after the share is packed (device work only): this rank's codes as records bucketed by owner, `own_cap` per
+        destination, with the true counts; the need flags of its positions on their own."""
+        G, dev, N = self.world, self.device, self.N
+        i32 = dict(dtype=torch.int32, device=dev)
+        z = torch.zeros(0, **i32)
+        n_all = self._n_all
+        n_per = -(-n_all // G)
+        lo_r, hi_r = min(n_all, self.rank * n_per), min(n_all, (self.rank + 1) * n_per)
+        cap = self._own_cap
+        if not cap:
+            # a rank's share spread over G owners + 6 % + 4,096 (the rule of the reference lists' capacity): the all-to-all moves
+            # the CAPACITY, so slack is bytes on the wire every epoch; a pair that holds more is exchanged again at the exact maximum
+            cap = self._own_cap = n_per * N if G == 1 else int(1.06 * n_per * N / G) + 4096
+        R = _lib.OC_REC_INTS
+        plan.own_cap = cap
+        plan.need_mine = self._persist(("own_need_mine", plan.bs), z, n_per)[:n_per]
+        plan.cnt_mine = self._persist(("own_cnt_mine", plan.bs), z, G)[:G]
+        plan.send = self._persist(("own_send",), z, R * G * cap)[:R * G * cap]
+        split = G > 1 or self.force_collectives
+        plan.need_all = self._persist(("own_need", plan.bs), z, G * n_per)[:G * n_per] if split else plan.need_mine
+        plan.cnt_all = self._persist(("own_cnt", plan.bs), z, G * G)[:G * G] if split else plan.cnt_mine
+        plan.recv = self._persist(("own_recv",), z, R * G * cap)[:R * G * cap] if split else plan.send
+        if hasattr(self.backend, "bucket_codes"):
+            self.backend.bucket_codes(plan.mine_codes, hi_r - lo_r, N, lo_r, G, cap, plan.need_mine, plan.send, plan.cnt_mine,
+                                      self._persist(("own_scratch",), z, G * _lib.OC_BUCKET_WAVES))
+        else:       # the tests' CPU backend: the same stable partition in torch
+            c = plan.mine_codes[:(hi_r - lo_r) * N]
+            code = c & _lib.OC_CODE_MASK
+            dest = (code >> 1) % G
+            order = torch.argsort(dest, stable=True)
+            cnt = torch.bincount(dest, minlength=G)
+            start = torch.cumsum(cnt, 0) - cnt
+            k = torch.arange(order.numel(), device=dev) - start[dest[order]]
+            keep = k < cap
+            o, d, k = order[keep], dest[order][keep].long(), k[keep]
+            send = plan.send.view(G, cap, R)
+            send[d, k, 0] = (lo_r + o // N).to(torch.int32)
+            send[d, k, 1] = (o % N).to(torch.int32)
+            send[d, k, 2] = code[o]
+            plan.cnt_mine.copy_(cnt.to(torch.int32))
+            if hi_r > lo_r:
+                plan.need_mine[:hi_r - lo_r].copy_(c.view(hi_r - lo_r, N)[:, 0] & -0x40000000)
+
+    def _owned_lists(self, plan):
+        """Owner form, after the exchange (device work only): the received buckets packed into this rank's owned list with its
+        offsets per epoch position; the counts table on its way to pinned memory."""
+        G, dev = self.world, self.device
+        i32 = dict(dtype=torch.int32, device=dev)
+        z = torch.zeros(0, **i32)
+        R, cap, n_all = _lib.OC_REC_INTS, plan.own_cap, self._n_all
+        plan.own_rec = self._persist(("own_rec", plan.bs), z, R * G * cap)
+        plan.own_off = self._persist(("own_off", plan.bs), z, n_all + 1)
+        col = plan.cnt_all.view(-1, G)[:, self.rank].contiguous()         # what every source addressed to this rank
+        if hasattr(self.backend, "owned_index"):
+            self.backend.owned_index(plan.recv, col, G, cap, n_all, plan.own_rec, plan.own_off)
+        else:
+            got = col.clamp(max=cap).tolist()
+            recs = torch.cat([plan.recv.view(G, cap, R)[s, :got[s]] for s in range(G)]) if cap else plan.recv.view(0, R)
+            plan.own_rec[:recs.numel()].copy_(recs.reshape(-1))
+            plan.own_off[:n_all + 1].copy_(torch.searchsorted(recs[:, 0].contiguous(), torch.arange(n_all + 1, **i32)).to(torch.int32))
+        host = self._persistent.get(("own_cnt_host", plan.bs))
+        if host is None or host.numel() != plan.cnt_all.numel():
+            host = self._persistent[("own_cnt_host", plan.bs)] = torch.empty(plan.cnt_all.numel(), dtype=torch.int32, pin_memory=dev.type == "cuda")
+        host.copy_(plan.cnt_all, non_blocking=True)
+        plan.own_cnt_host = host
 
     def _plan_sample(self, pos, rng_stream, bs):
         """First stage of a plan, into buffer set `bs` (device work only, no host synchronisation): this rank draws the negatives
@@ -467,7 +577,9 @@ class OwnerComputesTrainer:
         ph, pr, pt = pos
         n_all = self._n_all
         n_per = -(-n_all // G) if n_all else 0            # positions per rank (the last rank's share may be shorter)
-        codes = self._persist(("codes", bs), torch.zeros(0, **i32), max(1, G * n_per * N))
+        owner = self.codes_form == "owner" and n_all > 0 and N > 0
+        # (owner form on several ranks: nobody holds the whole epoch's codes)
+        codes = self._persist(("codes", bs), torch.zeros(0, **i32), 1 if owner and G > 1 else max(1, G * n_per * N))
         plan = EpochPlan(bs, pos, codes)
         if n_all and N:
             lo_r, hi_r = min(n_all, self.rank * n_per), min(n_all, (self.rank + 1) * n_per)
@@ -486,7 +598,10 @@ class OwnerComputesTrainer:
                     self.backend.sample_at((ph[a:e], pr[a:e], pt[a:e]), self._all_idx[a:e], b.pos_kg[a:e],
                                            b.side1, b.side2, N, b.rng_seed, rng_stream, out)
                     self.backend.pack_codes(ph[a:e], out[0], out[2], N, mine[(a - lo_r) * N:(e - lo_r) * N])
-            if G > 1 or self.force_collectives:      # (forced at one rank: an in-place all-gather of the whole array)
+            if owner:
+                plan.mine_codes = mine
+                self._bucket(plan)
+            elif G > 1 or self.force_collectives:      # (forced at one rank: an in-place all-gather of the whole array)
                 plan.codes_all, plan.mine = codes[:G * n_per * N], mine[:n_per * N]
         if dev.type == "cuda":
             plan.sampled = torch.cuda.Event()
@@ -509,13 +624,18 @@ class OwnerComputesTrainer:
         slot = [self._persist(("slot", x, bs), torch.zeros(0, **i32), max(1, n_all)) for x in range(2)]
         own = [self._persist(("own", x, bs), torch.zeros(0, **i32), max(1, n_all)) for x in range(2)]
         plan.slot, plan.own = slot, own
+        owner = plan.send is not None
+        if owner:
+            self._owned_lists(plan)
         if n_all:
             cnt = self._persist(("cnt", bs), torch.zeros(0, **i32), 2 * len(parts) * G)
             if hasattr(self.backend, "plan"):
-                self.backend.plan(ph, pt, codes, N, self._part_lo, len(parts), G, self.rank, slot[0], slot[1], own[0], own[1], cnt)
+                # (owner form: the all-gathered need flags are the layout the launch reads with one code per position)
+                self.backend.plan(ph, pt, plan.need_all if owner else codes, 1 if owner else N, self._part_lo, len(parts), G, self.rank,
+                                  slot[0], slot[1], own[0], own[1], cnt)
             else:
                 if N:
-                    first = codes[:n_all * N].view(n_all, N)[:, 0].long() & 0xFFFFFFFF
+                    first = (plan.need_all[:n_all] if owner else codes[:n_all * N].view(n_all, N)[:, 0]).long() & 0xFFFFFFFF
                     needs = ((first & _lib.OC_NEED_HR) != 0, (first & _lib.OC_NEED_RT) != 0)
                 else:
                     needs = (torch.ones(n_all, dtype=torch.bool, device=dev), torch.zeros(n_all, dtype=torch.bool, device=dev))
@@ -541,7 +661,7 @@ class OwnerComputesTrainer:
             host.copy_(c, non_blocking=True)
             plan.cnt_host = host
         if self.em:
-            plan.em = self._compute_em_plan(ph, pr, pt, codes, slot, bs)
+            plan.em = self._compute_em_plan(ph, pr, pt, codes, slot, bs, own=self._own_of(plan))
         if dev.type == "cuda":
             plan.ready = torch.cuda.Event()
             plan.ready.record()
@@ -570,9 +690,15 @@ class OwnerComputesTrainer:
             steps3=p(("em_steps3", bs), z64, 3 * S1).view(-1)[:3 * S1].view(3, S1),
             n_refs_dev=p(("em_n_refs", bs), z64, 1))
 
-    def _compute_em_plan(self, ph, pr, pt, codes, slot, bs, capacity=None):
+    @staticmethod
+    def _own_of(plan):
+        """(own_rec, own_off, records own_rec has room for) of a plan with owner-bucketed codes, else None."""
+        return (plan.own_rec, plan.own_off, plan.own_rec.numel() // _lib.OC_REC_INTS) if plan.own_off is not None else None
+
+    def _compute_em_plan(self, ph, pr, pt, codes, slot, bs, capacity=None, own=None):
         """The entity-major reference lists of the epoch in buffer set `bs` (device work only; the touched-row offsets of the
-        steps and the reference count go to pinned host memory asynchronously, read by `_finish_plan`)."""
+        steps and the reference count go to pinned host memory asynchronously, read by `_finish_plan`).  own: the negatives from
+        this rank's owned list (`_own_of`) instead of the all-gathered codes."""
         G, N = self.world, self.N
         upper = max(1, self._n_all * (N + 5))                          # every element of every positive
         if capacity is None:
@@ -584,7 +710,10 @@ class OwnerComputesTrainer:
                 capacity = upper if G == 1 else min(upper, int(1.06 * self._n_all * (N + 3) / G) + 4096)
         self._em_capacity[bs] = capacity
         em = self._em_buffers(bs, capacity)
-        self.backend.em_plan(self, ph, pr, pt, codes, slot, em)
+        if own is None:
+            self.backend.em_plan(self, ph, pr, pt, codes, slot, em)
+        else:
+            self.backend.em_plan(self, ph, pr, pt, codes, slot, em, own=own)
         S1 = self.steps + 1
         host = self._persistent.get(("em_host", bs))
         if host is None or host.numel() != 4 * S1 + 1:
@@ -601,6 +730,27 @@ class OwnerComputesTrainer:
         G, dev = self.world, self.device
         if plan.ready is not None:
             plan.ready.synchronize()
+        if plan.send is not None:
+            # owner-bucketed codes: every rank holds the same [G][G] table of true counts.  A pair beyond the capacity: every rank
+            # buckets, exchanges and plans again, in line, with room for the largest (the rule of the reference lists' regrow below)
+            most = int(plan.own_cnt_host.max())
+            if most > plan.own_cap:
+                self._own_cap = most
+                self.owner_replans += 1
+                plan.sampled = plan.gathered = None          # everything below is on the current stream
+                self._bucket(plan)
+                self._plan_gather(plan)
+                self._plan_rest(plan)
+                if plan.ready is not None:
+                    plan.ready.synchronize()
+            self._own_rec, self._own_off = plan.own_rec, plan.own_off
+            G, n_per = self.world, -(-self._n_all // self.world)
+            split = G > 1 or self.force_collectives
+            self._code_bytes = (4 * _lib.OC_REC_INTS * G * plan.own_cap + 4 * G * n_per + 4 * G * G) if split else 0
+        else:
+            self._own_rec = self._own_off = None
+            n_per = -(-self._n_all // self.world) if self._n_all else 0
+            self._code_bytes = 4 * self.world * n_per * self.N if plan.mine is not None else 0
         parts = self._parts
         self._codes, self._slot, self._own = plan.codes, plan.slot, plan.own
         self._own_cnt = []                      # per part: how many HR / RT vectors of it this rank owns
@@ -634,7 +784,8 @@ class OwnerComputesTrainer:
             S1 = self.steps + 1
             n_refs = int(em.host[4 * S1])
             if n_refs > em.capacity:        # more references than the 1 / G estimate allowed for (skewed ownership): re-plan in line, exactly
-                em = plan.em = self._compute_em_plan(*plan.pos, plan.codes, plan.slot, plan.bs, capacity=int(n_refs * 1.1) + 4096)
+                em = plan.em = self._compute_em_plan(*plan.pos, plan.codes, plan.slot, plan.bs, capacity=int(n_refs * 1.1) + 4096,
+                                                     own=self._own_of(plan))
                 if dev.type == "cuda":
                     torch.cuda.current_stream().synchronize()
                 n_refs = int(em.host[4 * S1])
@@ -785,7 +936,8 @@ class OwnerComputesTrainer:
         pw = getattr(b, "pos_w", None)
         return OcStep(b.pos_h[lo:hi], b.pos_r[lo:hi], b.pos_t[lo:hi], per, self._slot[0][lo:hi], self._slot[1][lo:hi],
                       self._own[0][lo:lo + nh], self._own[1][lo:lo + nt], tag, self._codes, code_off,
-                      pos_w=(pw[lo:hi] if pw is not None else None))
+                      pos_w=(pw[lo:hi] if pw is not None else None),
+                      own_rec=self._own_rec, own_off=(self._own_off[lo:hi + 1] if self._own_off is not None else None))
 
     def _exchange_tensors(self):
         return [*self._send, *self._v_all, *self._g_all, *self._gv, self.rel_grad]
@@ -992,7 +1144,11 @@ class OwnerComputesTrainer:
         out = {"capacity_vectors_per_owner": self.C, "block_bytes": self.block * 4, "chunks": self.chunks,
                "vectors_per_positive": self.vectors_planned / max(1, self._n_all),
                "entity_major": bool(self.em), "peer_direct": bool(self.peer_direct), "native_step_loop": bool(self._native_loop()[0]),
-               "reduce_scatter_under_second_pass": bool(self._overlap_rs()), "communicator": type(self.comm).__name__}
+               "reduce_scatter_under_second_pass": bool(self._overlap_rs()), "communicator": type(self.comm).__name__,
+               "codes": self.codes_form, "code_bytes_received_per_epoch": int(self._code_bytes)}
+        if self.codes_form == "owner":
+            out["owner_code_capacity_per_pair"] = int(self._own_cap)
+            out["owner_replans"] = int(self.owner_replans)
         if self.em:
             out["references_per_global_step"] = self._em.n_refs / max(1, self.steps)
             out["long_rows_per_global_step"] = int(self._em.long0[-1]) / max(1, self.steps)

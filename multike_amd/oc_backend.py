@@ -4,8 +4,9 @@ mke_oc_em.hip, mke_update.hip), launched through mke_oc_run (the phases of `phas
 mke_oc_steps (whole runs of steps, collectives included, enqueued from C++).
 
 The backend protocol: `device_type`, `make_known`, `sample_at`, `block_elems`, `pack_codes` and `run` are required;
-`plan`, `em_plan` (+ `em_temp_bytes`), `prepare_epoch` and `run_steps` are the HIP backend's own — the trainer probes
-for them, and a backend without them (the tests' NumPy oracle) gets the torch plan, the atomics form and the Python loop.
+`plan`, `em_plan` (+ `em_temp_bytes`), `bucket_codes`, `owned_index`, `prepare_epoch` and `run_steps` are the HIP backend's own —
+the trainer probes for them, and a backend without them (the tests' NumPy oracle) gets the torch plan (and the torch bucketing of
+owner-bucketed codes), the atomics form and the Python loop.
 """
 import ctypes as C
 from dataclasses import dataclass
@@ -34,6 +35,8 @@ class OcStep:
     codes: torch.Tensor = None      # the epoch's negative codes of every rank, [world][codes_per_rank]
     code_off: tuple = ()            # per home rank: offset of its codes of this part inside `codes`
     pos_w: torch.Tensor = None      # per-positive weights of the part (weighted cross-KG loops), or None
+    own_rec: torch.Tensor = None    # owner-bucketed codes: this rank's owned negatives of the epoch as (position, n, code) records ...
+    own_off: torch.Tensor = None    # ... and the part's [n_pos + 1] offsets into them (None: the code scan)
 
 
 class OcHipBackend:
@@ -66,7 +69,15 @@ class OcHipBackend:
         """slots, owned lists and per-(part, owner) counts of the whole epoch in ONE launch (mke_oc_plan)."""
         _lib.oc_plan(pos_h, pos_t, codes, neg_per_pos, part_lo, n_parts, n_ranks, rank, slot_h, slot_t, own_h, own_t, counts)
 
-    def em_plan(self, tr, ph, pr, pt, codes, slot, em):
+    def bucket_codes(self, codes, n_mine, neg_per_pos, pos0, n_ranks, cap, need, send, counts, scratch):
+        """mke_oc_bucket_codes: this rank's share of the codes bucketed by owner, (position, n) order per destination, true counts."""
+        _lib.oc_bucket_codes(codes, n_mine, neg_per_pos, pos0, n_ranks, cap, need, send, counts, scratch)
+
+    def owned_index(self, recv, counts, n_ranks, cap, n_all, own_rec, own_off):
+        """mke_oc_owned_index: the received buckets packed into this rank's owned list, with its offsets per epoch position."""
+        _lib.oc_owned_index(recv, counts, n_ranks, cap, n_all, own_rec, own_off)
+
+    def em_plan(self, tr, ph, pr, pt, codes, slot, em, own=None):
         """mke_oc_em_plan: the epoch's references to this rank's rows sorted by (step, row, positive, kind), the touched rows of
         every global step and their CSR offsets (entity-major second pass) — one native call, nothing synchronises."""
         i32, i64 = torch.int32, torch.int64
@@ -88,6 +99,8 @@ class OcHipBackend:
         a.long_row, a.long_part0 = _lib.ptr(em.long_row, i32, "long_row"), _lib.ptr(em.long_part0, i32, "long_part0")
         a.step_item0, a.step_long0, a.step_part0 = (_lib.ptr(em.steps3[k], i64, "steps3") for k in range(3))
         a.temp, a.temp_bytes = _lib.ptr(em.temp, torch.uint8, "temp"), em.temp.numel()
+        if own is not None:     # the negatives from this rank's owned list (own_rec, own_off, records own_rec has room for)
+            a.own_rec, a.own_off, a.own_cap = _lib.ptr(own[0], i32, "own_rec"), _lib.ptr(own[1], i32, "own_off"), int(own[2])
         _lib.oc_em_plan(a)
 
     def em_temp_bytes(self, capacity):
@@ -121,6 +134,8 @@ class OcHipBackend:
             s.hot.slot, s.hot.n_hot = _lib.ptr(tr.hot_slot, i32, "hot_slot"), tr.n_hot
             s.hot.copies, s.hot.row0 = tr.HOT_COPIES, tr.ent_grad_rows
         s.tuning = _lib.tuning_ptr(tr.tuning)
+        if st.own_off is not None:            # owner-bucketed codes: the part's offsets into this rank's owned list
+            s.own_rec, s.own_off = _lib.ptr(st.own_rec, i32, "own_rec"), _lib.ptr(st.own_off, i32, "own_off")
         s.n_peers = 0
         # peer-mapped blocks (chunk 0: peer-direct runs unchunked); with the entity-major form `prepare_epoch` points em_v[0] /
         # em_gv[0] at the LOCAL mirror and summed block (`_addr`), never at a peer's memory
@@ -146,13 +161,15 @@ class OcHipBackend:
         key = (tr.C, b.pos_h.data_ptr(), tr._slot[0].data_ptr(), tr._slot[1].data_ptr(), oh, ot, tr._codes.data_ptr(), len(tr._parts),
                tuple(t.data_ptr() for t in (*tr._peer_send, *tr._peer_inbox)) if tr.peer_direct and tr.world > 1 else 0,
                (em.refs.data_ptr(), em.item_row.data_ptr(), em.item_off.data_ptr(), tr._em_coef.data_ptr(),
-                tr._em_partials.data_ptr(), tr._addr[0][1], tr._addr[0][3]) if em else 0)
+                tr._em_partials.data_ptr(), tr._addr[0][1], tr._addr[0][3]) if em else 0,
+               (tr._own_rec.data_ptr(), tr._own_off.data_ptr()) if tr._own_off is not None else 0)
         if key not in self._cache:                        # first use of this buffer set, or a buffer was re-allocated
             base = self._struct(tr, tr._build_part_step(0, 0))
             ph, pr, pt = (_lib.ptr(x, i32, "pos") for x in (b.pos_h, b.pos_r, b.pos_t))
             sh, stt = _lib.ptr(tr._slot[0], i32, "slot"), _lib.ptr(tr._slot[1], i32, "slot")
             pw = getattr(b, "pos_w", None)
             pw = _lib.ptr(pw, torch.float32, "pos_w") if pw is not None else None
+            oo = _lib.ptr(tr._own_off, i32, "own_off") if tr._own_off is not None else None
             arr = (_lib.OcStepStruct * len(tr._parts))()     # contiguous: mke_oc_steps walks it (the list below holds views)
             out = []
             for k, (_, lo, hi) in enumerate(tr._parts):
@@ -161,6 +178,8 @@ class OcHipBackend:
                 s.pos_h, s.pos_r, s.pos_t = ph + 4 * lo, pr + 4 * lo, pt + 4 * lo
                 s.slot_h, s.slot_t = sh + 4 * lo, stt + 4 * lo
                 s.pos_w = (pw + 4 * lo) if pw is not None else None
+                if oo is not None:                      # (own_rec came with `base`: the list's base for every part)
+                    s.own_off = oo + 4 * lo
                 s.n_pos = hi - lo
                 s.per = max(1, -(-(hi - lo) // tr.world))
                 for g in range(tr.world):

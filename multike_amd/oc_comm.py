@@ -1,6 +1,7 @@
 """Communicators of the owner-computes trainer (multike_amd/distributed_oc.py): the three collectives of a global step —
 all-gather of the HR / RT vector blocks, reduce-scatter of their gradients, all-reduce of the relation gradient — and the
-once-per-epoch all-gather of the negative codes, on the SAME communicator (every rank issues every collective in one order).
+once-per-epoch exchange of the negative codes (an all-gather; with owner-bucketed codes two small all-gathers and an equal-split
+all-to-all), on the SAME communicator (every rank issues every collective in one order).
 `OcRcclComm` is the default of the HIP trainers (`default_comm`); `OcGlooComm` and `OcHostStagedComm` serve the tests.
 
 A communicator MAY have `native(tr)`: the mke_oc_comm struct the native step loop (mke_oc_steps) calls its collectives
@@ -32,6 +33,10 @@ class OcComm:
 
     def all_reduce(self, t, op=None):
         dist.all_reduce(t, group=self.group) if op is None else dist.all_reduce(t, op=op, group=self.group)
+
+    def all_to_all(self, out, inp):
+        """Equal split (the epoch plan's owner-bucketed codes): block g of `inp` goes to rank g, block g of `out` comes from rank g."""
+        dist.all_to_all_single(out.view(-1), inp.view(-1), group=self.group)
 
     def all_gather_list(self, parts, mine):
         dist.all_gather(parts, mine, group=self.group)
@@ -101,6 +106,9 @@ class OcRcclComm(OcComm):
             return super().all_reduce(t, op)
         self.c.all_reduce(t.view(-1))
 
+    def all_to_all(self, out, inp):
+        self.c.all_to_all(out.view(-1), inp.view(-1))
+
     def barrier(self, token):
         self.c.all_reduce(token.view(-1))
 
@@ -157,6 +165,10 @@ class OcGlooComm(OcComm):
         dist.all_reduce(tmp, group=self.group)
         out.copy_(tmp.view(w, -1)[r].view_as(out))
 
+    def all_to_all(self, out, inp):
+        """gloo's all_to_all_single on host tensors (what the row exchange of multike_amd/distributed.py goes through)."""
+        dist.all_to_all_single(out.view(-1), inp.view(-1), group=self.group)
+
 
 class OcHostStagedComm(OcGlooComm):
     """Test vehicle: the same collectives on DEVICE tensors through gloo, staged over the host.  Lets two ranks that SHARE
@@ -176,6 +188,11 @@ class OcHostStagedComm(OcGlooComm):
         c = t.cpu()
         super().all_reduce(c, op)
         t.copy_(c)
+
+    def all_to_all(self, out, inp):
+        o = torch.empty(out.shape, dtype=out.dtype)
+        super().all_to_all(o, inp.cpu())
+        out.copy_(o)
 
     def all_gather_list(self, parts, mine):
         cp = [torch.empty(p.shape, dtype=p.dtype) for p in parts]

@@ -57,6 +57,10 @@ def lib():
         L.ncclAllGather.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
         L.ncclReduceScatter.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.ncclAllReduce.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.ncclSend.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.ncclRecv.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        if hasattr(L, "ncclAllToAll"):      # RCCL's own (not part of NCCL's interface)
+            L.ncclAllToAll.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -111,6 +115,22 @@ class Communicator:
     def all_reduce(self, t, stream=None):
         _ck(lib().ncclAllReduce(self._buf(t, "t"), self._buf(t, "t"), t.numel(), _DT[t.dtype], _SUM, self._comm, self._stream(stream)),
             "ncclAllReduce")
+
+    def all_to_all(self, out, inp, stream=None):
+        """Equal split: block g of `inp` goes to rank g, block g of `out` comes from rank g.  RCCL's ncclAllToAll where the library
+        has it, else one group of sends and receives."""
+        if out.numel() != inp.numel() or inp.numel() % self.world or out.dtype != inp.dtype:
+            raise RcclError("all_to_all: out and inp must hold world equal blocks")
+        L, n, st = lib(), inp.numel() // self.world, self._stream(stream)
+        if hasattr(L, "ncclAllToAll"):
+            _ck(L.ncclAllToAll(self._buf(inp, "inp"), self._buf(out, "out"), n, _DT[inp.dtype], self._comm, st), "ncclAllToAll")
+            return
+        size = n * inp.element_size()
+        _ck(L.ncclGroupStart(), "ncclGroupStart")
+        for g in range(self.world):
+            _ck(L.ncclSend(C.c_void_p(inp.data_ptr() + g * size), n, _DT[inp.dtype], g, self._comm, st), "ncclSend")
+            _ck(L.ncclRecv(C.c_void_p(out.data_ptr() + g * size), n, _DT[inp.dtype], g, self._comm, st), "ncclRecv")
+        _ck(L.ncclGroupEnd(), "ncclGroupEnd")
 
     def self_check(self):
         """sum over ranks of (rank + 1) through all three collectives; raises when a result is wrong"""

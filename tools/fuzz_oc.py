@@ -2,7 +2,9 @@
 sharing the one GPU, collectives staged through gloo or peer-direct), entity counts that do not divide by the world size (from 60:
 re-draw rounds then make a fifth of the positives need BOTH vectors), Zipf head / tail entities with a low hub-row threshold, row
 widths, negatives per positive (0..64), chunk counts, exclusive-row path on / off, entity-major second pass on / off, native step
-loop (mke_oc_steps) or the Python loop.  python tools/fuzz_oc.py [cases] [seed]"""
+loop (mke_oc_steps) or the Python loop.  With MKE_OC_CODES=owner in the environment (owner-bucketed codes: entity-major form only)
+the same draws run with the entity-major second pass on every case — the peer-direct ones then on its entity-major transport.
+python tools/fuzz_oc.py [cases] [seed]"""
 import os, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -54,6 +56,8 @@ if __name__ == "__main__":
         kw["hot_min"] = [None, 3.0][int(rng.integers(0, 2))] if kw["zipf"] else None
         kw["em"] = bool(rng.random() < 0.7)                       # entity-major second pass (not with peer-direct: the trainer falls back)
         kw["native"] = bool(rng.random() < 0.6)                   # the native step loop
+        if os.environ.get("MKE_OC_CODES") == "owner":             # (after the draws: the sequence of cases stays the seed's)
+            kw["em"] = True
         ref_kw = dict(n_ent=kw["n_ent"], dim=kw["dim"], neg=kw["neg"], b=kw["b"], zipf=kw["zipf"])
         _, _, _, spe = T._reference(world, 1, **ref_kw)
         steps = int(min(spe, rng.integers(1, 7)))

@@ -8,7 +8,7 @@ rank's slice, the all-reduce is the identity — and every phase between two col
 numbers are NOT a training result (the arithmetic is fed copies), they are the per-rank COMPUTE terms of DESIGN.md §5.2, which
 round 3 had modelled.  Run it under rocprofv3 (tools/prof.sh) for the per-kernel table.
 
-    python tools/oc_rank_compute.py [--world 8] [--config c2|c5] [--steps 60] [--chunks 1]"""
+    python tools/oc_rank_compute.py [--world 8] [--config c2|c5] [--steps 60] [--chunks 1] [--codes gather|owner]"""
 import argparse
 import json
 import os
@@ -85,6 +85,21 @@ class LoopbackComm(OcComm):
         if self.latency_us > 0 or self.wire_gbps > 0:      # small replicated gradient: latency-bound
             self._run(lambda: None, 2 * (self.world - 1) / self.world * t.numel() * t.element_size(), False)
 
+    def all_to_all(self, out, inp):
+        """Owner-bucketed codes (`--codes owner`): what source s would address to this rank is stood in for by this rank's OWN bucket
+        for itself with its positions moved into s's share of the epoch (`n_per` positions per home rank; positions past the epoch's end
+        pile up on its last one) — the record and byte counts of the real exchange, ordered by position as the real one is; the counts'
+        all-gather hands every source this rank's own count."""
+        G = self.world
+
+        def fn():
+            o, i = out.view(G, -1, 3), inp.view(G, -1, 3)
+            o.copy_(i[self.rank].unsqueeze(0).expand(G, -1, -1))
+            shift = (torch.arange(G, device=o.device, dtype=torch.int32) - self.rank) * self.n_per
+            o[:, :, 0] += shift.view(G, 1)
+            o[:, :, 0].clamp_(min=0, max=self.n_all - 1)
+        self._run(fn, (G - 1) * (inp.numel() // G) * inp.element_size(), False)
+
     def barrier(self, token):
         pass
 
@@ -122,6 +137,7 @@ def main():
     ap.add_argument("--hi-prio", type=int, default=0, help="1: the steps run on a high-priority stream (the epoch plan's side stream then yields to them)")
     ap.add_argument("--native", type=int, default=1, help="1 (default): the timed steps go through mke_oc_steps (one native call); 0: the Python step loop")
     ap.add_argument("--em", type=int, default=1, help="1 (default): entity-major second pass; 0: the atomics form of rounds 2-5")
+    ap.add_argument("--codes", choices=["gather", "owner"], default="gather", help="the epoch's negative codes all-gathered (default) or bucketed by owner and exchanged all-to-all")
     ap.add_argument("--set", action="append", default=[], metavar="OPTION=VALUE", help="mke_set_option before the run (A/B of a kernel choice)")
     a = ap.parse_args()
     for kv in a.set:
@@ -137,7 +153,11 @@ def main():
         torch.cuda.set_stream(torch.cuda.Stream(priority=-1))
     comm = LoopbackComm(G, 0, a.wire_gbps, a.latency_us)
     comm.clock_hz = calibrate_sleep()
-    tr = OwnerComputesTrainer(kgs, ent0, rel0, B, cfg["neg"], 0, G, seed=1, chunks=a.chunks, comm=comm, prefetch=a.prefetch, entity_major=bool(a.em))
+    comm.n_all = sum(len(t) for t in kgs.triples)             # an epoch is every triple once; home rank s holds positions [s n_per, (s + 1) n_per)
+    comm.n_per = -(-comm.n_all // G)
+    tr = OwnerComputesTrainer(kgs, ent0, rel0, B, cfg["neg"], 0, G, seed=1, chunks=a.chunks, comm=comm, prefetch=a.prefetch, entity_major=bool(a.em),
+                              codes=a.codes)
+    assert tr._n_all == comm.n_all
     names = {BASES | COUNT: "bases+count", BASES: "bases", SCORE: "score", APPLY: "apply", UPDATE: "update", APPLY | UPDATE: "apply+update",
              BASES | COUNT | SCORE | APPLY | UPDATE: "whole step (one call)", PASS2: "pass2", PASS2 | UPDATE: "pass2+update",
              BASES | SCORE | PASS2 | UPDATE: "whole step (one call)"}
@@ -187,6 +207,42 @@ def main():
     p1.record()
     torch.cuda.synchronize()
     plan_ms = p0.elapsed_time(p1)
+    # the plan once more, its stages between events: sampling + packing (+ the bucket launch), the code exchange (loop-back), then
+    # owned index | slots | reference lists one by one
+    marks = []
+
+    def mark(name):
+        e = torch.cuda.Event(enable_timing=True)
+        e.record()
+        marks.append((name, e))
+
+    pos = (b.pos_h, b.pos_r, b.pos_t)
+    be = tr.backend
+    wrapped = {}
+    for meth in ("bucket_codes", "owned_index", "plan", "em_plan"):
+        orig_m = getattr(be, meth)
+
+        def timed(*args, _o=orig_m, _n=meth, **kw):
+            mark("before " + _n)
+            _o(*args, **kw)
+            mark(_n)
+        wrapped[meth] = orig_m
+        setattr(be, meth, timed)
+    mark("start")
+    plan = tr._plan_sample(pos, b.rng_stream, 1)
+    mark("sampled")
+    tr._plan_gather(plan)
+    mark("exchanged")
+    tr._plan_rest(plan)
+    mark("done")
+    torch.cuda.synchronize()
+    for meth, orig_m in wrapped.items():
+        setattr(be, meth, orig_m)
+    at = {name: marks[0][1].elapsed_time(e) * 1e3 for name, e in marks}
+    stage = lambda n: (at[n] - at["before " + n]) if n in at else 0.0
+    plan_stages = {"sample+pack_us": at["sampled"] - at["start"] - stage("bucket_codes"), "bucket_us": stage("bucket_codes"),
+                   "exchange_loopback_us": at["exchanged"] - at["sampled"], "owned_index_us": stage("owned_index"), "slots_us": stage("plan"),
+                   "em_plan_us": stage("em_plan"), "total_us": at["done"] - at["start"]}
     phases = {}
     for name, e0, e1 in ev:
         phases.setdefault(name, []).append(e0.elapsed_time(e1) * 1e3)
@@ -197,7 +253,8 @@ def main():
            "capacity_vectors": tr.C,
            "phase_us": {k: float(np.mean(v)) for k, v in phases.items()},
            "compute_us_per_step": float(sum(np.mean(v) * (len(v) / max(1, len(phases.get("score", v)))) for v in phases.values())),
-           "epoch_plan_ms": plan_ms, "epoch_plan_us_per_step": plan_ms * 1e3 / tr.steps,
+           "epoch_plan_ms": plan_ms, "epoch_plan_us_per_step": plan_ms * 1e3 / tr.steps, "epoch_plan_stages": plan_stages,
+           "codes": tr.check()["codes"], "code_bytes_received_per_epoch": tr.check()["code_bytes_received_per_epoch"],
            "wall_us_per_step_loopback": wall * 1e6, "host_us_per_step": host * 1e6,
            "wire_gbps_modelled": a.wire_gbps, "latency_us_modelled": a.latency_us, "prefetch": a.prefetch,
            "rank_share_of_epoch_sampled": 1.0 / G,
