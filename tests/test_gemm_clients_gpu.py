@@ -29,7 +29,7 @@ pytestmark = pytest.mark.gpu
 def test_mapping_step_at_the_tall_kernel_limits(d, B):
     """test_mapping_gpu.py's three native steps against mo.space_mapping_step_dense, same tolerances."""
     from test_mapping_gpu import test_native_steps_match_oracle as native_steps_match_oracle
-    native_steps_match_oracle(d, B + 300, B)
+    native_steps_match_oracle(d, B + 300, B, False)
 
 
 UNFUSED = [(75, 5000, 20000, 300, 8000),   # 16 K splits, the last one ragged (200 of 320)

@@ -14,8 +14,9 @@ def _orth(rng, d):
     return q * np.sign(np.diag(r))
 
 
-@pytest.mark.parametrize("d,n_ent,B", [(75, 3000, 700), (20, 400, 400)])
-def test_native_steps_match_oracle(d, n_ent, B):
+@pytest.mark.parametrize("d,n_ent,B,replace", [pytest.param(75, 3000, 700, False, id="75-3000-700"), pytest.param(20, 400, 400, False, id="20-400-400"),
+                                               pytest.param(20, 400, 400, True, id="20-400-400-replace")])
+def test_native_steps_match_oracle(d, n_ent, B, replace):
     from multike_amd.runner import SpaceMappingState, run_space_mapping_steps
     from multike_amd.tables import EmbeddingTable
     rng = np.random.default_rng(5)
@@ -29,7 +30,7 @@ def test_native_steps_match_oracle(d, n_ent, B):
     Ms = [_orth(rng, d) + 0.05 * rng.standard_normal((d, d)) for _ in range(3)]
     st = SpaceMappingState([torch.as_tensor(m, dtype=torch.float32) for m in Ms], "cuda")
     steps = 3
-    idx = np.stack([rng.choice(n_ent, size=B, replace=False) for _ in range(steps)]).astype(np.int32)
+    idx = np.stack([rng.choice(n_ent, size=B, replace=replace) for _ in range(steps)]).astype(np.int32)   # replace: rows hit several times
     ring = run_space_mapping_steps(st, ent, [name, rv, av], torch.as_tensor(idx.reshape(-1), device="cuda"),
                                    np.arange(steps + 1) * B, "shared_comb", 1, 0.01, 2.0)
     got = ring.sum(dim=(1, 2)).cpu().numpy()
