@@ -891,6 +891,47 @@ int mke_stable_rounds(const mke_stable_match_args* args, int64_t first_round, in
 int mke_stable_finish(const mke_stable_match_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * (9d) Sinkhorn re-scoring for the alignment evaluator, still without the n1 x n2 matrix (additions only; version unchanged).
+ *
+ * S is the n1 x n2 matrix of METRIC(i, j) as the sweep produces it (f32; inner or euclidean, as in (9b)).  Temperature
+ * tau > 0, iterations L >= 1.  Potentials are in similarity units: a^0 = 0 (n1) and b^0 = 0 (n2).  For l = 1..L, rows first
+ * and then columns:
+ *     a_i = tau log sum_j exp((s_ij - b_j) / tau)        (uses the b of the previous iteration)
+ *     b_j = tau log sum_i exp((s_ij - a_i) / tau)        (uses the a just computed)
+ * The re-scored similarity is s_ij - a_i - b_j: tau log of the Sinkhorn matrix after L iterations of row normalisation
+ * followed by column normalisation, starting from exp(S / tau).  The host hands it to mke_align_rank_ex / mke_stable_lists as
+ * csls_row = 2a, csls_col = 2b: their (2 s - csls_row[i]) - csls_col[j] is then 2 (s - a - b) in f32; the doubling is exact
+ * and the ranking is the same.
+ *
+ *   mke_align_lse: out[i] = tau log sum_{j < n_b} exp((METRIC(i, j) - sub_b[j]) / tau) for the n_a rows of a (sub_b NULL =
+ *     zeros).  a = E1, b = E2, sub_b = b-potential gives the row pass; a = E2, b = E1, sub_b = a-potential the column pass.
+ *     One sweep keeps an online log-sum-exp (running maximum and scaled sum, one v_exp_f32 of a non-positive argument per
+ *     similarity: no exp of a raw argument, so arguments of +-200 and beyond neither overflow nor vanish) per row and column
+ *     chunk; a second launch merges the chunks in chunk order in float64 and rounds to f32.  Every order is fixed: two calls
+ *     give the same bits.  Error against exact arithmetic, with M = max|S| + max|sub_b|: at most
+ *     tau (n_b + 8) 2^-23 + 6 * 2^-24 M.
+ *     tau <= 0 or not finite: MKE_E_RANGE.  n_b < 1: MKE_E_SHAPE.  Unknown metric / a kpad without an instantiation:
+ *     MKE_E_UNSUPPORTED.  n_a == 0: MKE_OK, nothing launched.  lda / ldb: multiples of 4 >= kpad; rows zero in [dim, kpad).
+ *   mke_align_lse_temp_bytes: scratch bytes for (n_a, n_b, kpad) (8 bytes per row and column chunk, at most 64 chunks), or a
+ *     negative MKE_E_* for arguments it rejects.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct mke_lse_args {
+  const float* a; int lda;          /* [n_a][lda] */
+  const float* b; int ldb;          /* [n_b][ldb] */
+  int kpad;
+  int64_t n_a, n_b;
+  int metric;
+  const float* sq_a;                /* [n_a], euclidean only (nullable otherwise) */
+  const float* sq_b;                /* [n_b], euclidean only */
+  const float* sub_b;               /* [n_b] subtracted from column j's similarities, or NULL: zeros */
+  float tau;
+  float* out;                       /* [n_a] */
+  void* temp; int64_t temp_bytes;   /* >= mke_align_lse_temp_bytes(n_a, n_b, kpad) */
+} mke_lse_args;
+int64_t mke_align_lse_temp_bytes(int64_t n_a, int64_t n_b, int kpad);
+int mke_align_lse(const mke_lse_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * (10) Small dense f32 GEMM on the matrix cores (v_mfma_f32_32x32x2_f32, exact f32) with arbitrary operand strides:
  *        C[M][N] (=|+=) A[M][K] . B[K][N],  A(i,k) = A[i*a_row_stride + k*a_col_stride], likewise B.
  *      splits > 1: split-K, partial products are added atomically (accumulate must be 1; C zeroed or holding the

@@ -14,7 +14,7 @@ from .base import evaluation as eva
 from .base.alignment import stable_alignment
 from .base.batch import neighbour_table
 from .MultiKE_model import MultiKE
-from .utils import task_divide
+from .utils import sinkhorn_option, task_divide
 
 
 def _view_embeddings(model, embed_choice, w):
@@ -78,7 +78,7 @@ def test(model, embed_choice='avg', w=(1, 1, 1)):
     embeds1, embeds2 = _eval_pair(model, embed_choice, w, "test1", lambda: k.test_entities1, "test2", lambda: k.test_entities2)
     print(embed_choice, 'test results:')
     _, mrr_12 = eva.valid(embeds1, embeds2, None, model.args.top_k, model.args.test_threads_num, normalize=True,
-                          csls_k=_csls_k(model))
+                          csls_k=_csls_k(model), sinkhorn=_sinkhorn(model))
     _stable(model, embeds1, embeds2)
     return mrr_12
 
@@ -89,12 +89,19 @@ def _csls_k(model):
     return int(getattr(model.args, "csls", 0) or 0)
 
 
+def _sinkhorn(model):
+    """Hyper-parameters `sinkhorn_iters` (0 = off) / `sinkhorn_tau`: Sinkhorn re-scoring of the test-time evaluations only,
+    as `csls` — validation and early stopping stay plain.  -> (iters, tau) or None."""
+    return sinkhorn_option(model.args)
+
+
 def _stable(model, embeds1, embeds2):
     """Hyper-parameter `stable_cut` (0 = off): after the greedy lines of a test, the one-to-one stable alignment of the same
-    rows (code/base/alignment.py:82-128) over every suitor's `stable_cut` best targets, CSLS re-scored as the test is."""
+    rows (code/base/alignment.py:82-128) over every suitor's `stable_cut` best targets, CSLS or Sinkhorn re-scored as the test is."""
     cut = int(getattr(model.args, "stable_cut", 0) or 0)
     if cut > 0:
-        stable_alignment(embeds1, embeds2, 'inner', True, _csls_k(model), model.args.test_threads_num, cut=cut)
+        stable_alignment(embeds1, embeds2, 'inner', True, _csls_k(model), model.args.test_threads_num, cut=cut,
+                         sinkhorn=_sinkhorn(model))
 
 
 def _unit_rows(x):
@@ -121,7 +128,7 @@ def wva(embeds1, embeds2, embeds3):
             _compute_weight(embeds3, embeds1, embeds2))
 
 
-def _wva_eval(model, ents1, ents2, label, keys=None, csls_k=0, stable=False):
+def _wva_eval(model, ents1, ents2, label, keys=None, csls_k=0, stable=False, sinkhorn=None):
     tabs = (model.name_embeds, model.rv_ent_embeds, model.av_ent_embeds)
     if keys is not None and getattr(model, "device", None) is not None and all(hasattr(t, "lookup") for t in tabs):
         ids1, ids2 = _device_ids(model, keys[0], lambda: ents1), _device_ids(model, keys[1], lambda: ents2)
@@ -137,7 +144,8 @@ def _wva_eval(model, ents1, ents2, label, keys=None, csls_k=0, stable=False):
     embeds1 = sum(float(w) * v for w, v in zip(wsum, v1))
     embeds2 = sum(float(w) * v for w, v in zip(wsum, v2))
     print(label)
-    _, mrr_12 = eva.valid(embeds1, embeds2, None, model.args.top_k, model.args.test_threads_num, normalize=True, csls_k=csls_k)
+    _, mrr_12 = eva.valid(embeds1, embeds2, None, model.args.top_k, model.args.test_threads_num, normalize=True, csls_k=csls_k,
+                          sinkhorn=sinkhorn)
     if stable:
         _stable(model, embeds1, embeds2)
     return mrr_12
@@ -152,7 +160,7 @@ def valid_WVA(model):
 def test_WVA(model):
     """code/MultiKE_Late.py:138-173."""
     return _wva_eval(model, model.kgs.test_entities1, model.kgs.test_entities2, 'wvag test results:', keys=("test1", "test2"),
-                     csls_k=_csls_k(model), stable=True)
+                     csls_k=_csls_k(model), stable=True, sinkhorn=_sinkhorn(model))
 
 
 class _ScheduledMultiKE(MultiKE):

@@ -26,7 +26,7 @@ from .attr_cnn import AttrCNN
 from .runner import RelationViewRunner
 from .sampling import KGSide, KnownTripleSet, RelationBatcher, int_triples
 from .tables import ADAGRAD_INIT_ACC, EmbeddingTable, StepEngine
-from .utils import generate_out_folder, save_embeddings, touch_library_kernels
+from .utils import generate_out_folder, save_embeddings, sinkhorn_option, touch_library_kernels
 
 _HIP_OPTS = ("Adagrad", "SGD")            # touched-rows rules: fused / native multi-step paths
 ATTR_GRAD_COPIES = 4
@@ -177,6 +177,7 @@ class MultiKE:
 
     def __check_args(self):
         assert self.args.alignment_module == 'swapping'  # for cross-KG inference (code/MultiKE_model.py:68-69)
+        sinkhorn_option(self.args)                       # `csls` together with `sinkhorn_iters`: refused here, not at the final test
 
     def __init__(self, data, args, attr_align_model):
         self.predicate_align_model = attr_align_model

@@ -40,6 +40,7 @@ SYMBOLS = (
     "mke_align_topk_mean_temp_bytes", "mke_align_topk_mean", "mke_align_rank_ex",
     "mke_stable_lists_temp_bytes", "mke_stable_lists", "mke_stable_rounds", "mke_stable_finish",
     "mke_tripleset_forget", "mke_tripleset_filter_bytes", "mke_epoch_positives",
+    "mke_align_lse_temp_bytes", "mke_align_lse",
 )
 ACT_NONE, ACT_TANH, ACT_SIGMOID = 0, 1, 2
 AE_MAX_LAYERS = 4
@@ -279,6 +280,7 @@ def lib():
         L.mke_oc_em_plan_temp_bytes.restype = C.c_int64
         L.mke_align_topk_mean_temp_bytes.restype = C.c_int64
         L.mke_stable_lists_temp_bytes.restype = C.c_int64
+        L.mke_align_lse_temp_bytes.restype = C.c_int64
         L.mke_tripleset_filter_bytes.restype = C.c_int64
         _lib = L
         # MKE_OPTIONS="name=value,name=value": mke_set_option calls applied at load (performance knobs for experiments)
@@ -1006,6 +1008,37 @@ def align_rank_ex(emb1, emb2, kpad, rank, ties, best, metric=METRIC_INNER, sq1=N
                      _dev(csls_row, torch.float32, "csls_row"), _dev(csls_col, torch.float32, "csls_col"),
                      _dev(rank, torch.int32, "rank"), _dev(ties, torch.int32, "ties"), _dev(best, torch.int64, "best"))
     _check(lib().mke_align_rank_ex(C.byref(args), _stream()), "mke_align_rank_ex")
+
+
+class LseArgs(C.Structure):
+    """mke_lse_args"""
+    _fields_ = [("a", C.c_void_p), ("lda", C.c_int), ("b", C.c_void_p), ("ldb", C.c_int), ("kpad", C.c_int),
+                ("n_a", C.c_int64), ("n_b", C.c_int64), ("metric", C.c_int), ("sq_a", C.c_void_p), ("sq_b", C.c_void_p),
+                ("sub_b", C.c_void_p), ("tau", C.c_float), ("out", C.c_void_p), ("temp", C.c_void_p), ("temp_bytes", C.c_int64)]
+
+
+def align_lse_temp_bytes(n_a: int, n_b: int, kpad: int) -> int:
+    """mke_align_lse_temp_bytes; raises on the arguments mke_align_lse would reject."""
+    r = int(lib().mke_align_lse_temp_bytes(C.c_int64(n_a), C.c_int64(n_b), C.c_int(kpad)))
+    _check(r if r < 0 else 0, "mke_align_lse_temp_bytes")
+    return r
+
+
+def align_lse(a, b, kpad, tau, metric=METRIC_INNER, sq_a=None, sq_b=None, sub_b=None, out=None):
+    """mke_align_lse over row-major padded a [n_a, lda] / b [n_b, ldb] -> float32 [n_a]: tau log sum_j exp((sim(i, j) -
+    sub_b[j]) / tau), sub_b None = zeros.  `out` (float32, at least n_a long) is written in its first n_a entries."""
+    n_a, n_b = a.shape[0], b.shape[0]
+    need = align_lse_temp_bytes(n_a, n_b, kpad)
+    if out is None:
+        out = torch.empty(n_a, dtype=torch.float32, device=a.device)
+    elif out.numel() < n_a:
+        raise MultiKEHipError(f"align_lse: out holds {out.numel()} floats, {n_a} rows")
+    temp = torch.empty(max(need, 8) // 4, dtype=torch.float32, device=a.device)
+    args = LseArgs(_dev(a, torch.float32, "a"), a.shape[1], _dev(b, torch.float32, "b"), b.shape[1], kpad, n_a, n_b, metric,
+                   _dev(sq_a, torch.float32, "sq_a"), _dev(sq_b, torch.float32, "sq_b"), _dev(sub_b, torch.float32, "sub_b"),
+                   float(tau), _dev(out, torch.float32, "out"), _dev(temp, torch.float32, "temp"), temp.numel() * 4)
+    _check(lib().mke_align_lse(C.byref(args), _stream()), "mke_align_lse")
+    return out
 
 
 class StableListsArgs(C.Structure):

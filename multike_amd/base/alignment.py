@@ -1,7 +1,8 @@
 """base/alignment.py surface of the reference (code/base/alignment.py:8-79): `greedy_alignment` — Hits@k / MR / MRR of
 the gold counterpart under the (normalised) inner-product similarity — on the f32 matrix cores via `mke_align_rank`; the
 euclidean metric and CSLS re-scoring via `mke_align_topk_mean` + `mke_align_rank_ex`; `stable_alignment` (:82-128) — the
-one-to-one Gale-Shapley matching — via `mke_stable_lists` + `mke_stable_rounds` + `mke_stable_finish`.
+one-to-one Gale-Shapley matching — via `mke_stable_lists` + `mke_stable_rounds` + `mke_stable_finish`; Sinkhorn re-scoring
+(`sinkhorn=(iters, tau)`, the soft one-to-one decoder) via `mke_align_lse`, whose potentials ride the CSLS plumbing.
 The n1 x n2 similarity matrix is never materialised (the reference holds 60K x 60K fp32 = 14 GB and argsorts its rows
 in `nums_threads` worker processes)."""
 from __future__ import annotations
@@ -66,13 +67,45 @@ def csls_means(a, b, kpad, metric_code, sq_a, sq_b, csls_k):
     return r_t, r_s
 
 
-def alignment_counts(embed1, embed2, normalize=True, device="cuda", metric="inner", csls_k=0, csls=None):
+def _check_sinkhorn(sinkhorn, csls_k, csls=None):
+    """(iters, tau) of a `sinkhorn=` argument, or None: Sinkhorn and CSLS are two re-scorings of one similarity, not a chain."""
+    if sinkhorn is None:
+        return None
+    iters, tau = sinkhorn
+    if (csls_k and csls_k > 0) or csls is not None:
+        raise _lib.MultiKEHipError("sinkhorn and csls_k are both set: choose one re-scoring")
+    if int(iters) != iters or int(iters) < 1 or not (float(tau) > 0.0) or not np.isfinite(float(tau)):
+        raise _lib.MultiKEHipError(f"sinkhorn=(iters, tau) needs iters >= 1 and a finite tau > 0, got ({iters}, {tau})")
+    return int(iters), float(tau)
+
+
+def sinkhorn_potentials(a, b, kpad, metric_code, sq_a, sq_b, iters, tau):
+    """(a-potential [n1], b-potential [n2]) after `iters` Sinkhorn iterations at temperature tau from padded operands, in
+    similarity units: a_i = tau log sum_j exp((s_ij - b_j) / tau), then b_j = tau log sum_i exp((s_ij - a_i) / tau), b starting
+    at zero — 2 * iters calls of mke_align_lse, no matrix."""
+    pa, pb = None, None
+    for _ in range(int(iters)):
+        pa = _lib.align_lse(a, b, kpad, tau, metric_code, sq_a, sq_b, pb)
+        pb = _lib.align_lse(b, a, kpad, tau, metric_code, sq_b, sq_a, pa)
+    return pa, pb
+
+
+def sinkhorn_terms(a, b, kpad, metric_code, sq_a, sq_b, iters, tau):
+    """(r_t, r_s) = (2 a-potential, 2 b-potential): as `csls_row` / `csls_col` of the rank and list kernels they turn
+    (2 s - r_t[i]) - r_s[j] into 2 (s - a_i - b_j), twice tau log of the Sinkhorn matrix (the doubling is exact in f32)."""
+    pa, pb = sinkhorn_potentials(a, b, kpad, metric_code, sq_a, sq_b, iters, tau)
+    return 2.0 * pa, 2.0 * pb
+
+
+def alignment_counts(embed1, embed2, normalize=True, device="cuda", metric="inner", csls_k=0, csls=None, *, sinkhorn=None):
     """(greater [n1] int64, ties [n1] int64, best [n1] int64): greater_i = #{j: sim_ij > sim_ii}, ties_i = #{j: sim_ij ==
     sim_ii} (the gold column included, so >= 1), best_i = argmax_j sim_ij.  `metric` 'inner' / 'cosine' / 'euclidean';
     csls_k > 0 re-scores every similarity by CSLS (code/base/similarity.py:56-75).  `csls` = (r_T, r_S) given by the caller
-    (the sharded driver, which computes them over all ranks) in place of computing them here."""
+    (the sharded driver, which computes them over all ranks) in place of computing them here.  `sinkhorn` = (iters, tau)
+    re-scores by Sinkhorn normalisation instead (not together with CSLS)."""
     _check_metric(metric, normalize)
-    if (not csls_k or csls_k <= 0) and csls is None and (metric == "inner" or (metric == "cosine" and normalize)):
+    sinkhorn = _check_sinkhorn(sinkhorn, csls_k, csls)
+    if (not csls_k or csls_k <= 0) and csls is None and sinkhorn is None and (metric == "inner" or (metric == "cosine" and normalize)):
         return _counts_inner(embed1, embed2, normalize, device)
     a, b, kpad, code, sq1, sq2 = prepare_operands(embed1, embed2, metric, normalize, device)
     n1, n2 = a.shape[0], b.shape[0]
@@ -80,6 +113,8 @@ def alignment_counts(embed1, embed2, normalize=True, device="cuda", metric="inne
         raise _lib.MultiKEHipError("greedy_alignment: gold column = row index needs len(embed2) >= len(embed1)")
     if csls is None and csls_k and csls_k > 0:
         csls = csls_means(a, b, kpad, code, sq1, sq2, int(csls_k))
+    if sinkhorn is not None:
+        csls = sinkhorn_terms(a, b, kpad, code, sq1, sq2, *sinkhorn)
     rank = torch.zeros(n1, dtype=torch.int32, device=device)
     ties = torch.zeros(n1, dtype=torch.int32, device=device)
     best = torch.zeros(n1, dtype=torch.int64, device=device)
@@ -106,11 +141,11 @@ def _counts_inner(embed1, embed2, normalize, device):
     return rank.long(), ties.long().clamp_min(1), col
 
 
-def alignment_ranks(embed1, embed2, normalize=True, device="cuda", metric="inner", csls_k=0):
+def alignment_ranks(embed1, embed2, normalize=True, device="cuda", metric="inner", csls_k=0, *, sinkhorn=None):
     """(rank [n1] float64, best [n1] int64): rank_i = greater_i + (ties_i - 1) / 2 — the gold's EXPECTED 0-based position when
     the columns that tie with it are ordered at random.  The reference's argsort / argpartition leaves the gold at an arbitrary
     position among them (code/base/alignment.py:152-160).  Without ties this is the reference's rank exactly."""
-    greater, ties, col = alignment_counts(embed1, embed2, normalize, device, metric=metric, csls_k=csls_k)
+    greater, ties, col = alignment_counts(embed1, embed2, normalize, device, metric=metric, csls_k=csls_k, sinkhorn=sinkhorn)
     return greater.double() + (ties.double() - 1.0) * 0.5, col
 
 
@@ -150,22 +185,24 @@ def _harmonic(n):
     return torch.where(small, table[torch.where(small, n, torch.zeros_like(n)).long()], big)
 
 
-def greedy_alignment(embed1, embed2, top_k, nums_threads, metric, normalize, csls_k, accurate, want_pairs=True):
+def greedy_alignment(embed1, embed2, top_k, nums_threads, metric, normalize, csls_k, accurate, want_pairs=True, *, sinkhorn=None):
     """code/base/alignment.py:8-79.  Returns (alignment_rest, hits1, mr, mrr).  `nums_threads` is accepted and ignored
     (one kernel launch; five with CSLS).  Metrics: 'inner', 'cosine' (== inner product of normalised rows), 'euclidean';
     csls_k > 0 re-scores by CSLS (code/base/similarity.py:56-75); the other cdist metrics raise.  want_pairs = False (base.evaluation.valid, which drops them): alignment_rest is None — the set of (row, best
-    column) tuples is a Python object per row."""
+    column) tuples is a Python object per row.  sinkhorn = (iters, tau) re-scores by Sinkhorn normalisation (2 * iters sweeps)
+    instead of CSLS; both together raise."""
     _check_metric(metric, normalize)
     csls_k = int(csls_k or 0)
+    sinkhorn = _check_sinkhorn(sinkhorn, csls_k)
     assert 1 in top_k
     t = time.time()
-    greater, ties, best = alignment_counts(embed1, embed2, normalize, metric=metric, csls_k=csls_k)
+    greater, ties, best = alignment_counts(embed1, embed2, normalize, metric=metric, csls_k=csls_k, sinkhorn=sinkhorn)
     num = greater.numel()
     hits, mr, mrr = tie_aware_metrics(greater, ties, top_k)
     hits = np.round(np.array(hits) / num * 100, 3)
     alignment_rest = set(zip(range(num), best.cpu().tolist())) if want_pairs else None
     cost = time.time() - t
-    print_results(top_k, hits, mr, mrr, cost, accurate, csls_k)
+    print_results(top_k, hits, mr, mrr, cost, accurate, csls_k, sinkhorn)
     return alignment_rest, hits[0], mr, mrr
 
 
@@ -215,15 +252,19 @@ def stable_matching(val, col, n2, batch=STABLE_ROUND_BATCH):
     return match, matched, gold, used
 
 
-def stable_alignment(embed1, embed2, metric, normalize, csls_k, nums_threads, cut=100, sim_mat=None):
+def stable_alignment(embed1, embed2, metric, normalize, csls_k, nums_threads, cut=100, sim_mat=None, *, sinkhorn=None):
     """code/base/alignment.py:82-128.  Returns (match, precision): match int64 [n1] on the host, match[i] = the row of embed2
     matched to row i of embed1 or -1 (the reference returns None); precision = matched golds / matched suitors * 100 (:123-128).
     The result is the suitor-optimal stable matching with every suitor's list truncated to its `cut` best columns, run to its
     fixed point — the reference's result whenever its galeshapley matches every suitor within `cut` rounds.  Ties: a suitor
     prefers the lower column, a reviewer the lower row.  `nums_threads` is accepted and ignored.  `sim_mat`: a float32
-    [n1, n2] similarity matrix on the device given by the caller, used in place of sim(embed1, embed2, ...)."""
+    [n1, n2] similarity matrix on the device given by the caller, used in place of sim(embed1, embed2, ...).  `sinkhorn` =
+    (iters, tau): the lists are taken under the Sinkhorn re-scored similarity (not with csls_k, not with sim_mat)."""
     _check_metric(metric, normalize)
     csls_k = int(csls_k or 0)
+    sinkhorn = _check_sinkhorn(sinkhorn, csls_k)
+    if sinkhorn is not None and sim_mat is not None:
+        raise _lib.MultiKEHipError("stable_alignment: sinkhorn re-scores the embeddings' similarities; a given sim_mat is used as it is")
     t = time.time()
     if sim_mat is not None:
         if not isinstance(sim_mat, torch.Tensor):
@@ -235,6 +276,8 @@ def stable_alignment(embed1, embed2, metric, normalize, csls_k, nums_threads, cu
         a, b, kpad, code, sq1, sq2 = prepare_operands(embed1, embed2, metric, normalize, "cuda")
         n1, n2 = a.shape[0], b.shape[0]
         csls = csls_means(a, b, kpad, code, sq1, sq2, csls_k) if csls_k > 0 else None
+        if sinkhorn is not None:
+            csls = sinkhorn_terms(a, b, kpad, code, sq1, sq2, *sinkhorn)
         val, col, _ = candidate_lists(a, b, kpad, max(1, min(int(cut), n2)), code, sq1, sq2, csls)
     torch.cuda.synchronize()
     print("generating candidate lists costs time {:.3f} s ".format(time.time() - t))
@@ -247,8 +290,16 @@ def stable_alignment(embed1, embed2, metric, normalize, csls_k, nums_threads, cu
     return match, precision
 
 
-def print_results(top_k, hits, mr, mrr, cost, accurate, csls_k=0):
-    """The reference's result lines (code/base/alignment.py:64-73)."""
+def print_results(top_k, hits, mr, mrr, cost, accurate, csls_k=0, sinkhorn=None):
+    """The reference's result lines (code/base/alignment.py:64-73); with sinkhorn = (iters, tau) lines of the same shape."""
+    if sinkhorn is not None:
+        iters, tau = sinkhorn
+        if accurate:
+            print("accurate results with sinkhorn: iters={}, tau={}, hits@{} = {}%, mr = {:.3f}, mrr = {:.6f}, time = {:.3f} s ".
+                  format(iters, tau, top_k, hits, mr, mrr, cost))
+        else:
+            print("quick results with sinkhorn: iters={}, tau={}, hits@{} = {}%, time = {:.3f} s ".format(iters, tau, top_k, hits, cost))
+        return
     if accurate:
         if csls_k > 0:
             print("accurate results with csls: csls={}, hits@{} = {}%, mr = {:.3f}, mrr = {:.6f}, time = {:.3f} s ".

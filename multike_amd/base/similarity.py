@@ -41,9 +41,12 @@ def _device_products(a, b):
     return _lib.sim_sample(ap, kpad, 0, a.shape[0], bp)
 
 
-def sim(embed1, embed2, metric='inner', normalize=False, csls_k=0):
-    """code/base/similarity.py:9-53: the n1 x n2 similarity matrix (float32) under `metric`, CSLS re-scored when csls_k > 0."""
+def sim(embed1, embed2, metric='inner', normalize=False, csls_k=0, sinkhorn=None):
+    """code/base/similarity.py:9-53: the n1 x n2 similarity matrix (float32) under `metric`, CSLS re-scored when csls_k > 0,
+    Sinkhorn re-scored with sinkhorn = (iters, tau) (one or the other)."""
     _check(metric)
+    if sinkhorn is not None and csls_k > 0:
+        raise _lib.MultiKEHipError("sim: sinkhorn and csls_k are both set: choose one re-scoring")
     if isinstance(embed1, torch.Tensor) or isinstance(embed2, torch.Tensor):
         dev = embed1.device if isinstance(embed1, torch.Tensor) else embed2.device
         a = torch.as_tensor(embed1, device=dev).float()
@@ -71,7 +74,43 @@ def sim(embed1, embed2, metric='inner', normalize=False, csls_k=0):
             mat = (a64 @ b64.T).astype(np.float32)
     if csls_k > 0:
         mat = csls_sim(mat, csls_k)
+    if sinkhorn is not None:
+        mat = sinkhorn_sim(mat, *sinkhorn)
     return mat
+
+
+def sinkhorn_potentials(sim_mat, iters, tau):
+    """(a [n1], b [n2]) in float64: a = b = 0, then `iters` times a_i = tau log sum_j exp((s_ij - b_j) / tau) followed by
+    b_j = tau log sum_i exp((s_ij - a_i) / tau) (the maximum taken out of every sum)."""
+    if int(iters) != iters or iters < 1 or not tau > 0 or not np.isfinite(tau):
+        raise _lib.MultiKEHipError(f"sinkhorn_sim: need iters >= 1 and a finite tau > 0, got ({iters}, {tau})")
+    if isinstance(sim_mat, torch.Tensor):
+        s = sim_mat.double()
+        a, b = torch.zeros(s.shape[0], dtype=torch.float64, device=s.device), torch.zeros(s.shape[1], dtype=torch.float64, device=s.device)
+        for _ in range(int(iters)):
+            a = tau * torch.logsumexp((s - b[None, :]) / tau, dim=1)
+            b = tau * torch.logsumexp((s - a[:, None]) / tau, dim=0)
+        return a, b
+    s = np.asarray(sim_mat, dtype=np.float64)
+    a, b = np.zeros(s.shape[0]), np.zeros(s.shape[1])
+
+    def lse(x, axis):
+        m = x.max(axis=axis, keepdims=True)
+        return np.squeeze(m, axis) + np.log(np.exp(x - m).sum(axis=axis))
+
+    for _ in range(int(iters)):
+        a = tau * lse((s - b[None, :]) / tau, 1)
+        b = tau * lse((s - a[:, None]) / tau, 0)
+    return a, b
+
+
+def sinkhorn_sim(sim_mat, iters, tau):
+    """s_ij - a_i - b_j (float32) with the potentials of `iters` Sinkhorn iterations at temperature tau: tau log of the matrix
+    exp(S / tau) after `iters` rounds of row normalisation followed by column normalisation.  Computed in float64."""
+    a, b = sinkhorn_potentials(sim_mat, iters, tau)
+    if isinstance(sim_mat, torch.Tensor):
+        return ((sim_mat.double() - a[:, None]) - b[None, :]).float()
+    return ((np.asarray(sim_mat, dtype=np.float64) - a[:, None]) - b[None, :]).astype(np.float32)
 
 
 def csls_sim(sim_mat, k):

@@ -46,11 +46,25 @@ def default_args(**over):
         csls=0,
         # one-to-one (Gale-Shapley) alignment of the final tests over every suitor's `stable_cut` best targets (0 = off)
         stable_cut=0,
+        # Sinkhorn re-scoring of the final tests: `sinkhorn_iters` iterations (0 = off) at temperature `sinkhorn_tau`; not with `csls`
+        sinkhorn_iters=0, sinkhorn_tau=0.05,
         # view combination and predicate soft alignment
         orthogonal_weight=2, cv_name_weight=1, cv_weight=1, start_predicate_soft_alignment=10, predicate_soft_sim=0.85,
         predicate_init_sim=0.90)
     d.update(over)
     return ARGs(d)
+
+
+def sinkhorn_option(args):
+    """(iters, tau) of the hyper-parameters `sinkhorn_iters` / `sinkhorn_tau`, or None when off (0, or the keys absent).
+    `csls` and `sinkhorn_iters` both set is an error: they are two re-scorings of the same similarity."""
+    iters = int(getattr(args, "sinkhorn_iters", 0) or 0)
+    if iters <= 0:
+        return None
+    if int(getattr(args, "csls", 0) or 0) > 0:
+        from ._lib import MultiKEHipError
+        raise MultiKEHipError("csls and sinkhorn_iters are both set: choose one re-scoring of the final tests")
+    return iters, float(getattr(args, "sinkhorn_tau", 0.05))
 
 
 def task_divide(idx, n):
