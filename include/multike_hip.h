@@ -747,7 +747,9 @@ int mke_dense_update(float* param, float* acc /*nullable for SGD*/, float* grad,
  *   rank[i] += #{j < n2 : sim[i][j] > sim[i][i]}  (rank zeroed by the caller); with `ties` also the columns that tie with
  *   the gold (the reference's argsort puts the gold at an arbitrary place among them: the host reports the mid-rank);
  *   best[i]  = max over j of (ordered(sim[i][j]) << 32 | 0xFFFFFFFF - j)  (best zeroed by the caller; arg-max column =
- *              0xFFFFFFFF - low word, lowest column on ties).
+ *              0xFFFFFFFF - low word, lowest column on ties).  A row none of whose similarities exceeds -3.0e38f (all NaN,
+ *              all -inf) publishes (-3.0e38f, column 0).
+ *   One kernel (k_align_rank, mke_eval.hip) serves this entry point and mke_align_rank_ex of (9b).
  * ------------------------------------------------------------------------------------------------ */
 int mke_align_rank(const float* emb1, int ld1, const float* emb2, int ld2, int kpad, int64_t n1, int64_t n2,
                    int32_t* rank, int32_t* ties /* nullable: ties[i] += #{j : sim[i][j] == sim[i][i]} (j = i included) */,
@@ -780,7 +782,9 @@ int mke_align_rank(const float* emb1, int ld1, const float* emb2, int ld2, int k
  *     neither), s = (2 s - csls_row[i]) - csls_col[j] in f32 (code/base/similarity.py:73-74).  rank[i] += #{j : s_ij > s_ii},
  *     ties[i] += #{j : s_ij == s_ii} (j = i included), best[i] = max of (ordered(s_ij) << 32 | 0xFFFFFFFF - j) as
  *     mke_align_rank's; rank, ties, best zeroed by the caller.  The gold s_ii comes from the same diagonal MFMA product
- *     through the same epilogue.  ties is required here.  Unknown metric: MKE_E_UNSUPPORTED.
+ *     through the same epilogue.  ties is required here.  Unknown metric: MKE_E_UNSUPPORTED.  The same kernel as
+ *     mke_align_rank's; the one difference: a row whose s are all -inf publishes (-inf, its lowest column), a row whose s are
+ *     all NaN leaves best[i] as the caller zeroed it.
  * ------------------------------------------------------------------------------------------------ */
 #define MKE_METRIC_INNER 0
 #define MKE_METRIC_EUCLIDEAN 1

@@ -15,21 +15,34 @@ import torch
 from .. import _lib
 
 
-def _prep(x, device, normalize):
-    t = torch.as_tensor(np.asarray(x), dtype=torch.float32).to(device) if not isinstance(x, torch.Tensor) else x.to(device).float()
-    if normalize:  # sklearn.preprocessing.normalize: zero rows stay zero (code/base/similarity.py:30-32)
-        n = torch.linalg.norm(t, dim=1, keepdim=True)
-        t = t / torch.where(n == 0, torch.ones_like(n), n)
-    return t
-
-
 SUPPORTED_METRICS = ("inner", "cosine", "euclidean")
 
 
-def _check_metric(metric, normalize):
+def _unit(x):
+    """sklearn.preprocessing.normalize of a tensor or an array: zero rows stay zero (code/base/similarity.py:30-32)."""
+    if isinstance(x, torch.Tensor):
+        n = torch.linalg.norm(x, dim=1, keepdim=True)
+        return x / torch.where(n == 0, torch.ones_like(n), n)
+    n = np.linalg.norm(x, axis=1, keepdims=True)
+    return x / np.where(n == 0, 1, n).astype(x.dtype)
+
+
+def _prep(x, device, normalize):
+    t = torch.as_tensor(np.asarray(x), dtype=torch.float32).to(device) if not isinstance(x, torch.Tensor) else x.to(device).float()
+    return _unit(t) if normalize else t
+
+
+def _check_metric(metric, who="greedy_alignment", why="; the other cdist metrics are not GEMM-shaped"):
     if metric not in SUPPORTED_METRICS:
-        raise _lib.MultiKEHipError(f"greedy_alignment: metric {metric!r} is not built (supported: 'inner', 'cosine', 'euclidean'; "
-                                   "the other cdist metrics are not GEMM-shaped)")
+        raise _lib.MultiKEHipError(f"{who}: metric {metric!r} is not built (supported: 'inner', 'cosine', 'euclidean'{why})")
+
+
+def _kpad_for(d, too_wide=None):
+    """The narrowest supported row width >= d (MKE_MAX_STRIDE is the widest: there is no second backend)."""
+    if d > _lib.SIM_SELECT_KPADS[-1]:
+        raise _lib.MultiKEHipError(too_wide or f"greedy_alignment: rows of {d} floats exceed the widest k_align_rank instantiation "
+                                   f"({_lib.SIM_SELECT_KPADS[-1]} = MKE_MAX_STRIDE)")
+    return min(x for x in _lib.SIM_SELECT_KPADS if x >= d)
 
 
 def _padded(x, kpad, device):
@@ -39,18 +52,11 @@ def _padded(x, kpad, device):
     return p
 
 
-def _kpad_for(d):
-    if d > _lib.SIM_SELECT_KPADS[-1]:      # wider than the widest table the package supports (MKE_MAX_STRIDE): no second backend
-        raise _lib.MultiKEHipError(f"greedy_alignment: rows of {d} floats exceed the widest k_align_rank instantiation "
-                                   f"({_lib.SIM_SELECT_KPADS[-1]} = MKE_MAX_STRIDE)")
-    return min(x for x in _lib.SIM_SELECT_KPADS if x >= d)
-
-
 def prepare_operands(embed1, embed2, metric="inner", normalize=True, device="cuda"):
     """(a, b, kpad, metric code, sq_a, sq_b): the zero-padded f32 operands of the native evaluator.  'cosine' is the inner
     product of unit rows (code/base/similarity.py:34-44: normalised or not, cosine similarity is that); 'euclidean' hands the
     squared row norms over (1 - euclidean_distances, :38-41)."""
-    _check_metric(metric, normalize)
+    _check_metric(metric)
     a, b = _prep(embed1, device, normalize or metric == "cosine"), _prep(embed2, device, normalize or metric == "cosine")
     kpad = _kpad_for(a.shape[1])
     ap, bp = _padded(a, kpad, device), _padded(b, kpad, device)
@@ -67,16 +73,19 @@ def csls_means(a, b, kpad, metric_code, sq_a, sq_b, csls_k):
     return r_t, r_s
 
 
-def _check_sinkhorn(sinkhorn, csls_k, csls=None):
-    """(iters, tau) of a `sinkhorn=` argument, or None: Sinkhorn and CSLS are two re-scorings of one similarity, not a chain."""
+def _check_rescoring(csls_k, sinkhorn, csls=None):
+    """(csls_k as an int, 0 = none; (iters, tau) of a `sinkhorn=` argument, or None).  Sinkhorn and CSLS are two re-scorings of
+    one similarity, not a chain.  csls_k is truncated first, as greedy_alignment and stable_alignment always did: None, a
+    negative or a fraction below 1 is no CSLS."""
+    csls_k = max(int(csls_k or 0), 0)
     if sinkhorn is None:
-        return None
+        return csls_k, None
     iters, tau = sinkhorn
-    if (csls_k and csls_k > 0) or csls is not None:
+    if csls_k > 0 or csls is not None:
         raise _lib.MultiKEHipError("sinkhorn and csls_k are both set: choose one re-scoring")
     if int(iters) != iters or int(iters) < 1 or not (float(tau) > 0.0) or not np.isfinite(float(tau)):
         raise _lib.MultiKEHipError(f"sinkhorn=(iters, tau) needs iters >= 1 and a finite tau > 0, got ({iters}, {tau})")
-    return int(iters), float(tau)
+    return csls_k, (int(iters), float(tau))
 
 
 def sinkhorn_potentials(a, b, kpad, metric_code, sq_a, sq_b, iters, tau):
@@ -97,46 +106,37 @@ def sinkhorn_terms(a, b, kpad, metric_code, sq_a, sq_b, iters, tau):
     return 2.0 * pa, 2.0 * pb
 
 
+def _rescoring_terms(operands, csls_k, sinkhorn):
+    """(row_term [n1], col_term [n2]) of the re-scoring (2 s - row_term[i]) - col_term[j] from prepare_operands' tuple and the
+    checked (csls_k, sinkhorn): the CSLS means, or twice the Sinkhorn potentials; None when there is no re-scoring."""
+    if sinkhorn is not None:
+        return sinkhorn_terms(*operands, *sinkhorn)
+    return csls_means(*operands, csls_k) if csls_k > 0 else None
+
+
 def alignment_counts(embed1, embed2, normalize=True, device="cuda", metric="inner", csls_k=0, csls=None, *, sinkhorn=None):
     """(greater [n1] int64, ties [n1] int64, best [n1] int64): greater_i = #{j: sim_ij > sim_ii}, ties_i = #{j: sim_ij ==
     sim_ii} (the gold column included, so >= 1), best_i = argmax_j sim_ij.  `metric` 'inner' / 'cosine' / 'euclidean';
     csls_k > 0 re-scores every similarity by CSLS (code/base/similarity.py:56-75).  `csls` = (r_T, r_S) given by the caller
     (the sharded driver, which computes them over all ranks) in place of computing them here.  `sinkhorn` = (iters, tau)
-    re-scores by Sinkhorn normalisation instead (not together with CSLS)."""
-    _check_metric(metric, normalize)
-    sinkhorn = _check_sinkhorn(sinkhorn, csls_k, csls)
-    if (not csls_k or csls_k <= 0) and csls is None and sinkhorn is None and (metric == "inner" or (metric == "cosine" and normalize)):
-        return _counts_inner(embed1, embed2, normalize, device)
-    a, b, kpad, code, sq1, sq2 = prepare_operands(embed1, embed2, metric, normalize, device)
+    re-scores by Sinkhorn normalisation instead (not together with CSLS).  The plain inner product of the rows as they are
+    prepared goes through mke_align_rank, everything else through mke_align_rank_ex: one kernel, two rules for a row whose
+    similarities are all NaN or -inf (mke_eval.hip)."""
+    _check_metric(metric)
+    csls_k, sinkhorn = _check_rescoring(csls_k, sinkhorn, csls)
+    if len(embed2) < len(embed1):                          # before anything is copied, padded or refused for its width
+        raise _lib.MultiKEHipError("greedy_alignment: gold column = row index needs len(embed2) >= len(embed1)")
+    operands = prepare_operands(embed1, embed2, metric, normalize, device)
+    a, b, kpad, code, sq1, sq2 = operands
     n1, n2 = a.shape[0], b.shape[0]
-    if n2 < n1:
-        raise _lib.MultiKEHipError("greedy_alignment: gold column = row index needs len(embed2) >= len(embed1)")
-    if csls is None and csls_k and csls_k > 0:
-        csls = csls_means(a, b, kpad, code, sq1, sq2, int(csls_k))
-    if sinkhorn is not None:
-        csls = sinkhorn_terms(a, b, kpad, code, sq1, sq2, *sinkhorn)
+    terms = csls if csls is not None else _rescoring_terms(operands, csls_k, sinkhorn)
     rank = torch.zeros(n1, dtype=torch.int32, device=device)
     ties = torch.zeros(n1, dtype=torch.int32, device=device)
     best = torch.zeros(n1, dtype=torch.int64, device=device)
-    r_t, r_s = csls if csls is not None else (None, None)
-    _lib.align_rank_ex(a, b, kpad, rank, ties, best, code, sq1, sq2, r_t, r_s)
-    col = 0xFFFFFFFF - (best & 0xFFFFFFFF)
-    return rank.long(), ties.long().clamp_min(1), col
-
-
-def _counts_inner(embed1, embed2, normalize, device):
-    a, b = _prep(embed1, device, normalize), _prep(embed2, device, normalize)
-    n1, d = a.shape
-    n2 = b.shape[0]
-    if n2 < n1:
-        raise _lib.MultiKEHipError("greedy_alignment: gold column = row index needs len(embed2) >= len(embed1)")
-    kpad = _kpad_for(d)
-    ap = _padded(a, kpad, device)
-    bp = _padded(b, kpad, device)
-    rank = torch.zeros(n1, dtype=torch.int32, device=device)
-    ties = torch.zeros(n1, dtype=torch.int32, device=device)
-    best = torch.zeros(n1, dtype=torch.int64, device=device)
-    _lib.align_rank(ap, bp, kpad, n1, n2, rank, best, ties)
+    if terms is None and (metric == "inner" or (metric == "cosine" and normalize)):
+        _lib.align_rank(a, b, kpad, n1, n2, rank, best, ties)
+    else:
+        _lib.align_rank_ex(a, b, kpad, rank, ties, best, code, sq1, sq2, *(terms or (None, None)))
     col = 0xFFFFFFFF - (best & 0xFFFFFFFF)
     return rank.long(), ties.long().clamp_min(1), col
 
@@ -191,9 +191,8 @@ def greedy_alignment(embed1, embed2, top_k, nums_threads, metric, normalize, csl
     csls_k > 0 re-scores by CSLS (code/base/similarity.py:56-75); the other cdist metrics raise.  want_pairs = False (base.evaluation.valid, which drops them): alignment_rest is None — the set of (row, best
     column) tuples is a Python object per row.  sinkhorn = (iters, tau) re-scores by Sinkhorn normalisation (2 * iters sweeps)
     instead of CSLS; both together raise."""
-    _check_metric(metric, normalize)
-    csls_k = int(csls_k or 0)
-    sinkhorn = _check_sinkhorn(sinkhorn, csls_k)
+    _check_metric(metric)
+    csls_k, sinkhorn = _check_rescoring(csls_k, sinkhorn)
     assert 1 in top_k
     t = time.time()
     greater, ties, best = alignment_counts(embed1, embed2, normalize, metric=metric, csls_k=csls_k, sinkhorn=sinkhorn)
@@ -260,9 +259,8 @@ def stable_alignment(embed1, embed2, metric, normalize, csls_k, nums_threads, cu
     prefers the lower column, a reviewer the lower row.  `nums_threads` is accepted and ignored.  `sim_mat`: a float32
     [n1, n2] similarity matrix on the device given by the caller, used in place of sim(embed1, embed2, ...).  `sinkhorn` =
     (iters, tau): the lists are taken under the Sinkhorn re-scored similarity (not with csls_k, not with sim_mat)."""
-    _check_metric(metric, normalize)
-    csls_k = int(csls_k or 0)
-    sinkhorn = _check_sinkhorn(sinkhorn, csls_k)
+    _check_metric(metric)
+    csls_k, sinkhorn = _check_rescoring(csls_k, sinkhorn)
     if sinkhorn is not None and sim_mat is not None:
         raise _lib.MultiKEHipError("stable_alignment: sinkhorn re-scores the embeddings' similarities; a given sim_mat is used as it is")
     t = time.time()
@@ -273,12 +271,10 @@ def stable_alignment(embed1, embed2, metric, normalize, csls_k, nums_threads, cu
         n1, n2 = sim_mat.shape
         val, col, _ = candidate_lists(None, None, 0, max(1, min(int(cut), n2)), sim_mat=sim_mat)
     else:
-        a, b, kpad, code, sq1, sq2 = prepare_operands(embed1, embed2, metric, normalize, "cuda")
+        operands = prepare_operands(embed1, embed2, metric, normalize, "cuda")
+        a, b, kpad, code, sq1, sq2 = operands
         n1, n2 = a.shape[0], b.shape[0]
-        csls = csls_means(a, b, kpad, code, sq1, sq2, csls_k) if csls_k > 0 else None
-        if sinkhorn is not None:
-            csls = sinkhorn_terms(a, b, kpad, code, sq1, sq2, *sinkhorn)
-        val, col, _ = candidate_lists(a, b, kpad, max(1, min(int(cut), n2)), code, sq1, sq2, csls)
+        val, col, _ = candidate_lists(a, b, kpad, max(1, min(int(cut), n2)), code, sq1, sq2, _rescoring_terms(operands, csls_k, sinkhorn))
     torch.cuda.synchronize()
     print("generating candidate lists costs time {:.3f} s ".format(time.time() - t))
     t = time.time()
@@ -293,21 +289,8 @@ def stable_alignment(embed1, embed2, metric, normalize, csls_k, nums_threads, cu
 def print_results(top_k, hits, mr, mrr, cost, accurate, csls_k=0, sinkhorn=None):
     """The reference's result lines (code/base/alignment.py:64-73); with sinkhorn = (iters, tau) lines of the same shape."""
     if sinkhorn is not None:
-        iters, tau = sinkhorn
-        if accurate:
-            print("accurate results with sinkhorn: iters={}, tau={}, hits@{} = {}%, mr = {:.3f}, mrr = {:.6f}, time = {:.3f} s ".
-                  format(iters, tau, top_k, hits, mr, mrr, cost))
-        else:
-            print("quick results with sinkhorn: iters={}, tau={}, hits@{} = {}%, time = {:.3f} s ".format(iters, tau, top_k, hits, cost))
-        return
-    if accurate:
-        if csls_k > 0:
-            print("accurate results with csls: csls={}, hits@{} = {}%, mr = {:.3f}, mrr = {:.6f}, time = {:.3f} s ".
-                  format(csls_k, top_k, hits, mr, mrr, cost))
-        else:
-            print("accurate results: hits@{} = {}%, mr = {:.3f}, mrr = {:.6f}, time = {:.3f} s ".format(top_k, hits, mr, mrr, cost))
+        how = " with sinkhorn: iters={}, tau={},".format(*sinkhorn)
     else:
-        if csls_k > 0:
-            print("quick results with csls: csls={}, hits@{} = {}%, time = {:.3f} s ".format(csls_k, top_k, hits, cost))
-        else:
-            print("quick results: hits@{} = {}%, time = {:.3f} s ".format(top_k, hits, cost))
+        how = " with csls: csls={},".format(csls_k) if csls_k > 0 else ":"
+    rest = ", mr = {:.3f}, mrr = {:.6f}".format(mr, mrr) if accurate else ""
+    print("{} results{} hits@{} = {}%{}, time = {:.3f} s ".format("accurate" if accurate else "quick", how, top_k, hits, rest, cost))

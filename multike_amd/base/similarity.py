@@ -11,40 +11,19 @@ import numpy as np
 import torch
 
 from .. import _lib
-
-_METRICS = ("inner", "cosine", "euclidean")
-
-
-def _check(metric):
-    if metric not in _METRICS:
-        raise _lib.MultiKEHipError(f"sim: metric {metric!r} is not built (supported: 'inner', 'cosine', 'euclidean')")
-
-
-def _unit(x):
-    """sklearn.preprocessing.normalize: zero rows stay zero."""
-    if isinstance(x, torch.Tensor):
-        n = torch.linalg.norm(x, dim=1, keepdim=True)
-        return x / torch.where(n == 0, torch.ones_like(n), n)
-    n = np.linalg.norm(x, axis=1, keepdims=True)
-    return x / np.where(n == 0, 1, n).astype(x.dtype)
+from .alignment import _check_metric, _kpad_for, _padded, _unit
 
 
 def _device_products(a, b):
     """a . b^T on the device through mke_sim_sample (rows padded to a supported width)."""
-    kpad = min(x for x in _lib.SIM_SELECT_KPADS if x >= a.shape[1]) if a.shape[1] <= _lib.SIM_SELECT_KPADS[-1] else None
-    if kpad is None:
-        raise _lib.MultiKEHipError(f"sim: rows of {a.shape[1]} floats exceed MKE_MAX_STRIDE")
-    ap = torch.zeros(a.shape[0], kpad, dtype=torch.float32, device=a.device)
-    ap[:, :a.shape[1]] = a
-    bp = torch.zeros(b.shape[0], kpad, dtype=torch.float32, device=a.device)
-    bp[:, :b.shape[1]] = b
-    return _lib.sim_sample(ap, kpad, 0, a.shape[0], bp)
+    kpad = _kpad_for(a.shape[1], f"sim: rows of {a.shape[1]} floats exceed MKE_MAX_STRIDE")
+    return _lib.sim_sample(_padded(a, kpad, a.device), kpad, 0, a.shape[0], _padded(b, kpad, a.device))
 
 
 def sim(embed1, embed2, metric='inner', normalize=False, csls_k=0, sinkhorn=None):
     """code/base/similarity.py:9-53: the n1 x n2 similarity matrix (float32) under `metric`, CSLS re-scored when csls_k > 0,
     Sinkhorn re-scored with sinkhorn = (iters, tau) (one or the other)."""
-    _check(metric)
+    _check_metric(metric, "sim", "")
     if sinkhorn is not None and csls_k > 0:
         raise _lib.MultiKEHipError("sim: sinkhorn and csls_k are both set: choose one re-scoring")
     if isinstance(embed1, torch.Tensor) or isinstance(embed2, torch.Tensor):

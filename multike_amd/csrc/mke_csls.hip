@@ -5,7 +5,7 @@
 //   r_T(i)     = mean of the k largest sim(i, j) over the n2 columns     (calculate_nearest_k(sim_mat, k))
 //   r_S(j)     = mean of the k largest sim(i, j) over the n1 rows        (calculate_nearest_k(sim_mat.T, k))
 //   csls(i, j) = (2 sim(i, j) - r_T(i)) - r_S(j)                         (csls_sim, f32, in this order)
-// and the rank of the gold column under it.  The reference builds the matrix (60K x 60K fp32 = 14 GB) and partitions it
+// This file makes r_T / r_S.  The reference builds the matrix (60K x 60K fp32 = 14 GB) and partitions it
 // twice; here every similarity is made by the f32 MFMA sweep of mke_simtile.h and folded in registers / LDS:
 //
 //   k_topk_partial  the top-k of every row of A against one column chunk of B: a per-row LDS buffer of 64 floats takes the
@@ -17,9 +17,7 @@
 //                   k-th largest by radix_select_kth, the values above it sorted descending (sort_desc), summed in
 //                   float64 in descending order with the ties of the k-th last, divided by k, rounded to f32 — a unique,
 //                   run-to-run identical mean of the exact top-k multiset.
-//   k_align_rank_ex the fold of k_align_rank (greater / ties counters, best column with the lowest column winning a tie) with
-//                   every similarity passed through METRIC and, with CSLS, the re-scoring.  The gold is the diagonal MFMA
-//                   product through the SAME epilogue, so a row never counts itself and ties are exact comparisons.
+// The rank of the gold column under the re-scored similarity is k_align_rank of mke_eval.hip.
 #include "mke_rescore.h"
 
 #include <math.h>
@@ -28,7 +26,6 @@ namespace mke {
 
 #define CSLS_BUF 64          // per-row LDS buffer of k_topk_partial
 #define CSLS_FAST_K 32       // k <= CSLS_FAST_K: the partial sweep; above: whole rows through mke_sim_sample + k_topk_mean
-#define CSLS_MAX_CHUNKS 64
 #define CSLS_SORT_LDS 4096   // k_topk_mean sorts up to this many values in LDS, more in the caller's scratch
 
 __device__ __forceinline__ void wave_sync_lds() {
@@ -178,116 +175,20 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_topk_mean(const TopkMeanParams p)
   }
 }
 
-// ------------------------------------------------------------------------------------------------ rank sweep with metric / CSLS
-struct AlignRankExParams {
-  const float* __restrict__ emb1;
-  int ld1;
-  const float* __restrict__ emb2;
-  int ld2;
-  int n1, n2;
-  int tiles_per_chunk;
-  const float* __restrict__ sq1;
-  const float* __restrict__ sq2;
-  const float* __restrict__ csls_row;
-  const float* __restrict__ csls_col;
-  int32_t* __restrict__ rank;
-  int32_t* __restrict__ ties;
-  unsigned long long* __restrict__ best;
-};
-
-template <int KS, int MET, bool CSLS>
-__global__ __launch_bounds__(MKE_BLOCK) void k_align_rank_ex(const AlignRankExParams p) {
-  constexpr bool EUC = MET == MKE_METRIC_EUCLIDEAN;
-  __shared__ float s_gold[MKE_BLOCK / 64][32];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int half = lane >> 5, l31 = lane & 31;
-  const int strip0 = blockIdx.x * SIMT_BM + wv * 32;
-  float a[KS * 8];
-  float gold[16], sqi[16], rti[16];
-#pragma unroll
-  for (int reg = 0; reg < 16; ++reg) {
-    const int r = simt_row(reg, half, strip0);
-    sqi[reg] = (EUC && r < p.n1) ? p.sq1[r] : 0.f;
-    rti[reg] = (CSLS && r < p.n1) ? p.csls_row[r] : 0.f;
-  }
-  {
-    const int r = strip0 + l31;
-    const bool ok = r < p.n1;
-    simt_load_fragment<KS>(p.emb1 + (int64_t)(ok ? r : 0) * p.ld1, ok, half, a);
-    float b[KS * 8];
-    simt_load_fragment<KS>(p.emb2 + (int64_t)(ok ? r : 0) * p.ld2, ok, half, b);  // gold column i = row i (n2 >= n1)
-    const f32x16 d = simt_fragment_product<KS>(a, b);
-    const float sqj = (EUC && ok) ? p.sq2[r] : 0.f;  // this lane's column of the product is r
-    const float rsj = (CSLS && ok) ? p.csls_col[r] : 0.f;
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) {
-      const int m = simt_row(reg, half);
-      if (m == l31) s_gold[wv][m] = rescore<MET, CSLS>(d[reg], sqi[reg], sqj, rti[reg], rsj);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) gold[reg] = s_gold[wv][simt_row(reg, half)];
-  }
-  int cnt[16], eq[16];
-  float bestv[16];
-  int bestc[16];
-#pragma unroll
-  for (int reg = 0; reg < 16; ++reg) { cnt[reg] = 0; eq[reg] = 0; bestv[reg] = -INFINITY; bestc[reg] = 0x7FFFFFFF; }
-  const int ntiles = (p.n2 + SIMT_BN_FOR(KS) - 1) / SIMT_BN_FOR(KS);
-  const int t0 = blockIdx.y * p.tiles_per_chunk;
-  const int t1 = min(ntiles, t0 + p.tiles_per_chunk);
-  simt_sweep<KS>(a, p.emb2, p.ld2, p.n2, t0, t1, [&](const f32x16& acc, int col, bool col_ok) {
-    const float sqj = (EUC && col_ok) ? p.sq2[col] : 0.f;
-    const float rsj = (CSLS && col_ok) ? p.csls_col[col] : 0.f;
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) {
-      const float s = rescore<MET, CSLS>(acc[reg], sqi[reg], sqj, rti[reg], rsj);
-      cnt[reg] += (col_ok && s > gold[reg]) ? 1 : 0;
-      eq[reg] += (col_ok && s == gold[reg]) ? 1 : 0;
-      if (col_ok && (s > bestv[reg] || (s == bestv[reg] && col < bestc[reg]))) { bestv[reg] = s; bestc[reg] = col; }
-    }
-  });
-#pragma unroll
-  for (int reg = 0; reg < 16; ++reg) {
-    int c = cnt[reg], ce = eq[reg];
-    float bv = bestv[reg];
-    int bc = bestc[reg];
-#pragma unroll
-    for (int off = 1; off < 32; off <<= 1) {
-      c += __shfl_xor(c, off, 64);
-      ce += __shfl_xor(ce, off, 64);
-      const float ov = __shfl_xor(bv, off, 64);
-      const int oc = __shfl_xor(bc, off, 64);
-      if (ov > bv || (ov == bv && oc < bc)) { bv = ov; bc = oc; }
-    }
-    const int row = simt_row(reg, half, strip0);
-    if (l31 == 0 && row < p.n1 && t0 < t1) {
-      atomicAdd(&p.rank[row], c);
-      atomicAdd(&p.ties[row], ce);
-    }
-    if (l31 == 0 && row < p.n1 && t0 < t1 && bc != 0x7FFFFFFF) {  // bc unset: every similarity of the chunk was NaN
-      const unsigned long long key = best_key(bv, bc);
-      atomicMax(&p.best[row], key);
-    }
-  }
-}
-
-// column chunks of k_topk_partial: the scratch query and the launch agree on them
-static SimtSplit topk_partial_split(int64_t n_a, int64_t n_b, int kpad) { return simt_split(n_a, n_b, kpad, 6144, 16, CSLS_MAX_CHUNKS); }
-
 }  // namespace mke
 
-static int topk_mean_temp(int64_t n_a, int64_t n_b, int kpad, int k, int64_t* bytes) {
+static int topk_mean_temp(const mke::SweepOperands& o, int k, int64_t* bytes) {
   using namespace mke;
   *bytes = 0;
-  if (n_a < 0 || n_b < 0 || n_a > 0x7FFFFF00LL || n_b > 0x7FFFFF00LL) { set_error("mke_align_topk_mean: bad n_a / n_b"); return MKE_E_SHAPE; }
-  if (kpad <= 0 || kpad % 16 != 0 || kpad > MKE_MAX_STRIDE) { set_error("mke_align_topk_mean: kpad must be a multiple of 16 <= %d", MKE_MAX_STRIDE); return MKE_E_SHAPE; }
+  const int rc = check_operands(o, {OP_ROWS, OP_KPAD});
+  if (rc != MKE_OK) return rc;
+  const int64_t n_a = o.n_a, n_b = o.n_b;
   if (k < 1 || (int64_t)k > n_b - 2) { set_error("mke_align_topk_mean: need 1 <= k <= n_b - 2 (k = %d, n_b = %lld)", k, (long long)n_b); return MKE_E_SHAPE; }
   if (k > (1 << 30)) { set_error("mke_align_topk_mean: k above 2^30 (the sort of the large-k path counts with 32-bit ints)"); return MKE_E_RANGE; }
   if (n_a == 0) return MKE_OK;
   int64_t floats;
   if (k <= CSLS_FAST_K) {
-    floats = n_a * topk_partial_split(n_a, n_b, kpad).chunks * k;  // < 2^31 * 64 * 32: the kernels index it with int64 offsets
+    floats = n_a * partial_split(n_a, n_b, o.kpad).chunks * k;  // < 2^31 * 64 * 32: the kernels index it with int64 offsets
   } else {
     const int64_t r = fallback_rows(n_a, n_b);
     floats = r * n_b + (k > CSLS_SORT_LDS ? r * pow2_at_least(k) : 0);
@@ -299,7 +200,7 @@ static int topk_mean_temp(int64_t n_a, int64_t n_b, int kpad, int k, int64_t* by
 
 extern "C" int64_t mke_align_topk_mean_temp_bytes(int64_t n_a, int64_t n_b, int kpad, int k) {
   int64_t bytes = 0;
-  const int rc = topk_mean_temp(n_a, n_b, kpad, k, &bytes);
+  const int rc = topk_mean_temp({"mke_align_topk_mean: ", false, n_a, n_b, kpad}, k, &bytes);
   return rc != MKE_OK ? rc : bytes;
 }
 
@@ -307,15 +208,15 @@ extern "C" int mke_align_topk_mean(const mke_topk_mean_args* args, void* stream)
   using namespace mke;
   if (!args) { set_error("mke_align_topk_mean: NULL args"); return MKE_E_NULL; }
   const mke_topk_mean_args& g = *args;
+  const SweepOperands o = {"mke_align_topk_mean: ", false, g.n_a, g.n_b, g.kpad, g.lda, g.ldb, g.metric, g.sq_a, g.sq_b, nullptr, nullptr};
   int64_t need = 0;
-  const int rc = topk_mean_temp(g.n_a, g.n_b, g.kpad, g.k, &need);
+  int rc = topk_mean_temp(o, g.k, &need);
+  if (rc == MKE_OK) rc = check_operands(o, {OP_METRIC});
   if (rc != MKE_OK) return rc;
-  if (g.metric != MKE_METRIC_INNER && g.metric != MKE_METRIC_EUCLIDEAN) { set_error("mke_align_topk_mean: unknown metric %d", g.metric); return MKE_E_UNSUPPORTED; }
   if (g.n_a == 0) return MKE_OK;
   if (!g.a || !g.b || !g.out || (need > 0 && !g.temp)) { set_error("mke_align_topk_mean: NULL pointer"); return MKE_E_NULL; }
-  if (g.metric == MKE_METRIC_EUCLIDEAN && (!g.sq_a || !g.sq_b)) { set_error("mke_align_topk_mean: euclidean needs sq_a and sq_b"); return MKE_E_NULL; }
-  if (g.lda < g.kpad || g.ldb < g.kpad || g.lda % 4 != 0 || g.ldb % 4 != 0) { set_error("mke_align_topk_mean: lda, ldb must be multiples of 4 >= kpad"); return MKE_E_SHAPE; }
-  if (!simt_kpad_ok(g.kpad)) { set_error("mke_align_topk_mean: unsupported kpad %d", g.kpad); return MKE_E_UNSUPPORTED; }
+  rc = check_operands(o, {OP_NORMS, OP_LD, OP_WIDTH});
+  if (rc != MKE_OK) return rc;
   if (g.temp_bytes < need) { set_error("mke_align_topk_mean: temp below mke_align_topk_mean_temp_bytes (%lld)", (long long)need); return MKE_E_SHAPE; }
   hipStream_t st = (hipStream_t)stream;
   TopkMeanParams mp;
@@ -324,7 +225,7 @@ extern "C" int mke_align_topk_mean(const mke_topk_mean_args* args, void* stream)
     TopkPartialParams p;
     p.a = g.a; p.lda = g.lda; p.b = g.b; p.ldb = g.ldb; p.n_a = (int)g.n_a; p.n_b = (int)g.n_b; p.sq_a = g.sq_a; p.sq_b = g.sq_b;
     p.k = g.k;
-    const SimtSplit sp = topk_partial_split(g.n_a, g.n_b, g.kpad);
+    const SimtSplit sp = partial_split(g.n_a, g.n_b, g.kpad);
     p.chunks = sp.chunks; p.tiles_per_chunk = sp.tiles_per_chunk;
     p.part = (float*)g.temp;
     dim3 grid((unsigned)((g.n_a + SIMT_BM - 1) / SIMT_BM), (unsigned)p.chunks);
@@ -356,37 +257,4 @@ extern "C" int mke_align_topk_mean(const mke_topk_mean_args* args, void* stream)
     if (e) return e;
   }
   return MKE_OK;
-}
-
-extern "C" int mke_align_rank_ex(const mke_align_args* args, void* stream) {
-  using namespace mke;
-  if (!args) { set_error("mke_align_rank_ex: NULL args"); return MKE_E_NULL; }
-  const mke_align_args& g = *args;
-  if (g.n1 < 0 || g.n2 < 0 || g.n1 > 0x7FFFFF00LL || g.n2 > 0x7FFFFF00LL) { set_error("mke_align_rank_ex: bad n1/n2"); return MKE_E_SHAPE; }
-  if (g.metric != MKE_METRIC_INNER && g.metric != MKE_METRIC_EUCLIDEAN) { set_error("mke_align_rank_ex: unknown metric %d", g.metric); return MKE_E_UNSUPPORTED; }
-  if ((g.csls_row == nullptr) != (g.csls_col == nullptr)) { set_error("mke_align_rank_ex: csls_row and csls_col are both NULL or both set"); return MKE_E_NULL; }
-  if (g.n1 == 0) return MKE_OK;
-  if (!g.emb1 || !g.emb2 || !g.rank || !g.ties || !g.best) { set_error("mke_align_rank_ex: NULL pointer"); return MKE_E_NULL; }
-  if (g.metric == MKE_METRIC_EUCLIDEAN && (!g.sq1 || !g.sq2)) { set_error("mke_align_rank_ex: euclidean needs sq1 and sq2"); return MKE_E_NULL; }
-  if (g.kpad <= 0 || g.kpad % 16 != 0 || g.kpad > MKE_MAX_STRIDE || g.ld1 < g.kpad || g.ld2 < g.kpad || g.ld1 % 4 != 0 || g.ld2 % 4 != 0) {
-    set_error("mke_align_rank_ex: kpad must be a multiple of 16 <= %d and <= ld1, ld2 (both multiples of 4)", MKE_MAX_STRIDE);
-    return MKE_E_SHAPE;
-  }
-  if (g.n2 < g.n1) { set_error("mke_align_rank_ex: gold column = row index needs n2 >= n1"); return MKE_E_SHAPE; }
-  if (!simt_kpad_ok(g.kpad)) { set_error("mke_align_rank_ex: unsupported kpad %d", g.kpad); return MKE_E_UNSUPPORTED; }
-  AlignRankExParams p;
-  p.emb1 = g.emb1; p.ld1 = g.ld1; p.emb2 = g.emb2; p.ld2 = g.ld2; p.n1 = (int)g.n1; p.n2 = (int)g.n2;
-  p.sq1 = g.sq1; p.sq2 = g.sq2; p.csls_row = g.csls_row; p.csls_col = g.csls_col;
-  p.rank = g.rank; p.ties = g.ties; p.best = (unsigned long long*)g.best;
-  const SimtSplit sp = simt_split(g.n1, g.n2, g.kpad, 6144, 16, 1 << 16);
-  p.tiles_per_chunk = sp.tiles_per_chunk;
-  dim3 grid((unsigned)((g.n1 + SIMT_BM - 1) / SIMT_BM), (unsigned)sp.chunks);
-  hipStream_t st = (hipStream_t)stream;
-  simt_for_kpad(g.kpad, [&](auto ks) {
-    for_rescore(g.metric == MKE_METRIC_EUCLIDEAN, g.csls_row != nullptr, [&](auto met, auto csls) {
-      hipLaunchKernelGGL((k_align_rank_ex<decltype(ks)::value, decltype(met)::value, decltype(csls)::value>), grid, dim3(MKE_BLOCK), 0,
-                         st, p);
-    });
-  });
-  return check_launch("k_align_rank_ex");
 }

@@ -18,12 +18,10 @@ __device__ __forceinline__ unsigned float_key(float v) {
 }
 __device__ __forceinline__ float key_float(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
 
-// The `best` word of the two rank kernels (k_align_rank, k_align_rank_ex), for a 64-bit atomicMax: similarity in the high word,
-// the lowest column wins a tie.  Deliberately NOT float_key: -0 stays below +0 here, as it always has in the published keys.
-// This is where the two kernels meet; they are not one kernel, and their gold-diagonal prologues and closing folds stay
-// apart, because they differ on purpose where a row is all NaN or -inf: bestv starts at -3.0e38f with column 0 in the plain
-// kernel, at -inf with column 0x7FFFFFFF and a NaN guard in the other, and TIES is optional in the plain one only.  Making
-// them agree changes results.
+// The `best` word of the rank kernel (k_align_rank of mke_eval.hip), for a 64-bit atomicMax: similarity in the high word, the
+// lowest column wins a tie.  Deliberately NOT float_key: -0 stays below +0 here, as it always has in the published keys.
+// Which (value, column) a row of NaN or -inf publishes differs between the kernel's two entry points on purpose; the rule
+// and its constants are RankBest in mke_eval.hip.
 __device__ __forceinline__ unsigned long long best_key(float v, int col) {
   return ((unsigned long long)ordered_bits(__float_as_uint(v)) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)col);
 }

@@ -24,8 +24,6 @@
 
 namespace mke {
 
-#define LSE_MAX_CHUNKS 64
-
 struct LsePartialParams {
   const float* __restrict__ a;  // [n_a][lda]
   int lda;
@@ -121,25 +119,23 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_lse_merge(const LseMergeParams p)
   p.out[row] = (float)((double)p.tau * 0.69314718055994530942 * ((double)top + log2(sum)));
 }
 
-// column chunks of k_lse_partial: the scratch query and the launch agree on them
-static SimtSplit lse_split(int64_t n_a, int64_t n_b, int kpad) { return simt_split(n_a, n_b, kpad, 6144, 16, LSE_MAX_CHUNKS); }
-
 }  // namespace mke
 
-static int lse_temp(int64_t n_a, int64_t n_b, int kpad, int64_t* bytes) {
+static int lse_temp(const mke::SweepOperands& o, int64_t* bytes) {
   using namespace mke;
   *bytes = 0;
-  if (n_a < 0 || n_b < 0 || n_a > 0x7FFFFF00LL || n_b > 0x7FFFFF00LL) { set_error("mke_align_lse: bad n_a / n_b"); return MKE_E_SHAPE; }
-  if (kpad <= 0 || kpad % 16 != 0 || kpad > MKE_MAX_STRIDE) { set_error("mke_align_lse: kpad must be a multiple of 16 <= %d", MKE_MAX_STRIDE); return MKE_E_SHAPE; }
+  const int rc = check_operands(o, {OP_ROWS, OP_KPAD});
+  if (rc != MKE_OK) return rc;
+  const int64_t n_a = o.n_a, n_b = o.n_b;
   if (n_b < 1) { set_error("mke_align_lse: need n_b >= 1 (the sum over no column has no logarithm)"); return MKE_E_SHAPE; }
   if (n_a == 0) return MKE_OK;
-  *bytes = n_a * lse_split(n_a, n_b, kpad).chunks * (int64_t)sizeof(float2);  // < 2^31 * 64 * 8: indexed with int64 offsets
+  *bytes = n_a * partial_split(n_a, n_b, o.kpad).chunks * (int64_t)sizeof(float2);  // < 2^31 * 64 * 8: indexed with int64 offsets
   return MKE_OK;
 }
 
 extern "C" int64_t mke_align_lse_temp_bytes(int64_t n_a, int64_t n_b, int kpad) {
   int64_t bytes = 0;
-  const int rc = lse_temp(n_a, n_b, kpad, &bytes);
+  const int rc = lse_temp({"mke_align_lse: ", false, n_a, n_b, kpad}, &bytes);
   return rc != MKE_OK ? rc : bytes;
 }
 
@@ -147,23 +143,23 @@ extern "C" int mke_align_lse(const mke_lse_args* args, void* stream) {
   using namespace mke;
   if (!args) { set_error("mke_align_lse: NULL args"); return MKE_E_NULL; }
   const mke_lse_args& g = *args;
+  const SweepOperands o = {"mke_align_lse: ", false, g.n_a, g.n_b, g.kpad, g.lda, g.ldb, g.metric, g.sq_a, g.sq_b, nullptr, nullptr};
   int64_t need = 0;
-  const int rc = lse_temp(g.n_a, g.n_b, g.kpad, &need);
+  int rc = lse_temp(o, &need);
+  if (rc == MKE_OK) rc = check_operands(o, {OP_METRIC});
   if (rc != MKE_OK) return rc;
-  if (g.metric != MKE_METRIC_INNER && g.metric != MKE_METRIC_EUCLIDEAN) { set_error("mke_align_lse: unknown metric %d", g.metric); return MKE_E_UNSUPPORTED; }
   if (!(g.tau > 0.f) || !isfinite(g.tau)) { set_error("mke_align_lse: tau must be positive and finite"); return MKE_E_RANGE; }
   if (g.n_a == 0) return MKE_OK;
   if (!g.a || !g.b || !g.out || !g.temp) { set_error("mke_align_lse: NULL pointer"); return MKE_E_NULL; }
-  if (g.metric == MKE_METRIC_EUCLIDEAN && (!g.sq_a || !g.sq_b)) { set_error("mke_align_lse: euclidean needs sq_a and sq_b"); return MKE_E_NULL; }
-  if (g.lda < g.kpad || g.ldb < g.kpad || g.lda % 4 != 0 || g.ldb % 4 != 0) { set_error("mke_align_lse: lda, ldb must be multiples of 4 >= kpad"); return MKE_E_SHAPE; }
-  if (!simt_kpad_ok(g.kpad)) { set_error("mke_align_lse: unsupported kpad %d", g.kpad); return MKE_E_UNSUPPORTED; }
+  rc = check_operands(o, {OP_NORMS, OP_LD, OP_WIDTH});
+  if (rc != MKE_OK) return rc;
   if (g.temp_bytes < need) { set_error("mke_align_lse: temp below mke_align_lse_temp_bytes (%lld)", (long long)need); return MKE_E_SHAPE; }
   hipStream_t st = (hipStream_t)stream;
   LsePartialParams p;
   p.a = g.a; p.lda = g.lda; p.b = g.b; p.ldb = g.ldb; p.n_a = (int)g.n_a; p.n_b = (int)g.n_b; p.sq_a = g.sq_a; p.sq_b = g.sq_b;
   p.sub_b = g.sub_b;
   p.scale = (float)(1.4426950408889634074 / (double)g.tau);
-  const SimtSplit sp = lse_split(g.n_a, g.n_b, g.kpad);
+  const SimtSplit sp = partial_split(g.n_a, g.n_b, g.kpad);
   p.chunks = sp.chunks; p.tiles_per_chunk = sp.tiles_per_chunk;
   p.part = (float2*)g.temp;
   dim3 grid((unsigned)((g.n_a + SIMT_BM - 1) / SIMT_BM), (unsigned)p.chunks);

@@ -8,7 +8,7 @@
 // column, so no column is sorted at all.
 //
 // Candidate lists (mke_stable_lists), cut <= STABLE_FAST_CUT — the k-NN refresh's form (mke_knn.hip), with the evaluator's
-// metric / CSLS epilogue (rescore<MET, CSLS> of k_align_rank_ex):
+// metric / CSLS epilogue (rescore<MET, CSLS> of mke_rescore.h, as k_align_rank):
 //   tau             per row the m-th largest re-scored similarity to a strided sample of <= 4096 columns (mke_sim_sample on
 //                   b with a row stride, k_stable_rescore, mke_topk_rows), m chosen so that about 2 cut + 32 columns pass.
 //                   n_b <= STABLE_LIST_CAP: no sample, tau = -inf (every column is a candidate).
@@ -342,14 +342,16 @@ static int64_t up256(int64_t x) { return (x + 255) / 256 * 256; }
 
 }  // namespace mke
 
-static int stable_plan(const char* who, int64_t n_a, int64_t n_b, int kpad, int cut, bool whole, bool need_kpad, mke::StablePlan* pl) {
+static int stable_plan(const mke::SweepOperands& o, int cut, bool whole, bool need_kpad, mke::StablePlan* pl) {
   using namespace mke;
   pl->bytes = 0;
   pl->whole = whole || cut > STABLE_FAST_CUT;
-  if (n_a < 0 || n_b < 0 || n_a > 0x7FFFFF00LL || n_b > 0x7FFFFF00LL) { set_error("%s: bad n_a / n_b", who); return MKE_E_SHAPE; }
-  if (need_kpad && (kpad <= 0 || kpad % 16 != 0 || kpad > MKE_MAX_STRIDE)) { set_error("%s: kpad must be a multiple of 16 <= %d", who, MKE_MAX_STRIDE); return MKE_E_SHAPE; }
-  if (cut < 1 || (int64_t)cut > n_b) { set_error("%s: need 1 <= cut <= n_b (cut = %d, n_b = %lld)", who, cut, (long long)n_b); return MKE_E_SHAPE; }
-  if (cut > (1 << 30)) { set_error("%s: cut above 2^30 (the sort counts with 32-bit ints)", who); return MKE_E_RANGE; }
+  const int64_t n_a = o.n_a, n_b = o.n_b;
+  int rc = check_operands(o, {OP_ROWS});
+  if (rc == MKE_OK && need_kpad) rc = check_operands(o, {OP_KPAD});
+  if (rc != MKE_OK) return rc;
+  if (cut < 1 || (int64_t)cut > n_b) { set_error("%sneed 1 <= cut <= n_b (cut = %d, n_b = %lld)", o.who, cut, (long long)n_b); return MKE_E_SHAPE; }
+  if (cut > (1 << 30)) { set_error("%scut above 2^30 (the sort counts with 32-bit ints)", o.who); return MKE_E_RANGE; }
   if (n_a == 0) return MKE_OK;
   if (pl->whole) {
     pl->rows = fallback_rows(n_a, n_b);
@@ -358,7 +360,7 @@ static int stable_plan(const char* who, int64_t n_a, int64_t n_b, int kpad, int 
     pl->off_sel = up256(pl->rows * n_b * 4);                       // selected columns [rows][cut]
     pl->off_sort = pl->off_sel + up256(pl->rows * (int64_t)cut * 4);
     pl->bytes = pl->off_sort + (np2 > STABLE_SORT_LDS ? pl->rows * np2 * 8 : 0);
-    if (pl->bytes > ((int64_t)1 << 42)) { set_error("%s: scratch beyond 2^42 bytes", who); return MKE_E_RANGE; }
+    if (pl->bytes > ((int64_t)1 << 42)) { set_error("%sscratch beyond 2^42 bytes", o.who); return MKE_E_RANGE; }
     return MKE_OK;
   }
   const int64_t per_row = (int64_t)STABLE_LIST_CAP * 8;
@@ -376,7 +378,7 @@ static int stable_plan(const char* who, int64_t n_a, int64_t n_b, int kpad, int 
 
 extern "C" int64_t mke_stable_lists_temp_bytes(int64_t n_a, int64_t n_b, int kpad, int cut, int whole_rows) {
   mke::StablePlan pl;
-  const int rc = stable_plan("mke_stable_lists_temp_bytes", n_a, n_b, kpad, cut, whole_rows != 0, true, &pl);
+  const int rc = stable_plan({"mke_stable_lists_temp_bytes: ", false, n_a, n_b, kpad}, cut, whole_rows != 0, true, &pl);
   return rc != MKE_OK ? rc : pl.bytes;
 }
 
@@ -385,13 +387,11 @@ extern "C" int mke_stable_lists(const mke_stable_lists_args* args, void* stream)
   if (!args) { set_error("mke_stable_lists: NULL args"); return MKE_E_NULL; }
   const mke_stable_lists_args& g = *args;
   const bool given = g.sim_mat != nullptr;
+  const SweepOperands o = {"mke_stable_lists: ", false, g.n_a, g.n_b, g.kpad, g.lda, g.ldb, g.metric, g.sq_a, g.sq_b, g.csls_row, g.csls_col};
   StablePlan pl;
-  const int rc = stable_plan("mke_stable_lists", g.n_a, g.n_b, g.kpad, g.cut, g.whole_rows != 0 || given, !given, &pl);
+  int rc = stable_plan(o, g.cut, g.whole_rows != 0 || given, !given, &pl);
+  if (rc == MKE_OK && !given) rc = check_operands(o, {OP_METRIC, OP_TERMS});
   if (rc != MKE_OK) return rc;
-  if (!given) {
-    if (g.metric != MKE_METRIC_INNER && g.metric != MKE_METRIC_EUCLIDEAN) { set_error("mke_stable_lists: unknown metric %d", g.metric); return MKE_E_UNSUPPORTED; }
-    if ((g.csls_row == nullptr) != (g.csls_col == nullptr)) { set_error("mke_stable_lists: csls_row and csls_col are both NULL or both set"); return MKE_E_NULL; }
-  }
   if (g.sample_cols < 0) { set_error("mke_stable_lists: sample_cols < 0"); return MKE_E_SHAPE; }
   if (g.n_a == 0) return MKE_OK;
   if (!g.out_val || !g.out_col || !g.flags || !g.temp) { set_error("mke_stable_lists: NULL pointer"); return MKE_E_NULL; }
@@ -399,9 +399,8 @@ extern "C" int mke_stable_lists(const mke_stable_lists_args* args, void* stream)
     if (g.ld_sim < g.n_b) { set_error("mke_stable_lists: ld_sim below n_b"); return MKE_E_SHAPE; }
   } else {
     if (!g.a || !g.b) { set_error("mke_stable_lists: NULL pointer"); return MKE_E_NULL; }
-    if (g.metric == MKE_METRIC_EUCLIDEAN && (!g.sq_a || !g.sq_b)) { set_error("mke_stable_lists: euclidean needs sq_a and sq_b"); return MKE_E_NULL; }
-    if (g.lda < g.kpad || g.ldb < g.kpad || g.lda % 4 != 0 || g.ldb % 4 != 0) { set_error("mke_stable_lists: lda, ldb must be multiples of 4 >= kpad"); return MKE_E_SHAPE; }
-    if (!simt_kpad_ok(g.kpad)) { set_error("mke_stable_lists: unsupported kpad %d", g.kpad); return MKE_E_UNSUPPORTED; }
+    rc = check_operands(o, {OP_NORMS, OP_LD, OP_WIDTH});
+    if (rc != MKE_OK) return rc;
   }
   if (g.temp_bytes < pl.bytes) { set_error("mke_stable_lists: temp below mke_stable_lists_temp_bytes (%lld)", (long long)pl.bytes); return MKE_E_SHAPE; }
   hipStream_t st = (hipStream_t)stream;
