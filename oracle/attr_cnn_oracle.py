@@ -117,7 +117,14 @@ def dp_backward(p, c, t, g_out, S_global, T_global):
         dz = t["inv"] * g_out
     dzpre = dz * (1.0 - c["z"] ** 2)
     g = {"W": c["flat"].T @ dzpre, "bias": dzpre.sum(0)}
-    dflat = dzpre @ p["W"].T
+    g.update(conv_backward(p, c, dzpre @ p["W"].T))
+    return g
+
+
+def conv_backward(p, c, dflat):
+    """Backward of the conv stack alone, from dflat = dL/dflat [B, 4d]: the gradients of gamma, beta, K1, b1, K2, b2 and
+    'as' (w.r.t. the attribute rows).  `c` is the cache of `forward`."""
+    g = {}
     dy = dflat.reshape(c["y"].shape)
     dot = np.sum(dy * c["y"], axis=2, keepdims=True)
     dc2 = np.where(c["ssq"] > L2_EPS, c["n"] * (dy - c["y"] * dot), c["n"] * dy)

@@ -81,6 +81,9 @@ def test_reference_executed_attribute_graph(ci):
                                                     # its upper edge, and the first width past it
                                                     (8, 100, 60, 7, 30), (40, 300, 500, 13, 200), (64, 215, 300, 10, 100),
                                                     (80, 129, 400, 12, 150),
+                                                    # 1 / 2 / 3 positions per lane of the fused forward at their edges, with
+                                                    # n < dim: the unfused two-triples-per-wavefront backward inside the step
+                                                    (16, 33, 60, 7, 30), (17, 33, 60, 7, 30), (48, 47, 90, 7, 30),
                                                     # the widths past the fused launches (separate dense / tail-backward / product
                                                     # launches; round 6 built the fused form for 80 < dim <= 128 against these
                                                     # cases, measured it slower and removed it: EXPERIMENTS R6.12)

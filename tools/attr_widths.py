@@ -12,7 +12,7 @@ steps = int(sys.argv[1]) if len(sys.argv) > 1 else 300
 B = 5000
 g = torch.Generator(device="cuda"); g.manual_seed(0)
 print("| dim | fused launches (us/step) | `attr_fused_bwd` = 0 (us/step) |\n|---|---|---|")
-for d in (32, 64, 75, 80, 96, 100, 112, 128, 130):
+for d in (32, 64, 75, 80, 96, 100, 112, 128, 130, 200, 320):
     row = []
     for fused in (1, 0):
         _lib.set_option("attr_fused_bwd", fused)
