@@ -936,6 +936,51 @@ int64_t mke_align_lse_temp_bytes(int64_t n_a, int64_t n_b, int kpad);
 int mke_align_lse(const mke_lse_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * (9e) Mutual (bidirectional) nearest-neighbour alignment, still without the n_a x n_b matrix (additions only; version unchanged).
+ *
+ * Row i of a and row j of b are a predicted pair when j is i's best column AND i is j's best row, optionally at or above a
+ * similarity threshold: the high-precision decoder, and the one that needs no gold labels (any n_a, n_b).  The reference has no
+ * counterpart; it is the mining step of the bootstrapped alignment methods.
+ *
+ *   mke_align_mutual: ONE sweep; s_ij as in mke_align_rank_ex (METRIC, then (2 s - csls_row[i]) - csls_col[j] when both terms
+ *     are set: CSLS means, or twice the Sinkhorn potentials of (9d)) is evaluated once per pair and folded into both
+ *       row_best[i] = max over j of (ordered(s_ij) << 32 | 0xFFFFFFFF - j)     (the `best` word of mke_align_rank_ex)
+ *       col_best[j] = max over i of (ordered(s_ij) << 32 | 0xFFFFFFFF - i)
+ *     so the lowest index wins a tie in both directions and both directions compare the SAME f32 value (a second sweep with
+ *     the operands swapped would round the re-scoring differently).  row_best, col_best zeroed by the caller.  A NaN
+ *     similarity is never anybody's best; a row (column) whose similarities are all NaN leaves its word 0, one of all -inf
+ *     publishes (-inf, its lowest index).  The result does not depend on the order in which blocks finish.
+ *     n_a == 0 or n_b == 0: MKE_OK, nothing launched.  Unknown metric / flags, a kpad without an instantiation:
+ *     MKE_E_UNSUPPORTED.  lda / ldb: multiples of 4 >= kpad; rows zero in [dim, kpad).
+ *     flags: 0.  MKE_MUTUAL_NO_LDS_FOLD (every wavefront sends its own atomics for a column instead of folding the block's four
+ *     in LDS first) and MKE_MUTUAL_FILTER (a plain load of the word before a column's atomic, which is skipped when the word
+ *     already holds more) select the other forms of the column fold for measurements (tools/mutual_bench.py); the results are
+ *     the same bit for bit.
+ *   mke_mutual_pairs: match[i] = j when row_best[i] names a column j < n_b, col_best[j] names row i and the value of
+ *     row_best[i] is >= threshold (-INFINITY: no threshold; NaN: MKE_E_RANGE); else match[i] = -1.  counts[0] = matched rows,
+ *     counts[1] = rows with match[i] == i; counts is zeroed BY THE CALL.  A call per threshold, no second sweep.
+ * ------------------------------------------------------------------------------------------------ */
+#define MKE_MUTUAL_NO_LDS_FOLD 1
+#define MKE_MUTUAL_FILTER 2
+typedef struct mke_mutual_args {
+  const float* a; int lda;          /* [n_a][lda] */
+  const float* b; int ldb;          /* [n_b][ldb] */
+  int kpad;
+  int64_t n_a, n_b;
+  int metric;
+  const float* sq_a;                /* [n_a], euclidean only (nullable otherwise) */
+  const float* sq_b;                /* [n_b], euclidean only */
+  const float* csls_row;            /* [n_a] row term, or NULL: no re-scoring */
+  const float* csls_col;            /* [n_b] column term, or NULL (NULL exactly when csls_row is) */
+  uint64_t* row_best;               /* [n_a] */
+  uint64_t* col_best;               /* [n_b] */
+  int flags;                        /* 0, or MKE_MUTUAL_* */
+} mke_mutual_args;
+int mke_align_mutual(const mke_mutual_args* args, void* stream);
+int mke_mutual_pairs(const uint64_t* row_best, const uint64_t* col_best, int64_t n_a, int64_t n_b, float threshold,
+                     int32_t* match, int32_t* counts, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * (10) Small dense f32 GEMM on the matrix cores (v_mfma_f32_32x32x2_f32, exact f32) with arbitrary operand strides:
  *        C[M][N] (=|+=) A[M][K] . B[K][N],  A(i,k) = A[i*a_row_stride + k*a_col_stride], likewise B.
  *      splits > 1: split-K, partial products are added atomically (accumulate must be 1; C zeroed or holding the

@@ -11,7 +11,7 @@ import time
 import numpy as np
 
 from .base import evaluation as eva
-from .base.alignment import stable_alignment
+from .base.alignment import mutual_alignment, stable_alignment
 from .base.batch import neighbour_table
 from .MultiKE_model import MultiKE
 from .utils import sinkhorn_option, task_divide
@@ -80,6 +80,7 @@ def test(model, embed_choice='avg', w=(1, 1, 1)):
     _, mrr_12 = eva.valid(embeds1, embeds2, None, model.args.top_k, model.args.test_threads_num, normalize=True,
                           csls_k=_csls_k(model), sinkhorn=_sinkhorn(model))
     _stable(model, embeds1, embeds2)
+    _mutual(model, embeds1, embeds2)
     return mrr_12
 
 
@@ -102,6 +103,15 @@ def _stable(model, embeds1, embeds2):
     if cut > 0:
         stable_alignment(embeds1, embeds2, 'inner', True, _csls_k(model), model.args.test_threads_num, cut=cut,
                          sinkhorn=_sinkhorn(model))
+
+
+def _mutual(model, embeds1, embeds2):
+    """Hyper-parameters `mutual` (0 = off) / `mutual_threshold` (absent or None = none): after the greedy (and stable) lines of
+    a test, precision / recall / F1 of the mutual nearest-neighbour pairs of the same rows, CSLS or Sinkhorn re-scored as the
+    test is (the threshold is then in units of the re-scored value)."""
+    if int(getattr(model.args, "mutual", 0) or 0) > 0:
+        mutual_alignment(embeds1, embeds2, 'inner', True, _csls_k(model), model.args.test_threads_num,
+                         threshold=getattr(model.args, "mutual_threshold", None), sinkhorn=_sinkhorn(model))
 
 
 def _unit_rows(x):
@@ -148,6 +158,7 @@ def _wva_eval(model, ents1, ents2, label, keys=None, csls_k=0, stable=False, sin
                           sinkhorn=sinkhorn)
     if stable:
         _stable(model, embeds1, embeds2)
+        _mutual(model, embeds1, embeds2)
     return mrr_12
 
 

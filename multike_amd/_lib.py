@@ -41,6 +41,7 @@ SYMBOLS = (
     "mke_stable_lists_temp_bytes", "mke_stable_lists", "mke_stable_rounds", "mke_stable_finish",
     "mke_tripleset_forget", "mke_tripleset_filter_bytes", "mke_epoch_positives",
     "mke_align_lse_temp_bytes", "mke_align_lse",
+    "mke_align_mutual", "mke_mutual_pairs",
 )
 ACT_NONE, ACT_TANH, ACT_SIGMOID = 0, 1, 2
 AE_MAX_LAYERS = 4
@@ -1117,6 +1118,47 @@ def stable_rounds(args: StableMatchArgs, first_round: int, n_rounds: int):
 def stable_finish(args: StableMatchArgs):
     """mke_stable_finish: match[i] = the column holding suitor i or -1; counts = (matched, matched to its own index)."""
     _check(lib().mke_stable_finish(C.byref(args), _stream()), "mke_stable_finish")
+
+
+MUTUAL_NO_LDS_FOLD, MUTUAL_FILTER = 1, 2   # MKE_MUTUAL_*: the other forms of the column fold, for measurements
+
+
+class MutualArgs(C.Structure):
+    """mke_mutual_args"""
+    _fields_ = [("a", C.c_void_p), ("lda", C.c_int), ("b", C.c_void_p), ("ldb", C.c_int), ("kpad", C.c_int),
+                ("n_a", C.c_int64), ("n_b", C.c_int64), ("metric", C.c_int), ("sq_a", C.c_void_p), ("sq_b", C.c_void_p),
+                ("csls_row", C.c_void_p), ("csls_col", C.c_void_p), ("row_best", C.c_void_p), ("col_best", C.c_void_p),
+                ("flags", C.c_int)]
+
+
+def align_mutual(a, b, kpad, metric=METRIC_INNER, sq_a=None, sq_b=None, csls_row=None, csls_col=None, flags=0, out=None):
+    """mke_align_mutual over row-major padded a [n_a, lda] / b [n_b, ldb] -> (row_best int64 [n_a], col_best int64 [n_b]):
+    per row the packed (re-scored similarity, best column), per column the packed (same similarity, best row), from one
+    sweep.  `out` = (row_best, col_best) zeroed by the caller, in place of fresh tensors."""
+    n_a, n_b = a.shape[0], b.shape[0]
+    row_best, col_best = out if out is not None else (torch.zeros(n_a, dtype=torch.int64, device=a.device),
+                                                      torch.zeros(n_b, dtype=torch.int64, device=a.device))
+    if row_best.numel() < n_a or col_best.numel() < n_b:
+        raise MultiKEHipError(f"align_mutual: out holds ({row_best.numel()}, {col_best.numel()}) words, ({n_a}, {n_b}) rows and columns")
+    args = MutualArgs(_dev(a, torch.float32, "a"), a.shape[1], _dev(b, torch.float32, "b"), b.shape[1], kpad, n_a, n_b, metric,
+                      _dev(sq_a, torch.float32, "sq_a"), _dev(sq_b, torch.float32, "sq_b"),
+                      _dev(csls_row, torch.float32, "csls_row"), _dev(csls_col, torch.float32, "csls_col"),
+                      _dev(row_best, torch.int64, "row_best"), _dev(col_best, torch.int64, "col_best"), flags)
+    _check(lib().mke_align_mutual(C.byref(args), _stream()), "mke_align_mutual")
+    return row_best, col_best
+
+
+def mutual_pairs(row_best, col_best, threshold=float("-inf")):
+    """mke_mutual_pairs over the words of align_mutual -> (match int32 [n_a], counts int32 [2]): match[i] = the column whose best
+    row is i and that is i's best column, at a value >= threshold, else -1; counts = (matched, matched to its own index)."""
+    n_a, n_b = row_best.numel(), col_best.numel()
+    match = torch.empty(n_a, dtype=torch.int32, device=row_best.device)
+    counts = torch.empty(2, dtype=torch.int32, device=row_best.device)     # zeroed by the call
+    rc = lib().mke_mutual_pairs(_dev(row_best, torch.int64, "row_best"), _dev(col_best, torch.int64, "col_best"), C.c_int64(n_a),
+                                C.c_int64(n_b), C.c_float(threshold), _dev(match, torch.int32, "match"),
+                                _dev(counts, torch.int32, "counts"), _stream())
+    _check(rc, "mke_mutual_pairs")
+    return match, counts
 
 
 def gemm_f32(lhs, rhs, out, transpose_a=False, transpose_b=False, splits=1, accumulate=False):

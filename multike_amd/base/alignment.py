@@ -3,6 +3,8 @@ the gold counterpart under the (normalised) inner-product similarity — on the 
 euclidean metric and CSLS re-scoring via `mke_align_topk_mean` + `mke_align_rank_ex`; `stable_alignment` (:82-128) — the
 one-to-one Gale-Shapley matching — via `mke_stable_lists` + `mke_stable_rounds` + `mke_stable_finish`; Sinkhorn re-scoring
 (`sinkhorn=(iters, tau)`, the soft one-to-one decoder) via `mke_align_lse`, whose potentials ride the CSLS plumbing.
+`mutual_pairs` / `mutual_alignment` (no counterpart in the reference) — the pairs that are each other's best, with precision /
+recall / F1 — via `mke_align_mutual` + `mke_mutual_pairs`: one sweep folds every similarity into both directions.
 The n1 x n2 similarity matrix is never materialised (the reference holds 60K x 60K fp32 = 14 GB and argsorts its rows
 in `nums_threads` worker processes)."""
 from __future__ import annotations
@@ -284,6 +286,64 @@ def stable_alignment(embed1, embed2, metric, normalize, csls_k, nums_threads, cu
     cost = time.time() - t
     print("stable alignment precision = {:.3f}%, time = {:.3f} s ".format(precision, cost))
     return match, precision
+
+
+def _best_value(best):
+    """float32 values of packed `best` words (ordered(s) << 32 | ...) on the device; a word of 0 (no best) decodes to NaN."""
+    u = (best >> 32) & 0xFFFFFFFF
+    bits = torch.where((u & 0x80000000) != 0, u & 0x7FFFFFFF, ~u & 0xFFFFFFFF)
+    return (bits - ((bits >> 31) << 32)).to(torch.int32).view(torch.float32)       # the 32 bits as a signed word, then as a float
+
+
+def mutual_pairs(embed1, embed2, metric="inner", normalize=True, csls_k=0, threshold=None, *, sinkhorn=None):
+    """The mutual (bidirectional) nearest-neighbour decoder: (match int32 [n1], score float32 [n1]), both on the device.
+    match[i] = j when column j is row i's best AND row i is column j's best under the similarity (the lowest index wins a tie
+    in both directions), else -1; score[i] = the similarity of row i's best column, matched or not (NaN for a row whose
+    similarities are all NaN).  Any n1, n2 and no gold labels: this is the label-free decoder.  csls_k > 0 or sinkhorn = (iters,
+    tau) re-score as greedy_alignment does, and then `score` and `threshold` are in units of the RE-SCORED value the decoder
+    compares — (2 s - r_T[i]) - r_S[j] for CSLS, 2 (s - a_i - b_j) for Sinkhorn — not of the raw similarity.  `threshold`
+    (None = none) keeps the pairs whose value is >= it.  One sweep (mke_align_mutual) decides both directions on one f32 value."""
+    _check_metric(metric, "mutual_pairs")
+    csls_k, sinkhorn = _check_rescoring(csls_k, sinkhorn)
+    if threshold is not None and np.isnan(float(threshold)):
+        raise _lib.MultiKEHipError("mutual_pairs: the threshold is NaN (None = no threshold)")
+    match, _, row_best = _mutual(embed1, embed2, metric, normalize, csls_k, threshold, sinkhorn)
+    return match, _best_value(row_best)
+
+
+def _mutual(embed1, embed2, metric, normalize, csls_k, threshold, sinkhorn):
+    """(match, counts, row_best) of the checked arguments: the operand path of the other decoders, one sweep, one pairing."""
+    operands = prepare_operands(embed1, embed2, metric, normalize, "cuda")
+    a, b, kpad, code, sq1, sq2 = operands
+    terms = _rescoring_terms(operands, csls_k, sinkhorn) if min(a.shape[0], b.shape[0]) > 0 else None
+    row_best, col_best = _lib.align_mutual(a, b, kpad, code, sq1, sq2, *(terms or (None, None)))
+    match, counts = _lib.mutual_pairs(row_best, col_best, float("-inf") if threshold is None else float(threshold))
+    return match, counts, row_best
+
+
+def mutual_alignment(embed1, embed2, metric, normalize, csls_k, nums_threads, threshold=None, *, sinkhorn=None):
+    """Mutual nearest-neighbour alignment against the gold column = row index.  Returns (match, precision, recall, f1): match
+    int64 [n1] on the host as mutual_pairs'; precision = gold pairs / matched rows * 100, recall = gold pairs / n1 * 100, f1
+    their harmonic mean, all 0.0 when nothing matched.  `threshold` applies to the value the decoder compares (re-scored when
+    csls_k or sinkhorn is set, see mutual_pairs).  `nums_threads` is accepted and ignored."""
+    _check_metric(metric, "mutual_alignment")
+    csls_k, sinkhorn = _check_rescoring(csls_k, sinkhorn)
+    if len(embed2) < len(embed1):
+        raise _lib.MultiKEHipError("mutual_alignment: gold column = row index needs len(embed2) >= len(embed1)")
+    if threshold is not None and np.isnan(float(threshold)):
+        raise _lib.MultiKEHipError("mutual_alignment: the threshold is NaN (None = no threshold)")
+    t = time.time()
+    match, counts, _ = _mutual(embed1, embed2, metric, normalize, csls_k, threshold, sinkhorn)
+    matched, gold = (int(x) for x in counts.cpu().tolist())
+    match = match.cpu().numpy().astype(np.int64)
+    n1 = match.shape[0]
+    precision = gold / matched * 100 if matched else 0.0
+    recall = gold / n1 * 100 if matched else 0.0
+    f1 = 2 * precision * recall / (precision + recall) if gold else 0.0
+    cost = time.time() - t
+    print("mutual alignment precision = {:.3f}%, recall = {:.3f}%, f1 = {:.3f}%, matched = {}, time = {:.3f} s ".format(
+        precision, recall, f1, matched, cost))
+    return match, precision, recall, f1
 
 
 def print_results(top_k, hits, mr, mrr, cost, accurate, csls_k=0, sinkhorn=None):

@@ -1,5 +1,5 @@
 // mke_rescore.h — what the evaluator's sweeps share (k_align_rank of mke_eval.hip, k_topk_partial of mke_csls.hip,
-// k_lse_partial of mke_sinkhorn.hip, k_stable_select of mke_stable.hip): the metric / CSLS epilogue of one similarity, its
+// k_lse_partial of mke_sinkhorn.hip, k_stable_select of mke_stable.hip, k_align_mutual of mke_mutual.hip): the metric / CSLS epilogue of one similarity, its
 // dispatch on the host, the one check of a sweep client's operands, the column split of the partial sweeps, and the bounds of
 // the whole-row rounds.
 #pragma once

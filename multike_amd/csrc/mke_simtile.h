@@ -1,6 +1,6 @@
 // mke_simtile.h — the f32 MFMA sweep behind every similarity the project reports, and what its clients need besides it.
 // Clients: k_align_rank (mke_eval.hip, behind mke_align_rank and mke_align_rank_ex), k_topk_partial (mke_csls.hip),
-// k_lse_partial (mke_sinkhorn.hip), k_sim_select and k_sim_sample (mke_knn.hip), k_stable_select (mke_stable.hip).  The sweep: similarities of a block's 128 rows against a range of
+// k_lse_partial (mke_sinkhorn.hip), k_sim_select and k_sim_sample (mke_knn.hip), k_stable_select (mke_stable.hip), k_align_mutual (mke_mutual.hip).  The sweep: similarities of a block's 128 rows against a range of
 // 64-column tiles, handed tile by tile to an epilogue that folds them into whatever the client wants (candidate lists, rank
 // counters, top-k buffers) — the similarity matrix itself never exists.  Besides it: the accumulator row map (simt_row),
 // the one list of supported widths (simt_for_kpad) and the column split of a launch (simt_split, simt_split_fixed).

@@ -73,6 +73,10 @@ class _ShardedMixin:
             raise _lib.MultiKEHipError("sinkhorn_iters > 0: the Sinkhorn re-scoring is not sharded over ranks (its potentials "
                                        "couple every row with every column); run the single-GPU driver (python -m multike_amd.run) "
                                        "or set sinkhorn_iters=0")
+        if int(getattr(args, "mutual", 0) or 0) > 0:
+            raise _lib.MultiKEHipError("mutual > 0: the mutual nearest-neighbour alignment is not sharded over ranks (a column's "
+                                       "best row is taken over all rows); run the single-GPU driver (python -m multike_amd.run) "
+                                       "or set mutual=0")
         self.kgs = kgs = data.kgs
         self.kg1, self.kg2 = kgs.kg1, kgs.kg2
         self.rank, self.world = rank, world

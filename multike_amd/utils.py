@@ -48,6 +48,9 @@ def default_args(**over):
         stable_cut=0,
         # Sinkhorn re-scoring of the final tests: `sinkhorn_iters` iterations (0 = off) at temperature `sinkhorn_tau`; not with `csls`
         sinkhorn_iters=0, sinkhorn_tau=0.05,
+        # mutual nearest-neighbour alignment of the final tests (0 = off): precision / recall / F1 of the pairs that are each
+        # other's best, at or above `mutual_threshold` (None = none; in units of the re-scored value when `csls` / Sinkhorn is on)
+        mutual=0, mutual_threshold=None,
         # view combination and predicate soft alignment
         orthogonal_weight=2, cv_name_weight=1, cv_weight=1, start_predicate_soft_alignment=10, predicate_soft_sim=0.85,
         predicate_init_sim=0.90)
