@@ -232,6 +232,8 @@ int mke_count_entity_refs(const int32_t* pos_h, const int32_t* pos_t, int64_t n_
  *     normalize: s = sum w^2; inv = rsqrt(max(s,1e-12)); what = w*inv;
  *                g = (s > 1e-12) ? (ghat - what*(what.ghat))*inv : ghat*inv     else g = ghat
  *     ADAGRAD: acc += g*g; w -= lr*g/sqrt(acc)        SGD: w -= lr*g   (acc may be NULL)
+ *   The rule runs over all `stride` columns of a visited row, so accumulator pad columns must be positive (0.1, as TF
+ *   initialises the accumulator): with acc == 0 there, 0 * rsqrt(0) puts NaN into the table's pad column.
  * ------------------------------------------------------------------------------------------------ */
 int mke_rows_update(
     float* table, float* acc /*nullable for SGD*/, float* grad, int grad_copies /* grad is [copies][n_rows][stride] */,
