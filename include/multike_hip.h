@@ -983,6 +983,71 @@ int mke_mutual_pairs(const uint64_t* row_best, const uint64_t* col_best, int64_t
                      int32_t* match, int32_t* counts, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * (9f) Optimal one-to-one alignment: an auction over the candidate lists (additions only; version unchanged).
+ *
+ * The one-to-one pairing that maximises the sum of similarities ("Hungarian"), over the instance in which every row keeps
+ * only its `cut` best columns (the lists of mke_stable_lists, under any metric or re-scoring) and may stay unmatched at the
+ * value `floor`.  The reference has no counterpart.  Bertsekas' forward auction in Jacobi form: all prices start at 0; in a
+ * round every row that holds no column and has not settled unmatched takes, against the prices at the start of the round,
+ *     v1 = the largest val[k] - price[col[k]] over its list (the lowest list position among equal values),
+ *     v2 = the largest of the other entries and `floor`;
+ * v1 < floor: it settles unmatched for good; else it bids (price[j] + (v1 - v2)) + eps on its best column j.  Every column
+ * that received bids goes to the highest bid (the lowest row among equal bids), its price becomes that bid, and the row it
+ * held before bids again next round.  A column outside [0, n_b) ends a list; an entry whose value is not finite is skipped.
+ * Every step is one f32 operation in the order written, so state, price and progress are the same bits on every run, in
+ * every form below and in the NumPy definition (tests/assign_oracle.py).
+ *
+ * Guarantee at the fixed point (nobody bids): every row is within eps of its best option at the final prices (eps-
+ * complementary slackness), a column nobody holds still has price 0, and a column once held is held for ever.  By the duality
+ * argument for the asymmetric assignment problem,
+ *     total = sum of the matched values + floor x unmatched rows  >=  optimum of the truncated instance - n_a x eps.
+ * With f32 rounding the bound is n_a x (eps + 2^-16) provided (largest finite listed value - floor) + eps <= 16: prices then
+ * stay below 16, where an f32 ulp is at most 2^-19, and a bid with the two comparisons it rests on rounds at most six times
+ * (6 x 2^-19 < 2^-16).  The caller checks that range (base.alignment.assignment_alignment does); eps < 2^-14, where price +
+ * eps could stop being a strict increase, is refused here.
+ *
+ *   mke_assign_rounds: at most n_rounds more rounds; never synchronises.  The caller zeroes state, price, owner, bid and
+ *     progress before the first call; temp needs no initialisation and belongs to the run until it ends.
+ *       grid form: two launches per round (bid: a wavefront per bidding row, one 64-bit atomic max per bid; commit: a thread
+ *         per row), so that no block reads a word another block writes in the same launch.  Between the two launches of a
+ *         round state also holds -(j + 2) (bid on column j, undecided) and INT32_MIN (settling); never after a call.
+ *       tail form: once at most tail_cap rows are bidding (their number never grows: a winner displaces at most one row) the
+ *         grid launches return at once, having read progress, and ONE workgroup runs the remaining rounds of the call, the
+ *         bidding rows in LDS.  tail_cap: 0 = MKE_ASSIGN_TAIL_CAP; values above 4096 act as 4096.
+ *       flags: MKE_ASSIGN_NO_TAIL: every round as grid launches.  MKE_ASSIGN_TAIL_ONLY: the caller has read progress[1] <=
+ *         tail_cap (or n_a <= tail_cap before the first round): no grid launch is enqueued, the call is the tail's one launch
+ *         (it does nothing if the tail has not taken over).  Both together: MKE_E_UNSUPPORTED.
+ *     A call made when nobody is bidding any more costs launches that return at once: one with MKE_ASSIGN_TAIL_ONLY.
+ *     progress: [0] rounds run, [1] rows still bidding (valid once a round has run), [2] bids made, [3] rows settled unmatched.
+ *     Errors, before any launch: NULL pointers MKE_E_NULL; cut < 1, n_a / n_b negative or above 0x7FFFFF00, n_rounds < 0,
+ *     tail_cap < 0, temp below mke_assign_temp_bytes: MKE_E_SHAPE; eps or floor not finite, eps < 2^-14: MKE_E_RANGE.
+ *   mke_assign_temp_bytes(n_a, n_b, tail_cap): scratch bytes, or a negative MKE_E_*.
+ *   mke_assign_finish: match[i] = the column row i holds, or -1; counts[0] = matched rows, counts[1] = rows with match[i] == i,
+ *     counts[2] = rows settled unmatched; counts is zeroed BY THE CALL.
+ * ------------------------------------------------------------------------------------------------ */
+#define MKE_ASSIGN_TAIL_CAP 16
+#define MKE_ASSIGN_NO_TAIL 1
+#define MKE_ASSIGN_TAIL_ONLY 2
+typedef struct mke_assign_args {
+  int64_t n_a, n_b; int cut;
+  const float* val; const int32_t* col;     /* [n_a][cut], mke_stable_lists' layout */
+  float eps, floor;
+  int32_t* state;      /* [n_a]  0 = bids next round, j + 1 = holds column j, -1 = settled unmatched */
+  float* price;        /* [n_b] */
+  int32_t* owner;      /* [n_b]  row + 1, 0 = free */
+  uint64_t* bid;       /* [n_b]  ordered(bid) << 32 | 0xFFFFFFFF - row */
+  int64_t* progress;   /* [4]    rounds run, rows still bidding, bids made, rows settled unmatched */
+  int tail_cap;        /* 0 = default; > 0 forces the hand-over point (tests, tuning) */
+  int flags;           /* bit 0: no tail kernel, every round as grid launches; bit 1: the tail's launch only */
+  void* temp; int64_t temp_bytes;
+  int32_t* match;      /* [n_a], finish only: column or -1 */
+  int32_t* counts;     /* [3], finish only: matched rows, rows with match[i] == i, rows settled unmatched */
+} mke_assign_args;
+int64_t mke_assign_temp_bytes(int64_t n_a, int64_t n_b, int tail_cap);
+int mke_assign_rounds(const mke_assign_args* args, int n_rounds, void* stream);   /* at most n_rounds more rounds; never synchronises */
+int mke_assign_finish(const mke_assign_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * (10) Small dense f32 GEMM on the matrix cores (v_mfma_f32_32x32x2_f32, exact f32) with arbitrary operand strides:
  *        C[M][N] (=|+=) A[M][K] . B[K][N],  A(i,k) = A[i*a_row_stride + k*a_col_stride], likewise B.
  *      splits > 1: split-K, partial products are added atomically (accumulate must be 1; C zeroed or holding the

@@ -11,7 +11,7 @@ import time
 import numpy as np
 
 from .base import evaluation as eva
-from .base.alignment import mutual_alignment, stable_alignment
+from .base.alignment import assignment_alignment, mutual_alignment, stable_alignment
 from .base.batch import neighbour_table
 from .MultiKE_model import MultiKE
 from .utils import sinkhorn_option, task_divide
@@ -81,6 +81,7 @@ def test(model, embed_choice='avg', w=(1, 1, 1)):
                           csls_k=_csls_k(model), sinkhorn=_sinkhorn(model))
     _stable(model, embeds1, embeds2)
     _mutual(model, embeds1, embeds2)
+    _assign(model, embeds1, embeds2)
     return mrr_12
 
 
@@ -112,6 +113,18 @@ def _mutual(model, embeds1, embeds2):
     if int(getattr(model.args, "mutual", 0) or 0) > 0:
         mutual_alignment(embeds1, embeds2, 'inner', True, _csls_k(model), model.args.test_threads_num,
                          threshold=getattr(model.args, "mutual_threshold", None), sinkhorn=_sinkhorn(model))
+
+
+def _assign(model, embeds1, embeds2):
+    """Hyper-parameters `assign_cut` (0 = off) / `assign_eps` / `assign_floor` (absent or None = the smallest listed value - 1):
+    after the greedy (stable, mutual) lines of a test, precision / recall / F1 of the optimal one-to-one assignment of the same
+    rows over every row's `assign_cut` best targets, CSLS or Sinkhorn re-scored as the test is (the floor is then in units of
+    the re-scored value)."""
+    cut = int(getattr(model.args, "assign_cut", 0) or 0)
+    if cut > 0:
+        assignment_alignment(embeds1, embeds2, 'inner', True, _csls_k(model), model.args.test_threads_num, cut=cut,
+                             eps=float(getattr(model.args, "assign_eps", None) or 1e-3), floor=getattr(model.args, "assign_floor", None),
+                             sinkhorn=_sinkhorn(model))
 
 
 def _unit_rows(x):
@@ -159,6 +172,7 @@ def _wva_eval(model, ents1, ents2, label, keys=None, csls_k=0, stable=False, sin
     if stable:
         _stable(model, embeds1, embeds2)
         _mutual(model, embeds1, embeds2)
+        _assign(model, embeds1, embeds2)
     return mrr_12
 
 

@@ -42,6 +42,7 @@ SYMBOLS = (
     "mke_tripleset_forget", "mke_tripleset_filter_bytes", "mke_epoch_positives",
     "mke_align_lse_temp_bytes", "mke_align_lse",
     "mke_align_mutual", "mke_mutual_pairs",
+    "mke_assign_temp_bytes", "mke_assign_rounds", "mke_assign_finish",
 )
 ACT_NONE, ACT_TANH, ACT_SIGMOID = 0, 1, 2
 AE_MAX_LAYERS = 4
@@ -283,6 +284,7 @@ def lib():
         L.mke_stable_lists_temp_bytes.restype = C.c_int64
         L.mke_align_lse_temp_bytes.restype = C.c_int64
         L.mke_tripleset_filter_bytes.restype = C.c_int64
+        L.mke_assign_temp_bytes.restype = C.c_int64
         _lib = L
         # MKE_OPTIONS="name=value,name=value": mke_set_option calls applied at load (performance knobs for experiments)
         for kv in filter(None, os.environ.get("MKE_OPTIONS", "").split(",")):
@@ -1159,6 +1161,50 @@ def mutual_pairs(row_best, col_best, threshold=float("-inf")):
                                 _dev(counts, torch.int32, "counts"), _stream())
     _check(rc, "mke_mutual_pairs")
     return match, counts
+
+
+ASSIGN_TAIL_CAP = 16                       # MKE_ASSIGN_TAIL_CAP: the default hand-over point of the auction's tail kernel
+ASSIGN_TAIL_MAX = 4096                     # larger tail_cap values act as this one
+ASSIGN_NO_TAIL, ASSIGN_TAIL_ONLY = 1, 2    # MKE_ASSIGN_*
+ASSIGN_MIN_EPS = 2.0 ** -14
+
+
+class AssignArgs(C.Structure):
+    """mke_assign_args"""
+    _fields_ = [("n_a", C.c_int64), ("n_b", C.c_int64), ("cut", C.c_int), ("val", C.c_void_p), ("col", C.c_void_p),
+                ("eps", C.c_float), ("floor", C.c_float), ("state", C.c_void_p), ("price", C.c_void_p), ("owner", C.c_void_p),
+                ("bid", C.c_void_p), ("progress", C.c_void_p), ("tail_cap", C.c_int), ("flags", C.c_int), ("temp", C.c_void_p),
+                ("temp_bytes", C.c_int64), ("match", C.c_void_p), ("counts", C.c_void_p)]
+
+
+def assign_temp_bytes(n_a: int, n_b: int, tail_cap: int = 0) -> int:
+    """mke_assign_temp_bytes; raises on the arguments mke_assign_rounds would reject."""
+    r = int(lib().mke_assign_temp_bytes(C.c_int64(n_a), C.c_int64(n_b), C.c_int(tail_cap)))
+    _check(r if r < 0 else 0, "mke_assign_temp_bytes")
+    return r
+
+
+def assign_args(val, col, n_b, eps, floor, state, price, owner, bid, progress, temp, tail_cap=0, flags=0, match=None,
+                counts=None) -> AssignArgs:
+    """mke_assign_args over the lists val / col [n_a, cut] and the state of a run: state [n_a] int32, price [n_b] float32,
+    owner [n_b] int32, bid [n_b] int64, progress [4] int64 (all zeroed before the first round), temp (int32, at least
+    assign_temp_bytes); match [n_a] int32 and counts [3] int32 for assign_finish."""
+    n_a, cut = col.shape
+    return AssignArgs(n_a, n_b, cut, _dev(val, torch.float32, "val"), _dev(col, torch.int32, "col"), float(eps), float(floor),
+                      _dev(state, torch.int32, "state"), _dev(price, torch.float32, "price"), _dev(owner, torch.int32, "owner"),
+                      _dev(bid, torch.int64, "bid"), _dev(progress, torch.int64, "progress"), tail_cap, flags,
+                      _dev(temp, torch.int32, "temp"), temp.numel() * 4 if temp is not None else 0,
+                      _dev(match, torch.int32, "match"), _dev(counts, torch.int32, "counts"))
+
+
+def assign_rounds(args: AssignArgs, n_rounds: int):
+    """mke_assign_rounds: enqueue at most n_rounds more rounds of the auction (no synchronisation)."""
+    _check(lib().mke_assign_rounds(C.byref(args), C.c_int(n_rounds), _stream()), "mke_assign_rounds")
+
+
+def assign_finish(args: AssignArgs):
+    """mke_assign_finish: match[i] = the column row i holds or -1; counts = (matched, matched to its own index, settled unmatched)."""
+    _check(lib().mke_assign_finish(C.byref(args), _stream()), "mke_assign_finish")
 
 
 def gemm_f32(lhs, rhs, out, transpose_a=False, transpose_b=False, splits=1, accumulate=False):

@@ -5,6 +5,8 @@ one-to-one Gale-Shapley matching — via `mke_stable_lists` + `mke_stable_rounds
 (`sinkhorn=(iters, tau)`, the soft one-to-one decoder) via `mke_align_lse`, whose potentials ride the CSLS plumbing.
 `mutual_pairs` / `mutual_alignment` (no counterpart in the reference) — the pairs that are each other's best, with precision /
 recall / F1 — via `mke_align_mutual` + `mke_mutual_pairs`: one sweep folds every similarity into both directions.
+`assignment_matching` / `assignment_alignment` (no counterpart either) — the one-to-one pairing that maximises the total
+similarity over the stable matching's candidate lists, by a parallel auction — via `mke_assign_rounds` + `mke_assign_finish`.
 The n1 x n2 similarity matrix is never materialised (the reference holds 60K x 60K fp32 = 14 GB and argsorts its rows
 in `nums_threads` worker processes)."""
 from __future__ import annotations
@@ -343,6 +345,115 @@ def mutual_alignment(embed1, embed2, metric, normalize, csls_k, nums_threads, th
     cost = time.time() - t
     print("mutual alignment precision = {:.3f}%, recall = {:.3f}%, f1 = {:.3f}%, matched = {}, time = {:.3f} s ".format(
         precision, recall, f1, matched, cost))
+    return match, precision, recall, f1
+
+
+ASSIGN_ROUND_BATCH = 32      # rounds enqueued between two reads of the auction's progress counters (grid form)
+ASSIGN_TAIL_FACTOR = 32      # ... times this many once the tail kernel has taken over: a round is then a loop iteration, not two launches
+ASSIGN_VALUE_RANGE = 16.0    # (largest listed value - floor) + eps may not exceed this: the f32 form of the guarantee rests on it
+
+
+def _auction(val, col, n2, eps, floor, batch, max_rounds, tail_cap, flags):
+    """The auction to its fixed point -> (state int32 [n1], price float32 [n2], progress int64 [4], kernel launches enqueued);
+    the tensors on the device.  One read-back of two counters per batch of rounds, as stable_matching's loop."""
+    if flags & ~_lib.ASSIGN_NO_TAIL:
+        raise _lib.MultiKEHipError(f"assignment_matching: flags {flags} (0, or {_lib.ASSIGN_NO_TAIL}: no tail kernel)")
+    n1, dev = col.shape[0], col.device
+    state = torch.zeros(n1, dtype=torch.int32, device=dev)
+    price = torch.zeros(n2, dtype=torch.float32, device=dev)
+    owner = torch.zeros(n2, dtype=torch.int32, device=dev)
+    bid = torch.zeros(n2, dtype=torch.int64, device=dev)
+    progress = torch.zeros(4, dtype=torch.int64, device=dev)
+    temp = torch.empty(_lib.assign_temp_bytes(n1, n2, tail_cap) // 4, dtype=torch.int32, device=dev)
+    cap = 0 if flags & _lib.ASSIGN_NO_TAIL else min(tail_cap or _lib.ASSIGN_TAIL_CAP, _lib.ASSIGN_TAIL_MAX)
+    rounds, bidding, launches = 0, n1, 0
+    while bidding > 0:
+        if rounds >= max_rounds:
+            raise _lib.MultiKEHipError(f"assignment_matching: {bidding} rows are still bidding after {rounds} rounds (max_rounds); "
+                                       f"eps = {eps} may be too small for these values: the rounds grow like (value range) / eps")
+        tail = 0 < bidding <= cap          # the tail kernel has taken over for good: the number of bidding rows never grows
+        n = min(batch * ASSIGN_TAIL_FACTOR if tail else batch, max_rounds - rounds)
+        args = _lib.assign_args(val, col, n2, eps, floor, state, price, owner, bid, progress, temp, tail_cap,
+                                flags | (_lib.ASSIGN_TAIL_ONLY if tail else 0))
+        _lib.assign_rounds(args, n)
+        launches += (0 if tail else 2 * n) + (1 if cap else 0)
+        rounds, bidding = progress[:2].tolist()      # the only synchronisation: two counters per batch of rounds
+    return state, price, progress, launches
+
+
+def assignment_matching(val, col, n2, eps, floor, batch=ASSIGN_ROUND_BATCH, max_rounds=1 << 20, tail_cap=0, flags=0):
+    """(match int32 [n1], price float32 [n2], progress int64 [4]), all on the device: the optimal one-to-one assignment of the
+    instance in which every row keeps the columns of its list (val / col [n1, cut] of candidate_lists) and may stay unmatched
+    at the value `floor`, by Bertsekas' forward auction (mke_assign_rounds) run to its fixed point.  match[i] = the column of
+    row i or -1; total = sum of the matched values + floor * unmatched rows >= the optimum of that instance - n1 * eps (with
+    f32 rounding n1 * (eps + 2^-16) while (largest value - floor) + eps <= 16).  progress = rounds run, rows still bidding (0),
+    bids made, rows settled unmatched.  More than `max_rounds` rounds raise, naming eps.  `tail_cap` / `flags` select the
+    hand-over point of the tail kernel and the form without it (tests, tuning): the result is the same bit for bit."""
+    state, price, progress, _ = _auction(val, col, n2, eps, floor, int(batch), int(max_rounds), int(tail_cap), int(flags))
+    n1 = col.shape[0]
+    match = torch.empty(n1, dtype=torch.int32, device=col.device)
+    counts = torch.empty(3, dtype=torch.int32, device=col.device)     # zeroed by the call
+    _lib.assign_finish(_lib.assign_args(val, col, n2, eps, floor, state, None, None, None, None, None, match=match, counts=counts))
+    return match, price, progress
+
+
+def assignment_alignment(embed1, embed2, metric, normalize, csls_k, nums_threads, cut=100, eps=1e-3, floor=None, sim_mat=None, *,
+                         sinkhorn=None):
+    """Optimal one-to-one alignment ("Hungarian") against the gold column = row index, without the matrix.  Returns (match,
+    precision, recall, f1): match int64 [n1] on the host, match[i] = the row of embed2 assigned to row i of embed1 or -1; the
+    pairing maximises the sum of similarities over the instance in which every row keeps its `cut` best columns (the lists of
+    stable_alignment, under the same metric / CSLS / Sinkhorn re-scoring or a given sim_mat), to within n1 * (eps + 2^-16) of
+    that instance's optimum (assignment_matching).  `floor` is the value of staying unmatched, in units of the value the lists
+    hold (re-scored when csls_k or sinkhorn is set); None = the smallest finite listed value - 1, so that any listed pair beats
+    staying unmatched.  (largest listed value - floor) + eps above 16 is refused: the f32 form of the guarantee rests on it.
+    precision = gold pairs / matched rows * 100, recall = gold pairs / n1 * 100, f1 their harmonic mean, all 0.0 when nothing
+    matched.  `nums_threads` is accepted and ignored."""
+    _check_metric(metric, "assignment_alignment")
+    csls_k, sinkhorn = _check_rescoring(csls_k, sinkhorn)
+    if sinkhorn is not None and sim_mat is not None:
+        raise _lib.MultiKEHipError("assignment_alignment: sinkhorn re-scores the embeddings' similarities; a given sim_mat is used as it is")
+    if sim_mat is None and len(embed2) < len(embed1):
+        raise _lib.MultiKEHipError("assignment_alignment: gold column = row index needs len(embed2) >= len(embed1)")
+    if not (np.isfinite(float(eps)) and float(eps) >= _lib.ASSIGN_MIN_EPS):
+        raise _lib.MultiKEHipError(f"assignment_alignment: eps = {eps} (needs a finite eps >= 2^-14)")
+    t = time.time()
+    if sim_mat is not None:
+        if not isinstance(sim_mat, torch.Tensor):
+            sim_mat = torch.as_tensor(np.asarray(sim_mat), dtype=torch.float32).to("cuda")
+        sim_mat = sim_mat.float().contiguous()
+        n1, n2 = sim_mat.shape
+        if n2 < n1:
+            raise _lib.MultiKEHipError("assignment_alignment: gold column = row index needs len(embed2) >= len(embed1)")
+        val, col, _ = candidate_lists(None, None, 0, max(1, min(int(cut), n2)), sim_mat=sim_mat)
+    else:
+        operands = prepare_operands(embed1, embed2, metric, normalize, "cuda")
+        a, b, kpad, code, sq1, sq2 = operands
+        n1, n2 = a.shape[0], b.shape[0]
+        val, col, _ = candidate_lists(a, b, kpad, max(1, min(int(cut), n2)), code, sq1, sq2, _rescoring_terms(operands, csls_k, sinkhorn))
+    listed = (col >= 0) & torch.isfinite(val)
+    inf = torch.full_like(val, float("inf"))
+    lo, hi = torch.stack([torch.where(listed, val, inf).min(), torch.where(listed, val, -inf).max()]).tolist() if n1 > 0 else (0.0, 0.0)
+    print("generating candidate lists costs time {:.3f} s ".format(time.time() - t))     # the read-back above synchronised
+    if not np.isfinite(lo):                                                               # nothing listed at all
+        lo = hi = 0.0
+    floor = lo - 1.0 if floor is None else float(floor)
+    if not np.isfinite(floor):
+        raise _lib.MultiKEHipError(f"assignment_alignment: floor = {floor} is not finite")
+    if (hi - floor) + float(eps) > ASSIGN_VALUE_RANGE:
+        raise _lib.MultiKEHipError(f"assignment_alignment: (largest listed value {hi} - floor {floor}) + eps {eps} exceeds "
+                                   f"{ASSIGN_VALUE_RANGE}: scale the similarities or raise floor")
+    t = time.time()
+    match, _, progress = assignment_matching(val, col, n2, float(eps), floor)
+    match = match.cpu().numpy().astype(np.int64)
+    rounds = int(progress[0])
+    matched = int((match >= 0).sum())
+    gold = int((match == np.arange(n1)).sum())
+    precision = gold / matched * 100 if matched else 0.0
+    recall = gold / n1 * 100 if matched else 0.0
+    f1 = 2 * precision * recall / (precision + recall) if gold else 0.0
+    cost = time.time() - t
+    print("optimal assignment precision = {:.3f}%, recall = {:.3f}%, f1 = {:.3f}%, matched = {}, rounds = {}, time = {:.3f} s ".format(
+        precision, recall, f1, matched, rounds, cost))
     return match, precision, recall, f1
 
 

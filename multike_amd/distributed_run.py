@@ -69,6 +69,10 @@ class _ShardedMixin:
         if int(getattr(args, "stable_cut", 0) or 0) > 0:
             raise _lib.MultiKEHipError("stable_cut > 0: the stable (Gale-Shapley) alignment is not sharded over ranks; "
                                        "run the single-GPU driver (python -m multike_amd.run) or set stable_cut=0")
+        if int(getattr(args, "assign_cut", 0) or 0) > 0:
+            raise _lib.MultiKEHipError("assign_cut > 0: the optimal assignment (auction) is not sharded over ranks (a column's "
+                                       "price couples all rows); run the single-GPU driver (python -m multike_amd.run) or set "
+                                       "assign_cut=0")
         if int(getattr(args, "sinkhorn_iters", 0) or 0) > 0:
             raise _lib.MultiKEHipError("sinkhorn_iters > 0: the Sinkhorn re-scoring is not sharded over ranks (its potentials "
                                        "couple every row with every column); run the single-GPU driver (python -m multike_amd.run) "

@@ -51,6 +51,10 @@ def default_args(**over):
         # mutual nearest-neighbour alignment of the final tests (0 = off): precision / recall / F1 of the pairs that are each
         # other's best, at or above `mutual_threshold` (None = none; in units of the re-scored value when `csls` / Sinkhorn is on)
         mutual=0, mutual_threshold=None,
+        # optimal one-to-one assignment ("Hungarian", by auction) of the final tests over every row's `assign_cut` best targets
+        # (0 = off), to within n * `assign_eps` of that instance's optimum; `assign_floor` = the value of staying unmatched (None =
+        # the smallest listed value - 1; in units of the re-scored value when `csls` / Sinkhorn is on)
+        assign_cut=0, assign_eps=1e-3, assign_floor=None,
         # view combination and predicate soft alignment
         orthogonal_weight=2, cv_name_weight=1, cv_weight=1, start_predicate_soft_alignment=10, predicate_soft_sim=0.85,
         predicate_init_sim=0.90)
