@@ -147,8 +147,11 @@ int mke_triple_score_fwd_bwd(
  *   negative (uniform sampling: ~70 % of the touched rows at the DBP-WD shape).  Such a row is read by one quarter-wave and
  *   receives one gradient contribution, so that quarter-wave can apply the Jacobian + optimizer update itself — the
  *   scatter (atomic read-modify-write of the gradient row) and the later visit by mke_rows_update (3 row reads, 3 row
- *   writes) collapse into 1 accumulator read + 2 row writes.  Result: identical to the two-kernel path (same formulas,
- *   one contribution => no summation-order freedom).
+ *   writes) collapse into 1 accumulator read + 2 row writes.  Result: the two-kernel path's up to rounding (one contribution
+ *   => no summation-order freedom, but not bit for bit: the Jacobian is associated differently (a2 w + a1 ghat here,
+ *   (ghat - w coef) inv in mke_rows_update) and w - lr g s is not contracted alike in the two kernels at every width, so
+ *   from none to a seventh of the table elements of such rows differ in the last bit; tests/test_score_exact_gpu.py holds
+ *   both against float64 within a counted rounding bound).
  *
  *   mke_count_entity_refs: ref_count[e] += occurrences of e in (pos_h, pos_t, neg_h, neg_t), not counting a negative's
  *     entry that repeats its own positive's entity on that side (grouped negatives, neg_per_pos >= 1).  ref_count is
