@@ -624,6 +624,9 @@ int mke_attr_conv_bwd(const float* attr_table, int attr_stride, int attr_normali
                                           left all-zero by every call.  Without it every block accumulates straight into
                                           grad_params: same result, ~3x slower at 5000 triples */,
                       void* stream);
+/* mke_attr_tail_z rewrites all MKE_LOSS_PARTIALS slots of sumsq_partials, mke_attr_tail_loss all slots of dot_partials and
+ * loss_partials (n == 0: zeros); tail_loss and tail_bwd add up every slot of the arrays they read ([total, 0, ...] is valid).
+ * bias is indexed by column (i % dim); grad_ent, touched_ent and grad_bias are added to / marked, never cleared. */
 int mke_attr_tail_z(float* z /* in: zpre, out: z */, const float* bias /* nullable: already in zpre */, int64_t n, int dim,
                     double* sumsq_partials /* [MKE_LOSS_PARTIALS] */, void* stream);
 int mke_attr_tail_loss(const float* z, const double* sumsq_partials, const float* ent_table, int ent_stride,
@@ -724,7 +727,11 @@ int mke_mapping_step(const mke_mapping_step_args* args, double* loss_partials, v
  * owns; multike_amd/distributed_views.py): FWD (gathers, P_k = V_k M_k, partials block 2k) | all-reduce of sum P_k^2 — the
  * caller replaces block 2k by the total | TAIL (losses, G_k, partials block 2k+1) | all-reduce of sum G_k . out_k, block 2k+1
  * replaced | BWD (gM += V_k^T dP_k) | all-reduce of gM | UPD (orthogonality / norm terms added to gM, row scatter, updates).
- * A part with n == 0 contributes zeros.  MKE_MAP_ALL in one call is mke_mapping_step. */
+ * A part with n == 0 contributes zeros.  MKE_MAP_ALL in one call is mke_mapping_step.
+ * FWD rewrites all MKE_LOSS_PARTIALS slots of block 2k, TAIL all slots of block 2k+1 and of every loss block (zeros for the views
+ * beyond n_views), UPD all slots of the last loss block: none needs clearing first.  TAIL and BWD add up every slot of the blocks
+ * they read, so the caller may leave a total as [total, 0, ...] or split over any slots.  BWD adds to gM; UPD adds the
+ * orthogonality / norm terms to gM also when n == 0 (MKE_MAP_ALL with n == 0 moves nothing). */
 #define MKE_MAP_FWD 1
 #define MKE_MAP_TAIL 2
 #define MKE_MAP_BWD 4
