@@ -1058,6 +1058,53 @@ int mke_assign_rounds(const mke_assign_args* args, int n_rounds, void* stream); 
 int mke_assign_finish(const mke_assign_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * (9g) Self-training: a decoder's pairs as a link table, a link table as 'swapping' supervision lists in HBM (additions only;
+ *      version unchanged).
+ *
+ * replaces (for links found DURING training): code/base/read.py:130-164 generate_sup_relation_triples /
+ * generate_sup_attribute_triples, which the reference runs once on the host over train_links.
+ *
+ *   mke_boot_partner: partner[e] = the entity e is paired with, or -1.  The call first sets all n_entities words to -1 (whatever
+ *     they held), then for every i with match[i] = j in [0, n_b) writes partner[ids_a[i]] = ids_b[j] and partner[ids_b[j]] =
+ *     ids_a[i].  match is one-to-one (mke_mutual_pairs, mke_stable_finish, mke_assign_finish write such a match) and the ids of a
+ *     side are distinct.  A match entry outside [-1, n_b) is ignored; a pair either of whose ids lies outside [0, n_entities) is
+ *     ignored as a whole (a one-sided link would put that id into a triple).  n_a == 0 or n_b == 0: only the fill.
+ *     Errors, before any launch: n_a / n_b negative or above 0x7FFFFF00, n_entities outside [0, 2^31): MKE_E_SHAPE; NULL
+ *     pointers: MKE_E_NULL.
+ *   mke_swap_triples: walk k = 0 .. n-1; if partner[h_k] >= 0 emit (partner[h_k], p_k, t_k) with weight[h_k]; then, unless
+ *     heads_only, if partner[t_k] >= 0 emit (h_k, p_k, partner[t_k]) with weight[t_k].  A triple with both ends linked yields two
+ *     entries, head form first, never one entry with both ends replaced (base/kgs.py swap_relation_triples); heads_only = 1 is
+ *     swap_attribute_triples, whose third column is a value id.  An id outside [0, n_entities) counts as unlinked.  The output
+ *     holds the entries in the walk's order (an ordered stream compaction: per-tile counts, an exclusive scan, ranked stores; no
+ *     atomic cursor), so two runs are the same bits.  count[0] = the number of entries the walk emits even when it exceeds
+ *     capacity; entries at positions >= capacity are not stored and nothing is written there.  capacity = 0 asks for the count
+ *     alone.  n == 0: no kernel is launched, count[0] is zeroed by a hipMemsetAsync on the stream.
+ *     A tile of the compaction is MKE_SWAP_TILE consecutive triples (one wavefront).
+ *     Errors, before any launch: NULL args / pointers, weight and out_w not both NULL or both set: MKE_E_NULL; n or n_entities
+ *     outside [0, 2^31), capacity < 0, temp_bytes below mke_swap_temp_bytes(n), temp not 8-byte aligned: MKE_E_SHAPE; flags != 0,
+ *     heads_only not 0 or 1: MKE_E_UNSUPPORTED.
+ *   mke_swap_temp_bytes(n): scratch bytes for a list of n triples, or a negative MKE_E_*.
+ * ------------------------------------------------------------------------------------------------ */
+#define MKE_SWAP_TILE 64
+typedef struct mke_swap_args {
+  const int32_t* h; const int32_t* p; const int32_t* t;   /* [n] the triples in list order */
+  int64_t n;
+  const int32_t* partner; int64_t n_entities;              /* [n_entities] mke_boot_partner's table */
+  const float* weight;                                      /* [n_entities] per linked entity, or NULL: unweighted lists */
+  int heads_only;                                           /* 1: attribute triples, only the head is an entity */
+  int32_t* out_h; int32_t* out_p; int32_t* out_t;         /* [capacity] */
+  float* out_w;                                             /* [capacity], NULL exactly when weight is */
+  int64_t capacity;
+  int64_t* count;                                           /* [1] entries the walk emits */
+  void* temp; int64_t temp_bytes;
+  int flags;                                                /* 0 */
+} mke_swap_args;
+int mke_boot_partner(const int32_t* match, const int32_t* ids_a, int64_t n_a, const int32_t* ids_b, int64_t n_b,
+                     int32_t* partner, int64_t n_entities, void* stream);
+int64_t mke_swap_temp_bytes(int64_t n);
+int mke_swap_triples(const mke_swap_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * (10) Small dense f32 GEMM on the matrix cores (v_mfma_f32_32x32x2_f32, exact f32) with arbitrary operand strides:
  *        C[M][N] (=|+=) A[M][K] . B[K][N],  A(i,k) = A[i*a_row_stride + k*a_col_stride], likewise B.
  *      splits > 1: split-K, partial products are added atomically (accumulate must be 1; C zeroed or holding the

@@ -39,6 +39,7 @@ class MultiKE_CV(_ScheduledMultiKE):
                     break
             if i >= a.start_predicate_soft_alignment and i % 10 == 0:
                 self._update_predicate_alignment()
+            self._bootstrap(i)
             self._refresh_neighbours(i)
         self._finish_predicate_update()
         self._save_async = True

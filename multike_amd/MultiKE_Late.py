@@ -10,9 +10,13 @@ import time
 
 import numpy as np
 
+from . import _lib
+from .base import bootstrap as boot
 from .base import evaluation as eva
 from .base.alignment import assignment_alignment, mutual_alignment, stable_alignment
 from .base.batch import neighbour_table
+from .base.bootstrap import bootstrap_options
+from .base.kgs import TripleArray
 from .MultiKE_model import MultiKE
 from .utils import sinkhorn_option, task_divide
 
@@ -221,6 +225,99 @@ class _ScheduledMultiKE(MultiKE):
         self._refresh_predicate_lists()
         self._neighbors = (None, None)
         self._entity_list = kgs.kg1.entities_list + kgs.kg2.entities_list
+        self._seed_ckge = (self._ckge_rel_triples, self._ckge_attr_triples)    # what `_bootstrap` appends its lists to
+        self.bootstrap_links = None
+        bootstrap_options(a)                                                   # refuse a bad combination before the first epoch
+
+    bootstrap_default_view = ('final', (1, 1, 1))     # the embedding the driver validates on (MultiKE_Late: 'avg')
+
+    def _bootstrap(self, i):
+        """Self-training refresh at the end of epoch i (hyper-parameters `bootstrap_*`, off unless `bootstrap_freq` > 0): decode
+        the unlabelled entities, keep the mutual pairs, swap them into triples ON THE DEVICE and train the two cross-KG
+        entity-inference loops on the seed lists plus these until the next refresh replaces them.  The candidates are the valid
+        + test entities of each KG, in that order on both sides; no gold link is read to choose pairs (the precision printed
+        is a diagnostic: gold = the same index, which the pairing kernel counts anyway).  Decode, link table, both swaps and the
+        weight table are enqueued without waiting; one read-back (the two list lengths and the two counters) ends the refresh.
+        Not done: the sampler's known-triple filter does not grow by the bootstrapped triples, and `kg.add_sup_*` is not called."""
+        opt = bootstrap_options(self.args)
+        if opt is None:
+            return
+        freq, start, threshold, csls_k, view, weighted = opt
+        if i < start or (i - start) % freq != 0 or i >= self.args.max_epoch:
+            return
+        import torch
+        t0 = time.time()
+        k = self.kgs
+        ids1 = _device_ids(self, "valid1+test1", lambda: k.valid_entities1 + k.test_entities1)
+        ids2 = _device_ids(self, "valid2+test2", lambda: k.valid_entities2 + k.test_entities2)
+        choice, w = (view, (1, 1, 1)) if view is not None else self.bootstrap_default_view
+        e1 = _view_rows(self, choice, w, ids1)
+        if e1 is None:
+            raise _lib.MultiKEHipError("bootstrap_freq > 0: the tables of this model are not device tables")
+        e2 = _view_rows(self, choice, w, ids2)
+        src = self._bootstrap_sources()
+        partner, match, counts, score = boot.bootstrap_links(e1, e2, ids1, ids2, k.entities_num, threshold, csls_k, scores=True)
+        weight = None
+        if weighted:
+            # weight[e] = clamp(score of e's pair, 0, 1) for both entities of a pair; unmatched rows write a spare last word
+            n = k.entities_num
+            m = match >= 0
+            spare = torch.full_like(ids1, n)
+            weight = torch.zeros(n + 1, dtype=torch.float32, device=self.device)
+            val = score.clamp(0.0, 1.0)
+            weight[torch.where(m, ids1, spare).long()] = val
+            weight[torch.where(m, ids2[match.clamp(min=0).long()], spare).long()] = val
+            weight = weight[:n]
+        rel = boot._swap_launch(src["rel"], partner, False, weight)
+        attr = boot._swap_launch(src["attr"], partner, True, weight)
+        n_rel, n_attr, pairs, gold = torch.cat([rel[-1], attr[-1], counts.long()]).cpu().tolist()      # the one read-back
+        lists = (boot._swap_finish(rel, n_rel), boot._swap_finish(attr, n_attr))
+        self._ckge_rel_triples, self._ckge_attr_triples = (
+            new if seed is None else seed + new for seed, new in zip(self._bootstrap_seeds(weighted), lists))
+        self.bootstrap_links = boot.BootstrapLinks(match, ids1, ids2, pairs)
+        self._bootstrap_partner = partner
+        print("bootstrapping after epoch {}: {} pairs, precision = {:.3f}%, {} relation triples, {} attribute triples, "
+              "time = {:.3f} s".format(i, pairs, gold / pairs * 100 if pairs else 0.0, n_rel, n_attr, time.time() - t0))
+
+    def _bootstrap_sources(self):
+        """Device columns of the KG1 ++ KG2 local (pre-supervision) relation and attribute id-triples: uploaded once per model."""
+        src = self.__dict__.get("_boot_sources")
+        if src is None:
+            import torch
+            kg1, kg2 = self.kgs.kg1, self.kgs.kg2
+
+            def up(a, b):
+                arr = np.concatenate([np.asarray(a, dtype=np.int32).reshape(-1, 3), np.asarray(b, dtype=np.int32).reshape(-1, 3)])
+                t = torch.as_tensor(arr, device=self.device)
+                return tuple(t[:, c].contiguous() for c in range(3))
+            src = self._boot_sources = {"rel": up(kg1.local_relation_triples_list, kg2.local_relation_triples_list),
+                                        "attr": up(kg1.local_attribute_triples_list, kg2.local_attribute_triples_list)}
+        return src
+
+    def _bootstrap_seeds(self, weighted):
+        """The two seed lists in the form the bootstrapped lists are appended to: their device columns (the ones the training
+        loops already hold) as `TripleArray`s, with weights of 1.0 when the bootstrapped triples are weighted.  None for an empty
+        seed list.  The lists `_prepare` made stay as they are."""
+        key = bool(weighted)
+        cache = self.__dict__.setdefault("_boot_seeds", {})
+        if cache.get("of") is not self._seed_ckge:
+            cache.clear()
+            cache["of"] = self._seed_ckge
+        if key not in cache:
+            import torch
+            out = []
+            for seed in self._seed_ckge:
+                if len(seed) == 0:
+                    out.append(None)
+                    continue
+                lst = self._list(seed)
+                ones = torch.ones(lst.n, dtype=torch.float32, device=self.device) if weighted else None
+
+                def host(seed=seed, n=lst.n):
+                    return np.asarray([t[:3] for t in seed], dtype=np.int64).reshape(-1, 3), (np.ones(n) if weighted else None)
+                out.append(TripleArray.on_device(lst.cols, ones, host))
+            cache[key] = tuple(out)
+        return cache[key]
 
     def _refresh_predicate_lists(self):
         pam = self.predicate_align_model
@@ -386,6 +483,8 @@ class _ScheduledMultiKE(MultiKE):
 class MultiKE_Late(_ScheduledMultiKE):
     """code/MultiKE_Late.py:176-280 — run_SSL.py's model."""
 
+    bootstrap_default_view = ('avg', (1, 1, 1))
+
     def __init__(self, data, args, attr_align_model):
         super().__init__(data, args, attr_align_model)
         self.flag1, self.flag2, self.early_stop = -1, -1, False
@@ -420,6 +519,7 @@ class MultiKE_Late(_ScheduledMultiKE):
                     self._update_predicate_alignment()
             if self.early_stop or i == a.max_epoch:
                 break
+            self._bootstrap(i)
             self._refresh_neighbours(i)
         for i in range(1, a.shared_learning_max_epoch + 1):
             self.train_shared_space_mapping_1epo(i, self._entity_list)

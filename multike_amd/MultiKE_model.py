@@ -528,14 +528,14 @@ class MultiKE:
     def train_cross_kg_entity_inference_relation_view_1epo(self, epoch, sup_triples):
         """code/MultiKE_model.py:349-369."""
         return self._positives_epoch(epoch, sup_triples, self.args.batch_size,
-                                     lambda cols, w, off: self._relation_positive_steps(self._ckge_rel, cols, None, off),
+                                     lambda cols, w, off: self._relation_positive_steps(self._ckge_rel, cols, w, off),
                                      'cross-kg entity inference in rel. view', 0, 'ckge_rel')
 
     def train_cross_kg_entity_inference_attribute_view_1epo(self, epoch, sup_triples):
         """code/MultiKE_model.py:371-391: 2 * sum log(1+exp(-conv))."""
         return self._positives_epoch(
             epoch, sup_triples, self.args.attribute_batch_size,
-            lambda cols, w, off: self._run_attr_steps(self._ckge_attr_cnn, cols, None, off, 2.0, "ckge_attr"),
+            lambda cols, w, off: self._run_attr_steps(self._ckge_attr_cnn, cols, w, off, 2.0, "ckge_attr"),
             'cross-kg entity inference in attr. view', 1, 'ckge_attr')
 
     def train_cross_kg_relation_inference_1epo(self, epoch, sup_triples):

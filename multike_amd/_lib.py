@@ -43,6 +43,7 @@ SYMBOLS = (
     "mke_align_lse_temp_bytes", "mke_align_lse",
     "mke_align_mutual", "mke_mutual_pairs",
     "mke_assign_temp_bytes", "mke_assign_rounds", "mke_assign_finish",
+    "mke_boot_partner", "mke_swap_temp_bytes", "mke_swap_triples",
 )
 ACT_NONE, ACT_TANH, ACT_SIGMOID = 0, 1, 2
 AE_MAX_LAYERS = 4
@@ -285,6 +286,7 @@ def lib():
         L.mke_align_lse_temp_bytes.restype = C.c_int64
         L.mke_tripleset_filter_bytes.restype = C.c_int64
         L.mke_assign_temp_bytes.restype = C.c_int64
+        L.mke_swap_temp_bytes.restype = C.c_int64
         _lib = L
         # MKE_OPTIONS="name=value,name=value": mke_set_option calls applied at load (performance knobs for experiments)
         for kv in filter(None, os.environ.get("MKE_OPTIONS", "").split(",")):
@@ -1205,6 +1207,68 @@ def assign_rounds(args: AssignArgs, n_rounds: int):
 def assign_finish(args: AssignArgs):
     """mke_assign_finish: match[i] = the column row i holds or -1; counts = (matched, matched to its own index, settled unmatched)."""
     _check(lib().mke_assign_finish(C.byref(args), _stream()), "mke_assign_finish")
+
+
+SWAP_TILE = 64                             # MKE_SWAP_TILE: triples per tile of the ordered compaction (one wavefront)
+
+
+class SwapArgs(C.Structure):
+    """mke_swap_args"""
+    _fields_ = [("h", C.c_void_p), ("p", C.c_void_p), ("t", C.c_void_p), ("n", C.c_int64), ("partner", C.c_void_p),
+                ("n_entities", C.c_int64), ("weight", C.c_void_p), ("heads_only", C.c_int), ("out_h", C.c_void_p),
+                ("out_p", C.c_void_p), ("out_t", C.c_void_p), ("out_w", C.c_void_p), ("capacity", C.c_int64), ("count", C.c_void_p),
+                ("temp", C.c_void_p), ("temp_bytes", C.c_int64), ("flags", C.c_int)]
+
+
+def boot_partner(match, ids_a, ids_b, n_entities: int, out=None):
+    """mke_boot_partner -> partner int32 [n_entities]: -1 everywhere, then partner[ids_a[i]] = ids_b[match[i]] and back for every
+    matched row i of the one-to-one `match` int32 [n_a] (-1 = unmatched).  `out` = a table to overwrite instead of a fresh one."""
+    partner = out if out is not None else torch.empty(n_entities, dtype=torch.int32, device=match.device)
+    if partner.numel() != n_entities:
+        raise MultiKEHipError(f"boot_partner: out holds {partner.numel()} words, the table has {n_entities}")
+    if match.numel() != ids_a.numel():
+        raise MultiKEHipError(f"boot_partner: match has {match.numel()} rows, ids_a {ids_a.numel()}")
+    rc = lib().mke_boot_partner(_dev(match, torch.int32, "match"), _dev(ids_a, torch.int32, "ids_a"), C.c_int64(ids_a.numel()),
+                                _dev(ids_b, torch.int32, "ids_b"), C.c_int64(ids_b.numel()), _dev(partner, torch.int32, "partner"),
+                                C.c_int64(n_entities), _stream())
+    _check(rc, "mke_boot_partner")
+    return partner
+
+
+def swap_temp_bytes(n: int) -> int:
+    """mke_swap_temp_bytes; raises on an n mke_swap_triples would reject."""
+    r = int(lib().mke_swap_temp_bytes(C.c_int64(n)))
+    _check(r if r < 0 else 0, "mke_swap_temp_bytes")
+    return r
+
+
+def swap_triples(h, p, t, partner, heads_only=False, weight=None, capacity=None, out=None):
+    """mke_swap_triples over the int32 columns h, p, t [n] and the link table `partner` int32 [n_entities] -> ((out_h, out_p,
+    out_t), out_w or None, count int64 [1] on the device): the 'swapping' supervision entries in the order of the walk over the
+    list.  capacity: None = the worst case (2 n, or n with heads_only); entries past it are counted, not stored.  `out` =
+    (out_h, out_p, out_t, out_w or None) of at least `capacity` words instead of fresh tensors.  Nothing is read back here."""
+    n = h.numel()
+    if p.numel() != n or t.numel() != n:
+        raise MultiKEHipError(f"swap_triples: columns of {n}, {p.numel()}, {t.numel()} triples")
+    cap = (n if heads_only else 2 * n) if capacity is None else int(capacity)
+    dev = h.device
+    if out is None:
+        out = tuple(torch.empty(cap, dtype=torch.int32, device=dev) for _ in range(3)) + (
+            None if weight is None else torch.empty(cap, dtype=torch.float32, device=dev),)
+    out_h, out_p, out_t, out_w = out
+    if min(x.numel() for x in out if x is not None) < cap:
+        raise MultiKEHipError(f"swap_triples: out is shorter than the capacity {cap}")
+    if weight is not None and weight.numel() != partner.numel():
+        raise MultiKEHipError(f"swap_triples: weight has {weight.numel()} entries, partner {partner.numel()}")
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    temp = torch.empty((swap_temp_bytes(n) + 7) // 8, dtype=torch.int64, device=dev)
+    args = SwapArgs(_dev(h, torch.int32, "h"), _dev(p, torch.int32, "p"), _dev(t, torch.int32, "t"), n,
+                    _dev(partner, torch.int32, "partner"), partner.numel(), _dev(weight, torch.float32, "weight"),
+                    1 if heads_only else 0, _dev(out_h, torch.int32, "out_h"), _dev(out_p, torch.int32, "out_p"),
+                    _dev(out_t, torch.int32, "out_t"), _dev(out_w, torch.float32, "out_w"), cap, _dev(count, torch.int64, "count"),
+                    _dev(temp, torch.int64, "temp"), temp.numel() * 8, 0)
+    _check(lib().mke_swap_triples(C.byref(args), _stream()), "mke_swap_triples")
+    return (out_h, out_p, out_t), out_w, count
 
 
 def gemm_f32(lhs, rhs, out, transpose_a=False, transpose_b=False, splits=1, accumulate=False):

@@ -81,6 +81,10 @@ class _ShardedMixin:
             raise _lib.MultiKEHipError("mutual > 0: the mutual nearest-neighbour alignment is not sharded over ranks (a column's "
                                        "best row is taken over all rows); run the single-GPU driver (python -m multike_amd.run) "
                                        "or set mutual=0")
+        if int(getattr(args, "bootstrap_freq", 0) or 0) > 0:
+            raise _lib.MultiKEHipError("bootstrap_freq > 0: self-training is not sharded over ranks (its decode takes a column's "
+                                       "best row over all rows, and its lists are built from the whole link table); run the "
+                                       "single-GPU driver (python -m multike_amd.run) or set bootstrap_freq=0")
         self.kgs = kgs = data.kgs
         self.kg1, self.kg2 = kgs.kg1, kgs.kg2
         self.rank, self.world = rank, world

@@ -55,6 +55,13 @@ def default_args(**over):
         # (0 = off), to within n * `assign_eps` of that instance's optimum; `assign_floor` = the value of staying unmatched (None =
         # the smallest listed value - 1; in units of the re-scored value when `csls` / Sinkhorn is on)
         assign_cut=0, assign_eps=1e-3, assign_floor=None,
+        # self-training of the single-GPU schedules (0 = off): from epoch `bootstrap_start` on, every `bootstrap_freq` epochs the
+        # mutual nearest-neighbour pairs of the unlabelled (valid + test) entities, at or above `bootstrap_threshold` (None = none),
+        # are swapped into the two cross-KG entity-inference lists beside the seed links, replacing the pairs of the refresh before.
+        # `bootstrap_csls` > 0 decodes on CSLS re-scored values (the threshold is then in those units); `bootstrap_view` names the
+        # embedding decoded (None = the one the driver validates on: 'final' for ITC, 'avg' for SSL); `bootstrap_weighted` = 1
+        # weights a bootstrapped triple by its pair's similarity clamped to [0, 1] (seed triples 1.0; not with `bootstrap_csls`)
+        bootstrap_freq=0, bootstrap_start=10, bootstrap_threshold=None, bootstrap_csls=0, bootstrap_view=None, bootstrap_weighted=0,
         # view combination and predicate soft alignment
         orthogonal_weight=2, cv_name_weight=1, cv_weight=1, start_predicate_soft_alignment=10, predicate_soft_sim=0.85,
         predicate_init_sim=0.90)
