@@ -64,8 +64,8 @@ const char* mke_last_error(void);
 #define MKE_TUNE_DEFAULT (-2)
 typedef struct mke_tuning {
   int score_splits, score_half_groups, score_offsets32, score_lane_ids, count_in_score, update_chunk, oc_score_quarter,
-      attr_fused_bwd, sampler_fast;
-  int reserved[7];   /* MKE_TUNE_DEFAULT */
+      attr_fused_bwd, sampler_fast, neg_codes;
+  int reserved[6];   /* MKE_TUNE_DEFAULT */
 } mke_tuning;
 int mke_tuning_init(mke_tuning* t);   /* every field = MKE_TUNE_DEFAULT */
 
@@ -94,6 +94,8 @@ int mke_tuning_init(mke_tuning* t);   /* every field = MKE_TUNE_DEFAULT */
  *                     negative per lane, and gathers accumulator rows only for rows it finishes in place; 0 = per round
  *   "count_in_score"    : 1 (default) = mke_relation_steps lets the NEXT step's reference counting ride in the score
  *                     launch (mke_score_args.next_count); 0 = in the update launch (mke_rows_update_multi_count)
+ *   "neg_codes"         : 1 (default) = mke_relation_steps bakes one code word per negative when it samples a chunk and runs the
+ *                     code-word form of the training kernel (section (1c)); 0 = reference counts per step
  * Returns the previous value through *old_value when it is not NULL. */
 int mke_set_option(const char* name, int value, int* old_value);
 
@@ -212,12 +214,40 @@ typedef struct mke_score_args {
   float* stage_rows; int64_t* stage_keys; int64_t stage_slots;
   double* loss_partials;             /* [MKE_LOSS_PARTIALS] */
   const mke_tuning* tuning;          /* host pointer, NULL = the enclosing call's knobs / the process defaults */
+  const int32_t* neg_code;           /* nullable: one code word per negative (section (1c)); NULL = today's forms */
 } mke_score_args;
 int mke_triple_score_step(const mke_score_args* args, void* stream);
 int mke_stage_reduce(const float* stage_rows, const int64_t* sorted_keys, const int64_t* order, int64_t n_slots, int stride,
                      float* grad_ent, float* grad_rel, int32_t* touched_ent, int32_t* touched_rel, int32_t tag, void* stream);
 int mke_count_entity_refs(const int32_t* pos_h, const int32_t* pos_t, int64_t n_pos, const int32_t* neg_h,
                           const int32_t* neg_t, int64_t n_neg, int neg_per_pos, int32_t* ref_count, void* stream);
+
+/* (1c) Code words.  What the training kernel derives from a negative's three ids and from ref_count is a property of the ids
+ *   alone, so it can be computed once for all the steps whose negatives exist, instead of once per step:
+ *       code = entity | MKE_CODE_HEAD | MKE_CODE_FAST | MKE_CODE_EXCL
+ *     entity (bits 0..25)  the corrupted entity: neg_h when it differs from the positive's head, else neg_t
+ *     MKE_CODE_HEAD        neg_h differs from the positive's head
+ *     MKE_CODE_FAST        same relation as the positive and exactly one side differs (the kernel's one-gather path)
+ *     MKE_CODE_EXCL        mke_count_entity_refs of the negative's STEP gives the entity the count 1
+ *   mke_neg_codes: steps [step_begin, step_end) of step_off (a DEVICE copy of the plan's array; pos_* are the epoch's arrays,
+ *   indexed by epoch position; neg_* and neg_code start at the first negative of step_begin).  Counting is done in `bits`, two bits
+ *   per entity and step ((step_end - step_begin) rows of mke_neg_code_row_words(n_ent) words: bit 0 = referenced, bit 1 =
+ *   referenced again), which the call writes for its steps (no need to zero them); bits_words is the buffer's size.  n_ent <= 2^26.
+ *   Rows of up to 64 KB (262,144 entities) are marked in the LDS by one workgroup per step; wider ones by device-scope atomics in
+ *   `bits` itself, which costs more than the code words save at the C2 shape (mke_relation_steps then keeps the counts).
+ *   mke_score_args.neg_code: the training kernel (ref_count semantics, 32-bit offsets, lane ids: score_offsets32 and
+ *   score_lane_ids on, tables below 2^30 floats) reads one word per negative, neither reads nor resets ref_count and updates
+ *   MKE_CODE_EXCL rows in place; negatives without MKE_CODE_FAST are scored from neg_h / neg_r / neg_t as before.  Where that
+ *   form is not legal the call runs the ref_count form (ref_count != NULL) or fails (MKE_E_UNSUPPORTED). */
+#define MKE_CODE_ENT_BITS 26
+#define MKE_CODE_HEAD (1 << 26)
+#define MKE_CODE_FAST (1 << 27)
+#define MKE_CODE_EXCL (1 << 28)
+int64_t mke_neg_code_row_words(int64_t n_ent);
+int mke_neg_codes(const int32_t* pos_h, const int32_t* pos_r, const int32_t* pos_t, const int64_t* step_off /* device */,
+                  int step_begin, int step_end, int64_t pos_begin /* step_off[step_begin] */, int64_t pos_end /* step_off[step_end] */,
+                  const int32_t* neg_h, const int32_t* neg_r, const int32_t* neg_t, int neg_per_pos, int64_t n_ent,
+                  uint32_t* bits, int64_t bits_words, int32_t* neg_code, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * (2) Per-row optimizer step on the rows touched in this step: Jacobian of normalise-on-read, then
@@ -508,6 +538,10 @@ typedef struct mke_relation_plan {
   mke_hot_rows hot;                          /* version 103: hub rows of the entity table (slot == NULL: none); ent_grad then has
                                                 hot.row0 + hot.copies * hot.n_hot rows */
   const mke_tuning* tuning;                  /* version 105: host pointer, NULL = the process defaults */
+  /* code words (section (1c); all nullable = reference counts per step): a chunk's codes are baked right after it is sampled */
+  const int64_t* step_off_dev;               /* device copy of step_off */
+  int32_t* neg_code;                         /* device scratch, as large as neg_h (neg_chunk_capacity) */
+  uint32_t* code_bits; int64_t code_bits_words;  /* device scratch of the bake; a chunk that needs more runs the ref_count form */
 } mke_relation_plan;
 
 int mke_relation_steps(const mke_relation_plan* plan, int step_begin, int step_end, void* stream);

@@ -44,6 +44,7 @@ SYMBOLS = (
     "mke_align_mutual", "mke_mutual_pairs",
     "mke_assign_temp_bytes", "mke_assign_rounds", "mke_assign_finish",
     "mke_boot_partner", "mke_swap_temp_bytes", "mke_swap_triples",
+    "mke_neg_code_row_words", "mke_neg_codes",
 )
 ACT_NONE, ACT_TANH, ACT_SIGMOID = 0, 1, 2
 AE_MAX_LAYERS = 4
@@ -114,7 +115,7 @@ class ScoreArgs(C.Structure):
                 ("ref_count", C.c_void_p), ("ent_acc", C.c_void_p), ("optimizer", C.c_int), ("lr", C.c_float),
                 ("next_count", C.c_void_p), ("hot", HotRowsStruct),
                 ("stage_rows", C.c_void_p), ("stage_keys", C.c_void_p), ("stage_slots", C.c_int64),
-                ("loss_partials", C.c_void_p), ("tuning", C.c_void_p)]
+                ("loss_partials", C.c_void_p), ("tuning", C.c_void_p), ("neg_code", C.c_void_p)]
 
 
 class OcStepStruct(C.Structure):
@@ -142,12 +143,12 @@ class OcStepStruct(C.Structure):
 
 TUNE_DEFAULT = -2
 TUNING_FIELDS = ("score_splits", "score_half_groups", "score_offsets32", "score_lane_ids", "count_in_score", "update_chunk",
-                 "oc_score_quarter", "attr_fused_bwd", "sampler_fast")
+                 "oc_score_quarter", "attr_fused_bwd", "sampler_fast", "neg_codes")
 
 
 class TuningStruct(C.Structure):
     """mke_tuning: the performance knobs of ONE plan / call (a field at TUNE_DEFAULT follows mke_set_option's process default)."""
-    _fields_ = [(f, C.c_int) for f in TUNING_FIELDS] + [("reserved", C.c_int * 7)]
+    _fields_ = [(f, C.c_int) for f in TUNING_FIELDS] + [("reserved", C.c_int * 6)]
 
 
 def tuning(**knobs) -> TuningStruct:
@@ -254,6 +255,7 @@ class RelationPlanStruct(C.Structure):
         ("optimizer", C.c_int), ("lr", C.c_float), ("scale", C.c_float),
         ("loss_partials", C.c_void_p), ("loss_ring", C.c_int), ("tag_base", C.c_int32), ("pos_w", C.c_void_p),
         ("hot", HotRowsStruct), ("tuning", C.c_void_p),
+        ("step_off_dev", C.c_void_p), ("neg_code", C.c_void_p), ("code_bits", C.c_void_p), ("code_bits_words", C.c_int64),
     ]
 
 _lib = None
@@ -287,6 +289,7 @@ def lib():
         L.mke_tripleset_filter_bytes.restype = C.c_int64
         L.mke_assign_temp_bytes.restype = C.c_int64
         L.mke_swap_temp_bytes.restype = C.c_int64
+        L.mke_neg_code_row_words.restype = C.c_int64
         _lib = L
         # MKE_OPTIONS="name=value,name=value": mke_set_option calls applied at load (performance knobs for experiments)
         for kv in filter(None, os.environ.get("MKE_OPTIONS", "").split(",")):
@@ -614,6 +617,23 @@ def align_steps(plan: AlignPlanStruct):
 def relation_steps(plan: RelationPlanStruct, step_begin: int, step_end: int):
     rc = lib().mke_relation_steps(C.byref(plan), C.c_int(step_begin), C.c_int(step_end), _stream())
     _check(rc, "mke_relation_steps")
+
+
+CODE_ENT_BITS, CODE_HEAD, CODE_FAST, CODE_EXCL = 26, 1 << 26, 1 << 27, 1 << 28   # MKE_CODE_*
+
+
+def neg_code_row_words(n_ent: int) -> int:
+    """Words of one step's row of the code-word bake's bitmap (2 bits per entity)."""
+    return int(lib().mke_neg_code_row_words(C.c_int64(n_ent)))
+
+
+def neg_codes(pos, step_off_dev, step_begin, step_end, pos_begin, pos_end, neg, neg_per_pos, n_ent, bits, neg_code):
+    """mke_neg_codes: one code word per negative of steps [step_begin, step_end).  pos: the epoch's (h, r, t); neg: the chunk's."""
+    rc = lib().mke_neg_codes(*(_dev(x, torch.int32, "pos") for x in pos), _dev(step_off_dev, torch.int64, "step_off"),
+                             C.c_int(step_begin), C.c_int(step_end), C.c_int64(pos_begin), C.c_int64(pos_end),
+                             *(_dev(x, torch.int32, "neg") for x in neg), C.c_int(neg_per_pos), C.c_int64(n_ent),
+                             _dev(bits, torch.int32, "bits"), C.c_int64(bits.numel()), _dev(neg_code, torch.int32, "neg_code"), _stream())
+    _check(rc, "mke_neg_codes")
 
 
 def tripleset_build(h, r, t, keys):

@@ -33,6 +33,7 @@ int g_score_half_max = -1;   // largest neg_per_pos scored two groups per wavefr
 int g_score_o32 = 1;         // 32-bit row offsets in the training kernel when the tables allow (mke_score.hip, row_at)
 int g_count_in_score = 1;    // runner: the next step's reference counting rides in the score launch (0: in the update launch)
 int g_score_lane_ids = 1;    // training kernel: a group's ids and reference counts fetched once, one negative per lane (mke_score.hip)
+int g_neg_codes = 1;         // runner: one code word per negative baked when a chunk is sampled, code-word form of the training kernel (0: reference counts per step)
 int g_update_chunk = 0;      // rows per wavefront of the row-update kernel on large tables: 0 = by table size, 16, 64
 int g_deterministic = 0;     // fixed-order gradient reduction (parity / debugging mode)
 int g_sampler_fast = 1;      // mke_sampler.hip: coin block in the draw evaluation's idle lane, LDS duplicate test (0: the earlier form)
@@ -74,6 +75,11 @@ extern "C" int mke_set_option(const char* name, int value, int* old_value) {
   if (!strcmp(name, "score_lane_ids")) {
     if (old_value) *old_value = mke::g_score_lane_ids;
     mke::g_score_lane_ids = value != 0;
+    return MKE_OK;
+  }
+  if (!strcmp(name, "neg_codes")) {
+    if (old_value) *old_value = mke::g_neg_codes;
+    mke::g_neg_codes = value != 0;
     return MKE_OK;
   }
   if (!strcmp(name, "update_chunk")) {

@@ -136,7 +136,7 @@ struct TuningScope {
   ~TuningScope() { tl_tuning = prev; }
 };
 extern int g_score_splits, g_score_half_max, g_score_o32, g_score_lane_ids, g_count_in_score, g_update_chunk, g_oc_score_quarter,
-    g_attr_fused_bwd, g_sampler_fast;
+    g_attr_fused_bwd, g_sampler_fast, g_neg_codes;
 #define MKE_TUNE(field, dflt) ((mke::tl_tuning && mke::tl_tuning->field != MKE_TUNE_DEFAULT) ? mke::tl_tuning->field : (dflt))
 inline int tune_score_splits() { const int v = MKE_TUNE(score_splits, g_score_splits); return v < 0 ? 0 : v; }
 inline int tune_score_half_max() { const int v = MKE_TUNE(score_half_groups, g_score_half_max); return v < 0 ? -1 : (v > 64 ? 64 : v); }
@@ -146,6 +146,18 @@ inline int tune_count_in_score() { return MKE_TUNE(count_in_score, g_count_in_sc
 inline int tune_update_chunk() { const int v = MKE_TUNE(update_chunk, g_update_chunk); return v == 16 ? 16 : (v == 64 ? 64 : 0); }
 inline int tune_oc_score_quarter() { const int v = MKE_TUNE(oc_score_quarter, g_oc_score_quarter); return v < 0 ? -1 : (v != 0); }
 inline int tune_attr_fused_bwd() { return MKE_TUNE(attr_fused_bwd, g_attr_fused_bwd) != 0; }
+inline int tune_neg_codes() { return MKE_TUNE(neg_codes, g_neg_codes) != 0; }
+// The code-word form of the training kernel (mke_score_args.neg_code) exists for the 32-bit-offset, lane-id instantiation only:
+// gradient rows (hub copies included) and relation rows below 2^30 floats, so that an entity id fits MKE_CODE_ENT_BITS
+inline bool score_codes_legal(int64_t n_ent, int64_t grad_rows, int64_t n_rel, int stride) {
+  return tune_score_o32() && tune_score_lane_ids() && grad_rows * (int64_t)stride < (1ll << 30) && n_rel * (int64_t)stride < (1ll << 30) &&
+         n_ent <= (1ll << MKE_CODE_ENT_BITS);
+}
+// mke_codes.hip: bitmap rows and code words of steps [step_begin, step_end) (arguments as mke_neg_codes, already checked)
+int launch_neg_codes(const int32_t* pos_h, const int32_t* pos_r, const int32_t* pos_t, const int64_t* step_off_dev, int step_begin,
+                     int step_end, int64_t pos_begin, int64_t pos_end, const int32_t* neg_h, const int32_t* neg_r, const int32_t* neg_t,
+                     int neg_per_pos, int64_t n_ent, uint32_t* bits, int32_t* neg_code, hipStream_t st);
+bool neg_codes_in_lds(int64_t n_ent);   // the bake is one launch, a step's bitmap row in the LDS (else device-scope atomics: slower than what it saves)
 inline int tune_sampler_fast() { return MKE_TUNE(sampler_fast, g_sampler_fast) != 0; }
 
 // Block-wide sum of one float per thread, accumulated in double; thread 0 gets the result.

@@ -145,6 +145,14 @@ extern "C" int mke_relation_steps(const mke_relation_plan* pl, int step_begin, i
   }
   sa.hot = pl->hot;
 
+  // Code words (mke_codes.hip): a chunk's negatives get one baked word each right after they are sampled, and its steps run the
+  // code-word form of the score launch — no reference counting, no count riders, no resets in the update launch.  Taken when the
+  // plan carries the scratch, the knob is on, the form is legal and a step's bitmap row fits the LDS (marks in global memory cost
+  // more than the form saves: mke_codes.hip); per chunk, when the chunk's bitmap fits the scratch.
+  const int64_t grad_rows = (pl->hot.slot && pl->hot.n_hot > 0) ? pl->hot.row0 + (int64_t)pl->hot.copies * pl->hot.n_hot : pl->n_ent;
+  const bool codes_ok = N > 0 && pl->ent_ref_count && !pl->negatives_ready && tune_neg_codes() && pl->step_off_dev && pl->neg_code &&
+                        pl->code_bits && neg_codes_in_lds(pl->n_ent) && score_codes_legal(pl->n_ent, grad_rows, pl->n_rel, pl->stride);
+  bool codes = false;    // the current chunk has code words
   int64_t chunk_lo = 0;  // first positive (epoch position) whose negatives sit at neg_*[0]
   int chunk_end = step_begin;  // steps < chunk_end are sampled
   bool counted_ahead = false;  // the current step's references were counted by the previous step's update launch
@@ -162,12 +170,18 @@ extern "C" int mke_relation_steps(const mke_relation_plan* pl, int step_begin, i
                                     pl->sides, N, pl->max_try, pl->seed_lo, pl->seed_hi, pl->stream_id, pl->neg_h, pl->neg_r,
                                     pl->neg_t, stream);
       if (rc) return rc;
+      codes = codes_ok && chunk_end - s <= 65535 && (int64_t)(chunk_end - s) * mke_neg_code_row_words(pl->n_ent) <= pl->code_bits_words;
+      if (codes) {
+        const int rc2 = launch_neg_codes(pl->pos_h, pl->pos_r, pl->pos_t, pl->step_off_dev, s, chunk_end, lo, lo + n, pl->neg_h, pl->neg_r,
+                                         pl->neg_t, N, pl->n_ent, pl->code_bits, pl->neg_code, (hipStream_t)stream);
+        if (rc2) return rc2;
+      }
     }
     const int64_t no = (lo - chunk_lo) * N;
     const int32_t tag = pl->tag_base + s;
     // exclusive-row fast path: steps alternate between the two halves of ent_ref_count; the counting of step s+1
     // rides in the update launch of step s when its negatives are already sampled (same chunk)
-    int32_t* refc = (N > 0 && pl->ent_ref_count) ? pl->ent_ref_count + (int64_t)(s & 1) * pl->n_ent : nullptr;
+    int32_t* refc = (N > 0 && pl->ent_ref_count && !codes) ? pl->ent_ref_count + (int64_t)(s & 1) * pl->n_ent : nullptr;
     int rc = MKE_OK;
     if (refc && !counted_ahead) {
       rc = mke_count_entity_refs(pl->pos_h + lo, pl->pos_t + lo, hi - lo, pl->neg_h + no, pl->neg_t + no, (hi - lo) * N, N, refc, stream);
@@ -189,6 +203,7 @@ extern "C" int mke_relation_steps(const mke_relation_plan* pl, int step_begin, i
     const bool in_score = tune_count_in_score() != 0;
     score_step_args(pl, s, no, refc, &sa);
     sa.next_count = in_score ? cjp : nullptr;
+    sa.neg_code = codes ? pl->neg_code + no : nullptr;
     rc = mke_triple_score_step(&sa, stream);
     if (rc) return rc;
     ut[1].ref_count = refc;

@@ -63,6 +63,8 @@ struct ScoreParams {
   const int32_t* __restrict__ hot_slot;
   int32_t n_hot, hot_copies;
   int32_t hot_row0;
+  // code-word form (CW): one baked word per negative (multike_hip.h, section (1c)) instead of its three ids and its entity's count
+  const int32_t* __restrict__ neg_code;
 };
 
 #define MKE_STAGE_REL (1ll << 40)
@@ -158,8 +160,11 @@ __device__ __forceinline__ float independent_triple(const ScoreParams& p, float*
 // idle in the last round and pays the positive's three row loads per 11 triples instead of per 22).
 // DET: deterministic staging compiled in (a separate instantiation: its slot arithmetic costs the training kernel ten
 // registers, 129 instead of 119 = three instead of four wavefronts per SIMD)
-template <int FPL, int U, bool X, int QPG, bool DET = false, bool O32 = false, bool LID = false>  // X: exclusive-row fast path compiled in; O32: see row_at; LID: see LIDS
+// CW (only with X && O32 && LID): a lane's negative is ONE baked code word — corrupted entity, side, fast, exclusive — instead of
+// three ids, five derived values and a dependent gather of refcount[entity]; nothing in the launch reads or resets refcount
+template <int FPL, int U, bool X, int QPG, bool DET = false, bool O32 = false, bool LID = false, bool CW = false>  // X: exclusive-row fast path compiled in; O32: see row_at; LID: see LIDS
 __global__ __launch_bounds__(MKE_BLOCK) void k_triple_score(const ScoreParams p) {
+  static_assert(!CW || (X && O32 && LID && !DET), "code words: the training instantiation only");
   constexpr bool LIDS = LID && X && !DET;   // ids and reference counts of a group fetched once, one negative per lane
   constexpr int LPG = 64 / (4 / QPG);            // lanes per group: the whole wavefront, or one half of it per group
   if ((int)blockIdx.x < p.count_blocks) {
@@ -219,14 +224,24 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_triple_score(const ScoreParams p)
         nblk = min(LPG, nend_ - b0);
         const bool has = active && lane - lbase < nblk;
         const int64_t idx = g * (int64_t)npp_ + (has ? b0 + (lane - lbase) : 0);   // an empty slice (b0 >= npp under a forced `score_splits`) reads the group's first id, never past the arrays
-        const int nh = p.nh[idx], nr = p.nr[idx], nt = p.nt[idx];
-        wl = p.nw ? p.nw[idx] : 1.0f;
-        const bool dh = nh != ph, dt = nt != pt;
-        const bool fastl = has && (nr == pr) && (dh != dt);
-        el = dh ? nh : nt;
-        fl = (fastl ? 1 : 0) | (dh ? 2 : 0);
-        slow_l = has && !fastl;
-        rcl = fastl ? p.refcount[el] : 0;
+        if constexpr (CW) {
+          const int c = p.neg_code[idx];
+          wl = p.nw ? p.nw[idx] : 1.0f;
+          const bool fastl = has && (c & MKE_CODE_FAST);
+          el = c & ((1 << MKE_CODE_ENT_BITS) - 1);
+          fl = (fastl ? 1 : 0) | ((c & MKE_CODE_HEAD) ? 2 : 0);
+          slow_l = has && !fastl;
+          rcl = (fastl && (c & MKE_CODE_EXCL)) ? 1 : 0;
+        } else {
+          const int nh = p.nh[idx], nr = p.nr[idx], nt = p.nt[idx];
+          wl = p.nw ? p.nw[idx] : 1.0f;
+          const bool dh = nh != ph, dt = nt != pt;
+          const bool fastl = has && (nr == pr) && (dh != dt);
+          el = dh ? nh : nt;
+          fl = (fastl ? 1 : 0) | (dh ? 2 : 0);
+          slow_l = has && !fastl;
+          rcl = fastl ? p.refcount[el] : 0;
+        }
       };
       if constexpr (LIDS) fetch_block(nlo_);
       float H[FPL], R[FPL], T[FPL];
@@ -389,13 +404,15 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_triple_score(const ScoreParams p)
                   for (int k = 0; k < FPL; ++k) {
                     const float a = fmaf(g[k], g[k], A[u][k]);
                     ap[k * 16] = a;
-                    wp[k * 16] = C[u][k] - p.lr * g[k] * adagrad_scale(a);
+                    // one fma, spelled out: left to the compiler, w - (lr g) s was contracted in some instantiations and in some
+                    // columns of a row only, so that two forms of this kernel differed in the last bit of a row they both finish
+                    wp[k * 16] = fmaf(-(p.lr * g[k]), adagrad_scale(a), C[u][k]);
                   }
                 } else {
 #pragma unroll
                   for (int k = 0; k < FPL; ++k) wp[k * 16] = C[u][k] - p.lr * g[k];
                 }
-                if (j == 0) p.refcount[e[u]] = 0;
+                if constexpr (!CW) { if (j == 0) p.refcount[e[u]] = 0; }
               } else {
                 emit_row<FPL, DET, O32>(p, false, p.gent, p.tent, e[u], stage_slot(g, npp, n0 + QPG * u, sideH[u] ? 0 : 2), j, d,
                               sideH[u] ? 1.0f : -1.0f);
@@ -498,16 +515,16 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_count_refs(const int32_t* __restr
 }  // namespace mke
 
 namespace mke {
-// The 12 instantiations of one row width, and the run-time flags that select each:
+// The 14 instantiations of one row width, and the run-time flags that select each:
 //   det (deterministic staging)            x {X, !X}          DET is its own instantiation (see k_triple_score), never O32 / LID
-//   x && o32 (the training step, < 4 GB)   x {LID on, off}    32-bit row offsets exist only with the exclusive-row path
+//   x && o32 (the training step, < 4 GB)   x {LID on, off, LID with code words}    32-bit row offsets exist only with the exclusive-row path
 //   otherwise                              x {X, !X}
 // each for QPG = 2 (two groups per wavefront) and 4.
 template <int FPL, int U, int QPG>
-static void launch_score(bool det, bool x, bool o32, bool lid, hipStream_t st, const ScoreParams& p) {
+static void launch_score(bool det, bool x, bool o32, bool lid, bool cw, hipStream_t st, const ScoreParams& p) {
 #define MKE_SCORE_LAUNCH(...) hipLaunchKernelGGL((k_triple_score<FPL, U, __VA_ARGS__>), dim3(MKE_LOSS_PARTIALS), dim3(MKE_BLOCK), 0, st, p)
   if (det) { if (x) MKE_SCORE_LAUNCH(true, QPG, true); else MKE_SCORE_LAUNCH(false, QPG, true); }
-  else if (x && o32) { if (lid) MKE_SCORE_LAUNCH(true, QPG, false, true, true); else MKE_SCORE_LAUNCH(true, QPG, false, true); }
+  else if (x && o32) { if (lid && cw) MKE_SCORE_LAUNCH(true, QPG, false, true, true, true); else if (lid) MKE_SCORE_LAUNCH(true, QPG, false, true, true); else MKE_SCORE_LAUNCH(true, QPG, false, true); }
   else { if (x) MKE_SCORE_LAUNCH(true, QPG); else MKE_SCORE_LAUNCH(false, QPG); }
 #undef MKE_SCORE_LAUNCH
 }
@@ -520,8 +537,8 @@ static int score_impl(const mke_score_args& a, void* stream) {
   const int stride = a.stride, neg_per_pos = a.neg_per_pos;
   const bool det = a.stage_keys != nullptr;
   if (a.optimizer != MKE_OPT_ADAGRAD && a.optimizer != MKE_OPT_SGD) { set_error("unsupported optimizer %d", a.optimizer); return MKE_E_UNSUPPORTED; }
-  if (a.ref_count && a.optimizer == MKE_OPT_ADAGRAD && !a.ent_acc) { set_error("exclusive-row path with Adagrad needs ent_acc"); return MKE_E_NULL; }
-  if (a.ref_count && !a.grad_ent) { set_error("exclusive-row path needs the gradient scratch (it is a training step)"); return MKE_E_NULL; }
+  if ((a.ref_count || a.neg_code) && a.optimizer == MKE_OPT_ADAGRAD && !a.ent_acc) { set_error("exclusive-row path with Adagrad needs ent_acc"); return MKE_E_NULL; }
+  if ((a.ref_count || a.neg_code) && !a.grad_ent) { set_error("exclusive-row path needs the gradient scratch (it is a training step)"); return MKE_E_NULL; }
   if (det && !a.stage_rows) { set_error("deterministic mode: NULL staging buffers"); return MKE_E_NULL; }
   if (!a.ent_table || !a.rel_table || !a.loss_partials) { set_error("mke_triple_score_step: NULL table/loss"); return MKE_E_NULL; }
   if (n_pos < 0 || n_neg < 0 || a.n_ent <= 0 || a.n_rel <= 0) { set_error("negative count"); return MKE_E_SHAPE; }
@@ -588,8 +605,13 @@ static int score_impl(const mke_score_args& a, void* stream) {
   p.grel_copy_elems = a.n_rel * (int64_t)stride;
   p.tent = a.touched_ent; p.trel = a.touched_rel; p.tag = a.tag;
   p.lossp = a.loss_partials;
-  const bool excl = a.ref_count != nullptr && neg_per_pos > 0;   // (a training step: checked above)
-  p.refcount = excl ? a.ref_count : nullptr; p.ent_w = a.ent_table;
+  // code words: legal where the 32-bit-offset lane-id instantiation is (hub copy rows included); otherwise the ref_count form
+  const int64_t code_rows = p.hot_slot ? (int64_t)p.hot_row0 + (int64_t)p.hot_copies * p.n_hot : a.n_ent;
+  const bool cw = a.neg_code != nullptr && neg_per_pos > 0 && !det && score_codes_legal(a.n_ent, code_rows, a.n_rel, stride);
+  if (a.neg_code && neg_per_pos > 0 && !cw && !a.ref_count) { set_error("neg_code: the code-word form needs 32-bit offsets, lane ids and n_ent <= 2^%d (or give ref_count)", MKE_CODE_ENT_BITS); return MKE_E_UNSUPPORTED; }
+  const bool excl = (a.ref_count != nullptr || cw) && neg_per_pos > 0;   // (a training step: checked above)
+  p.refcount = excl && !cw ? a.ref_count : nullptr; p.ent_w = a.ent_table;
+  p.neg_code = cw ? a.neg_code : nullptr;
   p.ent_acc = a.optimizer == MKE_OPT_ADAGRAD ? a.ent_acc : nullptr; p.optimizer = a.optimizer; p.lr = a.lr;
   const int fpl = stride / 16;
   // every row address of the launch fits 32 bits of byte offset (entity table = accumulator = gradient scratch in size)
@@ -610,8 +632,8 @@ static int score_impl(const mke_score_args& a, void* stream) {
     const bool half = neg_per_pos > 0 && neg_per_pos <= half_max && splits == 1;
     if (n_pos * (int64_t)splits > 0xFFFFFFFFll || n_pos + n_neg > 0xFFFFFFFFll) { set_error("more than 2^32 work items in one launch"); return MKE_E_RANGE; }
     const bool lid = tune_score_lane_ids() != 0;
-    if (half) launch_score<FPL, U, 2>(det, excl, o32, lid, (hipStream_t)stream, p);
-    else launch_score<FPL, U, 4>(det, excl, o32, lid, (hipStream_t)stream, p);
+    if (half) launch_score<FPL, U, 2>(det, excl, o32, lid, cw, (hipStream_t)stream, p);
+    else launch_score<FPL, U, 4>(det, excl, o32, lid, cw, (hipStream_t)stream, p);
   });
   return check_launch("k_triple_score");
 }

@@ -22,9 +22,10 @@ class RelationViewRunner:
     def __init__(self, ent: EmbeddingTable, rel: EmbeddingTable, batcher: RelationBatcher, opt_name: str = "relation",
                  lr: float = 0.001, optimizer: str = "Adagrad", scale: float = 1.0, sample_chunk: int | None = None,
                  max_try: int = 10, exclusive_rows: bool = True, overlap: bool | None = None, hot_rows: bool | None = None,
-                 tuning: dict | None = None, deterministic: bool | None = None):
+                 tuning: dict | None = None, deterministic: bool | None = None, code_bits_budget: int | None = None):
         """tuning: performance knobs of THIS runner's plan (names of `_lib.TUNING_FIELDS`; mke_relation_plan.tuning) — every knob
-        not named follows the process default; deterministic: the fixed-order mode for this runner (None: the process default)."""
+        not named follows the process default; deterministic: the fixed-order mode for this runner (None: the process default);
+        code_bits_budget: bytes the bitmap of the code-word bake may take (None: CODE_BITS_BUDGET; 0: reference counts per step)."""
         self.tuning = _lib.tuning(**tuning) if tuning else None
         self.deterministic = deterministic
         if optimizer not in _OPT:
@@ -57,6 +58,17 @@ class RelationViewRunner:
         self.neg = tuple(torch.empty(nbuf * self.neg_chunk_capacity, dtype=torch.int32, device=ent.device) for _ in range(3))
         # two halves: steps alternate, so that step s+1 can be counted while step s is being updated
         self.refcount = torch.zeros(2 * ent.n_rows, dtype=torch.int32, device=ent.device) if exclusive_rows else None
+        # Code words (mke_neg_codes): one int32 per negative beside the ids, the device copy of the step offsets, and the bake's bitmap
+        # of 2 bits per entity and step of a chunk (C2 epoch: 184 steps x 200K entities = 9.2 MB).  A chunk whose bitmap would not fit
+        # the budget keeps the reference counts (C5 epoch: 115 MB), and so does a table of more than 262,144 rows, whose row of the
+        # bitmap does not fit the LDS the bake marks it in (the library decides that: mke_codes.hip).
+        budget = self.CODE_BITS_BUDGET if code_bits_budget is None else int(code_bits_budget)
+        words = min(self.sample_chunk, max(self.steps, 1)) * _lib.neg_code_row_words(ent.n_rows)
+        self.neg_code = self.code_bits = self.step_off_dev = None
+        if exclusive_rows and N > 0 and not self.overlap and self.steps > 0 and 0 < 4 * words <= budget:
+            self.neg_code = torch.empty(self.neg_chunk_capacity, dtype=torch.int32, device=ent.device)
+            self.code_bits = torch.zeros(words, dtype=torch.int32, device=ent.device)
+            self.step_off_dev = torch.as_tensor(np.ascontiguousarray(off, dtype=np.int64), device=ent.device)
         self.loss = torch.zeros(max(1, self.steps), _lib.LOSS_PARTIALS, dtype=torch.float64, device=ent.device)
         self._step_off = np.ascontiguousarray(off, dtype=np.int64)
         self.tag = 0  # tags handed out so far; each epoch consumes `steps` of them
@@ -67,6 +79,7 @@ class RelationViewRunner:
     # measured on the Zipf(1.0) C2 shape (EXPERIMENTS R5.2): 4 copies already take the score launch from 44 to 37-38 us (uniform: 35.5);
     # more copies and a lower threshold only lengthen the update launch (each hub row sums its copies: 32 copies +4.5 us)
     HOT_MIN, HOT_MAX, HOT_COPIES = 20.0, 1024, 8
+    CODE_BITS_BUDGET = 64 << 20
 
     def _declare_hot_rows(self, ent: EmbeddingTable, b: RelationBatcher):
         deg = torch.bincount(torch.cat([b.pos_h, b.pos_t]).long(), minlength=ent.n_rows).float() / max(1, self.steps)
@@ -103,6 +116,10 @@ class RelationViewRunner:
         p.loss_partials, p.loss_ring = _lib.ptr(self.loss, torch.float64, "loss"), self.loss.shape[0]
         p.hot = e.hot_struct()
         p.tuning = _lib.tuning_ptr(self.tuning)
+        if self.neg_code is not None:
+            p.step_off_dev = _lib.ptr(self.step_off_dev, torch.int64, "step_off_dev")
+            p.neg_code = _lib.ptr(self.neg_code, torch.int32, "neg_code")
+            p.code_bits, p.code_bits_words = _lib.ptr(self.code_bits, torch.int32, "code_bits"), self.code_bits.numel()
 
     def _fill_epoch(self):
         p, b = self.plan, self.bat
