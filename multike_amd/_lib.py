@@ -16,139 +16,31 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, "libmultike_hip.so")
 
-LOSS_PARTIALS = 2048  # MKE_LOSS_PARTIALS
-MAX_STRIDE = 320  # MKE_MAX_STRIDE
-OPT_ADAGRAD, OPT_SGD, OPT_ADAM, OPT_ADADELTA = 0, 1, 2, 3
+# The structs, the prototypes and the MKE_* constants (MKE_X as X) come from _abi.py, which tools/gen_abi.py writes from the
+# header: nothing of the header is typed a second time here.  The names below are the ones the rest of the tree uses.
+from . import _abi
+from ._abi import *  # noqa: F401,F403  (LOSS_PARTIALS, MAX_STRIDE, OPT_*, OC_*, MAP_*, ATTR_*, AE_*, CODE_*, METRIC_*, ...)
+
+SYMBOLS = tuple(_abi.FUNCTIONS)     # every symbol include/multike_hip.h declares (tests/test_abi.py: the .so exports each of them)
+AttrStepArgs = _abi.mke_attr_step_args
+AlignTableStruct, AlignTermStruct, AlignPlanStruct = _abi.mke_align_table, _abi.mke_align_term, _abi.mke_align_plan
+MappingViewStruct, MappingStepArgs = _abi.mke_mapping_view, _abi.mke_mapping_step_args
+HotRowsStruct, ScoreArgs, UpdateTableStruct = _abi.mke_hot_rows, _abi.mke_score_args, _abi.mke_update_table
+KGSideStruct, RelationPlanStruct = _abi.mke_kg_side, _abi.mke_relation_plan
+OcStepStruct, OcEmPlanArgs, OcCommStruct, OcLoopStruct = _abi.mke_oc_step, _abi.mke_oc_em_plan_args, _abi.mke_oc_comm, _abi.mke_oc_loop
+AEPlanStruct, OptimizerStruct = _abi.mke_ae_plan, _abi.mke_optimizer          # mke_optimizer: TF1 defaults in optimizer_struct
+TopkMeanArgs, AlignArgs, LseArgs, MutualArgs = _abi.mke_topk_mean_args, _abi.mke_align_args, _abi.mke_lse_args, _abi.mke_mutual_args
+StableListsArgs, StableMatchArgs = _abi.mke_stable_lists_args, _abi.mke_stable_match_args
+AssignArgs, SwapArgs = _abi.mke_assign_args, _abi.mke_swap_args
+TuningStruct = _abi.mke_tuning      # the performance knobs of ONE plan / call (a field at TUNE_DEFAULT follows mke_set_option's default)
+TUNING_FIELDS = tuple(f for f, _ in TuningStruct._fields_ if f != "reserved")
+
+# what the header gives only in prose
 DENSE_OPTS = {"Adam": OPT_ADAM, "Adadelta": OPT_ADADELTA}   # TF1 rules that move zero-gradient weights: whole-variable kernels
 _SUPPORTED_FPL = (1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 13, 16, 20)
-
-# every symbol include/multike_hip.h declares (tests/test_abi.py checks the .so exports each of them)
-SYMBOLS = (
-    "mke_version", "mke_last_error", "mke_set_option", "mke_triple_score_fwd_bwd", "mke_triple_score_step",
-    "mke_count_entity_refs", "mke_stage_reduce", "mke_rows_update", "mke_rows_update_multi", "mke_rows_update_multi_count",
-    "mke_neg_sample", "mke_tripleset_build", "mke_tripleset_query", "mke_gathered_logistic_fwd_bwd",
-    "mke_gathered_alignment_fwd_bwd", "mke_align_fwd_bwd", "mke_gather_rows", "mke_relation_steps",
-    "mke_rowset_build", "mke_rowset_remap", "mke_rows_gather_padded", "mke_rows_scatter_add",
-    "mke_attr_conv_fwd", "mke_attr_conv_bwd", "mke_attr_tail_z", "mke_attr_tail_loss", "mke_attr_tail_bwd",
-    "mke_dense_update", "mke_align_rank", "mke_gemm_f32", "mke_attr_scratch_floats", "mke_attr_step", "mke_attr_steps", "mke_attr_step_phases",
-    "mke_sample_distinct", "mke_neg_sample_at", "mke_rows_update_dense", "mke_dense_update_opt", "mke_align_steps", "mke_sim_select", "mke_sim_sample", "mke_topk_rows", "mke_topk_candidates", "mke_mapping_scratch_floats", "mke_mapping_step", "mke_mapping_step_phases", "mke_mapping_steps",
-    "mke_ae_scratch_floats", "mke_ae_train_steps", "mke_ae_step_phases", "mke_ae_encode", "mke_dense_layer_fwd",
-    "mke_topk_long", "mke_probe_rows", "mke_oc_block_floats", "mke_oc_pack_codes", "mke_oc_plan", "mke_oc_bases", "mke_oc_count", "mke_oc_score", "mke_oc_apply", "mke_oc_run",
-    "mke_oc_em_plan_temp_bytes", "mke_oc_em_plan", "mke_oc_pass2", "mke_oc_steps", "mke_oc_gv_sum",
-    "mke_oc_bucket_codes", "mke_oc_owned_index",
-    "mke_tuning_init", "mke_rows_update_multi_t",
-    "mke_align_topk_mean_temp_bytes", "mke_align_topk_mean", "mke_align_rank_ex",
-    "mke_stable_lists_temp_bytes", "mke_stable_lists", "mke_stable_rounds", "mke_stable_finish",
-    "mke_tripleset_forget", "mke_tripleset_filter_bytes", "mke_epoch_positives",
-    "mke_align_lse_temp_bytes", "mke_align_lse",
-    "mke_align_mutual", "mke_mutual_pairs",
-    "mke_assign_temp_bytes", "mke_assign_rounds", "mke_assign_finish",
-    "mke_boot_partner", "mke_swap_temp_bytes", "mke_swap_triples",
-    "mke_neg_code_row_words", "mke_neg_codes",
-)
 ACT_NONE, ACT_TANH, ACT_SIGMOID = 0, 1, 2
-AE_MAX_LAYERS = 4
-
-
-class AttrStepArgs(C.Structure):
-    """mke_attr_step_args"""
-    _fields_ = [
-        ("ent_table", C.c_void_p), ("n_ent", C.c_int64), ("ent_stride", C.c_int), ("ent_normalize", C.c_int),
-        ("ent_acc", C.c_void_p), ("ent_grad", C.c_void_p), ("ent_touched", C.c_void_p),
-        ("attr_table", C.c_void_p), ("n_attr", C.c_int64), ("attr_stride", C.c_int), ("attr_normalize", C.c_int),
-        ("attr_acc", C.c_void_p), ("attr_grad", C.c_void_p), ("attr_touched", C.c_void_p),
-        ("lit_table", C.c_void_p), ("lit_stride", C.c_int), ("dim", C.c_int),
-        ("ih", C.c_void_p), ("ia", C.c_void_p), ("iv", C.c_void_p), ("weights", C.c_void_p), ("n", C.c_int64),
-        ("scale", C.c_float), ("params", C.c_void_p), ("param_grads", C.c_void_p), ("param_acc", C.c_void_p),
-        ("scratch", C.c_void_p), ("partials", C.c_void_p), ("optimizer", C.c_int), ("lr", C.c_float), ("tag", C.c_int32),
-        ("update", C.c_int), ("workspace", C.c_void_p), ("attr_grad_copies", C.c_int), ("tuning", C.c_void_p),
-    ]
-
-
-class AlignTableStruct(C.Structure):
-    """mke_align_table"""
-    _fields_ = [("table", C.c_void_p), ("acc", C.c_void_p), ("grad", C.c_void_p), ("touched", C.c_void_p), ("n_rows", C.c_int64),
-                ("normalize", C.c_int)]
-
-
-class AlignTermStruct(C.Structure):
-    """mke_align_term"""
-    _fields_ = [("a", C.c_int), ("b", C.c_int), ("weight", C.c_float)]
-
-
-class AlignPlanStruct(C.Structure):
-    """mke_align_plan"""
-    _fields_ = [("tables", AlignTableStruct * 4), ("n_tables", C.c_int), ("terms", AlignTermStruct * 4), ("n_terms", C.c_int),
-                ("stride", C.c_int), ("dim", C.c_int), ("ia", C.c_void_p), ("ib", C.c_void_p),
-                ("step_off", C.POINTER(C.c_int64)), ("n_steps", C.c_int), ("optimizer", C.c_int), ("lr", C.c_float),
-                ("tag_base", C.c_int32), ("loss_partials", C.c_void_p)]
-
-
-class MappingViewStruct(C.Structure):
-    """mke_mapping_view"""
-    _fields_ = [("table", C.c_void_p), ("normalize", C.c_int)]
-
-
-class MappingStepArgs(C.Structure):
-    """mke_mapping_step_args"""
-    _fields_ = [("ent_table", C.c_void_p), ("n_ent", C.c_int64), ("ent_normalize", C.c_int), ("ent_acc", C.c_void_p),
-                ("ent_grad", C.c_void_p), ("ent_touched", C.c_void_p), ("views", MappingViewStruct * 3), ("n_views", C.c_int),
-                ("stride", C.c_int), ("dim", C.c_int), ("idx", C.c_void_p), ("n", C.c_int64), ("M", C.c_void_p), ("gM", C.c_void_p),
-                ("accM", C.c_void_p), ("orthogonal_weight", C.c_float), ("norm_w", C.c_float), ("scratch", C.c_void_p),
-                ("partials", C.c_void_p), ("optimizer", C.c_int), ("lr", C.c_float), ("tag", C.c_int32), ("update", C.c_int)]
-
-
-class HotRowsStruct(C.Structure):
-    """mke_hot_rows"""
-    _fields_ = [("slot", C.c_void_p), ("n_hot", C.c_int32), ("copies", C.c_int32), ("row0", C.c_int64)]
-
-
-class ScoreArgs(C.Structure):
-    """mke_score_args"""
-    _fields_ = [("ent_table", C.c_void_p), ("n_ent", C.c_int64), ("ent_normalize", C.c_int),
-                ("rel_table", C.c_void_p), ("n_rel", C.c_int64), ("rel_normalize", C.c_int), ("stride", C.c_int), ("dim", C.c_int),
-                ("pos_h", C.c_void_p), ("pos_r", C.c_void_p), ("pos_t", C.c_void_p), ("pos_w", C.c_void_p), ("n_pos", C.c_int64),
-                ("neg_h", C.c_void_p), ("neg_r", C.c_void_p), ("neg_t", C.c_void_p), ("neg_w", C.c_void_p), ("n_neg", C.c_int64),
-                ("neg_per_pos", C.c_int), ("scale", C.c_float),
-                ("grad_ent", C.c_void_p), ("grad_rel", C.c_void_p), ("grad_rel_copies", C.c_int),
-                ("touched_ent", C.c_void_p), ("touched_rel", C.c_void_p), ("tag", C.c_int32),
-                ("ref_count", C.c_void_p), ("ent_acc", C.c_void_p), ("optimizer", C.c_int), ("lr", C.c_float),
-                ("next_count", C.c_void_p), ("hot", HotRowsStruct),
-                ("stage_rows", C.c_void_p), ("stage_keys", C.c_void_p), ("stage_slots", C.c_int64),
-                ("loss_partials", C.c_void_p), ("tuning", C.c_void_p), ("neg_code", C.c_void_p)]
-
-
-class OcStepStruct(C.Structure):
-    """mke_oc_step"""
-    _fields_ = [("ent", C.c_void_p), ("ent_acc", C.c_void_p), ("ent_grad", C.c_void_p), ("ent_touched", C.c_void_p),
-                ("ref_count", C.c_void_p), ("n_local", C.c_int64),
-                ("rel", C.c_void_p), ("rel_acc", C.c_void_p), ("rel_grad", C.c_void_p), ("rel_grad_copies", C.c_int), ("rel_touched", C.c_void_p),
-                ("n_rel", C.c_int64), ("stride", C.c_int), ("dim", C.c_int), ("rank", C.c_int), ("n_ranks", C.c_int),
-                ("pos_h", C.c_void_p), ("pos_r", C.c_void_p), ("pos_t", C.c_void_p), ("n_pos", C.c_int64), ("per", C.c_int64),
-                ("slot_h", C.c_void_p), ("slot_t", C.c_void_p), ("own_h", C.c_void_p), ("n_own_h", C.c_int64),
-                ("own_t", C.c_void_p), ("n_own_t", C.c_int64), ("neg_per_pos", C.c_int), ("capacity", C.c_int64),
-                ("codes", C.c_void_p), ("code_off", C.c_int64 * 16),
-                ("optimizer", C.c_int), ("lr", C.c_float), ("scale", C.c_float), ("tag", C.c_int32),
-                ("n_peers", C.c_int), ("peer_v", C.c_void_p * 16), ("peer_g", C.c_void_p * 16), ("pos_w", C.c_void_p),
-                ("hot", HotRowsStruct),
-                # version 105: entity-major second pass
-                ("em_coef", C.c_void_p), ("em_pos0", C.c_int64), ("em_refs", C.c_void_p), ("em_rows", C.c_void_p), ("em_off", C.c_void_p),
-                ("em_n_rows", C.c_int64), ("em_chunks", C.c_int), ("em_block_floats", C.c_int64), ("em_v", C.c_void_p * 4),
-                ("em_gv", C.c_void_p * 4),
-                ("em_part", C.c_void_p), ("em_long_rows", C.c_void_p), ("em_long_part0", C.c_void_p), ("em_n_long", C.c_int64),
-                ("em_part0", C.c_int64), ("em_partials", C.c_void_p), ("em_mode", C.c_int), ("tuning", C.c_void_p),
-                # owned code lists (mke_oc_owned_index) in place of the code scan; own_off advanced to the part's first positive
-                ("own_rec", C.c_void_p), ("own_off", C.c_void_p)]
-
-
-TUNE_DEFAULT = -2
-TUNING_FIELDS = ("score_splits", "score_half_groups", "score_offsets32", "score_lane_ids", "count_in_score", "update_chunk",
-                 "oc_score_quarter", "attr_fused_bwd", "sampler_fast", "neg_codes")
-
-
-class TuningStruct(C.Structure):
-    """mke_tuning: the performance knobs of ONE plan / call (a field at TUNE_DEFAULT follows mke_set_option's process default)."""
-    _fields_ = [(f, C.c_int) for f in TUNING_FIELDS] + [("reserved", C.c_int * 6)]
+OC_CB_MOVE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)     # all_gather / reduce_scatter callbacks
+OC_CB_REDUCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)              # all_reduce callback
 
 
 def tuning(**knobs) -> TuningStruct:
@@ -167,96 +59,9 @@ def tuning_ptr(t) -> int | None:
     return C.addressof(t) if t is not None else None
 
 
-OC_EM_MAX_CHUNKS = 4
-OC_EM_WAVES = 32768
-
-
-class OcEmPlanArgs(C.Structure):
-    """mke_oc_em_plan_args"""
-    _fields_ = [("pos_h", C.c_void_p), ("pos_r", C.c_void_p), ("pos_t", C.c_void_p), ("codes", C.c_void_p), ("neg_per_pos", C.c_int),
-                ("slot_h", C.c_void_p), ("slot_t", C.c_void_p), ("step_lo", C.c_void_p), ("n_steps", C.c_int), ("chunks", C.c_int),
-                ("n_all", C.c_int64), ("max_step", C.c_int64), ("n_ranks", C.c_int), ("rank", C.c_int), ("n_local", C.c_int64), ("n_rel", C.c_int64),
-                ("keys", C.c_void_p), ("keys_alt", C.c_void_p), ("capacity", C.c_int64), ("vals_alt", C.c_void_p), ("scratch8", C.c_void_p), ("wave_scratch", C.c_void_p),
-                ("refs", C.c_void_p), ("rows", C.c_void_p), ("off", C.c_void_p), ("flags", C.c_void_p), ("scan", C.c_void_p),
-                ("step_row0", C.c_void_p), ("n_refs", C.c_void_p),
-                ("item_row", C.c_void_p), ("item_off", C.c_void_p), ("item_part", C.c_void_p), ("long_row", C.c_void_p), ("long_part0", C.c_void_p),
-                ("step_item0", C.c_void_p), ("step_long0", C.c_void_p), ("step_part0", C.c_void_p),
-                ("temp", C.c_void_p), ("temp_bytes", C.c_int64),
-                ("own_rec", C.c_void_p), ("own_off", C.c_void_p), ("own_cap", C.c_int64)]
-
-
-OC_COMM_NCCL, OC_COMM_CALLBACK, OC_COMM_LOOPBACK = 0, 1, 2
-OC_CB_MOVE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)     # all_gather / reduce_scatter callbacks
-OC_CB_REDUCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)              # all_reduce callback
-
-
-class OcCommStruct(C.Structure):
-    """mke_oc_comm"""
-    _fields_ = [("kind", C.c_int), ("ctx", C.c_void_p), ("all_gather", C.c_void_p), ("reduce_scatter", C.c_void_p), ("all_reduce", C.c_void_p),
-                ("world", C.c_int), ("rank", C.c_int), ("wire_gbps", C.c_float), ("latency_us", C.c_float)]
-
-
-class OcLoopStruct(C.Structure):
-    """mke_oc_loop"""
-    _fields_ = [("parts", C.c_void_p), ("step_part0", C.c_void_p), ("n_steps", C.c_int), ("chunks", C.c_int),
-                ("send", C.c_void_p * 4), ("v_all", C.c_void_p * 4), ("g_all", C.c_void_p * 4), ("gv", C.c_void_p * 4), ("block_floats", C.c_int64),
-                ("loss_ring", C.c_void_p), ("loss_stride", C.c_int64), ("tag_base", C.c_int32), ("comm", C.c_void_p), ("comm_stream", C.c_void_p),
-                ("overlap_rs", C.c_int)]
-
-
-class AEPlanStruct(C.Structure):
-    """mke_ae_plan"""
-    _fields_ = [("n_layers", C.c_int), ("dims", C.c_int * 5), ("act", C.c_int), ("normalize", C.c_int),
-                ("params", C.c_void_p), ("grads", C.c_void_p), ("acc", C.c_void_p), ("n_params", C.c_int64),
-                ("w_off", C.c_int64 * 8), ("b_off", C.c_int64 * 8), ("optimizer", C.c_int), ("lr", C.c_float),
-                ("update", C.c_int), ("scratch", C.c_void_p), ("scratch_floats", C.c_int64), ("partials", C.c_void_p),
-                ("scalars", C.c_void_p)]
-
-
-class OptimizerStruct(C.Structure):
-    """mke_optimizer (TF1 defaults)"""
-    _fields_ = [("kind", C.c_int), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("epsilon", C.c_float),
-                ("rho", C.c_float), ("step", C.c_int64)]
-
-
 def optimizer_struct(name: str, lr: float, step: int = 1) -> OptimizerStruct:
     return OptimizerStruct(DENSE_OPTS[name], float(lr), 0.9, 0.999, 1e-8, 0.95, int(step))
 
-
-class KGSideStruct(C.Structure):
-    """mke_kg_side"""
-    _fields_ = [("ent_list", C.c_void_p), ("ent_lo", C.c_int32), ("n_ent", C.c_int32), ("cand_table", C.c_void_p),
-                ("cand_valid", C.c_void_p), ("cand_k", C.c_int32), ("known_keys", C.c_void_p),
-                ("known_capacity", C.c_uint64)]
-
-
-class UpdateTableStruct(C.Structure):
-    """mke_update_table"""
-    _fields_ = [("table", C.c_void_p), ("acc", C.c_void_p), ("grad", C.c_void_p), ("touched", C.c_void_p),
-                ("n_rows", C.c_int64), ("normalize", C.c_int), ("grad_copies", C.c_int), ("ref_count", C.c_void_p),
-                ("src_rows", C.c_void_p), ("slot_of", C.c_void_p), ("n_ranks", C.c_int), ("capacity", C.c_int64),
-                ("hot", HotRowsStruct)]
-
-
-class RelationPlanStruct(C.Structure):
-    """mke_relation_plan"""
-    _fields_ = [
-        ("ent_table", C.c_void_p), ("n_ent", C.c_int64), ("ent_normalize", C.c_int),
-        ("rel_table", C.c_void_p), ("n_rel", C.c_int64), ("rel_normalize", C.c_int),
-        ("ent_acc", C.c_void_p), ("rel_acc", C.c_void_p), ("ent_grad", C.c_void_p), ("rel_grad", C.c_void_p),
-        ("rel_grad_copies", C.c_int),
-        ("ent_touched", C.c_void_p), ("rel_touched", C.c_void_p), ("ent_ref_count", C.c_void_p), ("overlap", C.c_int),
-        ("neg_chunk_capacity", C.c_int64), ("stride", C.c_int), ("dim", C.c_int),
-        ("pos_h", C.c_void_p), ("pos_r", C.c_void_p), ("pos_t", C.c_void_p), ("pos_kg", C.c_void_p),
-        ("step_off", C.POINTER(C.c_int64)), ("n_steps", C.c_int), ("sides", KGSideStruct * 2),
-        ("neg_per_pos", C.c_int), ("max_try", C.c_int), ("sample_chunk", C.c_int), ("negatives_ready", C.c_int),
-        ("neg_h", C.c_void_p), ("neg_r", C.c_void_p), ("neg_t", C.c_void_p),
-        ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("stream_id", C.c_uint32),
-        ("optimizer", C.c_int), ("lr", C.c_float), ("scale", C.c_float),
-        ("loss_partials", C.c_void_p), ("loss_ring", C.c_int), ("tag_base", C.c_int32), ("pos_w", C.c_void_p),
-        ("hot", HotRowsStruct), ("tuning", C.c_void_p),
-        ("step_off_dev", C.c_void_p), ("neg_code", C.c_void_p), ("code_bits", C.c_void_p), ("code_bits_words", C.c_int64),
-    ]
 
 _lib = None
 
@@ -274,27 +79,14 @@ def lib():
                 f"{SO_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "or `make -C multike_amd/csrc`.  multike_amd has no CPU fallback.")
         L = C.CDLL(SO_PATH)
-        L.mke_version.restype = C.c_int
-        L.mke_last_error.restype = C.c_char_p
-        for name in SYMBOLS[2:]:
-            getattr(L, name).restype = C.c_int
-        L.mke_attr_scratch_floats.restype = C.c_int64
-        L.mke_mapping_scratch_floats.restype = C.c_int64
-        L.mke_ae_scratch_floats.restype = C.c_int64
-        L.mke_oc_block_floats.restype = C.c_int64
-        L.mke_oc_em_plan_temp_bytes.restype = C.c_int64
-        L.mke_align_topk_mean_temp_bytes.restype = C.c_int64
-        L.mke_stable_lists_temp_bytes.restype = C.c_int64
-        L.mke_align_lse_temp_bytes.restype = C.c_int64
-        L.mke_tripleset_filter_bytes.restype = C.c_int64
-        L.mke_assign_temp_bytes.restype = C.c_int64
-        L.mke_swap_temp_bytes.restype = C.c_int64
-        L.mke_neg_code_row_words.restype = C.c_int64
+        for name, (restype, argtypes) in _abi.FUNCTIONS.items():      # a wrongly typed argument raises ctypes.ArgumentError
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = L
         # MKE_OPTIONS="name=value,name=value": mke_set_option calls applied at load (performance knobs for experiments)
         for kv in filter(None, os.environ.get("MKE_OPTIONS", "").split(",")):
             k, _, v = kv.partition("=")
-            if L.mke_set_option(k.strip().encode(), C.c_int(int(v)), None):
+            if L.mke_set_option(k.strip().encode(), int(v), None):
                 raise MultiKEHipError(f"MKE_OPTIONS: {L.mke_last_error().decode()}")
     return _lib
 
@@ -314,17 +106,20 @@ def _check(rc: int, what: str):
         raise MultiKEHipError(f"{what} failed (code {rc}): {msg}")
 
 
-def _dev(t: torch.Tensor | None, dtype, name: str):
-    """data_ptr of a contiguous CUDA tensor of the given dtype (None -> NULL)."""
+def ptr(t: torch.Tensor | None, dtype, name: str) -> int | None:
+    """Raw device address of a contiguous CUDA tensor of the given dtype (None -> None = NULL), for an argument or a struct member."""
     if t is None:
-        return C.c_void_p(0)
+        return None
     if not t.is_cuda:
         raise MultiKEHipError(f"{name}: expected a CUDA/HIP tensor, got device {t.device} (no CPU path exists)")
     if t.dtype != dtype:
         raise MultiKEHipError(f"{name}: expected dtype {dtype}, got {t.dtype}")
     if not t.is_contiguous():
         raise MultiKEHipError(f"{name}: tensor must be contiguous")
-    return C.c_void_p(t.data_ptr())
+    return t.data_ptr()
+
+
+_dev = ptr      # for stable_match_args, whose own argument is called ptr
 
 
 _pinned_stream = None  # raw hipStream_t handle pinned by a hot loop (saves a torch.cuda.current_stream() per launch)
@@ -340,8 +135,8 @@ def pin_stream(handle: int | None):
 
 def _stream():
     if _pinned_stream is not None:
-        return C.c_void_p(_pinned_stream)
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        return _pinned_stream
+    return torch.cuda.current_stream().cuda_stream
 
 
 def version() -> int:
@@ -350,15 +145,15 @@ def version() -> int:
 
 def set_option(name: str, value: int) -> int:
     old = C.c_int(0)
-    _check(lib().mke_set_option(name.encode(), C.c_int(value), C.byref(old)), "mke_set_option")
+    _check(lib().mke_set_option(name.encode(), value, C.byref(old)), "mke_set_option")
     return old.value
 
 
 def stage_reduce(stage_rows, sorted_keys, order, grad_ent, grad_rel, touched_ent, touched_rel, tag):
-    rc = lib().mke_stage_reduce(_dev(stage_rows, torch.float32, "stage_rows"), _dev(sorted_keys, torch.int64, "keys"),
-                                _dev(order, torch.int64, "order"), C.c_int64(sorted_keys.numel()), C.c_int(stage_rows.shape[1]),
-                                _dev(grad_ent, torch.float32, "grad_ent"), _dev(grad_rel, torch.float32, "grad_rel"),
-                                _dev(touched_ent, torch.int32, "touched"), _dev(touched_rel, torch.int32, "touched"), C.c_int32(tag),
+    rc = lib().mke_stage_reduce(ptr(stage_rows, torch.float32, "stage_rows"), ptr(sorted_keys, torch.int64, "keys"),
+                                ptr(order, torch.int64, "order"), sorted_keys.numel(), stage_rows.shape[1],
+                                ptr(grad_ent, torch.float32, "grad_ent"), ptr(grad_rel, torch.float32, "grad_rel"),
+                                ptr(touched_ent, torch.int32, "touched"), ptr(touched_rel, torch.int32, "touched"), tag,
                                 _stream())
     _check(rc, "mke_stage_reduce")
 
@@ -370,10 +165,10 @@ def get_option(name: str) -> int:
 
 
 def count_entity_refs(pos_h, pos_t, neg_h, neg_t, neg_per_pos, ref_count):
-    rc = lib().mke_count_entity_refs(_dev(pos_h, torch.int32, "pos_h"), _dev(pos_t, torch.int32, "pos_t"),
-                                     C.c_int64(pos_h.numel()), _dev(neg_h, torch.int32, "neg_h"),
-                                     _dev(neg_t, torch.int32, "neg_t"), C.c_int64(0 if neg_h is None else neg_h.numel()),
-                                     C.c_int(neg_per_pos), _dev(ref_count, torch.int32, "ref_count"), _stream())
+    rc = lib().mke_count_entity_refs(ptr(pos_h, torch.int32, "pos_h"), ptr(pos_t, torch.int32, "pos_t"),
+                                     pos_h.numel(), ptr(neg_h, torch.int32, "neg_h"),
+                                     ptr(neg_t, torch.int32, "neg_t"), 0 if neg_h is None else neg_h.numel(),
+                                     neg_per_pos, ptr(ref_count, torch.int32, "ref_count"), _stream())
     _check(rc, "mke_count_entity_refs")
 
 
@@ -434,15 +229,10 @@ def triple_score_fwd_bwd_det(ent, ent_normalize, rel, rel_normalize, dim, pos, p
 def rows_update(table, acc, grad, touched, tag, dim, normalize, optimizer, lr):
     copies = 1 if grad.dim() == 2 else grad.shape[0]
     rc = lib().mke_rows_update(
-        _dev(table, torch.float32, "table"), _dev(acc, torch.float32, "acc"), _dev(grad, torch.float32, "grad"),
-        C.c_int(copies), _dev(touched, torch.int32, "touched"), C.c_int32(tag), C.c_int64(table.shape[0]), C.c_int(table.shape[1]),
-        C.c_int(dim), C.c_int(int(normalize)), C.c_int(optimizer), C.c_float(lr), _stream())
+        ptr(table, torch.float32, "table"), ptr(acc, torch.float32, "acc"), ptr(grad, torch.float32, "grad"),
+        copies, ptr(touched, torch.int32, "touched"), tag, table.shape[0], table.shape[1],
+        dim, int(normalize), optimizer, lr, _stream())
     _check(rc, "mke_rows_update")
-
-
-def ptr(t: torch.Tensor | None, dtype, name: str) -> int | None:
-    """Raw device address (for the plan / side structs)."""
-    return _dev(t, dtype, name).value
 
 
 def rows_update_multi(tables, tag, stride, dim, optimizer, lr, tuning=None):
@@ -475,12 +265,12 @@ def rows_update_multi(tables, tag, stride, dim, optimizer, lr, tuning=None):
         arr[k].normalize = int(normalize)
         arr[k].grad_copies = 1 if grad.dim() == 2 else grad.shape[0]
     if tuning is not None:       # this call's knobs (TuningStruct)
-        rc = lib().mke_rows_update_multi_t(arr, C.c_int(len(tables)), C.c_int32(tag), C.c_int(stride), C.c_int(dim),
-                                           C.c_int(optimizer), C.c_float(lr), None, C.byref(tuning), _stream())
+        rc = lib().mke_rows_update_multi_t(arr, len(tables), tag, stride, dim,
+                                           optimizer, lr, None, C.byref(tuning), _stream())
         _check(rc, "mke_rows_update_multi_t")
         return
-    rc = lib().mke_rows_update_multi(arr, C.c_int(len(tables)), C.c_int32(tag), C.c_int(stride), C.c_int(dim),
-                                     C.c_int(optimizer), C.c_float(lr), _stream())
+    rc = lib().mke_rows_update_multi(arr, len(tables), tag, stride, dim,
+                                     optimizer, lr, _stream())
     _check(rc, "mke_rows_update_multi")
 
 
@@ -489,11 +279,11 @@ def neg_sample(pos, pos_offset, pos_kg, sides, neg_per_pos, max_try, seed, strea
     ph, pr, pt = pos
     nh, nr, nt = neg_out
     rc = lib().mke_neg_sample(
-        _dev(ph, torch.int32, "pos_h"), _dev(pr, torch.int32, "pos_r"), _dev(pt, torch.int32, "pos_t"),
-        C.c_int64(ph.numel()), C.c_int64(pos_offset), _dev(pos_kg, torch.uint8, "pos_kg"), sides,
-        C.c_int(neg_per_pos), C.c_int(max_try), C.c_uint32(seed[0] & 0xFFFFFFFF), C.c_uint32(seed[1] & 0xFFFFFFFF),
-        C.c_uint32(stream_id & 0xFFFFFFFF), _dev(nh, torch.int32, "neg_h"), _dev(nr, torch.int32, "neg_r"),
-        _dev(nt, torch.int32, "neg_t"), _stream())
+        ptr(ph, torch.int32, "pos_h"), ptr(pr, torch.int32, "pos_r"), ptr(pt, torch.int32, "pos_t"),
+        ph.numel(), pos_offset, ptr(pos_kg, torch.uint8, "pos_kg"), sides,
+        neg_per_pos, max_try, seed[0] & 0xFFFFFFFF, seed[1] & 0xFFFFFFFF,
+        stream_id & 0xFFFFFFFF, ptr(nh, torch.int32, "neg_h"), ptr(nr, torch.int32, "neg_r"),
+        ptr(nt, torch.int32, "neg_t"), _stream())
     _check(rc, "mke_neg_sample")
 
 
@@ -502,15 +292,20 @@ def neg_sample_at(pos, pos_index, pos_kg, sides, neg_per_pos, max_try, seed, str
     ph, pr, pt = pos
     nh, nr, nt = neg_out
     rc = lib().mke_neg_sample_at(
-        _dev(ph, torch.int32, "pos_h"), _dev(pr, torch.int32, "pos_r"), _dev(pt, torch.int32, "pos_t"),
-        C.c_int64(ph.numel()), _dev(pos_index, torch.int32, "pos_index"), _dev(pos_kg, torch.uint8, "pos_kg"), sides,
-        C.c_int(neg_per_pos), C.c_int(max_try), C.c_uint32(seed[0] & 0xFFFFFFFF), C.c_uint32(seed[1] & 0xFFFFFFFF),
-        C.c_uint32(stream_id & 0xFFFFFFFF), _dev(nh, torch.int32, "neg_h"), _dev(nr, torch.int32, "neg_r"),
-        _dev(nt, torch.int32, "neg_t"), _stream())
+        ptr(ph, torch.int32, "pos_h"), ptr(pr, torch.int32, "pos_r"), ptr(pt, torch.int32, "pos_t"),
+        ph.numel(), ptr(pos_index, torch.int32, "pos_index"), ptr(pos_kg, torch.uint8, "pos_kg"), sides,
+        neg_per_pos, max_try, seed[0] & 0xFFFFFFFF, seed[1] & 0xFFFFFFFF,
+        stream_id & 0xFFFFFFFF, ptr(nh, torch.int32, "neg_h"), ptr(nr, torch.int32, "neg_r"),
+        ptr(nt, torch.int32, "neg_t"), _stream())
     _check(rc, "mke_neg_sample_at")
 
 
 SIM_SELECT_KPADS = (16, 32, 48, 64, 80, 96, 112, 128, 160, 192, 208, 256, 320)   # instantiations of k_sim_select / k_sim_sample / k_align_rank: up to MAX_STRIDE
+
+
+def _candidates(cand: torch.Tensor):
+    """The (column, similarity bits) int32 pairs of sim_select as the mke_candidate* the prototypes declare."""
+    return C.cast(ptr(cand, torch.int32, "cand"), C.POINTER(_abi.mke_candidate))
 
 
 def sim_select(emb: torch.Tensor, kpad: int, row_lo: int, row_hi: int, tau: torch.Tensor, n_seg: int, seg_cap: int):
@@ -522,9 +317,9 @@ def sim_select(emb: torch.Tensor, kpad: int, row_lo: int, row_hi: int, tau: torc
         raise MultiKEHipError("sim_select: one threshold per row")
     cand = torch.empty(rows, n_seg, seg_cap, 2, dtype=torch.int32, device=emb.device)
     cnt = torch.empty(rows, n_seg, dtype=torch.int32, device=emb.device)
-    rc = lib().mke_sim_select(C.c_void_p(emb.data_ptr()), C.c_int(emb.stride(0)), C.c_int(kpad), C.c_int64(emb.shape[0]),
-                              C.c_int64(row_lo), C.c_int64(row_hi), _dev(tau, torch.float32, "tau"), C.c_int(n_seg),
-                              C.c_int(seg_cap), _dev(cand, torch.int32, "cand"), _dev(cnt, torch.int32, "seg_count"), _stream())
+    rc = lib().mke_sim_select(emb.data_ptr(), emb.stride(0), kpad, emb.shape[0],
+                              row_lo, row_hi, ptr(tau, torch.float32, "tau"), n_seg,
+                              seg_cap, _candidates(cand), ptr(cnt, torch.int32, "seg_count"), _stream())
     _check(rc, "mke_sim_select")
     return cand, cnt
 
@@ -532,9 +327,9 @@ def sim_select(emb: torch.Tensor, kpad: int, row_lo: int, row_hi: int, tau: torc
 def sim_sample(emb: torch.Tensor, kpad: int, row_lo: int, row_hi: int, samp: torch.Tensor):
     """mke_sim_sample -> float32 [row_hi - row_lo, n_samp] similarities of the rows to the sample rows."""
     out = torch.empty(row_hi - row_lo, samp.shape[0], dtype=torch.float32, device=emb.device)
-    rc = lib().mke_sim_sample(_dev(emb, torch.float32, "emb"), C.c_int(emb.stride(0)), C.c_int(kpad), C.c_int64(emb.shape[0]),
-                              C.c_int64(row_lo), C.c_int64(row_hi), _dev(samp, torch.float32, "samp"), C.c_int(samp.stride(0)),
-                              C.c_int(samp.shape[0]), _dev(out, torch.float32, "out"), _stream())
+    rc = lib().mke_sim_sample(ptr(emb, torch.float32, "emb"), emb.stride(0), kpad, emb.shape[0],
+                              row_lo, row_hi, ptr(samp, torch.float32, "samp"), samp.stride(0),
+                              samp.shape[0], ptr(out, torch.float32, "out"), _stream())
     _check(rc, "mke_sim_sample")
     return out
 
@@ -544,9 +339,9 @@ def topk_candidates(cand: torch.Tensor, seg_count: torch.Tensor, k: int, id_map=
     rows, n_seg, seg_cap, _ = cand.shape
     out = torch.empty(rows, k, dtype=torch.int32, device=cand.device)
     status = torch.empty(rows, dtype=torch.int32, device=cand.device)
-    rc = lib().mke_topk_candidates(_dev(cand, torch.int32, "cand"), _dev(seg_count, torch.int32, "seg_count"), C.c_int64(rows),
-                                   C.c_int(n_seg), C.c_int(seg_cap), C.c_int(k), _dev(id_map, torch.int32, "id_map"),
-                                   _dev(out, torch.int32, "out_idx"), C.c_void_p(0), _dev(status, torch.int32, "status"), _stream())
+    rc = lib().mke_topk_candidates(_candidates(cand), ptr(seg_count, torch.int32, "seg_count"), rows,
+                                   n_seg, seg_cap, k, ptr(id_map, torch.int32, "id_map"),
+                                   ptr(out, torch.int32, "out_idx"), None, ptr(status, torch.int32, "status"), _stream())
     _check(rc, "mke_topk_candidates")
     return out, status
 
@@ -562,10 +357,10 @@ def topk_rows(vals: torch.Tensor, k: int, idx=None, seg_count=None, id_map=None,
     out = torch.empty(rows, k, dtype=torch.int32, device=vals.device) if want_idx else None
     kth = torch.empty(rows, dtype=torch.float32, device=vals.device) if want_kth else None
     status = torch.empty(rows, dtype=torch.int32, device=vals.device)
-    rc = lib().mke_topk_rows(_dev(vals, torch.float32, "vals"), _dev(idx, torch.int32, "idx"),
-                             _dev(seg_count, torch.int32, "seg_count"), C.c_int64(rows), C.c_int(n_seg), C.c_int(seg_cap),
-                             C.c_int(k), _dev(id_map, torch.int32, "id_map"), _dev(out, torch.int32, "out_idx"),
-                             _dev(kth, torch.float32, "out_kth"), _dev(status, torch.int32, "status"), _stream())
+    rc = lib().mke_topk_rows(ptr(vals, torch.float32, "vals"), ptr(idx, torch.int32, "idx"),
+                             ptr(seg_count, torch.int32, "seg_count"), rows, n_seg, seg_cap,
+                             k, ptr(id_map, torch.int32, "id_map"), ptr(out, torch.int32, "out_idx"),
+                             ptr(kth, torch.float32, "out_kth"), ptr(status, torch.int32, "status"), _stream())
     _check(rc, "mke_topk_rows")
     return out, kth, status
 
@@ -576,36 +371,32 @@ def topk_long(vals: torch.Tensor, k: int, id_map=None) -> torch.Tensor:
         raise MultiKEHipError("topk_long: vals must be [rows, n] with unit column stride")
     rows, n = vals.shape
     out = torch.empty(rows, k, dtype=torch.int32, device=vals.device)
-    rc = lib().mke_topk_long(C.c_void_p(vals.data_ptr()) if vals.is_cuda and vals.dtype == torch.float32 else _dev(vals, torch.float32, "vals"),
-                             C.c_int64(rows), C.c_int64(n), C.c_int64(vals.stride(0) if rows > 1 else n), C.c_int(k),
-                             _dev(id_map, torch.int32, "id_map"), _dev(out, torch.int32, "out_idx"), _stream())
+    rc = lib().mke_topk_long(vals.data_ptr() if vals.is_cuda and vals.dtype == torch.float32 else ptr(vals, torch.float32, "vals"),
+                             rows, n, vals.stride(0) if rows > 1 else n, k,
+                             ptr(id_map, torch.int32, "id_map"), ptr(out, torch.int32, "out_idx"), _stream())
     _check(rc, "mke_topk_long")
     return out
 
 
 def mapping_scratch_floats(n: int, dim: int) -> int:
-    return int(lib().mke_mapping_scratch_floats(C.c_int64(n), C.c_int(dim)))
-
-
-MAP_FWD, MAP_TAIL, MAP_BWD, MAP_UPD, MAP_ALL = 1, 2, 4, 8, 15
-MAPPING_MAX_VIEWS = 3
+    return int(lib().mke_mapping_scratch_floats(n, dim))
 
 
 def mapping_step_phases(args: MappingStepArgs, loss_partials: torch.Tensor, phases: int):
-    rc = lib().mke_mapping_step_phases(C.byref(args), _dev(loss_partials, torch.float64, "loss_partials"), C.c_int(phases), _stream())
+    rc = lib().mke_mapping_step_phases(C.byref(args), ptr(loss_partials, torch.float64, "loss_partials"), phases, _stream())
     _check(rc, "mke_mapping_step_phases")
 
 
 def mapping_step(args: MappingStepArgs, loss_partials: torch.Tensor):
-    rc = lib().mke_mapping_step(C.byref(args), _dev(loss_partials, torch.float64, "loss_partials"), _stream())
+    rc = lib().mke_mapping_step(C.byref(args), ptr(loss_partials, torch.float64, "loss_partials"), _stream())
     _check(rc, "mke_mapping_step")
 
 
 def mapping_steps(args: MappingStepArgs, step_off: np.ndarray, loss_ring: torch.Tensor):
     """loss_ring: float64 [ring, 4, LOSS_PARTIALS]."""
     off = np.ascontiguousarray(step_off, dtype=np.int64)
-    rc = lib().mke_mapping_steps(C.byref(args), off.ctypes.data_as(C.POINTER(C.c_int64)), C.c_int(len(off) - 1),
-                                 _dev(loss_ring, torch.float64, "loss_ring"), C.c_int(loss_ring.shape[0]), _stream())
+    rc = lib().mke_mapping_steps(C.byref(args), off.ctypes.data, len(off) - 1,
+                                 ptr(loss_ring, torch.float64, "loss_ring"), loss_ring.shape[0], _stream())
     _check(rc, "mke_mapping_steps")
 
 
@@ -615,30 +406,27 @@ def align_steps(plan: AlignPlanStruct):
 
 
 def relation_steps(plan: RelationPlanStruct, step_begin: int, step_end: int):
-    rc = lib().mke_relation_steps(C.byref(plan), C.c_int(step_begin), C.c_int(step_end), _stream())
+    rc = lib().mke_relation_steps(C.byref(plan), step_begin, step_end, _stream())
     _check(rc, "mke_relation_steps")
-
-
-CODE_ENT_BITS, CODE_HEAD, CODE_FAST, CODE_EXCL = 26, 1 << 26, 1 << 27, 1 << 28   # MKE_CODE_*
 
 
 def neg_code_row_words(n_ent: int) -> int:
     """Words of one step's row of the code-word bake's bitmap (2 bits per entity)."""
-    return int(lib().mke_neg_code_row_words(C.c_int64(n_ent)))
+    return int(lib().mke_neg_code_row_words(n_ent))
 
 
 def neg_codes(pos, step_off_dev, step_begin, step_end, pos_begin, pos_end, neg, neg_per_pos, n_ent, bits, neg_code):
     """mke_neg_codes: one code word per negative of steps [step_begin, step_end).  pos: the epoch's (h, r, t); neg: the chunk's."""
-    rc = lib().mke_neg_codes(*(_dev(x, torch.int32, "pos") for x in pos), _dev(step_off_dev, torch.int64, "step_off"),
-                             C.c_int(step_begin), C.c_int(step_end), C.c_int64(pos_begin), C.c_int64(pos_end),
-                             *(_dev(x, torch.int32, "neg") for x in neg), C.c_int(neg_per_pos), C.c_int64(n_ent),
-                             _dev(bits, torch.int32, "bits"), C.c_int64(bits.numel()), _dev(neg_code, torch.int32, "neg_code"), _stream())
+    rc = lib().mke_neg_codes(*(ptr(x, torch.int32, "pos") for x in pos), ptr(step_off_dev, torch.int64, "step_off"),
+                             step_begin, step_end, pos_begin, pos_end,
+                             *(ptr(x, torch.int32, "neg") for x in neg), neg_per_pos, n_ent,
+                             ptr(bits, torch.int32, "bits"), bits.numel(), ptr(neg_code, torch.int32, "neg_code"), _stream())
     _check(rc, "mke_neg_codes")
 
 
 def tripleset_build(h, r, t, keys):
-    rc = lib().mke_tripleset_build(_dev(h, torch.int32, "h"), _dev(r, torch.int32, "r"), _dev(t, torch.int32, "t"),
-                                   C.c_int64(h.numel()), _dev(keys, torch.int64, "keys"), C.c_uint64(keys.numel()),
+    rc = lib().mke_tripleset_build(ptr(h, torch.int32, "h"), ptr(r, torch.int32, "r"), ptr(t, torch.int32, "t"),
+                                   h.numel(), ptr(keys, torch.int64, "keys"), keys.numel(),
                                    _stream())
     _check(rc, "mke_tripleset_build")
 
@@ -646,12 +434,12 @@ def tripleset_build(h, r, t, keys):
 def tripleset_forget(keys):
     """Drop the library's prefilter of the table at `keys` (a tensor or a raw address); no-op when it has none."""
     addr = keys if isinstance(keys, int) else keys.data_ptr()
-    _check(lib().mke_tripleset_forget(C.c_void_p(addr)), "mke_tripleset_forget")
+    _check(lib().mke_tripleset_forget(addr), "mke_tripleset_forget")
 
 
 def tripleset_filter_bytes(keys) -> int:
     """Size of the prefilter the sampler uses for this table; 0 when it has none (the table is probed directly)."""
-    return int(lib().mke_tripleset_filter_bytes(_dev(keys, torch.int64, "keys"), C.c_uint64(keys.numel())))
+    return int(lib().mke_tripleset_filter_bytes(ptr(keys, torch.int64, "keys"), keys.numel()))
 
 
 def epoch_positives(list1, list2, perm1, perm2, b1, b2, n_steps, list1_out, list2_out, pos):
@@ -668,64 +456,64 @@ def epoch_positives(list1, list2, perm1, perm2, b1, b2, n_steps, list1_out, list
     for o, l in ((list1_out, list1), (list2_out, list2)):
         if o is not None and o.shape != l.shape:
             raise MultiKEHipError("a shuffled list must have its list's shape")
-    rc = lib().mke_epoch_positives(_dev(list1, i32, "list1"), _dev(list2, i32, "list2"), C.c_int64(n1), C.c_int64(n2),
-                                   _dev(perm1, i64, "perm1"), _dev(perm2, i64, "perm2"), C.c_int64(b1), C.c_int64(b2),
-                                   C.c_int64(n_steps), _dev(list1_out, i32, "list1_out"), _dev(list2_out, i32, "list2_out"),
-                                   _dev(pos[0], i32, "pos_h"), _dev(pos[1], i32, "pos_r"), _dev(pos[2], i32, "pos_t"), _stream())
+    rc = lib().mke_epoch_positives(ptr(list1, i32, "list1"), ptr(list2, i32, "list2"), n1, n2,
+                                   ptr(perm1, i64, "perm1"), ptr(perm2, i64, "perm2"), b1, b2,
+                                   n_steps, ptr(list1_out, i32, "list1_out"), ptr(list2_out, i32, "list2_out"),
+                                   ptr(pos[0], i32, "pos_h"), ptr(pos[1], i32, "pos_r"), ptr(pos[2], i32, "pos_t"), _stream())
     _check(rc, "mke_epoch_positives")
 
 
 def tripleset_query(h, r, t, keys, out):
-    rc = lib().mke_tripleset_query(_dev(h, torch.int32, "h"), _dev(r, torch.int32, "r"), _dev(t, torch.int32, "t"),
-                                   C.c_int64(h.numel()), _dev(keys, torch.int64, "keys"), C.c_uint64(keys.numel()),
-                                   _dev(out, torch.uint8, "out"), _stream())
+    rc = lib().mke_tripleset_query(ptr(h, torch.int32, "h"), ptr(r, torch.int32, "r"), ptr(t, torch.int32, "t"),
+                                   h.numel(), ptr(keys, torch.int64, "keys"), keys.numel(),
+                                   ptr(out, torch.uint8, "out"), _stream())
     _check(rc, "mke_tripleset_query")
 
 
 def gathered_logistic_fwd_bwd(hs, rs, ts, ws, sign, gh, gr, gt, loss_partials):
     n, dim = hs.shape
     rc = lib().mke_gathered_logistic_fwd_bwd(
-        _dev(hs, torch.float32, "hs"), _dev(rs, torch.float32, "rs"), _dev(ts, torch.float32, "ts"),
-        _dev(ws, torch.float32, "ws"), C.c_int64(n), C.c_int(dim), C.c_int(dim), C.c_int(sign),
-        _dev(gh, torch.float32, "gh"), _dev(gr, torch.float32, "gr"), _dev(gt, torch.float32, "gt"),
-        _dev(loss_partials, torch.float64, "loss_partials"), _stream())
+        ptr(hs, torch.float32, "hs"), ptr(rs, torch.float32, "rs"), ptr(ts, torch.float32, "ts"),
+        ptr(ws, torch.float32, "ws"), n, dim, dim, sign,
+        ptr(gh, torch.float32, "gh"), ptr(gr, torch.float32, "gr"), ptr(gt, torch.float32, "gt"),
+        ptr(loss_partials, torch.float64, "loss_partials"), _stream())
     _check(rc, "mke_gathered_logistic_fwd_bwd")
 
 
 def gathered_alignment_fwd_bwd(a, b, ga, gb, loss_partials):
     n, dim = a.shape
     rc = lib().mke_gathered_alignment_fwd_bwd(
-        _dev(a, torch.float32, "a"), _dev(b, torch.float32, "b"), C.c_int64(n), C.c_int(dim), C.c_int(dim),
-        _dev(ga, torch.float32, "ga"), _dev(gb, torch.float32, "gb"),
-        _dev(loss_partials, torch.float64, "loss_partials"), _stream())
+        ptr(a, torch.float32, "a"), ptr(b, torch.float32, "b"), n, dim, dim,
+        ptr(ga, torch.float32, "ga"), ptr(gb, torch.float32, "gb"),
+        ptr(loss_partials, torch.float64, "loss_partials"), _stream())
     _check(rc, "mke_gathered_alignment_fwd_bwd")
 
 
 def align_fwd_bwd(table_a, a_normalize, table_b, b_normalize, dim, ia, ib, weight, grad_a, touched_a, grad_b, touched_b,
                   tag, loss_partials):
     rc = lib().mke_align_fwd_bwd(
-        _dev(table_a, torch.float32, "table_a"), C.c_int(int(a_normalize)), _dev(table_b, torch.float32, "table_b"),
-        C.c_int(int(b_normalize)), C.c_int(table_a.shape[1]), C.c_int(dim), _dev(ia, torch.int32, "ia"),
-        _dev(ib, torch.int32, "ib"), C.c_int64(ia.numel()), C.c_float(weight), _dev(grad_a, torch.float32, "grad_a"),
-        _dev(touched_a, torch.int32, "touched_a"), _dev(grad_b, torch.float32, "grad_b"),
-        _dev(touched_b, torch.int32, "touched_b"), C.c_int32(tag), _dev(loss_partials, torch.float64, "loss_partials"),
+        ptr(table_a, torch.float32, "table_a"), int(a_normalize), ptr(table_b, torch.float32, "table_b"),
+        int(b_normalize), table_a.shape[1], dim, ptr(ia, torch.int32, "ia"),
+        ptr(ib, torch.int32, "ib"), ia.numel(), weight, ptr(grad_a, torch.float32, "grad_a"),
+        ptr(touched_a, torch.int32, "touched_a"), ptr(grad_b, torch.float32, "grad_b"),
+        ptr(touched_b, torch.int32, "touched_b"), tag, ptr(loss_partials, torch.float64, "loss_partials"),
         _stream())
     _check(rc, "mke_align_fwd_bwd")
 
 
 def gather_rows(table, normalize, dim, idx, out):
     n = out.shape[0]
-    rc = lib().mke_gather_rows(_dev(table, torch.float32, "table"), C.c_int(int(normalize)), C.c_int(table.shape[1]),
-                               C.c_int(dim), _dev(idx, torch.int32, "idx"), C.c_int64(n),
-                               _dev(out, torch.float32, "out"), _stream())
+    rc = lib().mke_gather_rows(ptr(table, torch.float32, "table"), int(normalize), table.shape[1],
+                               dim, ptr(idx, torch.int32, "idx"), n,
+                               ptr(out, torch.float32, "out"), _stream())
     _check(rc, "mke_gather_rows")
 
 
 def probe_rows(a, b, c, idx, out):
     """mke_probe_rows: rows idx of a (and b, c when given) read together; out [len(idx)] float32."""
-    rc = lib().mke_probe_rows(_dev(a, torch.float32, "a"), _dev(b, torch.float32, "b"), _dev(c, torch.float32, "c"),
-                              C.c_int(a.shape[1]), _dev(idx, torch.int32, "idx"), C.c_int64(idx.numel()),
-                              _dev(out, torch.float32, "out"), _stream())
+    rc = lib().mke_probe_rows(ptr(a, torch.float32, "a"), ptr(b, torch.float32, "b"), ptr(c, torch.float32, "c"),
+                              a.shape[1], ptr(idx, torch.int32, "idx"), idx.numel(),
+                              ptr(out, torch.float32, "out"), _stream())
     _check(rc, "mke_probe_rows")
 
 
@@ -734,10 +522,10 @@ def rowset_build(streams, flags, counts, req, id_map, overflow, n_ranks, capacit
     args = []
     for k in range(4):
         t = streams[k] if k < len(streams) else None
-        args += [_dev(t, torch.int32, f"ids{k}"), C.c_int64(0 if t is None else t.numel())]
-    rc = lib().mke_rowset_build(*args, _dev(flags, torch.int32, "flags"), _dev(counts, torch.int32, "counts"),
-                                _dev(req, torch.int32, "req"), _dev(id_map, torch.int32, "id_map"),
-                                _dev(overflow, torch.int32, "overflow"), C.c_int(n_ranks), C.c_int(capacity), _stream())
+        args += [ptr(t, torch.int32, f"ids{k}"), 0 if t is None else t.numel()]
+    rc = lib().mke_rowset_build(*args, ptr(flags, torch.int32, "flags"), ptr(counts, torch.int32, "counts"),
+                                ptr(req, torch.int32, "req"), ptr(id_map, torch.int32, "id_map"),
+                                ptr(overflow, torch.int32, "overflow"), n_ranks, capacity, _stream())
     _check(rc, "mke_rowset_build")
 
 
@@ -747,29 +535,29 @@ def rowset_remap(streams, outs, id_map, flags, reset_req=None, reset_counts=None
     for k in range(4):
         t = streams[k] if k < len(streams) else None
         o = outs[k] if k < len(outs) else None
-        args += [_dev(t, torch.int32, f"ids{k}"), _dev(o, torch.int32, f"out{k}"), C.c_int64(0 if t is None else t.numel())]
-    rc = lib().mke_rowset_remap(*args, _dev(id_map, torch.int32, "id_map"), _dev(flags, torch.int32, "flags"),
-                                _dev(reset_req, torch.int32, "reset_req"), C.c_int64(0 if reset_req is None else reset_req.numel()),
-                                _dev(reset_counts, torch.int32, "reset_counts"),
-                                C.c_int(0 if reset_counts is None else reset_counts.numel()),
-                                _dev(want, torch.int32, "want"), _dev(slot_of, torch.int32, "slot_of"), C.c_int(n_ranks),
-                                C.c_int(capacity), _stream())
+        args += [ptr(t, torch.int32, f"ids{k}"), ptr(o, torch.int32, f"out{k}"), 0 if t is None else t.numel()]
+    rc = lib().mke_rowset_remap(*args, ptr(id_map, torch.int32, "id_map"), ptr(flags, torch.int32, "flags"),
+                                ptr(reset_req, torch.int32, "reset_req"), 0 if reset_req is None else reset_req.numel(),
+                                ptr(reset_counts, torch.int32, "reset_counts"),
+                                0 if reset_counts is None else reset_counts.numel(),
+                                ptr(want, torch.int32, "want"), ptr(slot_of, torch.int32, "slot_of"), n_ranks,
+                                capacity, _stream())
     _check(rc, "mke_rowset_remap")
 
 
 def rows_gather_padded(table, idx, out, zero_rows=None):
-    rc = lib().mke_rows_gather_padded(_dev(table, torch.float32, "table"), C.c_int(table.shape[1]),
-                                      _dev(idx, torch.int32, "idx"), C.c_int64(idx.numel()),
-                                      _dev(out, torch.float32, "out"), _dev(zero_rows, torch.float32, "zero_rows"), _stream())
+    rc = lib().mke_rows_gather_padded(ptr(table, torch.float32, "table"), table.shape[1],
+                                      ptr(idx, torch.int32, "idx"), idx.numel(),
+                                      ptr(out, torch.float32, "out"), ptr(zero_rows, torch.float32, "zero_rows"), _stream())
     _check(rc, "mke_rows_gather_padded")
 
 
 def rows_scatter_add(idx, rows, dim, grad, touched, tag, reset_req=None, reset_counts=None):
-    rc = lib().mke_rows_scatter_add(_dev(idx, torch.int32, "idx"), _dev(rows, torch.float32, "rows"),
-                                    C.c_int64(idx.numel()), C.c_int(grad.shape[1]), C.c_int(dim),
-                                    _dev(grad, torch.float32, "grad"), _dev(touched, torch.int32, "touched"), C.c_int32(tag),
-                                    _dev(reset_req, torch.int32, "reset_req"), _dev(reset_counts, torch.int32, "reset_counts"),
-                                    C.c_int(0 if reset_counts is None else reset_counts.numel()), _stream())
+    rc = lib().mke_rows_scatter_add(ptr(idx, torch.int32, "idx"), ptr(rows, torch.float32, "rows"),
+                                    idx.numel(), grad.shape[1], dim,
+                                    ptr(grad, torch.float32, "grad"), ptr(touched, torch.int32, "touched"), tag,
+                                    ptr(reset_req, torch.int32, "reset_req"), ptr(reset_counts, torch.int32, "reset_counts"),
+                                    0 if reset_counts is None else reset_counts.numel(), _stream())
     _check(rc, "mke_rows_scatter_add")
 
 
@@ -782,11 +570,11 @@ def cnn_params(dim: int) -> int:
 
 
 def attr_conv_fwd(attr, attr_normalize, lit, dim, ia, iv, params, flat):
-    rc = lib().mke_attr_conv_fwd(_dev(attr, torch.float32, "attr_table"), C.c_int(attr.shape[1]), C.c_int(int(attr_normalize)),
-                                 _dev(lit, torch.float32, "lit_table"), C.c_int(lit.shape[1]), C.c_int(dim),
-                                 _dev(ia, torch.int32, "ia"), _dev(iv, torch.int32, "iv"), C.c_int64(ia.numel()),
-                                 _dev(params, torch.float32, "params"), _dev(flat, torch.float32, "flat"),
-                                 C.c_int(flat.shape[1]), _stream())
+    rc = lib().mke_attr_conv_fwd(ptr(attr, torch.float32, "attr_table"), attr.shape[1], int(attr_normalize),
+                                 ptr(lit, torch.float32, "lit_table"), lit.shape[1], dim,
+                                 ptr(ia, torch.int32, "ia"), ptr(iv, torch.int32, "iv"), ia.numel(),
+                                 ptr(params, torch.float32, "params"), ptr(flat, torch.float32, "flat"),
+                                 flat.shape[1], _stream())
     _check(rc, "mke_attr_conv_fwd")
 
 
@@ -797,81 +585,76 @@ def cnn_workspace_floats(dim: int) -> int:
 
 def attr_conv_bwd(attr, attr_normalize, lit, dim, ia, iv, params, dflat, grad_params, grad_attr, touched_attr, tag,
                   workspace=None):
-    rc = lib().mke_attr_conv_bwd(_dev(attr, torch.float32, "attr_table"), C.c_int(attr.shape[1]), C.c_int(int(attr_normalize)),
-                                 _dev(lit, torch.float32, "lit_table"), C.c_int(lit.shape[1]), C.c_int(dim),
-                                 _dev(ia, torch.int32, "ia"), _dev(iv, torch.int32, "iv"), C.c_int64(ia.numel()),
-                                 _dev(params, torch.float32, "params"), _dev(dflat, torch.float32, "dflat"),
-                                 _dev(grad_params, torch.float32, "grad_params"), _dev(grad_attr, torch.float32, "grad_attr"),
-                                 _dev(touched_attr, torch.int32, "touched_attr"), C.c_int32(tag),
-                                 _dev(workspace, torch.float32, "workspace"), _stream())
+    rc = lib().mke_attr_conv_bwd(ptr(attr, torch.float32, "attr_table"), attr.shape[1], int(attr_normalize),
+                                 ptr(lit, torch.float32, "lit_table"), lit.shape[1], dim,
+                                 ptr(ia, torch.int32, "ia"), ptr(iv, torch.int32, "iv"), ia.numel(),
+                                 ptr(params, torch.float32, "params"), ptr(dflat, torch.float32, "dflat"),
+                                 ptr(grad_params, torch.float32, "grad_params"), ptr(grad_attr, torch.float32, "grad_attr"),
+                                 ptr(touched_attr, torch.int32, "touched_attr"), tag,
+                                 ptr(workspace, torch.float32, "workspace"), _stream())
     _check(rc, "mke_attr_conv_bwd")
 
 
 def attr_tail_z(z, bias, sumsq_partials):
     n, dim = z.shape
-    rc = lib().mke_attr_tail_z(_dev(z, torch.float32, "z"), _dev(bias, torch.float32, "bias"), C.c_int64(n), C.c_int(dim),
-                               _dev(sumsq_partials, torch.float64, "sumsq_partials"), _stream())
+    rc = lib().mke_attr_tail_z(ptr(z, torch.float32, "z"), ptr(bias, torch.float32, "bias"), n, dim,
+                               ptr(sumsq_partials, torch.float64, "sumsq_partials"), _stream())
     _check(rc, "mke_attr_tail_z")
 
 
 def attr_tail_loss(z, sumsq_partials, ent, ent_normalize, ih, weights, scale, gout, dot_partials, grad_ent, touched_ent, tag,
                    loss_partials):
     n, dim = z.shape
-    rc = lib().mke_attr_tail_loss(_dev(z, torch.float32, "z"), _dev(sumsq_partials, torch.float64, "sumsq"),
-                                  _dev(ent, torch.float32, "ent_table"), C.c_int(ent.shape[1]), C.c_int(int(ent_normalize)),
-                                  _dev(ih, torch.int32, "ih"), _dev(weights, torch.float32, "weights"), C.c_float(scale),
-                                  C.c_int64(n), C.c_int(dim), _dev(gout, torch.float32, "gout"),
-                                  _dev(dot_partials, torch.float64, "dot_partials"), _dev(grad_ent, torch.float32, "grad_ent"),
-                                  _dev(touched_ent, torch.int32, "touched_ent"), C.c_int32(tag),
-                                  _dev(loss_partials, torch.float64, "loss_partials"), _stream())
+    rc = lib().mke_attr_tail_loss(ptr(z, torch.float32, "z"), ptr(sumsq_partials, torch.float64, "sumsq"),
+                                  ptr(ent, torch.float32, "ent_table"), ent.shape[1], int(ent_normalize),
+                                  ptr(ih, torch.int32, "ih"), ptr(weights, torch.float32, "weights"), scale,
+                                  n, dim, ptr(gout, torch.float32, "gout"),
+                                  ptr(dot_partials, torch.float64, "dot_partials"), ptr(grad_ent, torch.float32, "grad_ent"),
+                                  ptr(touched_ent, torch.int32, "touched_ent"), tag,
+                                  ptr(loss_partials, torch.float64, "loss_partials"), _stream())
     _check(rc, "mke_attr_tail_loss")
 
 
 def attr_tail_bwd(z, gout, sumsq_partials, dot_partials, grad_bias=None):
     n, dim = z.shape
-    rc = lib().mke_attr_tail_bwd(_dev(z, torch.float32, "z"), _dev(gout, torch.float32, "gout"),
-                                 _dev(sumsq_partials, torch.float64, "sumsq"), _dev(dot_partials, torch.float64, "dot"),
-                                 C.c_int64(n), C.c_int(dim), _dev(grad_bias, torch.float32, "grad_bias"), _stream())
+    rc = lib().mke_attr_tail_bwd(ptr(z, torch.float32, "z"), ptr(gout, torch.float32, "gout"),
+                                 ptr(sumsq_partials, torch.float64, "sumsq"), ptr(dot_partials, torch.float64, "dot"),
+                                 n, dim, ptr(grad_bias, torch.float32, "grad_bias"), _stream())
     _check(rc, "mke_attr_tail_bwd")
 
 
 def dense_update(param, acc, grad, optimizer, lr):
-    rc = lib().mke_dense_update(_dev(param, torch.float32, "param"), _dev(acc, torch.float32, "acc"),
-                                _dev(grad, torch.float32, "grad"), C.c_int64(param.numel()), C.c_int(optimizer), C.c_float(lr),
+    rc = lib().mke_dense_update(ptr(param, torch.float32, "param"), ptr(acc, torch.float32, "acc"),
+                                ptr(grad, torch.float32, "grad"), param.numel(), optimizer, lr,
                                 _stream())
     _check(rc, "mke_dense_update")
 
 
 def oc_block_floats(capacity: int, stride: int) -> int:
-    return int(lib().mke_oc_block_floats(C.c_int64(capacity), C.c_int(stride)))
+    return int(lib().mke_oc_block_floats(capacity, stride))
 
 
 def oc_pack_codes(pos_h, neg_h, neg_t, neg_per_pos: int, codes):
-    rc = lib().mke_oc_pack_codes(_dev(pos_h, torch.int32, "pos_h"), _dev(neg_h, torch.int32, "neg_h"),
-                                 _dev(neg_t, torch.int32, "neg_t"), C.c_int64(pos_h.numel()), C.c_int(neg_per_pos),
-                                 _dev(codes, torch.int32, "codes"), _stream())
+    rc = lib().mke_oc_pack_codes(ptr(pos_h, torch.int32, "pos_h"), ptr(neg_h, torch.int32, "neg_h"),
+                                 ptr(neg_t, torch.int32, "neg_t"), pos_h.numel(), neg_per_pos,
+                                 ptr(codes, torch.int32, "codes"), _stream())
     _check(rc, "mke_oc_pack_codes")
 
 
-OC_NEED_HR, OC_NEED_RT, OC_CODE_MASK = 0x40000000, 0x80000000, 0x3FFFFFFF
+OC_CODE_MASK = 0x3FFFFFFF       # a code without its OC_NEED_* group flags
 
 
 def oc_plan(pos_h, pos_t, codes, neg_per_pos: int, part_lo, n_parts: int, n_ranks: int, rank: int, slot_h, slot_t, own_h, own_t, counts):
     """The epoch's slots / owned lists / per-(part, owner) counts in one launch (mke_oc_plan); `codes`: the whole epoch's codes
     by epoch position (their group flags say which vector a positive needs), None when neg_per_pos == 0."""
     i32 = torch.int32
-    rc = lib().mke_oc_plan(_dev(pos_h, i32, "pos_h"), _dev(pos_t, i32, "pos_t"),
-                           _dev(codes, i32, "codes") if neg_per_pos else None, C.c_int(neg_per_pos), _dev(part_lo, torch.int64, "part_lo"),
-                           C.c_int(n_parts), C.c_int(n_ranks), C.c_int(rank), _dev(slot_h, i32, "slot_h"), _dev(slot_t, i32, "slot_t"),
-                           _dev(own_h, i32, "own_h"), _dev(own_t, i32, "own_t"), _dev(counts, i32, "counts"), _stream())
+    rc = lib().mke_oc_plan(ptr(pos_h, i32, "pos_h"), ptr(pos_t, i32, "pos_t"),
+                           ptr(codes, i32, "codes") if neg_per_pos else None, neg_per_pos, ptr(part_lo, torch.int64, "part_lo"),
+                           n_parts, n_ranks, rank, ptr(slot_h, i32, "slot_h"), ptr(slot_t, i32, "slot_t"),
+                           ptr(own_h, i32, "own_h"), ptr(own_t, i32, "own_t"), ptr(counts, i32, "counts"), _stream())
     _check(rc, "mke_oc_plan")
 
 
-OC_BASES, OC_COUNT, OC_SCORE, OC_APPLY, OC_UPDATE, OC_PASS2 = 1, 2, 4, 8, 16, 32
-OC_GVSUM = 64       # peer-direct entity-major: the inbox (mke_oc_run's g_all) summed into the local block (gv), before OC_PASS2
-
-
-OC_BUCKET_WAVES = 8192
 OC_REC_INTS = 3     # an owned-code record: (epoch position, n, code without flags), int32 each
 
 
@@ -881,9 +664,9 @@ def oc_bucket_codes(codes, n_mine: int, neg_per_pos: int, pos0: int, n_ranks: in
     i32 = torch.int32
     if scratch.numel() < n_ranks * OC_BUCKET_WAVES or counts.numel() < n_ranks or need.numel() < n_mine or send.numel() < OC_REC_INTS * n_ranks * cap:
         raise MultiKEHipError("mke_oc_bucket_codes: need / send / counts / scratch too small")
-    rc = lib().mke_oc_bucket_codes(_dev(codes, i32, "codes"), C.c_int64(n_mine), C.c_int(neg_per_pos), C.c_int64(pos0), C.c_int(n_ranks),
-                                   C.c_int64(cap), _dev(need, i32, "need"), _dev(send, i32, "send"), _dev(counts, i32, "counts"),
-                                   _dev(scratch, i32, "scratch"), _stream())
+    rc = lib().mke_oc_bucket_codes(ptr(codes, i32, "codes"), n_mine, neg_per_pos, pos0, n_ranks,
+                                   cap, ptr(need, i32, "need"), ptr(send, i32, "send"), ptr(counts, i32, "counts"),
+                                   ptr(scratch, i32, "scratch"), _stream())
     _check(rc, "mke_oc_bucket_codes")
 
 
@@ -892,13 +675,13 @@ def oc_owned_index(recv, counts, n_ranks: int, cap: int, n_all: int, own_rec, ow
     i32 = torch.int32
     if own_rec.numel() < OC_REC_INTS * n_ranks * cap or own_off.numel() < n_all + 1 or recv.numel() < OC_REC_INTS * n_ranks * cap or counts.numel() < n_ranks:
         raise MultiKEHipError("mke_oc_owned_index: recv / counts / own_rec / own_off too small")
-    rc = lib().mke_oc_owned_index(_dev(recv, i32, "recv"), _dev(counts, i32, "counts"), C.c_int(n_ranks), C.c_int64(cap), C.c_int64(n_all),
-                                  _dev(own_rec, i32, "own_rec"), _dev(own_off, i32, "own_off"), _stream())
+    rc = lib().mke_oc_owned_index(ptr(recv, i32, "recv"), ptr(counts, i32, "counts"), n_ranks, cap, n_all,
+                                  ptr(own_rec, i32, "own_rec"), ptr(own_off, i32, "own_off"), _stream())
     _check(rc, "mke_oc_owned_index")
 
 
 def oc_em_plan_temp_bytes(capacity: int) -> int:
-    n = lib().mke_oc_em_plan_temp_bytes(C.c_int64(capacity))
+    n = lib().mke_oc_em_plan_temp_bytes(capacity)
     if n < 0:
         raise MultiKEHipError("mke_oc_em_plan_temp_bytes: capacity out of range")
     return int(n)
@@ -911,7 +694,7 @@ def oc_em_plan(args: OcEmPlanArgs):
 
 def oc_steps(loop: OcLoopStruct, step_begin: int, step_end: int):
     """mke_oc_steps: global steps [step_begin, step_end) of the current epoch enqueued by one native call."""
-    _check(lib().mke_oc_steps(C.byref(loop), C.c_int(step_begin), C.c_int(step_end), _stream()), "mke_oc_steps")
+    _check(lib().mke_oc_steps(C.byref(loop), step_begin, step_end, _stream()), "mke_oc_steps")
 
 
 def oc_pass2(step: OcStepStruct):
@@ -921,19 +704,19 @@ def oc_pass2(step: OcStepStruct):
 def oc_gv_sum(step: OcStepStruct, inbox, gv):
     """mke_oc_gv_sum: the writers' slices of this rank's gradient inbox summed, in rank order, into the local block `gv`
     (peer-direct entity-major steps only)."""
-    rc = lib().mke_oc_gv_sum(C.byref(step), _dev(inbox, torch.float32, "inbox"), _dev(gv, torch.float32, "gv"), _stream())
+    rc = lib().mke_oc_gv_sum(C.byref(step), ptr(inbox, torch.float32, "inbox"), ptr(gv, torch.float32, "gv"), _stream())
     _check(rc, "mke_oc_gv_sum")
 
 
 def oc_run(step: OcStepStruct, phases: int, send, v_all, block_floats: int, g_all, gv, loss_partials):
     """mke_oc_run with RAW device addresses (ints / None) — the caller validated the tensors once per epoch."""
-    rc = lib().mke_oc_run(C.byref(step), C.c_int(phases), C.c_void_p(send), C.c_void_p(v_all), C.c_int64(block_floats),
-                          C.c_void_p(g_all), C.c_void_p(gv), C.c_void_p(loss_partials), _stream())
+    rc = lib().mke_oc_run(C.byref(step), phases, send, v_all, block_floats,
+                          g_all, gv, loss_partials, _stream())
     _check(rc, "mke_oc_run")
 
 
 def ae_scratch_floats(plan: AEPlanStruct, rows: int) -> int:
-    n = lib().mke_ae_scratch_floats(C.byref(plan), C.c_int64(rows))
+    n = lib().mke_ae_scratch_floats(C.byref(plan), rows)
     if n < 0:
         raise MultiKEHipError("mke_ae_scratch_floats: bad plan")
     return int(n)
@@ -941,24 +724,21 @@ def ae_scratch_floats(plan: AEPlanStruct, rows: int) -> int:
 
 def ae_train_steps(plan: AEPlanStruct, x: torch.Tensor, batch_rows: int, loss_out: torch.Tensor):
     """mke_ae_train_steps over the rows of x (float32 [n, ldx] CUDA, row-major); loss_out: float64 [n_batches]."""
-    rc = lib().mke_ae_train_steps(C.byref(plan), _dev(x, torch.float32, "x"), C.c_int64(x.shape[0]), C.c_int64(x.stride(0)),
-                                  C.c_int64(batch_rows), _dev(loss_out, torch.float64, "loss_out"), _stream())
+    rc = lib().mke_ae_train_steps(C.byref(plan), ptr(x, torch.float32, "x"), x.shape[0], x.stride(0),
+                                  batch_rows, ptr(loss_out, torch.float64, "loss_out"), _stream())
     _check(rc, "mke_ae_train_steps")
-
-
-AE_ENC, AE_DEC, AE_BWD, AE_UPD, AE_ALL = 1, 2, 4, 8, 15
 
 
 def ae_step_phases(plan: AEPlanStruct, x, rows: int, ldx: int, global_rows: int, phases: int, loss_out: torch.Tensor):
     """mke_ae_step_phases: one batch of the auto-encoder cut at its batch-wide sums (x: float32 [rows, ldx] CUDA or None)."""
-    rc = lib().mke_ae_step_phases(C.byref(plan), (_dev(x, torch.float32, "x") if rows else None), C.c_int64(rows), C.c_int64(ldx),
-                                  C.c_int64(global_rows), C.c_int(phases), _dev(loss_out, torch.float64, "loss_out"), _stream())
+    rc = lib().mke_ae_step_phases(C.byref(plan), (ptr(x, torch.float32, "x") if rows else None), rows, ldx,
+                                  global_rows, phases, ptr(loss_out, torch.float64, "loss_out"), _stream())
     _check(rc, "mke_ae_step_phases")
 
 
 def ae_encode(plan: AEPlanStruct, x: torch.Tensor, out: torch.Tensor):
-    rc = lib().mke_ae_encode(C.byref(plan), _dev(x, torch.float32, "x"), C.c_int64(x.shape[0]), C.c_int64(x.stride(0)),
-                             _dev(out, torch.float32, "out"), C.c_int64(out.stride(0)), _stream())
+    rc = lib().mke_ae_encode(C.byref(plan), ptr(x, torch.float32, "x"), x.shape[0], x.stride(0),
+                             ptr(out, torch.float32, "out"), out.stride(0), _stream())
     _check(rc, "mke_ae_encode")
 
 
@@ -971,43 +751,25 @@ def dense_layer_fwd(x: torch.Tensor, w: torch.Tensor, b, act: int, out: torch.Te
     for t, nm in ((x, "x"), (w, "w"), (out, "out")):       # row-major with any row stride (padded rows are not "contiguous")
         if not t.is_cuda or t.dtype != torch.float32:
             raise MultiKEHipError(f"dense_layer_fwd: {nm} must be a float32 CUDA tensor")
-    rc = lib().mke_dense_layer_fwd(C.c_void_p(x.data_ptr()), C.c_int64(x.stride(0)), C.c_void_p(w.data_ptr()),
-                                   C.c_int64(w.stride(0)), _dev(b, torch.float32, "b"), C.c_int(act),
-                                   C.c_void_p(out.data_ptr()), C.c_int64(out.stride(0)), C.c_int(M), C.c_int(N), C.c_int(K),
+    rc = lib().mke_dense_layer_fwd(x.data_ptr(), x.stride(0), w.data_ptr(),
+                                   w.stride(0), ptr(b, torch.float32, "b"), act,
+                                   out.data_ptr(), out.stride(0), M, N, K,
                                    _stream())
     _check(rc, "mke_dense_layer_fwd")
 
 
 def align_rank(emb1, emb2, kpad, n1, n2, rank, best, ties=None):
     """mke_align_rank over row-major padded emb1 [n1, ld1] / emb2 [n2, ld2]."""
-    rc = lib().mke_align_rank(_dev(emb1, torch.float32, "emb1"), C.c_int(emb1.shape[1]), _dev(emb2, torch.float32, "emb2"),
-                              C.c_int(emb2.shape[1]), C.c_int(kpad), C.c_int64(n1), C.c_int64(n2),
-                              _dev(rank, torch.int32, "rank"), _dev(ties, torch.int32, "ties"), _dev(best, torch.int64, "best"),
+    rc = lib().mke_align_rank(ptr(emb1, torch.float32, "emb1"), emb1.shape[1], ptr(emb2, torch.float32, "emb2"),
+                              emb2.shape[1], kpad, n1, n2,
+                              ptr(rank, torch.int32, "rank"), ptr(ties, torch.int32, "ties"), ptr(best, torch.int64, "best"),
                               _stream())
     _check(rc, "mke_align_rank")
 
 
-METRIC_INNER, METRIC_EUCLIDEAN = 0, 1   # MKE_METRIC_*
-
-
-class TopkMeanArgs(C.Structure):
-    """mke_topk_mean_args"""
-    _fields_ = [("a", C.c_void_p), ("lda", C.c_int), ("b", C.c_void_p), ("ldb", C.c_int), ("kpad", C.c_int),
-                ("n_a", C.c_int64), ("n_b", C.c_int64), ("metric", C.c_int), ("sq_a", C.c_void_p), ("sq_b", C.c_void_p),
-                ("k", C.c_int), ("out", C.c_void_p), ("temp", C.c_void_p), ("temp_bytes", C.c_int64)]
-
-
-class AlignArgs(C.Structure):
-    """mke_align_args"""
-    _fields_ = [("emb1", C.c_void_p), ("ld1", C.c_int), ("emb2", C.c_void_p), ("ld2", C.c_int), ("kpad", C.c_int),
-                ("n1", C.c_int64), ("n2", C.c_int64), ("metric", C.c_int), ("sq1", C.c_void_p), ("sq2", C.c_void_p),
-                ("csls_row", C.c_void_p), ("csls_col", C.c_void_p), ("rank", C.c_void_p), ("ties", C.c_void_p),
-                ("best", C.c_void_p)]
-
-
 def align_topk_mean_temp_bytes(n_a: int, n_b: int, kpad: int, k: int) -> int:
     """mke_align_topk_mean_temp_bytes; raises on the arguments mke_align_topk_mean would reject."""
-    r = int(lib().mke_align_topk_mean_temp_bytes(C.c_int64(n_a), C.c_int64(n_b), C.c_int(kpad), C.c_int(k)))
+    r = int(lib().mke_align_topk_mean_temp_bytes(n_a, n_b, kpad, k))
     _check(r if r < 0 else 0, "mke_align_topk_mean_temp_bytes")
     return r
 
@@ -1019,32 +781,25 @@ def align_topk_mean(a, b, kpad, k, metric=METRIC_INNER, sq_a=None, sq_b=None):
     need = align_topk_mean_temp_bytes(n_a, n_b, kpad, k)
     out = torch.empty(n_a, dtype=torch.float32, device=a.device)
     temp = torch.empty(max(need, 4) // 4, dtype=torch.float32, device=a.device)
-    args = TopkMeanArgs(_dev(a, torch.float32, "a"), a.shape[1], _dev(b, torch.float32, "b"), b.shape[1], kpad, n_a, n_b, metric,
-                        _dev(sq_a, torch.float32, "sq_a"), _dev(sq_b, torch.float32, "sq_b"), k, _dev(out, torch.float32, "out"),
-                        _dev(temp, torch.float32, "temp"), temp.numel() * 4)
+    args = TopkMeanArgs(ptr(a, torch.float32, "a"), a.shape[1], ptr(b, torch.float32, "b"), b.shape[1], kpad, n_a, n_b, metric,
+                        ptr(sq_a, torch.float32, "sq_a"), ptr(sq_b, torch.float32, "sq_b"), k, ptr(out, torch.float32, "out"),
+                        ptr(temp, torch.float32, "temp"), temp.numel() * 4)
     _check(lib().mke_align_topk_mean(C.byref(args), _stream()), "mke_align_topk_mean")
     return out
 
 
 def align_rank_ex(emb1, emb2, kpad, rank, ties, best, metric=METRIC_INNER, sq1=None, sq2=None, csls_row=None, csls_col=None):
     """mke_align_rank_ex over row-major padded emb1 [n1, ld1] / emb2 [n2, ld2] (rank / ties / best zeroed by the caller)."""
-    args = AlignArgs(_dev(emb1, torch.float32, "emb1"), emb1.shape[1], _dev(emb2, torch.float32, "emb2"), emb2.shape[1], kpad,
-                     emb1.shape[0], emb2.shape[0], metric, _dev(sq1, torch.float32, "sq1"), _dev(sq2, torch.float32, "sq2"),
-                     _dev(csls_row, torch.float32, "csls_row"), _dev(csls_col, torch.float32, "csls_col"),
-                     _dev(rank, torch.int32, "rank"), _dev(ties, torch.int32, "ties"), _dev(best, torch.int64, "best"))
+    args = AlignArgs(ptr(emb1, torch.float32, "emb1"), emb1.shape[1], ptr(emb2, torch.float32, "emb2"), emb2.shape[1], kpad,
+                     emb1.shape[0], emb2.shape[0], metric, ptr(sq1, torch.float32, "sq1"), ptr(sq2, torch.float32, "sq2"),
+                     ptr(csls_row, torch.float32, "csls_row"), ptr(csls_col, torch.float32, "csls_col"),
+                     ptr(rank, torch.int32, "rank"), ptr(ties, torch.int32, "ties"), ptr(best, torch.int64, "best"))
     _check(lib().mke_align_rank_ex(C.byref(args), _stream()), "mke_align_rank_ex")
-
-
-class LseArgs(C.Structure):
-    """mke_lse_args"""
-    _fields_ = [("a", C.c_void_p), ("lda", C.c_int), ("b", C.c_void_p), ("ldb", C.c_int), ("kpad", C.c_int),
-                ("n_a", C.c_int64), ("n_b", C.c_int64), ("metric", C.c_int), ("sq_a", C.c_void_p), ("sq_b", C.c_void_p),
-                ("sub_b", C.c_void_p), ("tau", C.c_float), ("out", C.c_void_p), ("temp", C.c_void_p), ("temp_bytes", C.c_int64)]
 
 
 def align_lse_temp_bytes(n_a: int, n_b: int, kpad: int) -> int:
     """mke_align_lse_temp_bytes; raises on the arguments mke_align_lse would reject."""
-    r = int(lib().mke_align_lse_temp_bytes(C.c_int64(n_a), C.c_int64(n_b), C.c_int(kpad)))
+    r = int(lib().mke_align_lse_temp_bytes(n_a, n_b, kpad))
     _check(r if r < 0 else 0, "mke_align_lse_temp_bytes")
     return r
 
@@ -1059,32 +814,16 @@ def align_lse(a, b, kpad, tau, metric=METRIC_INNER, sq_a=None, sq_b=None, sub_b=
     elif out.numel() < n_a:
         raise MultiKEHipError(f"align_lse: out holds {out.numel()} floats, {n_a} rows")
     temp = torch.empty(max(need, 8) // 4, dtype=torch.float32, device=a.device)
-    args = LseArgs(_dev(a, torch.float32, "a"), a.shape[1], _dev(b, torch.float32, "b"), b.shape[1], kpad, n_a, n_b, metric,
-                   _dev(sq_a, torch.float32, "sq_a"), _dev(sq_b, torch.float32, "sq_b"), _dev(sub_b, torch.float32, "sub_b"),
-                   float(tau), _dev(out, torch.float32, "out"), _dev(temp, torch.float32, "temp"), temp.numel() * 4)
+    args = LseArgs(ptr(a, torch.float32, "a"), a.shape[1], ptr(b, torch.float32, "b"), b.shape[1], kpad, n_a, n_b, metric,
+                   ptr(sq_a, torch.float32, "sq_a"), ptr(sq_b, torch.float32, "sq_b"), ptr(sub_b, torch.float32, "sub_b"),
+                   float(tau), ptr(out, torch.float32, "out"), ptr(temp, torch.float32, "temp"), temp.numel() * 4)
     _check(lib().mke_align_lse(C.byref(args), _stream()), "mke_align_lse")
     return out
 
 
-class StableListsArgs(C.Structure):
-    """mke_stable_lists_args"""
-    _fields_ = [("a", C.c_void_p), ("lda", C.c_int), ("b", C.c_void_p), ("ldb", C.c_int), ("kpad", C.c_int),
-                ("n_a", C.c_int64), ("n_b", C.c_int64), ("metric", C.c_int), ("sq_a", C.c_void_p), ("sq_b", C.c_void_p),
-                ("csls_row", C.c_void_p), ("csls_col", C.c_void_p), ("sim_mat", C.c_void_p), ("ld_sim", C.c_int64),
-                ("cut", C.c_int), ("whole_rows", C.c_int), ("sample_cols", C.c_int), ("out_val", C.c_void_p),
-                ("out_col", C.c_void_p), ("flags", C.c_void_p), ("temp", C.c_void_p), ("temp_bytes", C.c_int64)]
-
-
-class StableMatchArgs(C.Structure):
-    """mke_stable_match_args"""
-    _fields_ = [("n_a", C.c_int64), ("n_b", C.c_int64), ("cut", C.c_int), ("val", C.c_void_p), ("col", C.c_void_p),
-                ("ptr", C.c_void_p), ("holder", C.c_void_p), ("proposals", C.c_void_p), ("n_proposals", C.c_int64),
-                ("match", C.c_void_p), ("counts", C.c_void_p)]
-
-
 def stable_lists_temp_bytes(n_a: int, n_b: int, kpad: int, cut: int, whole_rows: bool = False) -> int:
     """mke_stable_lists_temp_bytes; raises on the arguments mke_stable_lists would reject."""
-    r = int(lib().mke_stable_lists_temp_bytes(C.c_int64(n_a), C.c_int64(n_b), C.c_int(kpad), C.c_int(cut), C.c_int(int(whole_rows))))
+    r = int(lib().mke_stable_lists_temp_bytes(n_a, n_b, kpad, cut, int(whole_rows)))
     _check(r if r < 0 else 0, "mke_stable_lists_temp_bytes")
     return r
 
@@ -1109,17 +848,17 @@ def stable_lists(a, b, kpad, cut, metric=METRIC_INNER, sq_a=None, sq_b=None, csl
     temp = torch.empty(max(need, 8) // 8, dtype=torch.int64, device=dev)
     args = StableListsArgs()
     if sim_mat is None:
-        args.a, args.lda, args.b, args.ldb = _dev(a, torch.float32, "a"), a.shape[1], _dev(b, torch.float32, "b"), b.shape[1]
+        args.a, args.lda, args.b, args.ldb = ptr(a, torch.float32, "a"), a.shape[1], ptr(b, torch.float32, "b"), b.shape[1]
         args.kpad, args.metric = kpad, metric
-        args.sq_a, args.sq_b = _dev(sq_a, torch.float32, "sq_a"), _dev(sq_b, torch.float32, "sq_b")
-        args.csls_row, args.csls_col = _dev(csls_row, torch.float32, "csls_row"), _dev(csls_col, torch.float32, "csls_col")
+        args.sq_a, args.sq_b = ptr(sq_a, torch.float32, "sq_a"), ptr(sq_b, torch.float32, "sq_b")
+        args.csls_row, args.csls_col = ptr(csls_row, torch.float32, "csls_row"), ptr(csls_col, torch.float32, "csls_col")
     else:
         if not sim_mat.is_cuda or sim_mat.dtype != torch.float32:
             raise MultiKEHipError("stable_lists: sim_mat must be a float32 CUDA/HIP tensor (no CPU path exists)")
-        args.sim_mat, args.ld_sim = C.c_void_p(sim_mat.data_ptr()), sim_mat.stride(0) if n_a > 1 else max(n_b, 1)
+        args.sim_mat, args.ld_sim = sim_mat.data_ptr(), sim_mat.stride(0) if n_a > 1 else max(n_b, 1)
     args.n_a, args.n_b, args.cut, args.whole_rows, args.sample_cols = n_a, n_b, cut, int(bool(whole_rows)), sample_cols
-    args.out_val, args.out_col = _dev(val, torch.float32, "out_val"), _dev(col, torch.int32, "out_col")
-    args.flags, args.temp, args.temp_bytes = _dev(flags, torch.int32, "flags"), _dev(temp, torch.int64, "temp"), temp.numel() * 8
+    args.out_val, args.out_col = ptr(val, torch.float32, "out_val"), ptr(col, torch.int32, "out_col")
+    args.flags, args.temp, args.temp_bytes = ptr(flags, torch.int32, "flags"), ptr(temp, torch.int64, "temp"), temp.numel() * 8
     _check(lib().mke_stable_lists(C.byref(args), _stream()), "mke_stable_lists")
     return val, col, flags
 
@@ -1136,23 +875,12 @@ def stable_match_args(val, col, n_b, ptr, holder, proposals, match=None, counts=
 
 def stable_rounds(args: StableMatchArgs, first_round: int, n_rounds: int):
     """mke_stable_rounds: enqueue rounds first_round .. first_round + n_rounds - 1 (no synchronisation)."""
-    _check(lib().mke_stable_rounds(C.byref(args), C.c_int64(first_round), C.c_int(n_rounds), _stream()), "mke_stable_rounds")
+    _check(lib().mke_stable_rounds(C.byref(args), first_round, n_rounds, _stream()), "mke_stable_rounds")
 
 
 def stable_finish(args: StableMatchArgs):
     """mke_stable_finish: match[i] = the column holding suitor i or -1; counts = (matched, matched to its own index)."""
     _check(lib().mke_stable_finish(C.byref(args), _stream()), "mke_stable_finish")
-
-
-MUTUAL_NO_LDS_FOLD, MUTUAL_FILTER = 1, 2   # MKE_MUTUAL_*: the other forms of the column fold, for measurements
-
-
-class MutualArgs(C.Structure):
-    """mke_mutual_args"""
-    _fields_ = [("a", C.c_void_p), ("lda", C.c_int), ("b", C.c_void_p), ("ldb", C.c_int), ("kpad", C.c_int),
-                ("n_a", C.c_int64), ("n_b", C.c_int64), ("metric", C.c_int), ("sq_a", C.c_void_p), ("sq_b", C.c_void_p),
-                ("csls_row", C.c_void_p), ("csls_col", C.c_void_p), ("row_best", C.c_void_p), ("col_best", C.c_void_p),
-                ("flags", C.c_int)]
 
 
 def align_mutual(a, b, kpad, metric=METRIC_INNER, sq_a=None, sq_b=None, csls_row=None, csls_col=None, flags=0, out=None):
@@ -1164,10 +892,10 @@ def align_mutual(a, b, kpad, metric=METRIC_INNER, sq_a=None, sq_b=None, csls_row
                                                       torch.zeros(n_b, dtype=torch.int64, device=a.device))
     if row_best.numel() < n_a or col_best.numel() < n_b:
         raise MultiKEHipError(f"align_mutual: out holds ({row_best.numel()}, {col_best.numel()}) words, ({n_a}, {n_b}) rows and columns")
-    args = MutualArgs(_dev(a, torch.float32, "a"), a.shape[1], _dev(b, torch.float32, "b"), b.shape[1], kpad, n_a, n_b, metric,
-                      _dev(sq_a, torch.float32, "sq_a"), _dev(sq_b, torch.float32, "sq_b"),
-                      _dev(csls_row, torch.float32, "csls_row"), _dev(csls_col, torch.float32, "csls_col"),
-                      _dev(row_best, torch.int64, "row_best"), _dev(col_best, torch.int64, "col_best"), flags)
+    args = MutualArgs(ptr(a, torch.float32, "a"), a.shape[1], ptr(b, torch.float32, "b"), b.shape[1], kpad, n_a, n_b, metric,
+                      ptr(sq_a, torch.float32, "sq_a"), ptr(sq_b, torch.float32, "sq_b"),
+                      ptr(csls_row, torch.float32, "csls_row"), ptr(csls_col, torch.float32, "csls_col"),
+                      ptr(row_best, torch.int64, "row_best"), ptr(col_best, torch.int64, "col_best"), flags)
     _check(lib().mke_align_mutual(C.byref(args), _stream()), "mke_align_mutual")
     return row_best, col_best
 
@@ -1178,30 +906,20 @@ def mutual_pairs(row_best, col_best, threshold=float("-inf")):
     n_a, n_b = row_best.numel(), col_best.numel()
     match = torch.empty(n_a, dtype=torch.int32, device=row_best.device)
     counts = torch.empty(2, dtype=torch.int32, device=row_best.device)     # zeroed by the call
-    rc = lib().mke_mutual_pairs(_dev(row_best, torch.int64, "row_best"), _dev(col_best, torch.int64, "col_best"), C.c_int64(n_a),
-                                C.c_int64(n_b), C.c_float(threshold), _dev(match, torch.int32, "match"),
-                                _dev(counts, torch.int32, "counts"), _stream())
+    rc = lib().mke_mutual_pairs(ptr(row_best, torch.int64, "row_best"), ptr(col_best, torch.int64, "col_best"), n_a,
+                                n_b, threshold, ptr(match, torch.int32, "match"),
+                                ptr(counts, torch.int32, "counts"), _stream())
     _check(rc, "mke_mutual_pairs")
     return match, counts
 
 
-ASSIGN_TAIL_CAP = 16                       # MKE_ASSIGN_TAIL_CAP: the default hand-over point of the auction's tail kernel
-ASSIGN_TAIL_MAX = 4096                     # larger tail_cap values act as this one
-ASSIGN_NO_TAIL, ASSIGN_TAIL_ONLY = 1, 2    # MKE_ASSIGN_*
+ASSIGN_TAIL_MAX = 4096                     # tail_cap values above this act as it (ASSIGN_TAIL_CAP: the default hand-over point)
 ASSIGN_MIN_EPS = 2.0 ** -14
-
-
-class AssignArgs(C.Structure):
-    """mke_assign_args"""
-    _fields_ = [("n_a", C.c_int64), ("n_b", C.c_int64), ("cut", C.c_int), ("val", C.c_void_p), ("col", C.c_void_p),
-                ("eps", C.c_float), ("floor", C.c_float), ("state", C.c_void_p), ("price", C.c_void_p), ("owner", C.c_void_p),
-                ("bid", C.c_void_p), ("progress", C.c_void_p), ("tail_cap", C.c_int), ("flags", C.c_int), ("temp", C.c_void_p),
-                ("temp_bytes", C.c_int64), ("match", C.c_void_p), ("counts", C.c_void_p)]
 
 
 def assign_temp_bytes(n_a: int, n_b: int, tail_cap: int = 0) -> int:
     """mke_assign_temp_bytes; raises on the arguments mke_assign_rounds would reject."""
-    r = int(lib().mke_assign_temp_bytes(C.c_int64(n_a), C.c_int64(n_b), C.c_int(tail_cap)))
+    r = int(lib().mke_assign_temp_bytes(n_a, n_b, tail_cap))
     _check(r if r < 0 else 0, "mke_assign_temp_bytes")
     return r
 
@@ -1212,32 +930,21 @@ def assign_args(val, col, n_b, eps, floor, state, price, owner, bid, progress, t
     owner [n_b] int32, bid [n_b] int64, progress [4] int64 (all zeroed before the first round), temp (int32, at least
     assign_temp_bytes); match [n_a] int32 and counts [3] int32 for assign_finish."""
     n_a, cut = col.shape
-    return AssignArgs(n_a, n_b, cut, _dev(val, torch.float32, "val"), _dev(col, torch.int32, "col"), float(eps), float(floor),
-                      _dev(state, torch.int32, "state"), _dev(price, torch.float32, "price"), _dev(owner, torch.int32, "owner"),
-                      _dev(bid, torch.int64, "bid"), _dev(progress, torch.int64, "progress"), tail_cap, flags,
-                      _dev(temp, torch.int32, "temp"), temp.numel() * 4 if temp is not None else 0,
-                      _dev(match, torch.int32, "match"), _dev(counts, torch.int32, "counts"))
+    return AssignArgs(n_a, n_b, cut, ptr(val, torch.float32, "val"), ptr(col, torch.int32, "col"), float(eps), float(floor),
+                      ptr(state, torch.int32, "state"), ptr(price, torch.float32, "price"), ptr(owner, torch.int32, "owner"),
+                      ptr(bid, torch.int64, "bid"), ptr(progress, torch.int64, "progress"), tail_cap, flags,
+                      ptr(temp, torch.int32, "temp"), temp.numel() * 4 if temp is not None else 0,
+                      ptr(match, torch.int32, "match"), ptr(counts, torch.int32, "counts"))
 
 
 def assign_rounds(args: AssignArgs, n_rounds: int):
     """mke_assign_rounds: enqueue at most n_rounds more rounds of the auction (no synchronisation)."""
-    _check(lib().mke_assign_rounds(C.byref(args), C.c_int(n_rounds), _stream()), "mke_assign_rounds")
+    _check(lib().mke_assign_rounds(C.byref(args), n_rounds, _stream()), "mke_assign_rounds")
 
 
 def assign_finish(args: AssignArgs):
     """mke_assign_finish: match[i] = the column row i holds or -1; counts = (matched, matched to its own index, settled unmatched)."""
     _check(lib().mke_assign_finish(C.byref(args), _stream()), "mke_assign_finish")
-
-
-SWAP_TILE = 64                             # MKE_SWAP_TILE: triples per tile of the ordered compaction (one wavefront)
-
-
-class SwapArgs(C.Structure):
-    """mke_swap_args"""
-    _fields_ = [("h", C.c_void_p), ("p", C.c_void_p), ("t", C.c_void_p), ("n", C.c_int64), ("partner", C.c_void_p),
-                ("n_entities", C.c_int64), ("weight", C.c_void_p), ("heads_only", C.c_int), ("out_h", C.c_void_p),
-                ("out_p", C.c_void_p), ("out_t", C.c_void_p), ("out_w", C.c_void_p), ("capacity", C.c_int64), ("count", C.c_void_p),
-                ("temp", C.c_void_p), ("temp_bytes", C.c_int64), ("flags", C.c_int)]
 
 
 def boot_partner(match, ids_a, ids_b, n_entities: int, out=None):
@@ -1248,16 +955,16 @@ def boot_partner(match, ids_a, ids_b, n_entities: int, out=None):
         raise MultiKEHipError(f"boot_partner: out holds {partner.numel()} words, the table has {n_entities}")
     if match.numel() != ids_a.numel():
         raise MultiKEHipError(f"boot_partner: match has {match.numel()} rows, ids_a {ids_a.numel()}")
-    rc = lib().mke_boot_partner(_dev(match, torch.int32, "match"), _dev(ids_a, torch.int32, "ids_a"), C.c_int64(ids_a.numel()),
-                                _dev(ids_b, torch.int32, "ids_b"), C.c_int64(ids_b.numel()), _dev(partner, torch.int32, "partner"),
-                                C.c_int64(n_entities), _stream())
+    rc = lib().mke_boot_partner(ptr(match, torch.int32, "match"), ptr(ids_a, torch.int32, "ids_a"), ids_a.numel(),
+                                ptr(ids_b, torch.int32, "ids_b"), ids_b.numel(), ptr(partner, torch.int32, "partner"),
+                                n_entities, _stream())
     _check(rc, "mke_boot_partner")
     return partner
 
 
 def swap_temp_bytes(n: int) -> int:
     """mke_swap_temp_bytes; raises on an n mke_swap_triples would reject."""
-    r = int(lib().mke_swap_temp_bytes(C.c_int64(n)))
+    r = int(lib().mke_swap_temp_bytes(n))
     _check(r if r < 0 else 0, "mke_swap_temp_bytes")
     return r
 
@@ -1282,11 +989,11 @@ def swap_triples(h, p, t, partner, heads_only=False, weight=None, capacity=None,
         raise MultiKEHipError(f"swap_triples: weight has {weight.numel()} entries, partner {partner.numel()}")
     count = torch.empty(1, dtype=torch.int64, device=dev)
     temp = torch.empty((swap_temp_bytes(n) + 7) // 8, dtype=torch.int64, device=dev)
-    args = SwapArgs(_dev(h, torch.int32, "h"), _dev(p, torch.int32, "p"), _dev(t, torch.int32, "t"), n,
-                    _dev(partner, torch.int32, "partner"), partner.numel(), _dev(weight, torch.float32, "weight"),
-                    1 if heads_only else 0, _dev(out_h, torch.int32, "out_h"), _dev(out_p, torch.int32, "out_p"),
-                    _dev(out_t, torch.int32, "out_t"), _dev(out_w, torch.float32, "out_w"), cap, _dev(count, torch.int64, "count"),
-                    _dev(temp, torch.int64, "temp"), temp.numel() * 8, 0)
+    args = SwapArgs(ptr(h, torch.int32, "h"), ptr(p, torch.int32, "p"), ptr(t, torch.int32, "t"), n,
+                    ptr(partner, torch.int32, "partner"), partner.numel(), ptr(weight, torch.float32, "weight"),
+                    1 if heads_only else 0, ptr(out_h, torch.int32, "out_h"), ptr(out_p, torch.int32, "out_p"),
+                    ptr(out_t, torch.int32, "out_t"), ptr(out_w, torch.float32, "out_w"), cap, ptr(count, torch.int64, "count"),
+                    ptr(temp, torch.int64, "temp"), temp.numel() * 8, 0)
     _check(lib().mke_swap_triples(C.byref(args), _stream()), "mke_swap_triples")
     return (out_h, out_p, out_t), out_w, count
 
@@ -1302,57 +1009,54 @@ def gemm_f32(lhs, rhs, out, transpose_a=False, transpose_b=False, splits=1, accu
     for t, nm in ((lhs, "lhs"), (rhs, "rhs"), (out, "out")):
         if not t.is_cuda or t.dtype != torch.float32:
             raise MultiKEHipError(f"gemm_f32: {nm} must be a float32 CUDA tensor")
-    rc = lib().mke_gemm_f32(C.c_void_p(a.data_ptr()), C.c_int64(a.stride(0)), C.c_int64(a.stride(1)),
-                            C.c_void_p(b.data_ptr()), C.c_int64(b.stride(0)), C.c_int64(b.stride(1)),
-                            C.c_void_p(out.data_ptr()), C.c_int64(out.stride(0)), C.c_int(M), C.c_int(N), C.c_int(K),
-                            C.c_int(splits), C.c_int(int(accumulate)), _stream())
+    rc = lib().mke_gemm_f32(a.data_ptr(), a.stride(0), a.stride(1),
+                            b.data_ptr(), b.stride(0), b.stride(1),
+                            out.data_ptr(), out.stride(0), M, N, K,
+                            splits, int(accumulate), _stream())
     _check(rc, "mke_gemm_f32")
 
 
 def rows_update_dense(table, slot1, slot2, grad, dim, normalize, opt: OptimizerStruct):
     """mke_rows_update_dense: Adam / Adadelta over EVERY row of the table (grad consumed)."""
-    rc = lib().mke_rows_update_dense(_dev(table, torch.float32, "table"), _dev(slot1, torch.float32, "slot1"),
-                                     _dev(slot2, torch.float32, "slot2"), _dev(grad, torch.float32, "grad"),
-                                     C.c_int64(table.shape[0]), C.c_int(table.shape[1]), C.c_int(dim), C.c_int(int(normalize)),
+    rc = lib().mke_rows_update_dense(ptr(table, torch.float32, "table"), ptr(slot1, torch.float32, "slot1"),
+                                     ptr(slot2, torch.float32, "slot2"), ptr(grad, torch.float32, "grad"),
+                                     table.shape[0], table.shape[1], dim, int(normalize),
                                      C.byref(opt), _stream())
     _check(rc, "mke_rows_update_dense")
 
 
 def dense_update_opt(param, slot1, slot2, grad, opt: OptimizerStruct):
     """mke_dense_update_opt: Adam / Adadelta over a flat parameter buffer (grad consumed)."""
-    rc = lib().mke_dense_update_opt(_dev(param, torch.float32, "param"), _dev(slot1, torch.float32, "slot1"),
-                                    _dev(slot2, torch.float32, "slot2"), _dev(grad, torch.float32, "grad"),
-                                    C.c_int64(param.numel()), C.byref(opt), _stream())
+    rc = lib().mke_dense_update_opt(ptr(param, torch.float32, "param"), ptr(slot1, torch.float32, "slot1"),
+                                    ptr(slot2, torch.float32, "slot2"), ptr(grad, torch.float32, "grad"),
+                                    param.numel(), C.byref(opt), _stream())
     _check(rc, "mke_dense_update_opt")
 
 
 def attr_scratch_floats(n: int, dim: int) -> int:
-    return int(lib().mke_attr_scratch_floats(C.c_int64(n), C.c_int(dim)))
+    return int(lib().mke_attr_scratch_floats(n, dim))
 
 
 def attr_steps(args: AttrStepArgs, step_off: np.ndarray, loss_ring: torch.Tensor):
     """mke_attr_steps: `step_off` host int64 [n_steps + 1]; loss_ring float64 [ring, LOSS_PARTIALS] on the device."""
     off = np.ascontiguousarray(step_off, dtype=np.int64)
-    rc = lib().mke_attr_steps(C.byref(args), off.ctypes.data_as(C.POINTER(C.c_int64)), C.c_int(len(off) - 1),
-                              _dev(loss_ring, torch.float64, "loss_ring"), C.c_int(loss_ring.shape[0]), _stream())
+    rc = lib().mke_attr_steps(C.byref(args), off.ctypes.data, len(off) - 1,
+                              ptr(loss_ring, torch.float64, "loss_ring"), loss_ring.shape[0], _stream())
     _check(rc, "mke_attr_steps")
 
 
 def sample_distinct(n: int, batch: int, n_steps: int, seed=(0, 0), stream_id: int = 0, device="cuda") -> torch.Tensor:
     """mke_sample_distinct -> int32 [n_steps, batch]: `batch` distinct positions of range(n) per step."""
     out = torch.empty(n_steps, batch, dtype=torch.int32, device=device)
-    rc = lib().mke_sample_distinct(C.c_int64(n), C.c_int(batch), C.c_int(n_steps), C.c_uint32(seed[0] & 0xFFFFFFFF),
-                                   C.c_uint32(seed[1] & 0xFFFFFFFF), C.c_uint32(stream_id & 0xFFFFFFFF),
-                                   _dev(out, torch.int32, "out"), _stream())
+    rc = lib().mke_sample_distinct(n, batch, n_steps, seed[0] & 0xFFFFFFFF,
+                                   seed[1] & 0xFFFFFFFF, stream_id & 0xFFFFFFFF,
+                                   ptr(out, torch.int32, "out"), _stream())
     _check(rc, "mke_sample_distinct")
     return out
 
 
-ATTR_FWD, ATTR_TAIL, ATTR_BWD, ATTR_UPD = 1, 2, 4, 8
-
-
 def attr_step_phases(args: AttrStepArgs, phases: int):
-    rc = lib().mke_attr_step_phases(C.byref(args), C.c_int(phases), _stream())
+    rc = lib().mke_attr_step_phases(C.byref(args), phases, _stream())
     _check(rc, "mke_attr_step_phases")
 
 

@@ -6,7 +6,6 @@ stream with no Python between the steps; this is the replacement of the referenc
 """
 from __future__ import annotations
 
-import ctypes as C
 
 import numpy as np
 import torch
@@ -108,7 +107,7 @@ class RelationViewRunner:
         p.neg_chunk_capacity = self.neg_chunk_capacity
         p.stride, p.dim = e.stride, e.dim
         p.pos_kg = _lib.ptr(b.pos_kg, torch.uint8, "pos_kg")
-        p.step_off = self._step_off.ctypes.data_as(C.POINTER(C.c_int64))
+        p.step_off = self._step_off.ctypes.data
         p.n_steps = self.steps
         p.neg_per_pos, p.max_try, p.sample_chunk = b.neg_per_pos, self.max_try, self.sample_chunk
         p.neg_h, p.neg_r, p.neg_t = (_lib.ptr(x, torch.int32, "neg") for x in self.neg)
@@ -262,7 +261,7 @@ def run_positive_steps(ent: EmbeddingTable, rel: EmbeddingTable, opt_name: str, 
     p.pos_h, p.pos_r, p.pos_t = (_lib.ptr(c, i32, "pos") for c in cols)
     p.pos_w = _lib.ptr(weights, f32, "pos_w") if weights is not None else None
     p.pos_kg = None
-    p.step_off, p.n_steps = off.ctypes.data_as(C.POINTER(C.c_int64)), steps
+    p.step_off, p.n_steps = off.ctypes.data, steps
     p.neg_per_pos, p.max_try, p.sample_chunk, p.negatives_ready = 0, 0, 1, 0
     p.neg_h = p.neg_r = p.neg_t = None
     p.optimizer, p.lr, p.scale = _OPT[optimizer], lr, scale
@@ -302,7 +301,7 @@ def run_alignment_steps(tables, terms, idx_a, idx_b, step_off, opt_name: str, ta
         p.terms[k].a, p.terms[k].b, p.terms[k].weight = int(a), int(b), float(w)
     p.stride, p.dim = tables[0].stride, tables[0].dim
     p.ia, p.ib = _lib.ptr(idx_a, i32, "ia"), _lib.ptr(idx_b, i32, "ib")
-    p.step_off, p.n_steps = off.ctypes.data_as(C.POINTER(C.c_int64)), steps
+    p.step_off, p.n_steps = off.ctypes.data, steps
     p.optimizer, p.lr, p.tag_base = _OPT[optimizer], float(lr), int(tag_base)
     p.loss_partials = _lib.ptr(loss, torch.float64, "loss")
     _lib.align_steps(p)

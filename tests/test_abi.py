@@ -1,6 +1,6 @@
 """CPU-side checks of the drop-in boundary: the C-ABI library loads without a GPU, exports every symbol
-include/multike_hip.h declares, argument validation returns error codes (no compute without a GPU), and the
-ctypes structs match the header's layout."""
+include/multike_hip.h declares, and argument validation returns error codes (no compute without a GPU).  That the ctypes
+structs, prototypes and constants are the header's: test_abi_generated.py."""
 import ctypes as C
 import os
 import re
@@ -39,27 +39,6 @@ def test_version_and_constants(lib):
     assert lib.mke_version() == int(re.search(r"#define MKE_VERSION (\d+)", h).group(1))
     assert _lib.LOSS_PARTIALS == int(re.search(r"#define MKE_LOSS_PARTIALS (\d+)", h).group(1))
     assert _lib.MAX_STRIDE == int(re.search(r"#define MKE_MAX_STRIDE (\d+)", h).group(1))
-
-
-def test_struct_layouts_match_header():
-    """Field order of each ctypes.Structure == member order in the header."""
-    from multike_amd import _lib
-    h = _header()
-    for cname, st in (("mke_kg_side", _lib.KGSideStruct), ("mke_update_table", _lib.UpdateTableStruct),
-                      ("mke_relation_plan", _lib.RelationPlanStruct), ("mke_oc_step", _lib.OcStepStruct),
-                      ("mke_ae_plan", _lib.AEPlanStruct), ("mke_oc_em_plan_args", _lib.OcEmPlanArgs), ("mke_oc_comm", _lib.OcCommStruct),
-                      ("mke_oc_loop", _lib.OcLoopStruct), ("mke_tuning", _lib.TuningStruct), ("mke_attr_step_args", _lib.AttrStepArgs),
-                      ("mke_score_args", _lib.ScoreArgs)):
-        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cname, cname), h, flags=re.S).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        names = []
-        for decl in body.split(";"):
-            decl = decl.strip()
-            if not decl:
-                continue
-            for part in decl.split(","):
-                names.append(re.search(r"(\w+)\s*(?:\[[^\]]*\])?$", part.strip()).group(1))
-        assert names == [f[0] for f in st._fields_], (cname, names)
 
 
 def test_argument_validation_without_gpu(lib):
@@ -117,10 +96,10 @@ def test_round6_entry_points_validate_without_gpu(lib):
     mixed with a slot_of table in one update call)."""
     from multike_amd import _lib
     null = C.c_void_p(0)
-    assert lib.mke_oc_em_plan(null, null) == -1 and b"NULL" in lib.mke_last_error()
-    assert lib.mke_oc_pass2(null, null) == -1
-    assert lib.mke_oc_steps(null, C.c_int(0), C.c_int(1), null) == -1
-    assert lib.mke_tuning_init(null) == -1
+    assert lib.mke_oc_em_plan(None, null) == -1 and b"NULL" in lib.mke_last_error()      # a struct pointer: None, byref or an array
+    assert lib.mke_oc_pass2(None, null) == -1
+    assert lib.mke_oc_steps(None, C.c_int(0), C.c_int(1), null) == -1
+    assert lib.mke_tuning_init(None) == -1
     a = _lib.OcEmPlanArgs()
     a.n_ranks, a.rank, a.n_local, a.n_rel, a.chunks, a.capacity = 2, 0, 10, 3, 9, 100
     assert lib.mke_oc_em_plan(C.byref(a), null) == -2 and b"chunks" in lib.mke_last_error()
@@ -150,7 +129,7 @@ def test_score_step_validates_without_gpu(lib):
     """mke_triple_score_step rejects bad arguments before any launch.  The codes are the ones the positional variants it
     replaced (ABI 106: _x, _xch, _det, plain) returned for the same arguments, recorded from a build of that version; the one
     difference: ref_count without grad_ent in deterministic mode was -2 from the staging check and is -1 from the common one."""
-    from multike_amd import _lib
+    from multike_amd import _abi, _lib
     one = 16
 
     def rc(**fields):
@@ -178,11 +157,7 @@ def test_score_step_validates_without_gpu(lib):
     assert rc(**dict(det, stage_rows=None)) == -1 and b"staging" in lib.mke_last_error()
     assert rc(**dict(det, stage_slots=17)) == -2 and b"18 staging slots needed, 17 given" in lib.mke_last_error()
     assert rc(hot=_lib.HotRowsStruct(one, 2, 4, 5)) == -2 and b"hub rows" in lib.mke_last_error()      # row0 5 < n_ent 10
-    class CountJob(C.Structure):     # mke_count_job (the Python side never fills one: the native step loop does)
-        _fields_ = [("pos_h", C.c_void_p), ("pos_t", C.c_void_p), ("n_pos", C.c_int64), ("neg_h", C.c_void_p), ("neg_t", C.c_void_p),
-                    ("n_neg", C.c_int64), ("neg_per_pos", C.c_int), ("ref_count", C.c_void_p)]
-
-    cj = CountJob(pos_h=one, pos_t=one, n_pos=2, neg_h=one, neg_t=one, n_neg=4, neg_per_pos=2, ref_count=None)
+    cj = _abi.mke_count_job(pos_h=one, pos_t=one, n_pos=2, neg_h=one, neg_t=one, n_neg=4, neg_per_pos=2, ref_count=None)
     assert rc(next_count=C.addressof(cj)) == -1 and b"count job" in lib.mke_last_error()
     # the positional wrapper that stays goes through the same checks
     p, null = C.c_void_p(one), C.c_void_p(0)

@@ -8,6 +8,7 @@ import re
 import numpy as np
 import pytest
 
+import abi_header as ah
 from conftest import ROOT
 
 NEW = ("mke_assign_temp_bytes", "mke_assign_rounds", "mke_assign_finish")
@@ -45,12 +46,7 @@ def test_new_symbols_exported_and_listed(lib):
 
 def test_struct_fields_match_header():
     from multike_amd import _lib
-    body = re.search(r"typedef struct mke_assign_args \{(.*?)\} mke_assign_args;", _header(), flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
-    for decl in body.split(";"):
-        if decl.strip():
-            names += [re.search(r"(\w+)\s*$", part.strip()).group(1) for part in decl.split(",")]
+    names = ah.members("mke_assign_args")
     assert names == [f for f, _ in _lib.AssignArgs._fields_]
     assert names == ["n_a", "n_b", "cut", "val", "col", "eps", "floor", "state", "price", "owner", "bid", "progress", "tail_cap",
                      "flags", "temp", "temp_bytes", "match", "counts"]                      # the order the issue fixed

@@ -4,12 +4,11 @@ multike_amd.base.similarity on host arrays reproduces the reference's sim / csls
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import abi_header as ah
 from conftest import GOLDEN, ROOT
 
 NEW = ("mke_align_topk_mean_temp_bytes", "mke_align_topk_mean", "mke_align_rank_ex")
@@ -34,31 +33,14 @@ def test_new_symbols_exported_and_listed(lib):
     assert int(re.search(r"#define MKE_VERSION (\d+)", h).group(1)) == 107 == lib.mke_version()
 
 
-def _c_layout(struct, fields, tmp_path):
-    cc = shutil.which("cc") or shutil.which("gcc")
-    if cc is None:
-        pytest.skip("no C compiler")
-    src = tmp_path / "layout.c"
-    body = "".join(f'  printf("%zu ", offsetof({struct}, {f}));\n' for f in fields)
-    src.write_text(f'#include <stddef.h>\n#include <stdio.h>\n#include "multike_hip.h"\nint main(void) {{\n{body}'
-                   f'  printf("%zu\\n", sizeof({struct}));\n  return 0;\n}}\n')
-    exe = tmp_path / "layout"
-    subprocess.check_call([cc, "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    return [int(x) for x in subprocess.check_output([str(exe)]).split()]
-
-
 @pytest.mark.parametrize("name", ["AlignArgs", "TopkMeanArgs"])
 def test_struct_layout_matches_header(name, tmp_path):
     from multike_amd import _lib
     S = getattr(_lib, name)
     struct = {"AlignArgs": "mke_align_args", "TopkMeanArgs": "mke_topk_mean_args"}[name]
     fields = [f for f, _ in S._fields_]
-    h = open(os.path.join(ROOT, "include", "multike_hip.h")).read()
-    body = re.search(r"typedef struct " + struct + r" \{(.*?)\} " + struct, h, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    declared = re.findall(r"\**\s*(\w+)\s*(?=[;,])", body)
-    assert declared == fields
-    got = _c_layout(struct, fields, tmp_path)
+    assert ah.members(struct) == fields
+    got = ah.offsets_and_size(tmp_path, struct, fields)
     assert got == [getattr(S, f).offset for f in fields] + [C.sizeof(S)]
 
 
@@ -140,6 +122,7 @@ def test_sweep_entry_points_refuse_a_width_without_instantiation(lib):
     mke_align_topk_mean on both of its paths) returns MKE_E_UNSUPPORTED with its own message once every other argument has
     passed its checks; none returns 0 without having launched.  Codes and texts as recorded from the build before the
     launch ladders became one width dispatcher (mke_align_rank's message carries no prefix)."""
+    from multike_amd import _abi
     fake = C.c_void_p(0x1000)
     err = lambda: lib.mke_last_error().decode()
     for kpad in UNSUPPORTED_KPADS:
@@ -147,7 +130,7 @@ def test_sweep_entry_points_refuse_a_width_without_instantiation(lib):
         rc = lib.mke_align_rank(fake, ld, fake, ld, C.c_int(kpad), C.c_int64(100), C.c_int64(120), fake, fake, fake, None)
         assert (rc, err()) == (-3, f"unsupported kpad {kpad}")
         rc = lib.mke_sim_select(fake, ld, C.c_int(kpad), C.c_int64(120), C.c_int64(0), C.c_int64(100), fake, C.c_int(4),
-                                C.c_int(64), fake, fake, None)
+                                C.c_int(64), C.cast(fake, C.POINTER(_abi.mke_candidate)), fake, None)
         assert (rc, err()) == (-3, f"mke_sim_select: unsupported kpad {kpad}")
         rc = lib.mke_sim_sample(fake, ld, C.c_int(kpad), C.c_int64(120), C.c_int64(0), C.c_int64(100), fake, ld, C.c_int(50),
                                 fake, None)

@@ -321,7 +321,7 @@ def test_unsupported_widths_are_refused_before_any_launch(lib):
     for k in (0, 1):
         plan.tables[k].table, plan.tables[k].n_rows = 16, 8
     plan.terms[0].a, plan.terms[0].b, plan.terms[0].weight = 0, 1, 1.0
-    plan.ia, plan.ib, plan.loss_partials, plan.step_off = 16, 16, 16, off
+    plan.ia, plan.ib, plan.loss_partials, plan.step_off = 16, 16, 16, C.addressof(off)
     plan.optimizer, plan.lr, plan.tag_base = _lib.OPT_SGD, 0.125, 1
     assert lib.mke_align_steps(C.byref(plan), null) == -3 and b"unsupported stride 144" in lib.mke_last_error()
     d = rc.REFUSED_DIM

@@ -47,16 +47,11 @@ import torch
 
 import score_cases as sc
 import update_cases as uc
+from multike_amd._abi import mke_count_job as CountJob
 from rows_cases import OLD_TAG, SENTINEL, STRIDES, TAG
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-
-
-class CountJob(C.Structure):
-    """mke_count_job"""
-    _fields_ = [("pos_h", C.c_void_p), ("pos_t", C.c_void_p), ("n_pos", C.c_int64), ("neg_h", C.c_void_p), ("neg_t", C.c_void_p),
-                ("n_neg", C.c_int64), ("neg_per_pos", C.c_int), ("ref_count", C.c_void_p)]
 
 
 def dev(a):

@@ -5,13 +5,12 @@ before any launch (invalid-argument paths only, fake pointers), the scratch quer
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import sinkhorn_oracle as O
+import abi_header as ah
 from conftest import GOLDEN, ROOT
 
 NEW = ("mke_align_lse_temp_bytes", "mke_align_lse")
@@ -47,19 +46,8 @@ def test_struct_layout_matches_header(tmp_path):
     S, struct = _lib.LseArgs, "mke_lse_args"
     fields = [f for f, _ in S._fields_]
     assert fields == ["a", "lda", "b", "ldb", "kpad", "n_a", "n_b", "metric", "sq_a", "sq_b", "sub_b", "tau", "out", "temp", "temp_bytes"]
-    body = re.search(r"typedef struct " + struct + r" \{(.*?)\} " + struct, _header(), flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    assert re.findall(r"\**\s*(\w+)\s*(?=[;,])", body) == fields
-    cc = shutil.which("cc") or shutil.which("gcc")
-    if cc is None:
-        pytest.skip("no C compiler")
-    src = tmp_path / "layout.c"
-    lines = "".join(f'  printf("%zu ", offsetof({struct}, {f}));\n' for f in fields)
-    src.write_text(f'#include <stddef.h>\n#include <stdio.h>\n#include "multike_hip.h"\nint main(void) {{\n{lines}'
-                   f'  printf("%zu\\n", sizeof({struct}));\n  return 0;\n}}\n')
-    exe = tmp_path / "layout"
-    subprocess.check_call([cc, "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
+    assert ah.members(struct) == fields
+    got = ah.offsets_and_size(tmp_path, struct, fields)
     assert got == [getattr(S, f).offset for f in fields] + [C.sizeof(S)]
 
 

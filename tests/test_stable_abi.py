@@ -5,13 +5,12 @@ reproduces the reference's matching of every fixture case."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import stable_oracle as O
+import abi_header as ah
 from conftest import GOLDEN, ROOT
 
 NEW = ("mke_stable_lists_temp_bytes", "mke_stable_lists", "mke_stable_rounds", "mke_stable_finish")
@@ -40,30 +39,14 @@ def test_new_symbols_exported_and_listed(lib):
     assert "code/base/alignment.py:82-128" in h and ":166-219" in h and ":131-138" in h          # what each replaces
 
 
-def _c_layout(struct, fields, tmp_path):
-    cc = shutil.which("cc") or shutil.which("gcc")
-    assert cc is not None, "no C compiler"
-    src = tmp_path / "layout.c"
-    body = "".join(f'  printf("%zu ", offsetof({struct}, {f}));\n' for f in fields)
-    src.write_text(f'#include <stddef.h>\n#include <stdio.h>\n#include "multike_hip.h"\nint main(void) {{\n{body}'
-                   f'  printf("%zu\\n", sizeof({struct}));\n  return 0;\n}}\n')
-    exe = tmp_path / "layout"
-    subprocess.check_call([cc, "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    return [int(x) for x in subprocess.check_output([str(exe)]).split()]
-
-
 @pytest.mark.parametrize("name", sorted(STRUCTS))
 def test_struct_layout_matches_header(name, tmp_path):
     from multike_amd import _lib
     S = getattr(_lib, name)
     struct = STRUCTS[name]
     fields = [f for f, _ in S._fields_]
-    h = open(os.path.join(ROOT, "include", "multike_hip.h")).read()
-    body = re.search(r"typedef struct " + struct + r" \{(.*?)\} " + struct, h, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    declared = re.findall(r"\**\s*(\w+)\s*(?=[;,])", body)
-    assert declared == fields
-    got = _c_layout(struct, fields, tmp_path)
+    assert ah.members(struct) == fields
+    got = ah.offsets_and_size(tmp_path, struct, fields)
     assert got == [getattr(S, f).offset for f in fields] + [C.sizeof(S)]
 
 

@@ -35,15 +35,10 @@ import pytest
 import torch
 
 import update_cases as uc
+from multike_amd._abi import mke_count_job as CountJob     # the generated class: the prototypes accept no other
 from rows_cases import TAG
 
 pytestmark = pytest.mark.gpu
-
-
-class CountJob(C.Structure):
-    """mke_count_job"""
-    _fields_ = [("pos_h", C.c_void_p), ("pos_t", C.c_void_p), ("n_pos", C.c_int64), ("neg_h", C.c_void_p), ("neg_t", C.c_void_p),
-                ("n_neg", C.c_int64), ("neg_per_pos", C.c_int), ("ref_count", C.c_void_p)]
 
 
 def dev(a):
