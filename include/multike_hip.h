@@ -64,8 +64,8 @@ const char* mke_last_error(void);
 #define MKE_TUNE_DEFAULT (-2)
 typedef struct mke_tuning {
   int score_splits, score_half_groups, score_offsets32, score_lane_ids, count_in_score, update_chunk, oc_score_quarter,
-      attr_fused_bwd, sampler_fast, neg_codes;
-  int reserved[6];   /* MKE_TUNE_DEFAULT */
+      attr_fused_bwd, sampler_fast, neg_codes, sampler_codes;
+  int reserved[5];   /* MKE_TUNE_DEFAULT */
 } mke_tuning;
 int mke_tuning_init(mke_tuning* t);   /* every field = MKE_TUNE_DEFAULT */
 
@@ -96,6 +96,10 @@ int mke_tuning_init(mke_tuning* t);   /* every field = MKE_TUNE_DEFAULT */
  *                     launch (mke_score_args.next_count); 0 = in the update launch (mke_rows_update_multi_count)
  *   "neg_codes"         : 1 (default) = mke_relation_steps bakes one code word per negative when it samples a chunk and runs the
  *                     code-word form of the training kernel (section (1c)); 0 = reference counts per step
+ *   "sampler_codes"     : 1 (default) = where mke_relation_steps takes the code-word form, the sampler writes the code words
+ *                     themselves (mke_neg_sample without neg_r / neg_t), the bake adds MKE_CODE_EXCL in place (mke_neg_codes without
+ *                     id arrays) and the training kernel runs without id arrays: neg_h / neg_r / neg_t are not written
+ *                     (mke_relation_plan.ids_stale); 0 = three id arrays, then mke_neg_codes.  No effect on any other path
  * Returns the previous value through *old_value when it is not NULL. */
 int mke_set_option(const char* name, int value, int* old_value);
 
@@ -214,7 +218,8 @@ typedef struct mke_score_args {
   float* stage_rows; int64_t* stage_keys; int64_t stage_slots;
   double* loss_partials;             /* [MKE_LOSS_PARTIALS] */
   const mke_tuning* tuning;          /* host pointer, NULL = the enclosing call's knobs / the process defaults */
-  const int32_t* neg_code;           /* nullable: one code word per negative (section (1c)); NULL = today's forms */
+  const int32_t* neg_code;           /* nullable: one code word per negative (section (1c)); NULL = today's forms.  With it,
+                                        neg_h == neg_r == neg_t == NULL is allowed where the code-word form is legal */
 } mke_score_args;
 int mke_triple_score_step(const mke_score_args* args, void* stream);
 int mke_stage_reduce(const float* stage_rows, const int64_t* sorted_keys, const int64_t* order, int64_t n_slots, int stride,
@@ -238,7 +243,27 @@ int mke_count_entity_refs(const int32_t* pos_h, const int32_t* pos_t, int64_t n_
  *   mke_score_args.neg_code: the training kernel (ref_count semantics, 32-bit offsets, lane ids: score_offsets32 and
  *   score_lane_ids on, tables below 2^30 floats) reads one word per negative, neither reads nor resets ref_count and updates
  *   MKE_CODE_EXCL rows in place; negatives without MKE_CODE_FAST are scored from neg_h / neg_r / neg_t as before.  Where that
- *   form is not legal the call runs the ref_count form (ref_count != NULL) or fails (MKE_E_UNSUPPORTED). */
+ *   form is not legal the call runs the ref_count form (ref_count != NULL) or fails (MKE_E_UNSUPPORTED).
+ *   Without id arrays (neg_h == neg_r == neg_t == NULL beside neg_code): every negative without MKE_CODE_FAST is scored as the
+ *   positive's own triple (h, r, t) — what such a word means when the sampler wrote it.  Legal only where the code-word form is
+ *   (grouped negatives, not deterministic); anywhere else MKE_E_UNSUPPORTED before anything is launched.
+ *
+ *   The sampler's own words.  mke_neg_sample holds, for every negative it keeps, the drawn entity, the side and whether the
+ *   draw differs from the id it replaces, so it can store the word instead of three ids (two of which copy the positive).
+ *   Both forms are reached through the existing entry points, by leaving the id arrays out (no new symbols):
+ *   mke_neg_sample / mke_neg_sample_at with neg_r == neg_t == NULL: ONE output, neg_h[o] for the negative whose ids would have
+ *     gone to neg_*[o] — same Philox stream, same order — is
+ *         draw != replaced id:  draw | (head corrupted ? MKE_CODE_HEAD : 0) | MKE_CODE_FAST
+ *         draw == replaced id:  pos_t, no flags   (the positive itself, kept in the last round: (1c)'s entity of (h, r, t))
+ *     i.e. mke_neg_codes' word of those ids without MKE_CODE_EXCL.  A contiguous side must end at or below 2^26 (MKE_E_RANGE);
+ *     ids of ent_list / cand_table are the caller's to keep below it.  (Exactly one of neg_r / neg_t NULL stays MKE_E_NULL.)
+ *   mke_neg_codes with neg_h == neg_r == neg_t == NULL: neg_code holds such words on entry and is baked in place, reading
+ *     nothing else per negative: marks the step's positives, then the entity of every word with MKE_CODE_FAST, then sets
+ *     MKE_CODE_EXCL in every word (cleared first) by the entity's two bits.  neg_code and bits come out bit-identical to
+ *     mke_neg_codes on the ids the words stand for.  Rows in the LDS only (n_ent <= 262,144, a chunk below 2^31 negatives), else
+ *     MKE_E_UNSUPPORTED.
+ *   The ids back from the words (a reader's job, not the loop's): MKE_CODE_FAST with MKE_CODE_HEAD -> (entity, r, t); FAST without
+ *     HEAD -> (h, r, entity); no FAST -> (h, r, t).  For the sampler's words these are mke_neg_sample's ids. */
 #define MKE_CODE_ENT_BITS 26
 #define MKE_CODE_HEAD (1 << 26)
 #define MKE_CODE_FAST (1 << 27)
@@ -355,7 +380,6 @@ int mke_neg_sample_at(
     uint32_t seed_lo, uint32_t seed_hi, uint32_t stream_id,
     int32_t* neg_h, int32_t* neg_r, int32_t* neg_t,
     void* stream);
-
 /* Known-triple hash set.  key = h<<38 | t<<12 | r  (h,t < 2^26, r < 2^12); empty slot = ~0.
  * keys must be filled with 0xFF bytes by the caller before the first build call; capacity is a power
  * of two >= 2 * (number of triples).  Several build calls may add to the same set.
@@ -542,6 +566,10 @@ typedef struct mke_relation_plan {
   const int64_t* step_off_dev;               /* device copy of step_off */
   int32_t* neg_code;                         /* device scratch, as large as neg_h (neg_chunk_capacity) */
   uint32_t* code_bits; int64_t code_bits_words;  /* device scratch of the bake; a chunk that needs more runs the ref_count form */
+  int* ids_stale;                            /* HOST int, nullable.  Written once per chunk the call samples: 1 = the chunk exists as code
+                                                words only ("sampler_codes": neg_h / neg_r / neg_t were NOT written and still hold
+                                                whatever they held; section (1c) says how a reader rebuilds them from neg_code), 0 = the ids
+                                                were written.  Not touched when the call samples nothing (negatives_ready) */
 } mke_relation_plan;
 
 int mke_relation_steps(const mke_relation_plan* plan, int step_begin, int step_end, void* stream);

@@ -80,7 +80,8 @@ class mke_tuning(C.Structure):
         ("attr_fused_bwd", C.c_int),
         ("sampler_fast", C.c_int),
         ("neg_codes", C.c_int),
-        ("reserved", C.c_int * 6),
+        ("sampler_codes", C.c_int),
+        ("reserved", C.c_int * 5),
     ]
 
 
@@ -268,6 +269,7 @@ class mke_relation_plan(C.Structure):
         ("neg_code", C.c_void_p),
         ("code_bits", C.c_void_p),
         ("code_bits_words", C.c_int64),
+        ("ids_stale", C.c_void_p),
     ]
 
 

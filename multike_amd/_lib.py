@@ -424,6 +424,27 @@ def neg_codes(pos, step_off_dev, step_begin, step_end, pos_begin, pos_end, neg, 
     _check(rc, "mke_neg_codes")
 
 
+def neg_sample_codes(pos, pos_offset, pos_index, pos_kg, sides, neg_per_pos, max_try, seed, stream_id, code_out):
+    """The sampler's code-word form (header section (1c)): mke_neg_sample (pos_index None) or mke_neg_sample_at with neg_r and neg_t
+    left out, one word per negative into `code_out`."""
+    ph, pr, pt = pos
+    head = (ptr(ph, torch.int32, "pos_h"), ptr(pr, torch.int32, "pos_r"), ptr(pt, torch.int32, "pos_t"), ph.numel())
+    tail = (ptr(pos_kg, torch.uint8, "pos_kg"), sides, neg_per_pos, max_try, seed[0] & 0xFFFFFFFF, seed[1] & 0xFFFFFFFF,
+            stream_id & 0xFFFFFFFF, ptr(code_out, torch.int32, "neg_code"), None, None, _stream())
+    if pos_index is None:
+        _check(lib().mke_neg_sample(*head, pos_offset, *tail), "mke_neg_sample")
+    else:
+        _check(lib().mke_neg_sample_at(*head, ptr(pos_index, torch.int32, "pos_index"), *tail), "mke_neg_sample_at")
+
+
+def neg_codes_inplace(pos, step_off_dev, step_begin, step_end, pos_begin, pos_end, neg_per_pos, n_ent, bits, neg_code):
+    """mke_neg_codes without id arrays: `neg_code` holds the words neg_sample_codes wrote and is baked in place; pos: the epoch's."""
+    rc = lib().mke_neg_codes(*(ptr(x, torch.int32, "pos") for x in pos), ptr(step_off_dev, torch.int64, "step_off"),
+                             step_begin, step_end, pos_begin, pos_end, None, None, None, neg_per_pos, n_ent,
+                             ptr(bits, torch.int32, "bits"), bits.numel(), ptr(neg_code, torch.int32, "neg_code"), _stream())
+    _check(rc, "mke_neg_codes")
+
+
 def tripleset_build(h, r, t, keys):
     rc = lib().mke_tripleset_build(ptr(h, torch.int32, "h"), ptr(r, torch.int32, "r"), ptr(t, torch.int32, "t"),
                                    h.numel(), ptr(keys, torch.int64, "keys"), keys.numel(),

@@ -34,6 +34,7 @@ int g_score_o32 = 1;         // 32-bit row offsets in the training kernel when t
 int g_count_in_score = 1;    // runner: the next step's reference counting rides in the score launch (0: in the update launch)
 int g_score_lane_ids = 1;    // training kernel: a group's ids and reference counts fetched once, one negative per lane (mke_score.hip)
 int g_neg_codes = 1;         // runner: one code word per negative baked when a chunk is sampled, code-word form of the training kernel (0: reference counts per step)
+int g_sampler_codes = 1;     // runner, code-word chunks: the sampler writes code words, the bake runs on them in place, no id arrays (0: ids, then mke_neg_codes)
 int g_update_chunk = 0;      // rows per wavefront of the row-update kernel on large tables: 0 = by table size, 16, 64
 int g_deterministic = 0;     // fixed-order gradient reduction (parity / debugging mode)
 int g_sampler_fast = 1;      // mke_sampler.hip: coin block in the draw evaluation's idle lane, LDS duplicate test (0: the earlier form)
@@ -80,6 +81,11 @@ extern "C" int mke_set_option(const char* name, int value, int* old_value) {
   if (!strcmp(name, "neg_codes")) {
     if (old_value) *old_value = mke::g_neg_codes;
     mke::g_neg_codes = value != 0;
+    return MKE_OK;
+  }
+  if (!strcmp(name, "sampler_codes")) {
+    if (old_value) *old_value = mke::g_sampler_codes;
+    mke::g_sampler_codes = value != 0;
     return MKE_OK;
   }
   if (!strcmp(name, "update_chunk")) {

@@ -11,6 +11,8 @@
 // marks into the LDS with LDS atomics, bakes out of it and writes the row out (k_code_step).  Marking in global memory costs a
 // device-scope returning atomic per reference — 25 M of them per C2 epoch, 1.24 ms measured on the MI355X, more than the code
 // words save — and is kept for rows that do not fit (k_code_mark, k_code_bake: one launch each per chunk, grid.y = step).
+// Where the sampler itself wrote the words (its code-word form: everything but the exclusive bit), the same workgroup per step
+// marks from and bakes into that one array (k_code_step_inplace).
 #include "mke_common.h"
 
 namespace mke {
@@ -134,6 +136,59 @@ __global__ __launch_bounds__(CODE_STEP_BLOCK) void k_code_step(const CodeParams 
   for (int w = tid; w < (int)p.row_words; w += CODE_STEP_BLOCK) row[w] = s_row[w];
 }
 
+// The same step from ONE stream, in place (mke_neg_codes without id arrays): p.code holds what the sampler's code-word form wrote — the word
+// without MKE_CODE_EXCL — so the entity to mark and whether it is marked at all (MKE_CODE_FAST: exactly one side differs; a
+// negative without it is the positive itself here and marks nothing, as in k_code_step) are in the word, and neither the three id
+// arrays nor the positive's ids per negative are read.  One 4-byte stream per item lets a thread keep sixteen loads in flight:
+// a C2 step (124K negatives) is 8 mark and 8 bake passes instead of 31 + 31 of four and six streams each.
+constexpr int CODE_INPLACE_V = 16;
+__global__ __launch_bounds__(CODE_STEP_BLOCK) void k_code_step_inplace(const CodeParams p) {
+  extern __shared__ uint32_t s_row[];
+  const int c = blockIdx.x, tid = threadIdx.x;
+  const int64_t lo = p.step_off[p.s0 + c];
+  const int n = (int)(p.step_off[p.s0 + c + 1] - lo), n_neg = n * p.npp;   // the launcher checks that a step's negatives fit 31 bits
+  int32_t* __restrict__ code = p.code + (lo - p.pos0) * p.npp;
+  const int32_t* __restrict__ ph = p.ph + lo;
+  const int32_t* __restrict__ pt = p.pt + lo;
+  for (int w = tid; w < (int)p.row_words; w += CODE_STEP_BLOCK) s_row[w] = 0u;
+  __syncthreads();
+  for (int i = tid; i < n; i += CODE_STEP_BLOCK) {
+    code_mark(s_row, ph[i]);
+    code_mark(s_row, pt[i]);
+  }
+  constexpr int V = CODE_INPLACE_V;
+  constexpr int ENT = (1 << MKE_CODE_ENT_BITS) - 1;
+  for (int k0 = tid; k0 < n_neg; k0 += V * CODE_STEP_BLOCK) {
+    int w[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      const int k = k0 + v * CODE_STEP_BLOCK;
+      w[v] = k < n_neg ? code[k] : 0;   // not live: no MKE_CODE_FAST, nothing marked
+    }
+#pragma unroll
+    for (int v = 0; v < V; ++v)
+      if (w[v] & MKE_CODE_FAST) code_mark(s_row, w[v] & ENT);
+  }
+  __syncthreads();
+  for (int k0 = tid; k0 < n_neg; k0 += V * CODE_STEP_BLOCK) {
+    int w[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      const int k = k0 + v * CODE_STEP_BLOCK;
+      w[v] = k < n_neg ? code[k] : 0;
+    }
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      const int k = k0 + v * CODE_STEP_BLOCK;
+      const int e = w[v] & ENT;
+      const uint32_t two = (s_row[e >> 4] >> ((e & 15) * 2)) & 3u;
+      if (k < n_neg) code[k] = (w[v] & ~MKE_CODE_EXCL) | (two == 1u ? MKE_CODE_EXCL : 0);
+    }
+  }
+  uint32_t* __restrict__ row = p.bits + (int64_t)c * p.row_words;
+  for (int w = tid; w < (int)p.row_words; w += CODE_STEP_BLOCK) row[w] = s_row[w];
+}
+
 // true: a step's row of the bitmap fits the LDS, the bake is the one-launch form
 bool neg_codes_in_lds(int64_t n_ent) { return mke_neg_code_row_words(n_ent) * (int64_t)sizeof(uint32_t) <= CODE_LDS_BYTES; }
 
@@ -163,6 +218,22 @@ int launch_neg_codes(const int32_t* pos_h, const int32_t* pos_r, const int32_t* 
   return check_launch("k_code_bake");
 }
 
+// the chunk's rows of the bitmap, and MKE_CODE_EXCL into its pre-codes: one launch; only where the rows fit the LDS
+int launch_neg_codes_inplace(const int32_t* pos_h, const int32_t* pos_t, const int64_t* step_off_dev, int step_begin, int step_end,
+                             int64_t pos_begin, int64_t pos_end, int neg_per_pos, int64_t n_ent, uint32_t* bits, int32_t* neg_code,
+                             hipStream_t st) {
+  if (!neg_codes_in_lds(n_ent) || (pos_end - pos_begin) * (int64_t)neg_per_pos >= (1ll << 31)) {
+    set_error("mke_neg_codes in place: a step's bitmap row must fit %lld bytes of LDS and the chunk 2^31 negatives", (long long)CODE_LDS_BYTES);
+    return MKE_E_UNSUPPORTED;
+  }
+  CodeParams p;
+  p.ph = pos_h; p.pr = nullptr; p.pt = pos_t; p.step_off = step_off_dev; p.s0 = step_begin; p.pos0 = pos_begin;
+  p.nh = p.nr = p.nt = nullptr; p.npp = neg_per_pos;
+  p.row_words = mke_neg_code_row_words(n_ent); p.bits = bits; p.code = neg_code;
+  hipLaunchKernelGGL(k_code_step_inplace, dim3(step_end - step_begin), dim3(CODE_STEP_BLOCK), (size_t)p.row_words * sizeof(uint32_t), st, p);
+  return check_launch("k_code_step_inplace");
+}
+
 }  // namespace mke
 
 extern "C" int64_t mke_neg_code_row_words(int64_t n_ent) { return n_ent > 0 ? (n_ent + 15) / 16 : 0; }
@@ -176,12 +247,17 @@ extern "C" int mke_neg_codes(const int32_t* pos_h, const int32_t* pos_r, const i
   if (step_end == step_begin || pos_end == pos_begin) return MKE_OK;
   if (neg_per_pos < 1 || neg_per_pos > 64) { set_error("mke_neg_codes: neg_per_pos must be in [1,64], got %d", neg_per_pos); return MKE_E_UNSUPPORTED; }
   if (n_ent <= 0 || n_ent > (1ll << MKE_CODE_ENT_BITS)) { set_error("mke_neg_codes: n_ent must be in [1, 2^%d]", MKE_CODE_ENT_BITS); return MKE_E_RANGE; }
-  if (!pos_h || !pos_r || !pos_t || !step_off || !neg_h || !neg_r || !neg_t || !bits || !neg_code) { set_error("mke_neg_codes: NULL pointer"); return MKE_E_NULL; }
+  // neg_h == neg_r == neg_t == NULL: neg_code holds the sampler's own words, baked in place (section (1c))
+  const bool inplace = !neg_h && !neg_r && !neg_t;
+  if (!pos_h || !pos_r || !pos_t || !step_off || (!inplace && (!neg_h || !neg_r || !neg_t)) || !bits || !neg_code) { set_error("mke_neg_codes: NULL pointer"); return MKE_E_NULL; }
   if (step_end - step_begin > 65535) { set_error("mke_neg_codes: more than 65535 steps in one call"); return MKE_E_SHAPE; }
   if ((int64_t)(step_end - step_begin) * mke_neg_code_row_words(n_ent) > bits_words) {
     set_error("mke_neg_codes: %lld words of bitmap needed, %lld given", (long long)((step_end - step_begin) * mke_neg_code_row_words(n_ent)), (long long)bits_words);
     return MKE_E_SHAPE;
   }
+  if (inplace)
+    return launch_neg_codes_inplace(pos_h, pos_t, step_off, step_begin, step_end, pos_begin, pos_end, neg_per_pos, n_ent, bits, neg_code,
+                                    (hipStream_t)stream);
   return launch_neg_codes(pos_h, pos_r, pos_t, step_off, step_begin, step_end, pos_begin, pos_end, neg_h, neg_r, neg_t, neg_per_pos, n_ent,
                           bits, neg_code, (hipStream_t)stream);
 }

@@ -1,7 +1,8 @@
 // mke_runner.hip — native step runner of the relation view: the host-side loop the reference runs in Python
 // (code/MultiKE_model.py:302-312: batch_queue.get() -> session.run) expressed as a C++ loop that only enqueues
 // kernels.  Per step: [sampler for the next `sample_chunk` steps when the previous chunk is used up] ->
-// fused triple step -> one update launch covering the relation and the entity table.
+// fused triple step -> one update launch covering the relation and the entity table.  A chunk that runs the code-word form is
+// sampled straight into code words and baked in place ("sampler_codes"): its three id arrays are never written.
 #include "mke_common.h"
 
 namespace mke {
@@ -153,6 +154,7 @@ extern "C" int mke_relation_steps(const mke_relation_plan* pl, int step_begin, i
   const bool codes_ok = N > 0 && pl->ent_ref_count && !pl->negatives_ready && tune_neg_codes() && pl->step_off_dev && pl->neg_code &&
                         pl->code_bits && neg_codes_in_lds(pl->n_ent) && score_codes_legal(pl->n_ent, grad_rows, pl->n_rel, pl->stride);
   bool codes = false;    // the current chunk has code words
+  bool no_ids = false;   // ... written by the sampler itself: neg_h / neg_r / neg_t do not hold the chunk
   int64_t chunk_lo = 0;  // first positive (epoch position) whose negatives sit at neg_*[0]
   int chunk_end = step_begin;  // steps < chunk_end are sampled
   bool counted_ahead = false;  // the current step's references were counted by the previous step's update launch
@@ -166,16 +168,29 @@ extern "C" int mke_relation_steps(const mke_relation_plan* pl, int step_begin, i
       chunk_end = s + pl->sample_chunk < step_end ? s + pl->sample_chunk : step_end;
       chunk_lo = lo;
       const int64_t n = pl->step_off[chunk_end] - lo;
-      const int rc = mke_neg_sample(pl->pos_h + lo, pl->pos_r + lo, pl->pos_t + lo, n, lo, pl->pos_kg ? pl->pos_kg + lo : nullptr,
-                                    pl->sides, N, pl->max_try, pl->seed_lo, pl->seed_hi, pl->stream_id, pl->neg_h, pl->neg_r,
-                                    pl->neg_t, stream);
-      if (rc) return rc;
       codes = codes_ok && chunk_end - s <= 65535 && (int64_t)(chunk_end - s) * mke_neg_code_row_words(pl->n_ent) <= pl->code_bits_words;
-      if (codes) {
-        const int rc2 = launch_neg_codes(pl->pos_h, pl->pos_r, pl->pos_t, pl->step_off_dev, s, chunk_end, lo, lo + n, pl->neg_h, pl->neg_r,
-                                         pl->neg_t, N, pl->n_ent, pl->code_bits, pl->neg_code, (hipStream_t)stream);
-        if (rc2) return rc2;
+      // sampler_codes: the sampler writes the chunk's code words (all but MKE_CODE_EXCL) straight into neg_code, the bake adds the
+      // bit in place, and the score launch runs without id arrays; neg_h / neg_r / neg_t are not written (*ids_stale = 1:
+      // the caller rebuilds them from the words if it wants to read them)
+      no_ids = codes && tune_sampler_codes() && n * N < (1ll << 31);
+      if (no_ids) {
+        int rc = mke_neg_sample(pl->pos_h + lo, pl->pos_r + lo, pl->pos_t + lo, n, lo, pl->pos_kg ? pl->pos_kg + lo : nullptr, pl->sides, N,
+                                pl->max_try, pl->seed_lo, pl->seed_hi, pl->stream_id, pl->neg_code, nullptr, nullptr, stream);
+        if (rc) return rc;
+        rc = launch_neg_codes_inplace(pl->pos_h, pl->pos_t, pl->step_off_dev, s, chunk_end, lo, lo + n, N, pl->n_ent, pl->code_bits,
+                                      pl->neg_code, (hipStream_t)stream);
+        if (rc) return rc;
+      } else {
+        int rc = mke_neg_sample(pl->pos_h + lo, pl->pos_r + lo, pl->pos_t + lo, n, lo, pl->pos_kg ? pl->pos_kg + lo : nullptr, pl->sides, N,
+                                pl->max_try, pl->seed_lo, pl->seed_hi, pl->stream_id, pl->neg_h, pl->neg_r, pl->neg_t, stream);
+        if (rc) return rc;
+        if (codes) {
+          rc = launch_neg_codes(pl->pos_h, pl->pos_r, pl->pos_t, pl->step_off_dev, s, chunk_end, lo, lo + n, pl->neg_h, pl->neg_r, pl->neg_t,
+                                N, pl->n_ent, pl->code_bits, pl->neg_code, (hipStream_t)stream);
+          if (rc) return rc;
+        }
       }
+      if (pl->ids_stale) *pl->ids_stale = no_ids ? 1 : 0;
     }
     const int64_t no = (lo - chunk_lo) * N;
     const int32_t tag = pl->tag_base + s;
@@ -202,6 +217,7 @@ extern "C" int mke_relation_steps(const mke_relation_plan* pl, int step_begin, i
     }
     const bool in_score = tune_count_in_score() != 0;
     score_step_args(pl, s, no, refc, &sa);
+    if (no_ids) sa.neg_h = sa.neg_r = sa.neg_t = nullptr;
     sa.next_count = in_score ? cjp : nullptr;
     sa.neg_code = codes ? pl->neg_code + no : nullptr;
     rc = mke_triple_score_step(&sa, stream);

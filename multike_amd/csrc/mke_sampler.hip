@@ -45,7 +45,7 @@ struct SampleParams {
   const uint32_t* __restrict__ filter[2];  // nullable, per side: bit array of the side's known-triple set
   int filter_shift[2];                     // bit index = mix64(key) >> filter_shift
   uint32_t seed_lo, seed_hi, sid;
-  int32_t* __restrict__ nh;
+  int32_t* __restrict__ nh;                // the code-word form (CODES) writes its one array through this pointer
   int32_t* __restrict__ nr;
   int32_t* __restrict__ nt;
 };
@@ -99,7 +99,11 @@ __device__ __forceinline__ bool filter_maybe(const uint32_t* __restrict__ filter
 //  * "is any first draw a duplicate of an earlier slot's" is answered by inserting the draws into a 2 GS-slot open-addressing
 //    table of the group in LDS (compare-and-swap, ~1.2 probes) instead of neg_per_pos rounds of shuffles; the exact sequential
 //    fix-up below runs only when the table saw an equal value (0.3 % of the groups at 25 draws from 100K).
-template <int GS, bool FAST>
+//
+// CODES (mke_neg_sample with neg_r == neg_t == NULL): a kept candidate is stored as ONE word, the code word of multike_hip.h (1c) without
+// MKE_CODE_EXCL, at the offset its three ids would have taken — the draw, the side and "differs from the id it replaces" are
+// all in registers here, and the three id arrays (two of them copies of the positive) are never written.  p.nh is that array.
+template <int GS, bool FAST, bool CODES = false>
 __global__ __launch_bounds__(MKE_BLOCK) void k_neg_sample(const SampleParams p) {
   constexpr int PPW = 64 / GS;
   constexpr int TS = 2 * GS;                                // slots of a group's duplicate table
@@ -205,7 +209,12 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_neg_sample(const SampleParams p) 
     if (keep) {
       const int rank = __popcll(mask & ((1ull << gl) - 1ull));
       const int64_t o = i * (int64_t)N + collected + rank;
-      p.nh[o] = nh; p.nr[o] = r; p.nt[o] = nt;
+      if constexpr (CODES) {
+        // ent != x: (ent, r, t) or (h, r, ent), the one-gather form; ent == x: the positive itself, entity = its tail, no flags
+        p.nh[o] = ent != x ? (ent | (corrupt_head ? MKE_CODE_HEAD : 0) | MKE_CODE_FAST) : t;
+      } else {
+        p.nh[o] = nh; p.nr[o] = r; p.nt[o] = nt;
+      }
     }
     collected += __popcll(mask);
   }
@@ -338,7 +347,8 @@ int validate_side(const mke_kg_side& sd, int neg_per_pos) {
 int launch_neg_sample(const int32_t* pos_h, const int32_t* pos_r, const int32_t* pos_t, int64_t n_pos, int64_t pos_offset,
                       const int32_t* pos_index,
                       const uint8_t* pos_kg, const mke_kg_side* sides, int neg_per_pos, int max_try, uint32_t seed_lo,
-                      uint32_t seed_hi, uint32_t stream_id, int32_t* neg_h, int32_t* neg_r, int32_t* neg_t, hipStream_t st) {
+                      uint32_t seed_hi, uint32_t stream_id, int32_t* neg_h, int32_t* neg_r, int32_t* neg_t, hipStream_t st,
+                      bool codes /* neg_h takes one code word per negative, neg_r / neg_t are not used */) {
   SampleParams p;
   p.ph = pos_h; p.pr = pos_r; p.pt = pos_t; p.pos_kg = pos_kg; p.n_pos = n_pos; p.pos_offset = pos_offset; p.pos_index = pos_index;
   p.npp = neg_per_pos; p.max_try = max_try;
@@ -356,7 +366,16 @@ int launch_neg_sample(const int32_t* pos_h, const int32_t* pos_r, const int32_t*
   const int64_t pos_per_block = (MKE_BLOCK / 64) * (64 / gs);
   const int64_t blocks = (n_pos + pos_per_block - 1) / pos_per_block;
   const dim3 grid((unsigned)blocks), blk(MKE_BLOCK);
-  if (tune_sampler_fast()) {
+  if (codes) {
+    if (tune_sampler_fast()) {
+      if (gs == 16) hipLaunchKernelGGL((k_neg_sample<16, true, true>), grid, blk, 0, st, p);
+      else if (gs == 32) hipLaunchKernelGGL((k_neg_sample<32, true, true>), grid, blk, 0, st, p);
+      else hipLaunchKernelGGL((k_neg_sample<64, true, true>), grid, blk, 0, st, p);
+    } else {
+      if (gs == 32) hipLaunchKernelGGL((k_neg_sample<32, false, true>), grid, blk, 0, st, p);
+      else hipLaunchKernelGGL((k_neg_sample<64, false, true>), grid, blk, 0, st, p);
+    }
+  } else if (tune_sampler_fast()) {
     if (gs == 16) hipLaunchKernelGGL((k_neg_sample<16, true>), grid, blk, 0, st, p);
     else if (gs == 32) hipLaunchKernelGGL((k_neg_sample<32, true>), grid, blk, 0, st, p);
     else hipLaunchKernelGGL((k_neg_sample<64, true>), grid, blk, 0, st, p);
@@ -415,7 +434,14 @@ static int neg_sample_checked(const int32_t* pos_h, const int32_t* pos_r, const 
   using namespace mke;
   if (n_pos < 0) { set_error("negative n_pos"); return MKE_E_SHAPE; }
   if (n_pos == 0 || neg_per_pos == 0) return MKE_OK;
-  if (!pos_h || !pos_r || !pos_t || !neg_h || !neg_r || !neg_t || !sides) { set_error("mke_neg_sample: NULL pointer"); return MKE_E_NULL; }
+  // neg_r == neg_t == NULL: the code-word form, one word per negative into neg_h (multike_hip.h, section (1c))
+  const bool codes = neg_h && !neg_r && !neg_t;
+  if (!pos_h || !pos_r || !pos_t || !neg_h || (!codes && (!neg_r || !neg_t)) || !sides) { set_error("mke_neg_sample: NULL pointer"); return MKE_E_NULL; }
+  for (int k = 0; codes && k < (pos_kg ? 2 : 1); ++k)   // a word holds MKE_CODE_ENT_BITS of entity (ids of lists are the caller's to keep below)
+    if (!sides[k].ent_list && (sides[k].ent_lo < 0 || (int64_t)sides[k].ent_lo + sides[k].n_ent > (1ll << MKE_CODE_ENT_BITS))) {
+      set_error("mke_neg_sample: code words hold entity ids below 2^%d, side %d draws up to %lld", MKE_CODE_ENT_BITS, k, (long long)sides[k].ent_lo + sides[k].n_ent);
+      return MKE_E_RANGE;
+    }
   if (neg_per_pos < 0 || neg_per_pos > 64) { set_error("neg_per_pos must be in [0,64], got %d", neg_per_pos); return MKE_E_UNSUPPORTED; }
   if (max_try < 1 || max_try > 255) { set_error("max_try must be in [1,255]"); return MKE_E_SHAPE; }
   for (int k = 0; k < (pos_kg ? 2 : 1); ++k) {
@@ -423,7 +449,7 @@ static int neg_sample_checked(const int32_t* pos_h, const int32_t* pos_r, const 
     if (rc) return rc;
   }
   return launch_neg_sample(pos_h, pos_r, pos_t, n_pos, pos_offset, pos_index, pos_kg, sides, neg_per_pos, max_try, seed_lo, seed_hi,
-                           stream_id, neg_h, neg_r, neg_t, (hipStream_t)stream);
+                           stream_id, neg_h, neg_r, neg_t, (hipStream_t)stream, codes);
 }
 
 extern "C" int mke_neg_sample(const int32_t* pos_h, const int32_t* pos_r, const int32_t* pos_t, int64_t n_pos,

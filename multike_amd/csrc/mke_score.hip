@@ -429,9 +429,18 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_triple_score(const ScoreParams p)
 #pragma unroll 1
         for (int n = n_lo + q; n < n_hi; n += QPG) {
           const int64_t idx = nbase + n;
-          const int nh = p.nh[idx], nr = p.nr[idx], nt = p.nt[idx];
-          if (!((nr == pr) && ((nh != ph) != (nt != pt))))
+          if constexpr (!CW) {
+            const int nh = p.nh[idx], nr = p.nr[idx], nt = p.nt[idx];
+            if (!((nr == pr) && ((nh != ph) != (nt != pt))))
+              loss += independent_triple<FPL, DET>(p, grel, j, nh, nr, nt, p.nw ? p.nw[idx] : 1.0f, -1.0f, stage_slot(g, npp, n, 0));
+          } else {
+            // the word says whether the negative is slow; without id arrays (the sampler wrote the words) a slow one is the
+            // positive drawn as its own negative
+            if (p.neg_code[idx] & MKE_CODE_FAST) continue;
+            const bool ids = p.nh != nullptr;
+            const int nh = ids ? p.nh[idx] : ph, nr = ids ? p.nr[idx] : pr, nt = ids ? p.nt[idx] : pt;
             loss += independent_triple<FPL, DET>(p, grel, j, nh, nr, nt, p.nw ? p.nw[idx] : 1.0f, -1.0f, stage_slot(g, npp, n, 0));
+          }
         }
       }
 
@@ -543,7 +552,9 @@ static int score_impl(const mke_score_args& a, void* stream) {
   if (!a.ent_table || !a.rel_table || !a.loss_partials) { set_error("mke_triple_score_step: NULL table/loss"); return MKE_E_NULL; }
   if (n_pos < 0 || n_neg < 0 || a.n_ent <= 0 || a.n_rel <= 0) { set_error("negative count"); return MKE_E_SHAPE; }
   if (n_pos > 0 && (!a.pos_h || !a.pos_r || !a.pos_t)) { set_error("NULL positive index stream"); return MKE_E_NULL; }
-  if (n_neg > 0 && (!a.neg_h || !a.neg_r || !a.neg_t)) { set_error("NULL negative index stream"); return MKE_E_NULL; }
+  // all three id arrays NULL beside neg_code: the code-word form alone (checked where that form is chosen, below)
+  const bool no_ids = n_neg > 0 && a.neg_code && !a.neg_h && !a.neg_r && !a.neg_t;
+  if (n_neg > 0 && !no_ids && (!a.neg_h || !a.neg_r || !a.neg_t)) { set_error("NULL negative index stream"); return MKE_E_NULL; }
   if (stride <= 0 || stride % 16 != 0 || a.dim <= 0 || a.dim > stride || stride > MKE_MAX_STRIDE) {
     set_error("bad stride/dim: stride=%d dim=%d (stride %% 16 == 0, dim <= stride <= %d)", stride, a.dim, MKE_MAX_STRIDE);
     return MKE_E_SHAPE;
@@ -609,6 +620,7 @@ static int score_impl(const mke_score_args& a, void* stream) {
   const int64_t code_rows = p.hot_slot ? (int64_t)p.hot_row0 + (int64_t)p.hot_copies * p.n_hot : a.n_ent;
   const bool cw = a.neg_code != nullptr && neg_per_pos > 0 && !det && score_codes_legal(a.n_ent, code_rows, a.n_rel, stride);
   if (a.neg_code && neg_per_pos > 0 && !cw && !a.ref_count) { set_error("neg_code: the code-word form needs 32-bit offsets, lane ids and n_ent <= 2^%d (or give ref_count)", MKE_CODE_ENT_BITS); return MKE_E_UNSUPPORTED; }
+  if (no_ids && !cw) { set_error("neg_code without neg_h / neg_r / neg_t: only where the code-word form is legal (grouped negatives, 32-bit offsets, lane ids, n_ent <= 2^%d, not deterministic)", MKE_CODE_ENT_BITS); return MKE_E_UNSUPPORTED; }
   const bool excl = (a.ref_count != nullptr || cw) && neg_per_pos > 0;   // (a training step: checked above)
   p.refcount = excl && !cw ? a.ref_count : nullptr; p.ent_w = a.ent_table;
   p.neg_code = cw ? a.neg_code : nullptr;

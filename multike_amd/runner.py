@@ -6,12 +6,13 @@ stream with no Python between the steps; this is the replacement of the referenc
 """
 from __future__ import annotations
 
+import ctypes
 
 import numpy as np
 import torch
 
 from . import _lib
-from .sampling import RelationBatcher
+from .sampling import RelationBatcher, ids_from_codes
 from .tables import EmbeddingTable
 
 _OPT = {"Adagrad": _lib.OPT_ADAGRAD, "SGD": _lib.OPT_SGD}
@@ -54,7 +55,11 @@ class RelationViewRunner:
         span = max(int(off[min(s + self.sample_chunk, self.steps)] - off[s]) for s in range(self.steps)) if self.steps else 0
         self.neg_chunk_capacity = max(1, span * N)
         nbuf = 2 if self.overlap else 1
-        self.neg = tuple(torch.empty(nbuf * self.neg_chunk_capacity, dtype=torch.int32, device=ent.device) for _ in range(3))
+        # (neg_h, neg_r, neg_t) of the chunk sampled last.  Read through the `neg` property: where the native loop samples straight
+        # into code words ("sampler_codes") it does not write these, sets `_ids_stale`, and the first reader has them rebuilt
+        self._neg = tuple(torch.empty(nbuf * self.neg_chunk_capacity, dtype=torch.int32, device=ent.device) for _ in range(3))
+        self._ids_stale = ctypes.c_int(0)        # mke_relation_plan.ids_stale points here
+        self._stale_chunk = None                 # (first epoch position, negatives, batcher epoch) of the chunk neg_code describes
         # two halves: steps alternate, so that step s+1 can be counted while step s is being updated
         self.refcount = torch.zeros(2 * ent.n_rows, dtype=torch.int32, device=ent.device) if exclusive_rows else None
         # Code words (mke_neg_codes): one int32 per negative beside the ids, the device copy of the step offsets, and the bake's bitmap
@@ -79,6 +84,26 @@ class RelationViewRunner:
     # more copies and a lower threshold only lengthen the update launch (each hub row sums its copies: 32 copies +4.5 us)
     HOT_MIN, HOT_MAX, HOT_COPIES = 20.0, 1024, 8
     CODE_BITS_BUDGET = 64 << 20
+
+    @property
+    def ids_stale(self) -> bool:
+        """True: the chunk sampled last exists as code words only; reading `neg` decodes it (and clears this)."""
+        return bool(self._ids_stale.value)
+
+    @property
+    def neg(self):
+        """(neg_h, neg_r, neg_t) of the chunk sampled last, laid out from its first step.  After a chunk sampled as code words the
+        ids are rebuilt first (sampling.ids_from_codes, on the current stream) from the batcher's CURRENT positives: after
+        a shuffle they are gone, and the read raises."""
+        if self._ids_stale.value:
+            pos_begin, n_neg, epoch = self._stale_chunk
+            if epoch != self.bat.epoch:
+                raise _lib.MultiKEHipError(f"the negatives of epoch {epoch} exist as code words only and the batcher has moved to epoch "
+                                           f"{self.bat.epoch}: read `neg` before the shuffle (or run with sampler_codes=0)")
+            b = self.bat
+            ids_from_codes((b.pos_h, b.pos_r, b.pos_t), pos_begin, self.neg_code, n_neg, b.neg_per_pos, self._neg)
+            self._ids_stale.value = 0
+        return self._neg
 
     def _declare_hot_rows(self, ent: EmbeddingTable, b: RelationBatcher):
         deg = torch.bincount(torch.cat([b.pos_h, b.pos_t]).long(), minlength=ent.n_rows).float() / max(1, self.steps)
@@ -110,7 +135,8 @@ class RelationViewRunner:
         p.step_off = self._step_off.ctypes.data
         p.n_steps = self.steps
         p.neg_per_pos, p.max_try, p.sample_chunk = b.neg_per_pos, self.max_try, self.sample_chunk
-        p.neg_h, p.neg_r, p.neg_t = (_lib.ptr(x, torch.int32, "neg") for x in self.neg)
+        p.neg_h, p.neg_r, p.neg_t = (_lib.ptr(x, torch.int32, "neg") for x in self._neg)
+        p.ids_stale = ctypes.addressof(self._ids_stale)
         p.optimizer, p.lr, p.scale = _OPT[self.optimizer], self.lr, self.scale
         p.loss_partials, p.loss_ring = _lib.ptr(self.loss, torch.float64, "loss"), self.loss.shape[0]
         p.hot = e.hot_struct()
@@ -144,7 +170,8 @@ class RelationViewRunner:
                 pos, neg = self.bat.batch(s)
                 if N and self.sample_chunk >= self.steps:       # the epoch's negatives where the native loop leaves them
                     lo = int(self.bat.off[s])
-                    for dst, src in zip(self.neg, neg):
+                    self._ids_stale.value = 0
+                    for dst, src in zip(self._neg, neg):
                         dst[lo * N:lo * N + src.numel()].copy_(src)
                 lp = self._det_engine.relation_step(self.ent, self.rel, self.opt_name, pos, neg if self.bat.neg_per_pos else None,
                                                     neg_per_pos=self.bat.neg_per_pos, lr=self.lr, scale=self.scale,
@@ -158,6 +185,10 @@ class RelationViewRunner:
         # StepEngine and this runner may share touched arrays: keep the tag spaces apart (runner: upper half)
         self.plan.tag_base = (1 << 30) + 1 + self._epoch_tag_base
         _lib.relation_steps(self.plan, step_begin, step_end)
+        if self._ids_stale.value:    # the last chunk of the call: what neg_code (and, once decoded, neg) describe
+            s0 = step_begin + (step_end - 1 - step_begin) // self.sample_chunk * self.sample_chunk
+            lo, hi = int(self._step_off[s0]), int(self._step_off[min(s0 + self.sample_chunk, step_end)])
+            self._stale_chunk = (lo, (hi - lo) * self.bat.neg_per_pos, self.bat.epoch)
 
     # ------------------------------------------------------------------------------------------------
     def run_epochs(self, n_epochs: int, on_epoch_end=None, prefetch: bool = False):
@@ -179,7 +210,7 @@ class RelationViewRunner:
         N = b.neg_per_pos
         total = int(b.off[-1]) * N
         if getattr(self, "_neg_sets", None) is None:
-            self._neg_sets = [tuple(x[:total] for x in self.neg) if self.neg[0].numel() >= total else
+            self._neg_sets = [tuple(x[:total] for x in self._neg) if self._neg[0].numel() >= total else
                               tuple(torch.empty(total, dtype=torch.int32, device=self.ent.device) for _ in range(3)),
                               tuple(torch.empty(total, dtype=torch.int32, device=self.ent.device) for _ in range(3))]
             self._side = torch.cuda.Stream(device=self.ent.device)
@@ -192,6 +223,7 @@ class RelationViewRunner:
             sample_negatives(pos, b.side1, N, seed=b.rng_seed, stream_id=stream_id, pos_offset=0, max_try=self.max_try, out=out,
                              side1=b.side2, pos_kg=b.pos_kg)
 
+        self._ids_stale.value = 0        # this path samples ids itself (negatives_ready: the native call leaves the flag alone)
         sample_epoch((b.pos_h, b.pos_r, b.pos_t), b.rng_stream, self._neg_sets[cur])      # first epoch: inline
         for e in range(n_epochs):
             if e + 1 < n_epochs:
@@ -217,7 +249,7 @@ class RelationViewRunner:
                 _lib.relation_steps(p, 0, self.steps)
             finally:
                 p.negatives_ready, p.sample_chunk = 0, self.sample_chunk
-                p.neg_h, p.neg_r, p.neg_t = (_lib.ptr(x, torch.int32, "neg") for x in self.neg)
+                p.neg_h, p.neg_r, p.neg_t = (_lib.ptr(x, torch.int32, "neg") for x in self._neg)
             if on_epoch_end:
                 on_epoch_end(e, self)
             if e + 1 < n_epochs:

@@ -112,6 +112,24 @@ def sample_negatives(pos, side: KGSide, neg_per_pos: int, seed=(0, 0), stream_id
     return out
 
 
+def ids_from_codes(pos, pos_begin: int, code: torch.Tensor, n_neg: int, neg_per_pos: int, out):
+    """(neg_h, neg_r, neg_t) of the first n_neg code words of `code` (header section (1c)) into `out`: the words belong to the
+    positives from epoch position pos_begin on, neg_per_pos each.  FAST with HEAD -> (entity, r, t); FAST without HEAD ->
+    (h, r, entity); no FAST -> (h, r, t).  For a reader of the negatives (a test, a dump, the instrumented benchmark pass), not for
+    the training loop, which never needs the ids: a handful of elementwise torch launches."""
+    n_pos = n_neg // neg_per_pos
+    if n_neg != n_pos * neg_per_pos or pos_begin + n_pos > pos[0].numel() or min(x.numel() for x in (code,) + tuple(out)) < n_neg:
+        raise _lib.MultiKEHipError(f"ids_from_codes: {n_neg} negatives of {neg_per_pos} per positive from position {pos_begin} do not fit the buffers")
+    ph, pr, pt = (x[pos_begin:pos_begin + n_pos].repeat_interleave(neg_per_pos) for x in pos)
+    c = code[:n_neg]
+    e = c & ((1 << _lib.CODE_ENT_BITS) - 1)
+    fast, head = (c & _lib.CODE_FAST) != 0, (c & _lib.CODE_HEAD) != 0
+    torch.where(fast & head, e, ph, out=out[0][:n_neg])
+    out[1][:n_neg].copy_(pr)
+    torch.where(fast & ~head, e, pt, out=out[2][:n_neg])
+    return out
+
+
 def int_triples(triples) -> np.ndarray:
     """(h, r, t) id triples — an array, or the reference's list / set of tuples — as an int32 array [n, 3].  Tuples go through one
     flat iterator (np.asarray of 700K tuples builds 700K temporary rows: 0.23 s against 0.07)."""
