@@ -81,7 +81,8 @@ class mke_tuning(C.Structure):
         ("sampler_fast", C.c_int),
         ("neg_codes", C.c_int),
         ("sampler_codes", C.c_int),
-        ("reserved", C.c_int * 5),
+        ("sampler_lean", C.c_int),
+        ("reserved", C.c_int * 4),
     ]
 
 

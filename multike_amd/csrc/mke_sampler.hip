@@ -21,6 +21,7 @@
 #include <unordered_map>
 
 #include "mke_common.h"
+#include "mke_sampler_o32.h"
 
 namespace mke {
 
@@ -220,10 +221,230 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_neg_sample(const SampleParams p) 
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// LEAN (`sampler_lean`, round 25; the fast form's stream, order of attempts and compaction: same output bit for bit).  A
+// wavefront of the fast form issues 247 VALU instructions (Philox about a third) but waits for 59 % of its cycles, and the
+// known-triple test owns 40 % of the C2 epoch launch (profiles/r25_sampler_issue.md).  This form cuts waits and issue slots
+// around the Philox block:
+//  * wave-uniform side: a step's positives are KG 1 first, then KG 2, so all live lanes of nearly every wavefront have ONE kg
+//    (one ballot).  Such a wavefront reads the side's fields through scalar loads and takes one code path with them; the
+//    side no longer costs a per-lane round trip to the kernel arguments behind the pos_kg byte.  A mixed wavefront (two per
+//    step) runs the rounds once per KG with the other KG's groups idle;
+//  * O32: positives, entity list, filter and outputs indexed with 32-bit byte offsets on scalar bases where the launcher
+//    proves that they fit (sampler_o32_fits); the 64-bit form is the fallback instantiation.  The candidate table and the
+//    exact probe keep 64-bit arithmetic (their sizes are not the launcher's to know / the rare branch);
+//  * the filter of this form is indexed by filter_mix32 of (h, r, t) — four 32-bit multiplies — and holds three
+//    bits of one word per key, so that the 64-bit mix64 is computed only by lanes that fall through to the exact probe, and
+//    fewer wavefronts have such a lane (0.9 % of the draws at the C2 shape, a third of the wavefronts, against 5 % with the
+//    one-bit filter: with 50 draws per wavefront that sends nine wavefronts in ten through the 64-bit multiplies and the
+//    probe).  It is a second bit array beside the fast form's, of the same size, written by the same two kernels; a set
+//    word still asks the table;
+//  * strided grid: a wavefront samples PPW positives at a time and strides by a capped grid instead of one wavefront launched
+//    per PPW positives (56 iterations per wavefront at the C2 epoch launch);
+//  * Lemire's rejection threshold `(0u - n) % n` is evaluated only by lanes with l < n, as draw_next does it.
+// ---------------------------------------------------------------------------------------------------------------
+// word and bits of a triple in the lean filter: y -> word y >> shift (shift = 32 - log2(words)), bits from y's low end
+__host__ __device__ __forceinline__ uint32_t filter_mix32(uint32_t h, uint32_t r, uint32_t t) {
+  uint32_t x = (h * 0x9E3779B1u) ^ (t * 0x85EBCA6Bu) ^ (r * 0xC2B2AE35u);
+  x ^= x >> 15;
+  return x * 0x2C1B3C6Du;
+}
+__host__ __device__ __forceinline__ uint32_t filter_mask32(uint32_t y, int shift) {
+  // three 5-bit fields below the word index (shift >= 12: the third overlaps the second by up to three bits at the 4 MB cap)
+  return (1u << (y & 31u)) | (1u << ((y >> 5) & 31u)) | (1u << ((y >> (shift - 5)) & 31u));
+}
+
+// Grid cap of the lean kernel, in workgroups per CU.  Eight are resident at once (at most 64 VGPRs: eight wavefronts per SIMD);
+// four times as many measured best at every neg_per_pos (24 .. 64 per CU within 2 %, 8 as slow as no cap, C2 epoch launch:
+// profiles/r25_sampler_issue.md): the workgroups that wait even out what the resident ones do not finish together.
+constexpr int LEAN_BLOCKS_PER_CU = 32;
+
+// draw_next with the block's word chosen by selects: a dynamically indexed register array costs a stack slot or LDS
+__device__ __forceinline__ uint32_t draw_next_sel(uint32_t gi, uint32_t round, uint32_t slot, uint32_t sid, uint32_t k0, uint32_t k1,
+                                                  uint32_t n, uint32_t& attempt) {
+  for (;;) {
+    const uint32_t blk = attempt >> 2, word = attempt & 3u;
+    const Philox4 ph = philox4x32_10(gi, round | (blk << 8), slot, sid, k0, k1);
+    const uint32_t x = word == 0 ? ph.v[0] : (word == 1 ? ph.v[1] : (word == 2 ? ph.v[2] : ph.v[3]));
+    ++attempt;
+    const uint64_t m = (uint64_t)x * (uint64_t)n;
+    const uint32_t l = (uint32_t)m;
+    if (l < n) {
+      const uint32_t thresh = (0u - n) % n;
+      if (l < thresh) continue;
+    }
+    return (uint32_t)(m >> 32);
+  }
+}
+
+struct LeanParams {
+  SampleParams s;                             // as the fast form's (s.filter / s.filter_shift are not read)
+  const uint32_t* __restrict__ lfilter[2];    // nullable, per side: the lean filter of the side's known-triple set
+  int lshift[2];                              // word index = filter_mix32 >> lshift
+};
+
+// Element idx of base; O32: byte offset formed in 32 bits, so that the access takes its base from scalar registers.
+template <bool O32, class T, class I>
+__device__ __forceinline__ T& elem_at(T* base, I idx) {
+  if constexpr (O32) return *(T*)((char*)base + (uint32_t)((uint32_t)idx * (uint32_t)sizeof(T)));
+  else return base[idx];
+}
+
+// The rounds of the wavefront's groups of KG `kg` (a constant, so every field of the side is a scalar at a fixed place of the
+// kernel arguments); a lane that is not `live` belongs to a group that idles.
+template <int GS, bool CODES, bool O32, int kg, class I>
+__device__ __forceinline__ void lean_rounds(const LeanParams& q, const bool live, const I i, const int h, const int r,
+                                            const int t, const uint32_t gi, uint32_t* __restrict__ tbl, const int gl, const int gbase) {
+  constexpr int TS = 2 * GS;
+  const SampleParams& p = q.s;
+  const mke_kg_side& sd = p.side[kg];
+  const uint32_t sid = p.sid + (uint32_t)kg;
+  const uint64_t* __restrict__ keys = sd.known_keys;
+  const uint32_t* __restrict__ filter = q.lfilter[kg];
+  const int lshift = q.lshift[kg];
+  // the side's sizes as scalars (read here, not through a per-lane choice of kernel-argument addresses)
+  const uint32_t side_n = (uint32_t)__builtin_amdgcn_readfirstlane(sd.n_ent), side_k = (uint32_t)__builtin_amdgcn_readfirstlane(sd.cand_k);
+  const int N = p.npp;
+  const uint64_t gmask_all = GS == 64 ? ~0ull : (((1ull << (GS & 63)) - 1ull) << gbase);
+  const I obase = i * (I)N;               // first output slot of the positive
+  const bool merged = N < GS;             // the group's last lane is never a draw lane: it evaluates the coin block
+  int collected = live ? 0 : N;
+  for (int round = 0; round < p.max_try; ++round) {
+    if (!__ballot(collected < N)) break;  // every positive of the wave is done
+    const int need = N - collected;       // 0 for finished groups
+    const bool active = gl < need;
+    bool corrupt_head;
+    uint32_t first_word = 0;
+    if (merged) {
+      const Philox4 ph = philox4x32_10(gi, (uint32_t)round, gl == GS - 1 ? 0xFFFFFFFFu : (uint32_t)gl, sid, p.seed_lo, p.seed_hi);
+      first_word = ph.v[0];               // draw lanes: attempt 0 = word 0 of block 0 of (positive, round, slot)
+      corrupt_head = ((uint32_t)__shfl((int)ph.v[0], gbase + GS - 1, 64) >> 31) != 0;
+    } else {
+      const Philox4 cph = philox4x32_10(gi, (uint32_t)round, 0xFFFFFFFFu, sid, p.seed_lo, p.seed_hi);
+      corrupt_head = (cph.v[0] >> 31) != 0;
+    }
+    const int x = corrupt_head ? h : t;
+    bool use_tbl = false;
+    if (sd.cand_table != nullptr) use_tbl = sd.cand_valid == nullptr || (live && sd.cand_valid[x] != 0);
+    const uint32_t n = use_tbl ? side_k : side_n;
+    uint32_t attempt = 0;
+    uint32_t pos = 0xFFFFFFFFu;
+    if (active) {
+      bool have = false;
+      if (merged) {                       // draw_next's first iteration on the word already at hand
+        attempt = 1;
+        const uint64_t m = (uint64_t)first_word * (uint64_t)n;
+        const uint32_t l = (uint32_t)m;
+        have = true;
+        if (l < n) have = l >= (0u - n) % n;
+        pos = (uint32_t)(m >> 32);
+      }
+      if (!have) pos = draw_next_sel(gi, (uint32_t)round, (uint32_t)gl, sid, p.seed_lo, p.seed_hi, n, attempt);
+    }
+    // duplicate detection among first draws (q runs to the largest `need` of the wave)
+    int need_max = max(need, __shfl_xor(need, 32, 64));
+    if (GS == 16) need_max = max(need_max, __shfl_xor(need_max, 16, 64));
+    bool dup = false;
+    tbl[gl] = 0xFFFFFFFFu;
+    tbl[gl + GS] = 0xFFFFFFFFu;
+    if (active) {
+      uint32_t sl = (pos * 0x9E3779B1u) >> (32 - (GS == 16 ? 5 : GS == 32 ? 6 : 7));
+      for (;;) {
+        const uint32_t old = atomicCAS(&tbl[sl], 0xFFFFFFFFu, pos);
+        if (old == 0xFFFFFFFFu) break;
+        if (old == pos) { dup = true; break; }
+        sl = (sl + 1) & (TS - 1);
+      }
+    }
+    if (__ballot(dup)) {
+      // sequential without-replacement semantics: slot q must differ from the final draws of slots < q
+      for (int q2 = 1; q2 < need_max; ++q2) {
+        for (;;) {
+          const uint32_t v = (uint32_t)__shfl((int)pos, gbase + q2, 64);
+          const bool hit = q2 < need && gl < q2 && pos == v;
+          const uint64_t hb = __ballot(hit);
+          if (!hb) break;
+          if ((hb & gmask_all) && gl == q2) pos = draw_next_sel(gi, (uint32_t)round, (uint32_t)gl, sid, p.seed_lo, p.seed_hi, n, attempt);
+        }
+      }
+    }
+    int ent = 0;
+    if (active) {
+      if (use_tbl) ent = sd.cand_table[(int64_t)x * (int64_t)side_k + pos];
+      else ent = sd.ent_list ? elem_at<O32>(sd.ent_list, pos) : sd.ent_lo + (int32_t)pos;
+    }
+    const int nh = corrupt_head ? ent : h;
+    const int nt = corrupt_head ? t : ent;
+    bool keep = active;
+    if (active && round < p.max_try - 1 && keys != nullptr) {
+      bool ask = true;
+      if (filter != nullptr) {            // a clear bit among the key's three: certainly not known
+        const uint32_t y = filter_mix32((uint32_t)nh, (uint32_t)r, (uint32_t)nt);
+        const uint32_t m = filter_mask32(y, lshift);
+        ask = (elem_at<true>(filter, y >> lshift) & m) == m;
+      }
+      if (ask) {
+        const uint64_t key = triple_key((uint32_t)nh, (uint32_t)r, (uint32_t)nt);
+        keep = !set_contains_hashed(keys, sd.known_capacity, key, mix64(key));
+      }
+    }
+    const uint64_t mask = (__ballot(keep) & gmask_all) >> gbase;  // this group's kept slots
+    if (keep) {
+      const int rank = __popcll(mask & ((1ull << gl) - 1ull));
+      const I o = obase + (I)(collected + rank);
+      if constexpr (CODES) {
+        // ent != x: (ent, r, t) or (h, r, ent), the one-gather form; ent == x: the positive itself, entity = its tail, no flags
+        elem_at<O32>(p.nh, o) = ent != x ? (ent | (corrupt_head ? MKE_CODE_HEAD : 0) | MKE_CODE_FAST) : t;
+      } else {
+        elem_at<O32>(p.nh, o) = nh; elem_at<O32>(p.nr, o) = r; elem_at<O32>(p.nt, o) = nt;
+      }
+    }
+    collected += __popcll(mask);
+  }
+}
+
+template <int GS, bool CODES, bool O32>
+__global__ __launch_bounds__(MKE_BLOCK) void k_neg_sample_lean(const LeanParams q) {
+  using I = std::conditional_t<O32, uint32_t, int64_t>;
+  constexpr int PPW = 64 / GS;
+  constexpr int TS = 2 * GS;
+  __shared__ uint32_t s_dup[(MKE_BLOCK / GS) * TS];
+  const SampleParams& p = q.s;
+  const int lane = threadIdx.x & 63;
+  const int gl = lane & (GS - 1);        // slot inside the group
+  const int gbase = lane & ~(GS - 1);    // first lane of the group
+  uint32_t* tbl = s_dup + (threadIdx.x / GS) * TS;
+  // a wavefront takes PPW positives at a time and strides by the grid, which the launcher caps (LEAN_BLOCKS_PER_CU): at C2 a
+  // wavefront's work per PPW positives is about 3 us, and a wavefront launched for each left the SIMDs short of wavefronts
+  const I n_waves = (I)gridDim.x * (I)(MKE_BLOCK / 64);
+  const I wave0 = (I)blockIdx.x * (I)(MKE_BLOCK / 64) + (I)(uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // a scalar
+  for (I wave = wave0; wave * (I)PPW < (I)p.n_pos; wave += n_waves) {
+    const I i = wave * (I)PPW + (I)(lane / GS);
+    const bool live = i < (I)p.n_pos;
+    const I ii = live ? i : (I)0;
+    // the positive's ids and its kg byte are requested together
+    const int h = elem_at<O32>(p.ph, ii), r = elem_at<O32>(p.pr, ii), t = elem_at<O32>(p.pt, ii);
+    const int kg = p.pos_kg ? (elem_at<O32>(p.pos_kg, ii) != 0) : 0;
+    const uint32_t gi = p.pos_index ? (uint32_t)elem_at<O32>(p.pos_index, ii) : (uint32_t)ii + (uint32_t)p.pos_offset;
+    const uint64_t lv = __ballot(live), k1 = __ballot(live && kg != 0);
+    // one pass when the live lanes are of one KG; a mixed wavefront takes a pass per KG, the other KG's groups idle in it
+    // (a group is one positive, and nothing a group computes depends on another group)
+    if (k1 != lv || lv == 0) lean_rounds<GS, CODES, O32, 0, I>(q, live && kg == 0, i, h, r, t, gi, tbl, gl, gbase);
+    if (k1 != 0) lean_rounds<GS, CODES, O32, 1, I>(q, live && kg == 1, i, h, r, t, gi, tbl, gl, gbase);
+  }
+}
+
+// the key's bits in the lean filter (k_tripleset_build from the ids, k_filter_from_table from the stored key's fields)
+__device__ __forceinline__ void lean_filter_set(uint32_t* __restrict__ lfilter, int lshift, uint32_t h, uint32_t r, uint32_t t) {
+  const uint32_t y = filter_mix32(h, r, t);
+  atomicOr(&lfilter[y >> lshift], filter_mask32(y, lshift));
+}
+
 __global__ __launch_bounds__(MKE_BLOCK) void k_tripleset_build(const int32_t* __restrict__ h, const int32_t* __restrict__ r,
                                                                const int32_t* __restrict__ t, int64_t n,
                                                                uint64_t* __restrict__ keys, uint64_t cap,
-                                                               uint32_t* __restrict__ filter, int filter_shift) {
+                                                               uint32_t* __restrict__ filter, int filter_shift,
+                                                               uint32_t* __restrict__ lfilter, int lshift) {
   const int64_t i = (int64_t)blockIdx.x * MKE_BLOCK + threadIdx.x;
   if (i >= n) return;
   const uint64_t key = triple_key((uint32_t)h[i], (uint32_t)r[i], (uint32_t)t[i]);
@@ -231,6 +452,8 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_tripleset_build(const int32_t* __
   if (filter) {
     const uint64_t bit = hash >> filter_shift;
     atomicOr(&filter[bit >> 5], 1u << (uint32_t)(bit & 31u));
+    // the fields as the key holds them (triple_key keeps 26 / 12 / 26 bits): what k_filter_from_table has to go by
+    lean_filter_set(lfilter, lshift, (uint32_t)(key >> 38), (uint32_t)(key & 0xFFFu), (uint32_t)((key >> 12) & 0x3FFFFFFu));
   }
   uint64_t slot = hash & (cap - 1);
   for (;;) {
@@ -252,13 +475,15 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_tripleset_query(const int32_t* __
 
 // A new filter starts from what its table already holds (a table may have been filled before it had a filter).
 __global__ __launch_bounds__(MKE_BLOCK) void k_filter_from_table(const uint64_t* __restrict__ keys, uint64_t cap,
-                                                                 uint32_t* __restrict__ filter, int filter_shift) {
+                                                                 uint32_t* __restrict__ filter, int filter_shift,
+                                                                 uint32_t* __restrict__ lfilter, int lshift) {
   const uint64_t i = (uint64_t)blockIdx.x * MKE_BLOCK + threadIdx.x;
   if (i >= cap) return;
   const uint64_t key = keys[i];
   if (key == MKE_EMPTY_KEY) return;
   const uint64_t bit = mix64(key) >> filter_shift;
   atomicOr(&filter[bit >> 5], 1u << (uint32_t)(bit & 31u));
+  lean_filter_set(lfilter, lshift, (uint32_t)(key >> 38), (uint32_t)(key & 0xFFFu), (uint32_t)((key >> 12) & 0x3FFFFFFu));
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -268,6 +493,8 @@ struct TripleFilter {
   uint64_t capacity;
   uint32_t* bits;
   int shift;      // 64 - log2(number of bits)
+  uint32_t* lbits;  // the lean form's array: the second half of the same allocation, as many bits again
+  int lshift;       // 32 - log2(number of words)
 };
 static std::mutex g_filter_mu;
 static std::unordered_map<const void*, TripleFilter> g_filters;
@@ -283,7 +510,7 @@ static int filter_bits_log2(uint64_t capacity) {
 static TripleFilter filter_lookup(const uint64_t* keys, uint64_t capacity) {
   std::lock_guard<std::mutex> lk(g_filter_mu);
   const auto it = g_filters.find(keys);
-  if (it == g_filters.end() || it->second.capacity != capacity) return TripleFilter{0, nullptr, 0};
+  if (it == g_filters.end() || it->second.capacity != capacity) return TripleFilter{0, nullptr, 0, nullptr, 0};
   return it->second;
 }
 
@@ -314,18 +541,20 @@ static int filter_for_build(uint64_t* keys, uint64_t capacity, hipStream_t st, T
   if (hipGetDevice(&cur) != hipSuccess) { set_error("mke_tripleset_build: no device"); return MKE_E_NULL; }
   dev = cur;
   if (hipPointerGetAttributes(&attr, keys) == hipSuccess) dev = attr.device; else (void)hipGetLastError();
-  TripleFilter f{capacity, nullptr, 64 - lg};
+  TripleFilter f{capacity, nullptr, 64 - lg, nullptr, 32 - (lg - 5)};
   if (dev != cur) (void)hipSetDevice(dev);
-  hipError_t e = hipMalloc((void**)&f.bits, bytes);
-  if (e == hipSuccess) e = hipMemsetAsync(f.bits, 0, bytes, st);
+  hipError_t e = hipMalloc((void**)&f.bits, 2 * bytes);   // both forms' arrays
+  if (e == hipSuccess) e = hipMemsetAsync(f.bits, 0, 2 * bytes, st);
+  f.lbits = f.bits ? f.bits + bytes / sizeof(uint32_t) : nullptr;
   if (dev != cur) (void)hipSetDevice(cur);
   if (e != hipSuccess) {
     if (f.bits) (void)hipFree(f.bits);
-    set_error("mke_tripleset_build: filter allocation (%zu bytes): %s", bytes, hipGetErrorString(e));
+    set_error("mke_tripleset_build: filter allocation (%zu bytes): %s", 2 * bytes, hipGetErrorString(e));
     return (int)e;
   }
   const uint64_t blocks = (capacity + MKE_BLOCK - 1) / MKE_BLOCK;
-  hipLaunchKernelGGL(k_filter_from_table, dim3((unsigned)blocks), dim3(MKE_BLOCK), 0, st, keys, capacity, f.bits, f.shift);
+  hipLaunchKernelGGL(k_filter_from_table, dim3((unsigned)blocks), dim3(MKE_BLOCK), 0, st, keys, capacity, f.bits, f.shift,
+                     f.lbits, f.lshift);
   const int rc = check_launch("k_filter_from_table");
   if (rc) { (void)hipFree(f.bits); return rc; }
   g_filters.emplace(keys, f);
@@ -344,6 +573,39 @@ int validate_side(const mke_kg_side& sd, int neg_per_pos) {
   return MKE_OK;
 }
 
+// The lean form of the fast kernels (`sampler_lean`): same grid, same group sizes.
+template <bool CODES, bool O32>
+static void launch_lean_gs(int gs, dim3 grid, dim3 blk, hipStream_t st, const LeanParams& q) {
+  if (gs == 16) hipLaunchKernelGGL((k_neg_sample_lean<16, CODES, O32>), grid, blk, 0, st, q);
+  else if (gs == 32) hipLaunchKernelGGL((k_neg_sample_lean<32, CODES, O32>), grid, blk, 0, st, q);
+  else hipLaunchKernelGGL((k_neg_sample_lean<64, CODES, O32>), grid, blk, 0, st, q);
+}
+// LEAN_BLOCKS_PER_CU workgroups for every CU of the current device.
+static int64_t lean_resident_blocks() {
+  static int cus[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); return 2048; }
+  if (cus[dev] == 0) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) { (void)hipGetLastError(); n = 256; }
+    cus[dev] = n;
+  }
+  return (int64_t)cus[dev] * LEAN_BLOCKS_PER_CU;
+}
+static int launch_neg_sample_lean(const SampleParams& p, const uint32_t* const* lbits, const int* lshift, bool codes, hipStream_t st) {
+  const LeanParams q{p, {lbits[0], lbits[1]}, {lshift[0], lshift[1]}};
+  const int gs = p.npp <= 15 ? 16 : (p.npp <= 32 ? 32 : 64);
+  const int64_t pos_per_block = (MKE_BLOCK / 64) * (64 / gs);
+  int64_t blocks = (p.n_pos + pos_per_block - 1) / pos_per_block;
+  const int64_t resident = lean_resident_blocks();
+  if (blocks > resident) blocks = resident;   // the kernel strides by its grid
+  const dim3 grid((unsigned)blocks), blk(MKE_BLOCK);
+  const bool o32 = sampler_o32_fits(p.n_pos, p.npp, p.side[0].n_ent, p.side[1].n_ent);
+  if (codes) { if (o32) launch_lean_gs<true, true>(gs, grid, blk, st, q); else launch_lean_gs<true, false>(gs, grid, blk, st, q); }
+  else { if (o32) launch_lean_gs<false, true>(gs, grid, blk, st, q); else launch_lean_gs<false, false>(gs, grid, blk, st, q); }
+  return check_launch("k_neg_sample_lean");
+}
+
 int launch_neg_sample(const int32_t* pos_h, const int32_t* pos_r, const int32_t* pos_t, int64_t n_pos, int64_t pos_offset,
                       const int32_t* pos_index,
                       const uint8_t* pos_kg, const mke_kg_side* sides, int neg_per_pos, int max_try, uint32_t seed_lo,
@@ -354,13 +616,18 @@ int launch_neg_sample(const int32_t* pos_h, const int32_t* pos_r, const int32_t*
   p.npp = neg_per_pos; p.max_try = max_try;
   p.side[0] = sides[0];
   p.side[1] = pos_kg ? sides[1] : sides[0];
+  const uint32_t* lbits[2];
+  int lshift[2];
   for (int k = 0; k < 2; ++k) {       // a set without a filter (or with one of another capacity) is probed directly
-    const TripleFilter f = p.side[k].known_keys ? filter_lookup(p.side[k].known_keys, p.side[k].known_capacity) : TripleFilter{0, nullptr, 0};
+    const TripleFilter f = p.side[k].known_keys ? filter_lookup(p.side[k].known_keys, p.side[k].known_capacity) : TripleFilter{0, nullptr, 0, nullptr, 0};
     p.filter[k] = f.bits;
     p.filter_shift[k] = f.shift;
+    lbits[k] = f.lbits;
+    lshift[k] = f.lshift;
   }
   p.seed_lo = seed_lo; p.seed_hi = seed_hi; p.sid = stream_id;
   p.nh = neg_h; p.nr = neg_r; p.nt = neg_t;
+  if (tune_sampler_fast() && tune_sampler_lean()) return launch_neg_sample_lean(p, lbits, lshift, codes, st);
   // lanes per positive: 16 (four positives per wavefront; fast form only, which needs an idle lane: neg_per_pos <= 15), 32, 64
   const int gs = (tune_sampler_fast() && neg_per_pos <= 15) ? 16 : (neg_per_pos <= 32 ? 32 : 64);
   const int64_t pos_per_block = (MKE_BLOCK / 64) * (64 / gs);
@@ -484,12 +751,12 @@ extern "C" int mke_tripleset_build(const int32_t* h, const int32_t* r, const int
   if (rc) return rc;
   const int64_t blocks = (n + MKE_BLOCK - 1) / MKE_BLOCK;
   hipLaunchKernelGGL(k_tripleset_build, dim3((unsigned)blocks), dim3(MKE_BLOCK), 0, (hipStream_t)stream, h, r, t, n,
-                     keys, capacity, f.bits, f.shift);
+                     keys, capacity, f.bits, f.shift, f.lbits, f.lshift);
   return check_launch("k_tripleset_build");
 }
 
 extern "C" int64_t mke_tripleset_filter_bytes(const uint64_t* keys, uint64_t capacity) {
-  const mke::TripleFilter f = keys ? mke::filter_lookup(keys, capacity) : mke::TripleFilter{0, nullptr, 0};
+  const mke::TripleFilter f = keys ? mke::filter_lookup(keys, capacity) : mke::TripleFilter{0, nullptr, 0, nullptr, 0};
   return f.bits ? (int64_t)1 << (64 - f.shift - 3) : 0;
 }
 
