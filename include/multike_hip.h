@@ -64,7 +64,8 @@ const char* mke_last_error(void);
 #define MKE_TUNE_DEFAULT (-2)
 typedef struct mke_tuning {
   int score_splits, score_half_groups, score_offsets32, score_lane_ids, count_in_score, update_chunk, oc_score_quarter,
-      attr_fused_bwd, sampler_fast, neg_codes, sampler_codes, sampler_lean;
+      attr_fused_bwd, retired_sampler_fast /* ignored; kept so that no field moves */, neg_codes, sampler_codes,
+      retired_sampler_lean /* ignored; kept so that no field moves */;
   int reserved[4];   /* MKE_TUNE_DEFAULT */
 } mke_tuning;
 int mke_tuning_init(mke_tuning* t);   /* every field = MKE_TUNE_DEFAULT */
@@ -80,14 +81,6 @@ int mke_tuning_init(mke_tuning* t);   /* every field = MKE_TUNE_DEFAULT */
  *   "oc_em_keys64"  : mke_oc_em_plan sorts its (step, row) keys as 64-bit words even when n_steps * (n_local + n_rel) < 2^32 (0, the
  *                     default: 32-bit words whenever they fit) — the instantiation a KG with >= 2^32 (step, row) pairs per epoch takes;
  *                     same lists bit for bit
- *   "sampler_fast"  : mke_neg_sample*: 1 (default) = a round's coin block evaluated in the idle last lane of the group's draw
- *                     evaluation and duplicates among first draws found through an LDS table; 0 = separate coin evaluation and
- *                     a shuffle loop.  Same Philox stream, same output bit for bit
- *   "sampler_lean"  : mke_neg_sample* in the fast form: 1 (default) = a wavefront whose positives are of one KG reads that side
- *                     through scalar loads, 32-bit offsets where the launch's sizes allow, and a known-triple prefilter of its own
- *                     (three bits of one word per key, indexed by a 32-bit mix; a second bit array of the same size beside the
- *                     fast form's, kept by mke_tripleset_build); 0 = the fast form's kernels as they were.  Same Philox stream,
- *                     same output bit for bit; no effect with sampler_fast = 0
  *   "deterministic" : 1 = the host side (tables.StepEngine) takes the deterministic path below (read by the caller; the
  *                     kernels themselves are selected by which entry point is called)
  *   "score_half_groups" : largest neg_per_pos for which mke_triple_score_fwd_bwd scores TWO groups per wavefront (one per
@@ -395,12 +388,11 @@ int mke_tripleset_build(
 
 /* Prefilter of the set.  The sampler asks a set of C2's size (8 MB of slots per KG) 23 M times per epoch and almost
  * always hears "not known", each time at the price of one random read past the L2.  So mke_tripleset_build also keeps a
- * one-hash Bloom filter per set (8 bits per slot, at most 4 MB): device memory that the LIBRARY owns, found by
- * (keys, capacity) on the host when mke_neg_sample / mke_neg_sample_at launch.  A clear bit answers "not known" from L2;
- * a set bit falls through to the table, so the sampler's output does not depend on whether a set has a filter.
- * The lean form of the sampler ("sampler_lean") reads a second bit array of the same size in the same allocation, indexed by
- * a 32-bit mix of (h, r, t) with three bits of one word per key; both arrays are written by the same launches, so everything
- * below holds for the pair.
+ * Bloom filter per set (8 bits per slot, at most 4 MB): device memory that the LIBRARY owns, found by (keys, capacity) on
+ * the host when mke_neg_sample / mke_neg_sample_at launch.  A key sets three bits of one 32-bit word, word and bits picked by a
+ * 32-bit mix of (h, r, t).  A clear bit among the three answers "not known" from L2; three set bits fall through to the table
+ * (0.9 % of the candidates at the C2 shape, profiles/r25_sampler_issue.md; unmeasured at C5), so the sampler's output does not
+ * depend on whether a set has a filter.
  *
  * What keeps the filter in step with the set: mke_tripleset_build writes both, on the same stream.  The first build call
  * on a table creates the filter from whatever the table already holds plus the new keys; every later call adds its keys to
@@ -412,8 +404,7 @@ int mke_tripleset_build(
  * safe without it: a filter of another capacity is dropped, one of the same capacity keeps the old set's bits and only
  * filters less.)  mke_tripleset_forget frees the filter after waiting for the device; unknown addresses are ignored. */
 int mke_tripleset_forget(const uint64_t* keys);
-/* Bytes of the filter the sampler would use for (keys, capacity) (one form's bit array; the library holds two of that size);
- * 0 = none: the set is probed directly. */
+/* Bytes of the filter the sampler would use for (keys, capacity); 0 = none: the set is probed directly. */
 int64_t mke_tripleset_filter_bytes(const uint64_t* keys, uint64_t capacity);
 
 /* Membership query (used by tests and by the host-side mirror of the filter): out[i] = 1 if present. */

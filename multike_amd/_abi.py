@@ -78,10 +78,10 @@ class mke_tuning(C.Structure):
         ("update_chunk", C.c_int),
         ("oc_score_quarter", C.c_int),
         ("attr_fused_bwd", C.c_int),
-        ("sampler_fast", C.c_int),
+        ("retired_sampler_fast", C.c_int),
         ("neg_codes", C.c_int),
         ("sampler_codes", C.c_int),
-        ("sampler_lean", C.c_int),
+        ("retired_sampler_lean", C.c_int),
         ("reserved", C.c_int * 4),
     ]
 

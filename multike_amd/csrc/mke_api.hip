@@ -37,8 +37,6 @@ int g_neg_codes = 1;         // runner: one code word per negative baked when a 
 int g_sampler_codes = 1;     // runner, code-word chunks: the sampler writes code words, the bake runs on them in place, no id arrays (0: ids, then mke_neg_codes)
 int g_update_chunk = 0;      // rows per wavefront of the row-update kernel on large tables: 0 = by table size, 16, 64
 int g_deterministic = 0;     // fixed-order gradient reduction (parity / debugging mode)
-int g_sampler_fast = 1;      // mke_sampler.hip: coin block in the draw evaluation's idle lane, LDS duplicate test (0: the earlier form)
-int g_sampler_lean = 1;      // mke_sampler.hip: wave-uniform side, 32-bit offsets, 32-bit prefilter mix in the fast form (0: the fast form as it was)
 int g_attr_fused_bwd = 1;    // mke_attr_cnn.hip: dflat product inside the convolution-backward launch, dW on rider blocks (every dim <= 80)
 int g_oc_em_keys64 = 0;      // mke_oc_em.hip: sort the epoch's (step, row) keys as 64-bit words even when they fit 32 bits (the path large KGs take)
 int g_oc_score_quarter = -1; // mke_oc.hip: quarter-wave per positive in the owner-computes score kernel: -1 = by shape, 0 / 1
@@ -102,16 +100,6 @@ extern "C" int mke_set_option(const char* name, int value, int* old_value) {
   if (!strcmp(name, "attr_fused_bwd")) {
     if (old_value) *old_value = mke::g_attr_fused_bwd;
     mke::g_attr_fused_bwd = value != 0;
-    return MKE_OK;
-  }
-  if (!strcmp(name, "sampler_fast")) {
-    if (old_value) *old_value = mke::g_sampler_fast;
-    mke::g_sampler_fast = value != 0;
-    return MKE_OK;
-  }
-  if (!strcmp(name, "sampler_lean")) {
-    if (old_value) *old_value = mke::g_sampler_lean;
-    mke::g_sampler_lean = value != 0;
     return MKE_OK;
   }
   if (!strcmp(name, "oc_em_keys64")) {

@@ -136,7 +136,7 @@ struct TuningScope {
   ~TuningScope() { tl_tuning = prev; }
 };
 extern int g_score_splits, g_score_half_max, g_score_o32, g_score_lane_ids, g_count_in_score, g_update_chunk, g_oc_score_quarter,
-    g_attr_fused_bwd, g_sampler_fast, g_neg_codes, g_sampler_codes, g_sampler_lean;
+    g_attr_fused_bwd, g_neg_codes, g_sampler_codes;
 #define MKE_TUNE(field, dflt) ((mke::tl_tuning && mke::tl_tuning->field != MKE_TUNE_DEFAULT) ? mke::tl_tuning->field : (dflt))
 inline int tune_score_splits() { const int v = MKE_TUNE(score_splits, g_score_splits); return v < 0 ? 0 : v; }
 inline int tune_score_half_max() { const int v = MKE_TUNE(score_half_groups, g_score_half_max); return v < 0 ? -1 : (v > 64 ? 64 : v); }
@@ -158,8 +158,6 @@ int launch_neg_codes(const int32_t* pos_h, const int32_t* pos_r, const int32_t* 
                      int step_end, int64_t pos_begin, int64_t pos_end, const int32_t* neg_h, const int32_t* neg_r, const int32_t* neg_t,
                      int neg_per_pos, int64_t n_ent, uint32_t* bits, int32_t* neg_code, hipStream_t st);
 bool neg_codes_in_lds(int64_t n_ent);   // the bake is one launch, a step's bitmap row in the LDS (else device-scope atomics: slower than what it saves)
-inline int tune_sampler_fast() { return MKE_TUNE(sampler_fast, g_sampler_fast) != 0; }
-inline int tune_sampler_lean() { return MKE_TUNE(sampler_lean, g_sampler_lean) != 0; }   // the lean form of the fast kernels (mke_sampler.hip)
 // runner, code-word chunks only: the sampler writes the code words themselves and the bake works on them in place
 inline int tune_sampler_codes() { return MKE_TUNE(sampler_codes, g_sampler_codes) != 0; }
 // mke_codes.hip: the same rows and MKE_CODE_EXCL from the words the sampler's code-word form left in neg_code (rows in the LDS only)
@@ -248,6 +246,13 @@ __host__ __device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t 
 // known-triple key: h<<38 | t<<12 | r
 __host__ __device__ __forceinline__ uint64_t triple_key(uint32_t h, uint32_t r, uint32_t t) {
   return ((uint64_t)h << 38) | ((uint64_t)t << 12) | (uint64_t)r;
+}
+// the ids as a key holds them: 26 / 12 / 26 bits
+struct TripleIds {
+  uint32_t h, r, t;
+};
+__host__ __device__ __forceinline__ TripleIds triple_of_key(uint64_t key) {
+  return {(uint32_t)(key >> 38), (uint32_t)(key & 0xFFFu), (uint32_t)((key >> 12) & 0x3FFFFFFu)};
 }
 __host__ __device__ __forceinline__ uint64_t mix64(uint64_t x) {  // splitmix64 finaliser
   x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;

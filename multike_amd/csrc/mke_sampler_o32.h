@@ -1,11 +1,11 @@
-// mke_sampler_o32.h — which instantiation of the lean sampler a launch takes (plain C++, no HIP: the host test of
-// tests/test_sampler_lean_gpu.py compiles it by itself).
+// mke_sampler_o32.h — which instantiation of the sampler a launch takes (plain C++, no HIP: the host test of
+// tests/test_sampler_exact_gpu.py compiles it by itself).
 #pragma once
 #include <stdint.h>
 
 namespace mke {
 
-// The lean sampler forms byte offsets in 32 bits (on scalar bases) for the epoch's positives, the output arrays, a side's
+// The sampler's O32 instantiation forms byte offsets in 32 bits (on scalar bases) for the epoch's positives, the output arrays, a side's
 // entity list and the filter.  That is legal when every such offset stays below 2^32:
 //   outputs       n_pos * neg_per_pos int32 words  -> n_pos * neg_per_pos <= 2^30 (the positives, n_pos words, are fewer)
 //   entity lists  n_ent int32 words per side       -> n_ent <= 2^30

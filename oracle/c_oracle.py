@@ -30,7 +30,7 @@ def lib():
             fn = getattr(_lib, "mko_relation_step_" + suf)
             fn.restype = C.c_double
             getattr(_lib, "mko_relation_step_mt_" + suf).restype = C.c_double
-        _lib.mko_neg_sample.restype = C.c_int
+        _lib.mko_neg_sample_at.restype = C.c_int
         _lib.mko_set_threads.restype = None
         _lib.mko_set_insert.restype = None
     return _lib
@@ -123,19 +123,22 @@ class TripleSet:
 
 
 def neg_sample(pos_h, pos_r, pos_t, want, n_all, ent_lo=0, ent_list=None, cand_table=None, cand_valid=None,
-               known: TripleSet | None = None, seed=(0, 0), stream_id=0, pos_offset=0, max_try=10):
+               known: TripleSet | None = None, seed=(0, 0), stream_id=0, pos_offset=0, max_try=10, pos_index=None):
+    """pos_index: the stream position of every positive (as mke_neg_sample_at takes it); None = pos_offset + i."""
     ph, pr, pt = (np.ascontiguousarray(a, np.int32) for a in (pos_h, pos_r, pos_t))
     n = len(ph)
+    pi = None if pos_index is None else np.ascontiguousarray(pos_index, np.int32)
+    assert pi is None or len(pi) == n
     nh = np.zeros(n * want, np.int32)
     nr = np.zeros(n * want, np.int32)
     nt = np.zeros(n * want, np.int32)
     el = None if ent_list is None else np.ascontiguousarray(ent_list, np.int32)
     ct = None if cand_table is None else np.ascontiguousarray(cand_table, np.int32)
     cv = None if cand_valid is None else np.ascontiguousarray(cand_valid, np.uint8)
-    rc = lib().mko_neg_sample(_p(ph), _p(pr), _p(pt), C.c_int64(n), C.c_int64(pos_offset), C.c_int(want),
-                              C.c_int(max_try), _p(el), C.c_int32(ent_lo), C.c_int32(n_all), _p(ct), _p(cv),
-                              C.c_int32(0 if ct is None else ct.shape[1]), _p(None if known is None else known.keys),
-                              C.c_uint64(0 if known is None else known.cap), C.c_uint32(seed[0]), C.c_uint32(seed[1]),
-                              C.c_uint32(stream_id), _p(nh), _p(nr), _p(nt))
+    rc = lib().mko_neg_sample_at(_p(ph), _p(pr), _p(pt), C.c_int64(n), C.c_int64(pos_offset), _p(pi), C.c_int(want),
+                                 C.c_int(max_try), _p(el), C.c_int32(ent_lo), C.c_int32(n_all), _p(ct), _p(cv),
+                                 C.c_int32(0 if ct is None else ct.shape[1]), _p(None if known is None else known.keys),
+                                 C.c_uint64(0 if known is None else known.cap), C.c_uint32(seed[0]), C.c_uint32(seed[1]),
+                                 C.c_uint32(stream_id), _p(nh), _p(nr), _p(nt))
     assert rc == 0
     return nh, nr, nt

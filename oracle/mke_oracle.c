@@ -88,16 +88,17 @@ static inline int set_has(const uint64_t* keys, uint64_t cap, uint64_t k) {
   }
 }
 
-int mko_neg_sample(const int32_t* ph, const int32_t* pr, const int32_t* pt, int64_t n_pos, int64_t pos_offset, int want,
-                   int max_try, const int32_t* ent_list, int32_t ent_lo, int32_t n_all, const int32_t* cand_table,
-                   const uint8_t* cand_valid, int32_t cand_k, const uint64_t* keys, uint64_t cap, uint32_t k0,
-                   uint32_t k1, uint32_t sid, int32_t* nh, int32_t* nr, int32_t* nt) {
+/* positive i is stream position pos_index[i] (the device's mke_neg_sample_at), or pos_offset + i when pos_index is NULL */
+int mko_neg_sample_at(const int32_t* ph, const int32_t* pr, const int32_t* pt, int64_t n_pos, int64_t pos_offset,
+                      const int32_t* pos_index, int want, int max_try, const int32_t* ent_list, int32_t ent_lo, int32_t n_all,
+                      const int32_t* cand_table, const uint8_t* cand_valid, int32_t cand_k, const uint64_t* keys, uint64_t cap,
+                      uint32_t k0, uint32_t k1, uint32_t sid, int32_t* nh, int32_t* nr, int32_t* nt) {
   if (want > 64) return -1;
 #pragma omp parallel for schedule(static) num_threads(mko_threads > 0 ? mko_threads : 1)
   for (int64_t i = 0; i < n_pos; ++i) {
     uint32_t fin[64];
     const int32_t h = ph[i], r = pr[i], t = pt[i];
-    const uint32_t gi = (uint32_t)(i + pos_offset);
+    const uint32_t gi = pos_index ? (uint32_t)pos_index[i] : (uint32_t)(i + pos_offset);
     int got = 0;
     for (int rnd = 0; rnd < max_try && got < want; ++rnd) {
       const int need = want - got;
@@ -127,4 +128,12 @@ int mko_neg_sample(const int32_t* ph, const int32_t* pr, const int32_t* pt, int6
     }
   }
   return 0;
+}
+
+int mko_neg_sample(const int32_t* ph, const int32_t* pr, const int32_t* pt, int64_t n_pos, int64_t pos_offset, int want,
+                   int max_try, const int32_t* ent_list, int32_t ent_lo, int32_t n_all, const int32_t* cand_table,
+                   const uint8_t* cand_valid, int32_t cand_k, const uint64_t* keys, uint64_t cap, uint32_t k0,
+                   uint32_t k1, uint32_t sid, int32_t* nh, int32_t* nr, int32_t* nt) {
+  return mko_neg_sample_at(ph, pr, pt, n_pos, pos_offset, NULL, want, max_try, ent_list, ent_lo, n_all, cand_table, cand_valid,
+                           cand_k, keys, cap, k0, k1, sid, nh, nr, nt);
 }

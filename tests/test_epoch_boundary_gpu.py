@@ -54,20 +54,14 @@ def c2():
     return kgs, known, filt, plain, bat
 
 
-@pytest.mark.parametrize("fast", [1, 0])
 @pytest.mark.parametrize("N", [1, 10, 15, 25, 32, 64])
-def test_filtered_sampler_equals_unfiltered_on_the_c2_epoch(c2, N, fast):
-    from multike_amd import _lib
+def test_filtered_sampler_equals_unfiltered_on_the_c2_epoch(c2, N):
     from multike_amd.sampling import sample_negatives
     kgs, known, filt, plain, bat = c2
     pos = (bat.pos_h, bat.pos_r, bat.pos_t)
-    old = _lib.set_option("sampler_fast", fast)
-    try:
-        a = sample_negatives(pos, filt[0], N, seed=(1234, 0), stream_id=2, side1=filt[1], pos_kg=bat.pos_kg)
-        b = sample_negatives(pos, plain[0], N, seed=(1234, 0), stream_id=2, side1=plain[1], pos_kg=bat.pos_kg)
-    finally:
-        _lib.set_option("sampler_fast", old)
-    _assert_same_negatives(a, b, f"N={N} fast={fast}")
+    a = sample_negatives(pos, filt[0], N, seed=(1234, 0), stream_id=2, side1=filt[1], pos_kg=bat.pos_kg)
+    b = sample_negatives(pos, plain[0], N, seed=(1234, 0), stream_id=2, side1=plain[1], pos_kg=bat.pos_kg)
+    _assert_same_negatives(a, b, f"N={N}")
     # and the membership test did its work: with max_try = 10 a known triple would have to be drawn ten rounds in a row
     got = known[0].contains(a[0], a[1], a[2]) | known[1].contains(a[0], a[1], a[2])
     assert int(got.sum()) == 0
@@ -127,14 +121,9 @@ def test_filtered_sampler_equals_unfiltered_on_a_dense_kg(N, max_try, near):
         for s in sides:
             s.set_neighbours(tbl, valid)
     pos = tuple(torch.as_tensor(np.ascontiguousarray(tr[:, k]), device="cuda") for k in range(3))
-    for fast in (1, 0):
-        old = _lib.set_option("sampler_fast", fast)
-        try:
-            a = sample_negatives(pos, sides[0], N, seed=(3, 4), stream_id=1, max_try=max_try)
-            b = sample_negatives(pos, sides[1], N, seed=(3, 4), stream_id=1, max_try=max_try)
-        finally:
-            _lib.set_option("sampler_fast", old)
-        _assert_same_negatives(a, b, f"dense N={N} max_try={max_try} near={near} fast={fast}")
+    a = sample_negatives(pos, sides[0], N, seed=(3, 4), stream_id=1, max_try=max_try)
+    b = sample_negatives(pos, sides[1], N, seed=(3, 4), stream_id=1, max_try=max_try)
+    _assert_same_negatives(a, b, f"dense N={N} max_try={max_try} near={near}")
     if max_try == 10 and not near:            # the setting is what it claims: many first-round candidates were known
         one = sample_negatives(pos, sides[1], N, seed=(3, 4), stream_id=1, max_try=1)
         assert float(ks.contains(*one).float().mean()) > 0.5

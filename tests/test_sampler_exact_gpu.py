@@ -1,9 +1,9 @@
-"""The lean form of the fast sampler kernels (`sampler_lean`, mke_sampler.hip): wave-uniform side, 32-bit offsets, a prefilter
-of its own in front of the known-triple table, a strided grid.  It is a performance option: every case here is exact equality
-of integer arrays, against the fast form as it was (`sampler_lean` = 0, same process) for every positive, and against the Python
-specification (oracle/sampler_oracle.py) for a spread of positives (the specification is a Python loop per draw).  Shapes are
-small and chosen for where the new paths can go wrong: wavefronts of two KGs, sides of different form, populations that force
-the duplicate fix-up, dense sets that force later rounds, sets whose filter came late."""
+"""The epoch sampler (k_neg_sample, mke_sampler.hip): group shapes of 16 / 32 / 64 lanes, wave-uniform side with a double pass for
+wavefronts of two KGs, 32-bit offsets, the prefilter in front of the known-triple table, a strided grid.  Every case here is
+exact equality of integer arrays: against the C restatement of the specification (oracle/mke_oracle.c) for every output word,
+and against the Python specification itself (oracle/sampler_oracle.py) for a spread of positives (it is a Python loop per
+draw).  Shapes are small and chosen for where the kernel's paths can go wrong: wavefronts of two KGs, sides of different form,
+populations that force the duplicate fix-up, dense sets that force later rounds, sets whose filter came late."""
 import os
 import shutil
 import subprocess
@@ -12,7 +12,10 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import sampler_oracle as so
+from oracle import c_oracle as co
+from sampler_cases import Side as _Side
+from sampler_cases import dev as _dev
+from sampler_cases import expected_negatives
 
 pytestmark = pytest.mark.gpu
 
@@ -20,33 +23,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CODE_HEAD, CODE_FAST = 1 << 26, 1 << 27
 
 
-def _dev(a, dtype=np.int32):
-    return torch.as_tensor(np.ascontiguousarray(a, dtype=dtype), device="cuda")
+def _positions(n, at, offset=11):
+    """Stream position of every positive: the epoch positions 3 i + 5 that `at` launches pass, else pos_offset + i."""
+    return 3 * np.arange(n) + 5 if at else np.arange(n) + offset
 
 
-class _Side:
-    """One KG's sampling context, on the host (for the specification) and on the device."""
-
-    def __init__(self, ents, known=None, cand_table=None, cand_valid=None):
-        from multike_amd.sampling import KGSide, KnownTripleSet
-        self.ents = np.ascontiguousarray(ents, dtype=np.int64)
-        self.contiguous = bool(np.array_equal(self.ents, np.arange(self.ents[0], self.ents[0] + len(self.ents))))
-        self.known_np = None if known is None else np.asarray(known, dtype=np.int32)
-        self.known_py = None if known is None else {tuple(x) for x in self.known_np.tolist()}
-        self.cand_table, self.cand_valid = cand_table, cand_valid
-        self.ks = None if known is None else KnownTripleSet(*(_dev(self.known_np[:, k]) for k in range(3)))
-        self.dev = KGSide(self.ents, self.ks)
-        if cand_table is not None:
-            self.dev.set_neighbours(_dev(cand_table), None if cand_valid is None else _dev(cand_valid, np.uint8))
-
-    def spec(self, h, r, t, N, seed, stream_id, gi, max_try):
-        return so.philox_negatives([h], [r], [t], N, len(self.ents), ent_lo=int(self.ents[0]) if self.contiguous else 0,
-                                   ent_list=None if self.contiguous else self.ents, cand_table=self.cand_table,
-                                   cand_valid=self.cand_valid, known=self.known_py, seed=seed, stream_id=stream_id, pos_offset=gi,
-                                   max_try=max_try)
-
-
-def _sample(pos, kg, sides, N, lean, codes, at, max_try, seed, sid, offset=11):
+def _sample(pos, kg, sides, N, codes, at, max_try, seed, sid, offset=11):
     """Device output as numpy arrays: (neg_h, neg_r, neg_t), or (code,) in the code-word form.  `at`: mke_neg_sample_at with the
     epoch positions 3 i + 5, else mke_neg_sample with pos_offset."""
     from multike_amd import _lib
@@ -55,21 +37,17 @@ def _sample(pos, kg, sides, N, lean, codes, at, max_try, seed, sid, offset=11):
     dpos = tuple(_dev(x) for x in pos)
     dkg = None if kg is None else _dev(kg, np.uint8)
     sa = side_array(sides[0].dev, sides[-1].dev)
-    index = _dev(3 * np.arange(n) + 5) if at else None
-    old = _lib.set_option("sampler_lean", lean)
-    try:
-        if codes:
-            out = (torch.full((n * N,), -1, dtype=torch.int32, device="cuda"),)
-            _lib.neg_sample_codes(dpos, offset, index, dkg, sa, N, max_try, seed, sid, out[0])
+    index = _dev(_positions(n, True)) if at else None
+    if codes:
+        out = (torch.full((n * N,), -1, dtype=torch.int32, device="cuda"),)
+        _lib.neg_sample_codes(dpos, offset, index, dkg, sa, N, max_try, seed, sid, out[0])
+    else:
+        out = tuple(torch.full((n * N,), -1, dtype=torch.int32, device="cuda") for _ in range(3))
+        if at:
+            _lib.neg_sample_at(dpos, index, dkg, sa, N, max_try, seed, sid, out)
         else:
-            out = tuple(torch.full((n * N,), -1, dtype=torch.int32, device="cuda") for _ in range(3))
-            if at:
-                _lib.neg_sample_at(dpos, index, dkg, sa, N, max_try, seed, sid, out)
-            else:
-                _lib.neg_sample(dpos, offset, dkg, sa, N, max_try, seed, sid, out)
-        torch.cuda.synchronize()
-    finally:
-        _lib.set_option("sampler_lean", old)
+            _lib.neg_sample(dpos, offset, dkg, sa, N, max_try, seed, sid, out)
+    torch.cuda.synchronize()
     return tuple(o.cpu().numpy() for o in out)
 
 
@@ -99,19 +77,24 @@ def _spread(n, count=40):
 
 def _check(pos, kg, sides, N, max_try=10, seed=(123, 456), sid=7, forms=((False, False), (True, False), (False, True), (True, True)),
            spec_count=40):
-    """lean == the fast form as it was, everywhere; == the specification on a spread of positives.  forms: (codes, at) pairs."""
+    """device == the C restatement, every output word; == the Python specification on a spread of positives.  forms: (codes, at)
+    pairs."""
     n = len(pos[0])
     rows = np.array(_spread(n, spec_count))
     for at in sorted({a for _, a in forms}):
         spec = _spec_rows(pos, kg, sides, N, at, max_try, seed, sid, rows)
+        ids = expected_negatives(pos, kg, sides, N, _positions(n, at), max_try, seed, sid)
+        for a, w in zip(ids, spec):
+            assert np.array_equal(a[rows], w), f"C restatement != specification: N={N} at={at}"
         for codes in sorted({c for c, a in forms if a == at}):
-            lean = _sample(pos, kg, sides, N, 1, codes, at, max_try, seed, sid)
-            plain = _sample(pos, kg, sides, N, 0, codes, at, max_try, seed, sid)
-            for a, b in zip(lean, plain):
-                assert np.array_equal(a, b), f"lean != fast form: N={N} codes={codes} at={at}: {int((a != b).sum())} of {a.size} words"
+            got = _sample(pos, kg, sides, N, codes, at, max_try, seed, sid)
+            want = (_codes_of(ids, pos, np.arange(n)),) if codes else ids
+            for a, w in zip(got, want):
+                a = a.reshape(n, N)
+                assert np.array_equal(a, w), f"device != C restatement: N={N} codes={codes} at={at}: {int((a != w).sum())} of {a.size} words"
             want = (_codes_of(spec, pos, rows),) if codes else spec
-            for a, w in zip(lean, want):
-                assert np.array_equal(a.reshape(n, N)[rows], w), f"lean != specification: N={N} codes={codes} at={at}"
+            for a, w in zip(got, want):
+                assert np.array_equal(a.reshape(n, N)[rows], w), f"device != specification: N={N} codes={codes} at={at}"
 
 
 def _triples(rng, ents, n_rel, count):
@@ -153,13 +136,17 @@ def test_every_group_size_both_forms_both_entry_points(two_kgs, N):
 
 @pytest.mark.parametrize("N", [1, 25, 40])
 def test_a_launch_larger_than_the_grid_cap(two_kgs, N):
-    """The lean kernel strides by a capped grid (32 workgroups per CU: 8,192 on the MI355X = 131,072 / 65,536 / 32,768 positives
+    """The kernel strides by a capped grid (32 workgroups per CU: 8,192 on the MI355X = 131,072 / 65,536 / 32,768 positives
     of the 16- / 32- / 64-lane form).  150,001 positives pass the cap in every form, so wavefronts take a second, partly
     filled, iteration."""
     rng, ents, known, sides = two_kgs
     n = 150_001
     kg = _runner_kg(n)
-    _check(_positives(known, kg, n), kg, sides, N, forms=((True, False), (False, True)), spec_count=24)
+    co.set_threads(16)                  # N = 40: six million draws of the C restatement; its output does not depend on the threads
+    try:
+        _check(_positives(known, kg, n), kg, sides, N, forms=((True, False), (False, True)), spec_count=24)
+    finally:
+        co.set_threads(1)               # its default
 
 
 @pytest.mark.parametrize("n", [1, 2, 3, 5, 129, 4095])
@@ -235,15 +222,15 @@ def test_later_rounds_and_the_keep_anyway_rule_on_a_dense_kg(N, max_try):
     pos = _positives((k0, k1), kg, n)
     _check(pos, kg, sides, N, max_try=max_try, forms=((False, False), (True, True)), spec_count=30)
     if max_try == 1:                   # the setting is what it claims: most first-round candidates are known triples
-        ids = _sample(pos, kg, sides, N, 1, False, False, 1, (123, 456), 7)
+        ids = _sample(pos, kg, sides, N, False, False, 1, (123, 456), 7)
         known = {tuple(x) for x in np.concatenate([k0, k1]).tolist()}
         assert np.mean([tuple(x) in known for x in np.stack(ids, 1)[:2000].tolist()]) > 0.5
 
 
-def test_a_set_built_before_and_after_its_filters_exist():
-    """Both filters of a set (the fast form's and the lean form's) are created late, from a table that already holds keys
-    (k_filter_from_table has only the stored key to go by), and then extended by a second build: the lean form must keep
-    answering what the unfiltered table answers."""
+def test_a_set_built_before_and_after_its_filter_exists():
+    """The filter of a set is created late, from a table that already holds keys (k_filter_from_table has only the stored key to
+    go by), and then extended by a second build: the sampler must keep answering what the table answers — the C restatement with
+    the first half of the triples known, then with both halves."""
     from multike_amd import _lib
     tr = _dense_kg(0, share=0.6, seed=2)
     half = len(tr) // 2
@@ -252,22 +239,22 @@ def test_a_set_built_before_and_after_its_filters_exist():
 
     def both(what):
         for N in (10, 25):
-            lean = _sample(pos, None, [side], N, 1, False, False, 3, (9, 9), 1)
-            plain = _sample(pos, None, [side], N, 0, False, False, 3, (9, 9), 1)
-            for a, b in zip(lean, plain):
-                assert np.array_equal(a, b), what
-        return lean
+            got = _sample(pos, None, [side], N, False, False, 3, (9, 9), 1)
+            want = expected_negatives(pos, None, [side], N, _positions(len(tr), False), 3, (9, 9), 1)
+            for a, w in zip(got, want):
+                assert np.array_equal(a.reshape(len(tr), N), w), what
+        return got
 
-    # a copy of the table that the library never built: no filter of either form, both kernels probe it directly
+    # a copy of the table that the library never built: no filter, the kernel probes it directly
     keys = side.ks.keys.clone()
     _lib.tripleset_forget(keys)
     assert _lib.tripleset_filter_bytes(keys) == 0
     owner, side.dev.known = side.ks, type("K", (), {"keys": keys})()
     first = both("no filter")
-    # the second half arrives through mke_tripleset_build: the filters are created now, from the first half + the second
+    # the second half arrives through mke_tripleset_build: the filter is created now, from the first half + the second
     _lib.tripleset_build(_dev(tr[half:, 0]), _dev(tr[half:, 1]), _dev(tr[half:, 2]), keys)
     assert _lib.tripleset_filter_bytes(keys) > 0
-    side.known_py = {tuple(x) for x in tr.tolist()}
+    side.set_host_known(tr)
     second = both("late filter")
     rows = np.array(_spread(len(tr), 30))
     spec = _spec_rows(pos, None, [side], 25, False, 3, (9, 9), 1, rows)

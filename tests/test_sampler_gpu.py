@@ -153,31 +153,29 @@ def test_sample_distinct_bit_exact_and_distinct():
     assert _lib.sample_distinct(5, 0, 3).shape == (3, 0)
 
 
-def test_fast_and_plain_kernel_forms_are_the_same_stream():
-    """`sampler_fast` (coin block in the draw evaluation's idle lane, LDS duplicate table, 16-lane groups) is a
-    performance option: the output is the plain form's, bit for bit, at every group shape, with and without the known-triple
-    filter and the truncated-sampling candidate table."""
+def test_every_group_shape_is_the_c_restatements_stream():
+    """The device output is the C restatement's (oracle/mke_oracle.c), bit for bit, for every positive, at every group shape
+    (16 / 32 / 64 lanes, with and without an idle lane for the coin block), with the known-triple set behind its prefilter,
+    with and without the truncated-sampling candidate table."""
     from gpu_util import dev_i32
-    from multike_amd import _lib
     from multike_amd.sampling import KGSide, KnownTripleSet, sample_negatives
     rng = np.random.default_rng(11)
     n, P = 700, 1999
     tri = np.stack([rng.integers(0, n, 6000), rng.integers(0, 9, 6000), rng.integers(0, n, 6000)], axis=1).astype(np.int32)
     ks = KnownTripleSet(dev_i32(tri[:, 0]), dev_i32(tri[:, 1]), dev_i32(tri[:, 2]))
+    cts = co.TripleSet(tri[:, 0], tri[:, 1], tri[:, 2])
     pos = tuple(dev_i32(tri[:P, k]) for k in range(3))
-    try:
-        for N in (1, 7, 15, 16, 25, 31, 32, 33, 63, 64):
-            for near in (False, True):
-                side = KGSide(np.arange(n), ks)
-                if near:
-                    K = 70
-                    tab = np.stack([rng.choice(n, K, replace=False) for _ in range(n)]).astype(np.int32)
-                    side.set_neighbours(dev_i32(tab), torch.as_tensor((np.arange(n) % 4 != 0).astype(np.uint8), device="cuda"))
-                outs = []
-                for fast in (0, 1):
-                    _lib.set_option("sampler_fast", fast)
-                    outs.append([x.cpu().numpy() for x in sample_negatives(pos, side, N, seed=(5, N), stream_id=2, pos_offset=31)])
-                for a, b in zip(*outs):
-                    assert np.array_equal(a, b), (N, near)
-    finally:
-        _lib.set_option("sampler_fast", 1)
+    for N in (1, 7, 15, 16, 25, 31, 32, 33, 63, 64):
+        for near in (False, True):
+            side = KGSide(np.arange(n), ks)
+            tab = valid = None
+            if near:
+                K = 70
+                tab = np.stack([rng.choice(n, K, replace=False) for _ in range(n)]).astype(np.int32)
+                valid = (np.arange(n) % 4 != 0).astype(np.uint8)
+                side.set_neighbours(dev_i32(tab), torch.as_tensor(valid, device="cuda"))
+            got = [x.cpu().numpy() for x in sample_negatives(pos, side, N, seed=(5, N), stream_id=2, pos_offset=31)]
+            exp = co.neg_sample(tri[:P, 0], tri[:P, 1], tri[:P, 2], N, n, cand_table=tab, cand_valid=valid, known=cts, seed=(5, N),
+                                stream_id=2, pos_offset=31)
+            for a, b in zip(got, exp):
+                assert np.array_equal(a, b), (N, near)

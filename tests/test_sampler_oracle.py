@@ -178,3 +178,41 @@ def test_invariants_hold_in_both():
             d = _draw(kind, which, 25)
             assert d["n_neg"] == 25 * d["n_pos"]
             assert d["repl"].min() >= 0 and d["repl"].max() < d["n_ent"]
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the C restatement (oracle/mke_oracle.c), the referee of the device tests, against the specification
+# ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("max_try", [1, 3])
+@pytest.mark.parametrize("side", ["list", "table_valid"])
+def test_c_restatement_at_explicit_positions_is_the_specification(side, max_try):
+    """`co.neg_sample(..., pos_index=...)` (mko_neg_sample_at: every positive at a stream position of its own, as the device's
+    mke_neg_sample_at takes them) == `philox_negatives` positive by positive, on an entity-list side and on a candidate-table side
+    with `cand_valid`, with a known set that holds most possible triples (later rounds, the unfiltered last round); and the
+    contiguous call is the case pos_index = pos_offset + arange."""
+    from oracle import c_oracle as co
+    rng = np.random.default_rng(26)
+    n_ent, n_rel, N, P = 48, 3, 25, 300
+    ents = rng.permutation(np.arange(1, 2 * n_ent, 2)) if side == "list" else np.arange(n_ent)
+    every = np.array([(h, r, t) for h in ents for r in range(n_rel) for t in ents], np.int32)
+    known = every[rng.random(len(every)) < 0.8]
+    pos = known[rng.integers(0, len(known), P)]
+    kw = dict(ent_lo=0, ent_list=ents) if side == "list" else dict(
+        ent_lo=0, cand_table=np.stack([rng.choice(n_ent, 30, replace=False) for _ in range(n_ent)]).astype(np.int32),
+        cand_valid=(np.arange(n_ent) % 3 != 0).astype(np.uint8))
+    common = dict(seed=(26, 7), stream_id=4, max_try=max_try, **kw)
+    known_c, known_py = co.TripleSet(known[:, 0], known[:, 1], known[:, 2]), {tuple(x) for x in known.tolist()}
+    pos_index = rng.permutation(5 * P)[:P] + 3                # distinct, unordered, not contiguous
+    got = co.neg_sample(pos[:, 0], pos[:, 1], pos[:, 2], N, n_ent, known=known_c, pos_index=pos_index, **common)
+    for i in range(P):
+        want = so.philox_negatives([pos[i, 0]], [pos[i, 1]], [pos[i, 2]], N, n_ent, known=known_py, pos_offset=int(pos_index[i]), **common)
+        for a, w in zip(got, want):
+            assert np.array_equal(a[i * N:(i + 1) * N], w), (side, max_try, i)
+    if max_try == 3:                                          # the workload does what it was built for: known triples leak only from the last round
+        leaked = np.mean([tuple(x) in known_py for x in np.stack(got, 1).tolist()])
+        assert 0 < leaked < 0.8
+    contiguous = co.neg_sample(pos[:, 0], pos[:, 1], pos[:, 2], N, n_ent, known=known_c, pos_offset=77, **common)
+    indexed = co.neg_sample(pos[:, 0], pos[:, 1], pos[:, 2], N, n_ent, known=known_c, pos_index=77 + np.arange(P), **common)
+    for a, b in zip(contiguous, indexed):
+        assert np.array_equal(a, b)
+    assert any(not np.array_equal(a, b) for a, b in zip(got, contiguous))     # the positions do matter

@@ -91,7 +91,7 @@ def test_a_plans_tuning_is_read_and_defaults_are_untouched():
             _lib.set_option("score_half_groups", old)
 
     base_l, base_e = epoch(None, -1)
-    for tuning, dflt in ((dict(score_half_groups=64, count_in_score=0), 0), (dict(score_half_groups=0, sampler_fast=0), 64)):
+    for tuning, dflt in ((dict(score_half_groups=64, count_in_score=0), 0), (dict(score_half_groups=0, sampler_codes=0), 64)):
         l, e = epoch(tuning, dflt)
         np.testing.assert_allclose(l, base_l, rtol=2e-6)
         np.testing.assert_allclose(e, base_e, rtol=1e-4, atol=2e-6)
@@ -99,3 +99,7 @@ def test_a_plans_tuning_is_read_and_defaults_are_untouched():
     assert t.score_splits == 3 and t.update_chunk == _lib.TUNE_DEFAULT and t.reserved[0] == _lib.TUNE_DEFAULT
     with pytest.raises(_lib.MultiKEHipError):
         _lib.tuning(no_such_knob=1)
+    with pytest.raises(_lib.MultiKEHipError):      # a retired knob is an unknown one, as a process default and in a plan
+        _lib.set_option("sampler_fast", 0)
+    with pytest.raises(_lib.MultiKEHipError):
+        _lib.tuning(sampler_fast=0)
