@@ -1,53 +1,37 @@
 """world_size-2 gloo test of the entity-row sharded trainer's exchange logic (ids out / rows back / gradients
 home / owner-side single update / relation all-reduce) with the oracle as the compute backend.  The sharded
 result must equal a single-process dense oracle run on the same global batches."""
-import os
-import socket
-
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
+import ranks
 from oracle import c_oracle as co
 from oracle import multike_oracle as mo
-
-
-def _free_port():
-    """A fresh rendezvous file for init_method="file://..." (a TCP port picked by bind-and-close can be taken again before the
-    workers listen on it: one EADDRINUSE in ~200 runs on the GPU boxes)."""
-    import tempfile
-    return tempfile.mktemp(prefix="mke_rdv_")
 
 
 N_REL, DIM, B, NEG, STEPS, SEED = 12, 20, 64, 5, 4, 7
 
 
-def _worker(rank, world, port, ret, N_ENT):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    dist.init_process_group("gloo", init_method=f"file://{port}", rank=rank, world_size=world)   # `port`: a rendezvous FILE (no TCP port to collide on)
-    try:
-        from multike_amd.distributed import ShardedRelationTrainer
-        from multike_amd.synthetic import SyntheticKGs
-        from oracle_backend import OracleBackend
-        kgs = SyntheticKGs(n_ent=N_ENT, n_rel=N_REL, seed=SEED)
-        rng = np.random.default_rng(SEED)
-        ent0 = mo.xavier_truncated_normal((N_ENT, DIM), rng).astype(np.float64)
-        rel0 = mo.xavier_truncated_normal((N_REL, DIM), rng).astype(np.float64)
-        tr = ShardedRelationTrainer(kgs, ent0, rel0, B, NEG, rank, world, seed=SEED, lr=0.05, backend=OracleBackend(),
-                                    device="cpu", dtype=torch.float64)
-        stats = []
-        tr.keep_stats = True
-        for i in range(STEPS):
-            tr.step(i)
-            stats.append(tr.stats())
-        full = tr.gather_entity_table().numpy()
-        loss = tr.epoch_loss()
-        if rank == 0:
-            ret.put((full, tr.rel[:, :DIM].numpy().copy(), loss, stats, float(tr.pending_slots())))
-    finally:
-        dist.destroy_process_group()
+def _worker(rank, world, N_ENT):
+    from multike_amd.distributed import ShardedRelationTrainer
+    from multike_amd.synthetic import SyntheticKGs
+    from oracle_backend import OracleBackend
+    kgs = SyntheticKGs(n_ent=N_ENT, n_rel=N_REL, seed=SEED)
+    rng = np.random.default_rng(SEED)
+    ent0 = mo.xavier_truncated_normal((N_ENT, DIM), rng).astype(np.float64)
+    rel0 = mo.xavier_truncated_normal((N_REL, DIM), rng).astype(np.float64)
+    tr = ShardedRelationTrainer(kgs, ent0, rel0, B, NEG, rank, world, seed=SEED, lr=0.05, backend=OracleBackend(),
+                                device="cpu", dtype=torch.float64)
+    stats = []
+    tr.keep_stats = True
+    for i in range(STEPS):
+        tr.step(i)
+        stats.append(tr.stats())
+    full = tr.gather_entity_table().numpy()
+    loss = tr.epoch_loss()
+    if rank == 0:
+        return full, tr.rel[:, :DIM].numpy().copy(), loss, stats, float(tr.pending_slots())
 
 
 @pytest.mark.timeout(300)
@@ -55,16 +39,7 @@ def _worker(rank, world, port, ret, N_ENT):
 def test_sharded_equals_single_process_oracle(world, N_ENT):
     """world 3 with 602 entities: shards of unequal size (201 / 201 / 200 rows), KG id ranges that do not fall on shard
     boundaries."""
-    ctx = mp.get_context("spawn")
-    ret = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, ret, N_ENT)) for r in range(world)]
-    for p in procs:
-        p.start()
-    full, rel, loss, stats, gmax = ret.get(timeout=240)
-    for p in procs:
-        p.join(60)
-        assert p.exitcode == 0
+    full, rel, loss, stats, gmax = ranks.run_ranks(world, _worker, (N_ENT,), limit=240)[0]
     # single-process reference: same global batches (world*B positives per step), dense float64 oracle
     from multike_amd.sampling import KGSide, RelationBatcher
     from multike_amd.synthetic import SyntheticKGs

@@ -2,12 +2,11 @@
 one GPU of the test box (collectives staged through gloo) against ONE rank on the same global batches — sharding must not change
 the result beyond fp32 atomic-order noise — and the one-rank run's phases against the dense float64 oracle where one exists for
 the exact batches (the relation view's first epoch)."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
+import ranks
 from oracle import attr_cnn_oracle as ao
 from oracle import multike_oracle as mo
 
@@ -58,40 +57,23 @@ def _train(rank, world, comm_oc=None, comm_views=None, ssl=False):
     return m, losses
 
 
-def _worker(rank, world, port, ret, ssl=False):
-    import torch.distributed as dist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    dist.init_process_group("gloo", init_method=f"file://{port}", rank=rank, world_size=world)
-    try:
-        from multike_amd.distributed_oc import OcHostStagedComm
-        from multike_amd.distributed_views import HostStagedViewComm
-        torch.cuda.set_device(0)
-        m, losses = _train(rank, world, OcHostStagedComm(), HostStagedViewComm(), ssl)
-        out = m.gather()
-        if rank == 0:
-            ret.put((out, losses))
-    finally:
-        dist.destroy_process_group()
+def _worker(rank, world, ssl=False):
+    from multike_amd.distributed_oc import OcHostStagedComm
+    from multike_amd.distributed_views import HostStagedViewComm
+    torch.cuda.set_device(0)
+    m, losses = _train(rank, world, OcHostStagedComm(), HostStagedViewComm(), ssl)
+    out = m.gather()
+    if rank == 0:
+        return out, losses
 
 
 @pytest.mark.timeout(900)
 @pytest.mark.parametrize("ssl", [False, True])
 def test_two_ranks_equal_one_rank_over_two_epochs(ssl):
     """ssl: the SSL schedule's phases — space mapping of the three views onto the shared table instead of the common-space step."""
-    import tempfile
-    import torch.multiprocessing as mp
     m1, l1 = _train(0, 1, ssl=ssl)
     ref = m1.gather()
-    port = tempfile.mktemp(prefix="mke_rdv_")
-    ctx = mp.get_context("spawn")
-    ret = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, ret, ssl)) for r in range(2)]
-    for p in procs:
-        p.start()
-    got, l2 = ret.get(timeout=800)
-    for p in procs:
-        p.join(120)
-        assert p.exitcode == 0
+    got, l2 = ranks.run_ranks(2, _worker, (ssl,), limit=800)[0]
     for ep in range(EPOCHS):
         for k in l1[ep]:
             assert np.isfinite(l1[ep][k]) and l1[ep][k] > 0.0, (ep, k)

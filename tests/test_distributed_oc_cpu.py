@@ -2,59 +2,42 @@
 compute backend: slots, per-epoch code exchange, ownership filtering, the all-gather / reduce-scatter / all-reduce
 sequence, split-batch chunks and the epoch boundary.  The sharded result must equal a single-process dense float64
 oracle run on the same global batches (every row updated once per step from the sum of all its contributions)."""
-import os
-import socket
-
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
+import ranks
 from oracle import c_oracle as co
 from oracle import multike_oracle as mo
-
-
-def _free_port():
-    """A fresh rendezvous file for init_method="file://..." (a TCP port picked by bind-and-close can be taken again before the
-    workers listen on it: one EADDRINUSE in ~200 runs on the GPU boxes)."""
-    import tempfile
-    return tempfile.mktemp(prefix="mke_rdv_")
-
 
 N_REL, DIM, B, NEG, SEED = 12, 20, 64, 5, 7
 
 
-def _worker(rank, world, port, ret, n_ent, steps, chunks, excl):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    dist.init_process_group("gloo", init_method=f"file://{port}", rank=rank, world_size=world)   # `port`: a rendezvous FILE (no TCP port to collide on)
-    try:
-        from multike_amd.distributed_oc import OwnerComputesTrainer
-        from multike_amd.synthetic import SyntheticKGs
-        from oracle_backend import OcOracleBackend
-        if n_ent < 100:
-            OwnerComputesTrainer.SAMPLE_RUN = 23 * NEG        # the rank's share of an epoch sampled in several runs (bounded scratch)
-        kgs = SyntheticKGs(n_ent=n_ent, n_rel=N_REL, seed=SEED)
-        rng = np.random.default_rng(SEED)
-        ent0 = mo.xavier_truncated_normal((n_ent, DIM), rng).astype(np.float64)
-        rel0 = mo.xavier_truncated_normal((N_REL, DIM), rng).astype(np.float64)
-        be = OcOracleBackend()
-        drawn, orig_sample_at = [], be.sample_at
-        be.sample_at = lambda pos, *a, **k: (drawn.append(int(pos[0].numel())), orig_sample_at(pos, *a, **k))[1]
-        tr = OwnerComputesTrainer(kgs, ent0, rel0, B, NEG, rank, world, seed=SEED, lr=0.05, backend=be,
-                                  device="cpu", dtype=torch.float64, chunks=chunks, exclusive_rows=excl)
-        for i in range(steps):
-            tr.step(i)
-        # no rank draws more than its 1 / world share of an epoch's negatives (one sampler call per planned epoch)
-        assert drawn and max(drawn) <= -(-tr._n_all // world), (drawn, tr._n_all)
-        full = tr.gather_entity_table().numpy()
-        assert float(tr.ent_grad.abs().max()) == 0.0 and float(tr.rel_grad.abs().max()) == 0.0   # scratch consumed
-        assert tr.ref_count is None or int(tr.ref_count.abs().sum()) == 0
-        loss = tr.epoch_loss()
-        if rank == 0:
-            ret.put((full, tr.rel[:, :DIM].numpy().copy(), loss, tr.steps, tr.check()))
-    finally:
-        dist.destroy_process_group()
+def _worker(rank, world, n_ent, steps, chunks, excl):
+    from multike_amd.distributed_oc import OwnerComputesTrainer
+    from multike_amd.synthetic import SyntheticKGs
+    from oracle_backend import OcOracleBackend
+    if n_ent < 100:
+        OwnerComputesTrainer.SAMPLE_RUN = 23 * NEG        # the rank's share of an epoch sampled in several runs (bounded scratch)
+    kgs = SyntheticKGs(n_ent=n_ent, n_rel=N_REL, seed=SEED)
+    rng = np.random.default_rng(SEED)
+    ent0 = mo.xavier_truncated_normal((n_ent, DIM), rng).astype(np.float64)
+    rel0 = mo.xavier_truncated_normal((N_REL, DIM), rng).astype(np.float64)
+    be = OcOracleBackend()
+    drawn, orig_sample_at = [], be.sample_at
+    be.sample_at = lambda pos, *a, **k: (drawn.append(int(pos[0].numel())), orig_sample_at(pos, *a, **k))[1]
+    tr = OwnerComputesTrainer(kgs, ent0, rel0, B, NEG, rank, world, seed=SEED, lr=0.05, backend=be,
+                              device="cpu", dtype=torch.float64, chunks=chunks, exclusive_rows=excl)
+    for i in range(steps):
+        tr.step(i)
+    # no rank draws more than its 1 / world share of an epoch's negatives (one sampler call per planned epoch)
+    assert drawn and max(drawn) <= -(-tr._n_all // world), (drawn, tr._n_all)
+    full = tr.gather_entity_table().numpy()
+    assert float(tr.ent_grad.abs().max()) == 0.0 and float(tr.rel_grad.abs().max()) == 0.0   # scratch consumed
+    assert tr.ref_count is None or int(tr.ref_count.abs().sum()) == 0
+    loss = tr.epoch_loss()
+    if rank == 0:
+        return full, tr.rel[:, :DIM].numpy().copy(), loss, tr.steps, tr.check()
 
 
 def _reference(world, n_ent, steps):
@@ -96,16 +79,7 @@ def test_owner_computes_equals_single_process_oracle(world, n_ent, chunks, excl)
     chunks 2 / 3: split-batch parts; steps run past the epoch boundary (shuffle + re-plan)."""
     ref_e, ref_r, ref_losses, steps_per_epoch = _reference(world, n_ent, 1)   # steps per epoch only
     steps = steps_per_epoch + 2
-    ctx = mp.get_context("spawn")
-    ret = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, ret, n_ent, steps, chunks, excl)) for r in range(world)]
-    for p in procs:
-        p.start()
-    full, rel, loss, tsteps, info = ret.get(timeout=500)
-    for p in procs:
-        p.join(60)
-        assert p.exitcode == 0
+    full, rel, loss, tsteps, info = ranks.run_ranks(world, _worker, (n_ent, steps, chunks, excl), limit=500)[0]
     e, r, losses, _ = _reference(world, n_ent, steps)
     assert tsteps == steps_per_epoch
     np.testing.assert_allclose(full, e, rtol=1e-9, atol=1e-12)
@@ -170,25 +144,20 @@ def _ck_list(triples, weighted):
     return [(int(h), int(r), int(t), float(x)) for (h, r, t), x in zip(triples, w)]
 
 
-def _ck_worker(rank, world, port, ret, steps, chunks, weighted=False):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    dist.init_process_group("gloo", init_method=f"file://{port}", rank=rank, world_size=world)
-    try:
-        from multike_amd.distributed_oc import OwnerComputesTrainer, TripleListBatcher
-        from oracle_backend import OcOracleBackend
-        triples, ent0, rel0 = _ck_setup()
-        bat = TripleListBatcher(_ck_list(triples, weighted), CK_B, device="cpu", seed=SEED)
-        tr = OwnerComputesTrainer(None, ent0, rel0, CK_B, 0, rank, world, seed=SEED, lr=0.05, backend=OcOracleBackend(), device="cpu",
-                                  dtype=torch.float64, chunks=chunks, batcher=bat, scale=2.0)
-        for i in range(steps):
-            tr.step(i)
-        full = tr.gather_entity_table().numpy()
-        assert float(tr.ent_grad.abs().max()) == 0.0 and float(tr.rel_grad.abs().max()) == 0.0
-        loss = tr.epoch_loss()
-        if rank == 0:
-            ret.put((full, tr.rel[:, :DIM].numpy().copy(), loss, tr.steps))
-    finally:
-        dist.destroy_process_group()
+def _ck_worker(rank, world, steps, chunks, weighted=False):
+    from multike_amd.distributed_oc import OwnerComputesTrainer, TripleListBatcher
+    from oracle_backend import OcOracleBackend
+    triples, ent0, rel0 = _ck_setup()
+    bat = TripleListBatcher(_ck_list(triples, weighted), CK_B, device="cpu", seed=SEED)
+    tr = OwnerComputesTrainer(None, ent0, rel0, CK_B, 0, rank, world, seed=SEED, lr=0.05, backend=OcOracleBackend(), device="cpu",
+                              dtype=torch.float64, chunks=chunks, batcher=bat, scale=2.0)
+    for i in range(steps):
+        tr.step(i)
+    full = tr.gather_entity_table().numpy()
+    assert float(tr.ent_grad.abs().max()) == 0.0 and float(tr.rel_grad.abs().max()) == 0.0
+    loss = tr.epoch_loss()
+    if rank == 0:
+        return full, tr.rel[:, :DIM].numpy().copy(), loss, tr.steps
 
 
 @pytest.mark.timeout(600)
@@ -198,16 +167,7 @@ def test_cross_kg_positive_steps_equal_single_process_oracle(world, chunks, weig
     every step a `random.sample` of the triple list (drawn identically on every rank), 2 x the loss; past the epoch boundary."""
     from multike_amd.distributed_oc import TripleListBatcher
     steps = 6
-    ctx = mp.get_context("spawn")
-    ret = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_ck_worker, args=(r, world, port, ret, steps, chunks, weighted)) for r in range(world)]
-    for p in procs:
-        p.start()
-    full, rel, loss, spe = ret.get(timeout=500)
-    for p in procs:
-        p.join(60)
-        assert p.exitcode == 0
+    full, rel, loss, spe = ranks.run_ranks(world, _ck_worker, (steps, chunks, weighted), limit=500)[0]
     triples, e, r = _ck_setup()
     ae, ar = np.full_like(e, 0.1), np.full_like(r, 0.1)
     bat = TripleListBatcher(_ck_list(triples, weighted), CK_B, device="cpu", seed=SEED)
@@ -242,32 +202,27 @@ def _group_setup():
     return kgs, _ck_list(triples, True), ent0, rel0
 
 
-def _group_worker(rank, world, port, ret, epochs):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    dist.init_process_group("gloo", init_method=f"file://{port}", rank=rank, world_size=world)
-    try:
-        from multike_amd.distributed_oc import OwnerComputesTrainer, TripleListBatcher
-        from oracle_backend import OcOracleBackend
-        kgs, lst, ent0, rel0 = _group_setup()
-        a = OwnerComputesTrainer(kgs, ent0, rel0, B, NEG, rank, world, seed=SEED, lr=0.05, backend=OcOracleBackend(), device="cpu",
-                                 dtype=torch.float64)
-        b = OwnerComputesTrainer(None, None, None, CK_B, 0, rank, world, seed=SEED, lr=0.05, backend=OcOracleBackend(), device="cpu",
-                                 dtype=torch.float64, batcher=TripleListBatcher(lst, CK_B, device="cpu", seed=SEED), scale=2.0,
-                                 tables_of=a)
-        assert b.ent is a.ent and b.rel is a.rel and b.ent_acc is not a.ent_acc
-        losses = []
-        for ep in range(epochs):
-            for s in range(a.steps):
-                a.step(ep * a.steps + s)
-            la = a.epoch_loss()
-            for s in range(b.steps):
-                b.step(ep * b.steps + s)
-            losses.append((la, b.epoch_loss()))
-        full = a.gather_entity_table().numpy()
-        if rank == 0:
-            ret.put((full, a.rel[:, :DIM].numpy().copy(), losses, a.steps, b.steps))
-    finally:
-        dist.destroy_process_group()
+def _group_worker(rank, world, epochs):
+    from multike_amd.distributed_oc import OwnerComputesTrainer, TripleListBatcher
+    from oracle_backend import OcOracleBackend
+    kgs, lst, ent0, rel0 = _group_setup()
+    a = OwnerComputesTrainer(kgs, ent0, rel0, B, NEG, rank, world, seed=SEED, lr=0.05, backend=OcOracleBackend(), device="cpu",
+                             dtype=torch.float64)
+    b = OwnerComputesTrainer(None, None, None, CK_B, 0, rank, world, seed=SEED, lr=0.05, backend=OcOracleBackend(), device="cpu",
+                             dtype=torch.float64, batcher=TripleListBatcher(lst, CK_B, device="cpu", seed=SEED), scale=2.0,
+                             tables_of=a)
+    assert b.ent is a.ent and b.rel is a.rel and b.ent_acc is not a.ent_acc
+    losses = []
+    for ep in range(epochs):
+        for s in range(a.steps):
+            a.step(ep * a.steps + s)
+        la = a.epoch_loss()
+        for s in range(b.steps):
+            b.step(ep * b.steps + s)
+        losses.append((la, b.epoch_loss()))
+    full = a.gather_entity_table().numpy()
+    if rank == 0:
+        return full, a.rel[:, :DIM].numpy().copy(), losses, a.steps, b.steps
 
 
 @pytest.mark.timeout(600)
@@ -278,16 +233,7 @@ def test_relation_group_on_shared_sharded_tables_equals_single_process_oracle():
     from multike_amd.distributed_oc import TripleListBatcher
     from multike_amd.sampling import KGSide, RelationBatcher
     world, epochs = 2, 2
-    ctx = mp.get_context("spawn")
-    ret = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_group_worker, args=(r, world, port, ret, epochs)) for r in range(world)]
-    for p in procs:
-        p.start()
-    full, rel, losses, sa, sb = ret.get(timeout=500)
-    for p in procs:
-        p.join(60)
-        assert p.exitcode == 0
+    full, rel, losses, sa, sb = ranks.run_ranks(world, _group_worker, (epochs,), limit=500)[0]
     kgs, lst, e, r = _group_setup()
     acc_a = (np.full_like(e, 0.1), np.full_like(r, 0.1))
     acc_b = (np.full_like(e, 0.1), np.full_like(r, 0.1))

@@ -4,12 +4,12 @@ refuses two ranks on one device) — against the float64 dense oracle on the sam
 (slots, codes, chunks, epoch boundary) is covered under gloo in tests/test_distributed_oc_cpu.py; what is left unexercised
 is RCCL's own transport at G > 1."""
 import os
-import socket
 
 import numpy as np
 import pytest
 import torch
 
+import ranks
 from oracle import c_oracle as co
 from oracle import multike_oracle as mo
 
@@ -366,29 +366,23 @@ def test_one_rank_across_the_epoch_boundary_equals_single_table_path(chunks):
     np.testing.assert_allclose(tr.rel[:, :d].cpu().numpy(), R.raw().cpu().numpy(), rtol=1e-4, atol=1e-6)
 
 
-def _two_rank_worker(rank, world, port, ret, chunks, steps, peer=False, neg=NEG, em=None, native=False, n_ent=N_ENT, b=B):
-    import torch.distributed as dist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    dist.init_process_group("gloo", init_method=f"file://{port}", rank=rank, world_size=world)   # `port`: a rendezvous FILE (no TCP port to collide on)
-    try:
-        from multike_amd.distributed_oc import OcHostStagedComm
-        torch.cuda.set_device(0)
-        if native == "overlap":         # the reduce-scatter on the communication stream, the second pass's gv-free work items under it
-            os.environ["MKE_OC_OVERLAP_RS"] = "1"
-        tr = _make(rank, world, comm=OcHostStagedComm(), chunks=chunks, peer=peer, neg=neg, em=em, n_ent=n_ent, b=b)
-        if native:                      # mke_oc_steps: the schedule (two streams when chunks > 1) enqueued from C++, collectives by callback
-            assert tr._native_loop()[0]
-            tr.run(0, steps)
-        else:
-            for i in range(steps):
-                tr.step(i)
-        full = tr.gather_entity_table().cpu().numpy()
-        ok = tr.scratch_clean()
-        loss = tr.epoch_loss()
-        if rank == 0:
-            ret.put((full, tr.rel[:, :DIM].cpu().numpy().copy(), loss, ok))
-    finally:
-        dist.destroy_process_group()
+def _two_rank_worker(rank, world, chunks, steps, peer=False, neg=NEG, em=None, native=False, n_ent=N_ENT, b=B):
+    from multike_amd.distributed_oc import OcHostStagedComm
+    torch.cuda.set_device(0)
+    if native == "overlap":         # the reduce-scatter on the communication stream, the second pass's gv-free work items under it
+        os.environ["MKE_OC_OVERLAP_RS"] = "1"
+    tr = _make(rank, world, comm=OcHostStagedComm(), chunks=chunks, peer=peer, neg=neg, em=em, n_ent=n_ent, b=b)
+    if native:                      # mke_oc_steps: the schedule (two streams when chunks > 1) enqueued from C++, collectives by callback
+        assert tr._native_loop()[0]
+        tr.run(0, steps)
+    else:
+        for i in range(steps):
+            tr.step(i)
+    full = tr.gather_entity_table().cpu().numpy()
+    ok = tr.scratch_clean()
+    loss = tr.epoch_loss()
+    if rank == 0:
+        return full, tr.rel[:, :DIM].cpu().numpy().copy(), loss, ok
 
 
 @pytest.mark.timeout(600)
@@ -399,21 +393,10 @@ def _two_rank_worker(rank, world, port, ret, chunks, steps, peer=False, neg=NEG,
 def test_two_ranks_on_one_gpu_equal_dense_oracle(chunks, peer, neg, em, native):
     """world_size 2 with the HIP kernels: owner = id % 2; each rank scores, for all 600 positives of the global step, the
     negatives whose corrupt entity it owns; gradient vectors summed across ranks; relation gradient all-reduced."""
-    import torch.multiprocessing as mp
-    import tempfile
-    port = tempfile.mktemp(prefix="mke_rdv_")   # rendezvous file (init_method="file://..."): no TCP port to collide on
     world, steps = 2, 7
-    ctx = mp.get_context("spawn")
-    ret = ctx.Queue()
     # peer = True: no all-gather / reduce-scatter — each process maps the other's send block and gradient inbox (IPC) and the
     # score kernel reads / writes them directly
-    procs = [ctx.Process(target=_two_rank_worker, args=(r, world, port, ret, chunks, steps, peer, neg, em, native)) for r in range(world)]
-    for p in procs:
-        p.start()
-    full, rel, loss, ok = ret.get(timeout=480)
-    for p in procs:
-        p.join(120)
-        assert p.exitcode == 0
+    full, rel, loss, ok = ranks.run_ranks(world, _two_rank_worker, (chunks, steps, peer, neg, em, native), limit=480)[0]
     e, r, losses, spe = _reference(world, steps, neg=neg)
     assert steps <= spe and ok
     np.testing.assert_allclose(loss, sum(losses), rtol=2e-6)
@@ -429,19 +412,8 @@ def test_eight_ranks_on_one_gpu_equal_dense_oracle(world, chunks, em, native):
     and of the plan walks), 2,400 positives per global step, each rank scoring the eighth of the negatives it owns, entity-major
     second pass + the native step loop (collectives by callback into the host-staged communicator), against the float64 dense
     oracle.  world 5: the division instantiation."""
-    import torch.multiprocessing as mp
-    import tempfile
-    port = tempfile.mktemp(prefix="mke_rdv_")
     steps = 4
-    ctx = mp.get_context("spawn")
-    ret = ctx.Queue()
-    procs = [ctx.Process(target=_two_rank_worker, args=(r, world, port, ret, chunks, steps, False, NEG, em, native)) for r in range(world)]
-    for p in procs:
-        p.start()
-    full, rel, loss, ok = ret.get(timeout=800)
-    for p in procs:
-        p.join(180)
-        assert p.exitcode == 0
+    full, rel, loss, ok = ranks.run_ranks(world, _two_rank_worker, (chunks, steps, False, NEG, em, native), limit=800)[0]
     e, r, losses, spe = _reference(world, steps)
     assert steps <= spe and ok
     np.testing.assert_allclose(loss, sum(losses), rtol=2e-6)
@@ -455,20 +427,8 @@ def test_ranks_without_entity_rows_equal_dense_oracle():
     the plan and the step both count (relation row r is local row max(1, n_local) + r for the second pass) — and still score
     their share of the negatives and store their partial relation gradient.  Entity-major, native step loop, 8 positives
     and 2 negatives each per global step, against the float64 dense oracle."""
-    import torch.multiprocessing as mp
-    import tempfile
-    port = tempfile.mktemp(prefix="mke_rdv_")
     world, steps, n_ent, b, neg = 8, 3, 6, 1, 2
-    ctx = mp.get_context("spawn")
-    ret = ctx.Queue()
-    procs = [ctx.Process(target=_two_rank_worker, args=(r, world, port, ret, 1, steps, False, neg, True, True, n_ent, b))
-             for r in range(world)]
-    for p in procs:
-        p.start()
-    full, rel, loss, ok = ret.get(timeout=800)
-    for p in procs:
-        p.join(180)
-        assert p.exitcode == 0
+    full, rel, loss, ok = ranks.run_ranks(world, _two_rank_worker, (1, steps, False, neg, True, True, n_ent, b), limit=800)[0]
     e, r, losses, spe = _reference(world, steps, n_ent=n_ent, neg=neg, b=b)
     assert steps <= spe and ok
     np.testing.assert_allclose(loss, sum(losses), rtol=2e-6)
@@ -503,13 +463,8 @@ def test_apply_phase_on_an_entity_major_step_is_refused():
 def test_one_rank_rccl_collectives_run():
     """1-rank RCCL group: the trainer's own communicator class (all_gather_into_tensor / reduce_scatter_tensor / all_reduce)
     is importable and the G = 1 short-cuts leave it untouched."""
-    import torch.distributed as dist
     from multike_amd.distributed_oc import OcComm
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    import tempfile
-    dist.init_process_group("nccl", init_method="file://" + tempfile.mktemp(prefix="mke_rdv_"), rank=0, world_size=1,
-                            device_id=torch.device("cuda", 0))
-    try:
+    with ranks.one_rank_group():
         cm = OcComm()
         a = torch.arange(8, dtype=torch.float32, device="cuda")
         o = torch.empty(8, device="cuda")
@@ -523,32 +478,21 @@ def test_one_rank_rccl_collectives_run():
         tr = _make(0, 1, comm=cm)
         tr.step(0)
         torch.cuda.synchronize()
-    finally:
-        dist.destroy_process_group()
 
 
-def _rccl_native_worker(ret, chunks, em, overlap=False):
+def _rccl_native_worker(rank, world, chunks, em, overlap=False):
     """(spawned: MKE_OC_FORCE_COLLECTIVES is read when the trainer is built, and a process has one default process group)"""
-    import tempfile
-    import torch.distributed as dist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MKE_OC_FORCE_COLLECTIVES"] = "1"
     if overlap:
         os.environ["MKE_OC_OVERLAP_RS"] = "1"
-    dist.init_process_group("nccl", init_method="file://" + tempfile.mktemp(prefix="mke_rdv_"), rank=0, world_size=1,
-                            device_id=torch.device("cuda", 0))
-    try:
-        from multike_amd.distributed_oc import OcRcclComm
-        _, _, _, spe = _reference(1, 1, neg=25)
-        steps = min(spe, 6)
-        tr = _make(0, 1, chunks=chunks, neg=25, em=em)
-        ok, cs = tr._native_loop()
-        kind = (type(tr.comm).__name__, bool(ok), None if cs is None else int(cs.kind), bool(tr.force_collectives))
-        tr.run(0, steps)
-        torch.cuda.synchronize()
-        ret.put((kind, tr.epoch_loss(), tr.gather_entity_table().cpu().numpy(), tr.rel[:, :DIM].cpu().numpy().copy(), tr.scratch_clean(), steps))
-    finally:
-        dist.destroy_process_group()
+    _, _, _, spe = _reference(1, 1, neg=25)
+    steps = min(spe, 6)
+    tr = _make(0, 1, chunks=chunks, neg=25, em=em)
+    ok, cs = tr._native_loop()
+    kind = (type(tr.comm).__name__, bool(ok), None if cs is None else int(cs.kind), bool(tr.force_collectives))
+    tr.run(0, steps)
+    torch.cuda.synchronize()
+    return kind, tr.epoch_loss(), tr.gather_entity_table().cpu().numpy(), tr.rel[:, :DIM].cpu().numpy().copy(), tr.scratch_clean(), steps
 
 
 @pytest.mark.timeout(600)
@@ -558,14 +502,7 @@ def test_native_step_loop_over_rccl_entry_points(chunks, em, overlap):
     addresses the host side hands over (a real one-rank RCCL communicator, the G > 1 path forced: all three collectives of every
     step are issued for real; chunks 2: on the second stream, ordered by the call's events; overlap: the reduce-scatter on the second
     stream with the second pass's gradient-vector-free work items under it) — against the float64 dense oracle."""
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
-    ret = ctx.Queue()
-    p = ctx.Process(target=_rccl_native_worker, args=(ret, chunks, em, overlap))
-    p.start()
-    kind, loss, full, rel, clean, steps = ret.get(timeout=500)
-    p.join(120)
-    assert p.exitcode == 0
+    kind, loss, full, rel, clean, steps = ranks.run_ranks(1, _rccl_native_worker, (chunks, em, overlap), limit=500, backend="nccl")[0]
     assert kind == ("OcRcclComm", True, 0, True), kind          # RCCL through ctypes, native loop usable, MKE_OC_COMM_NCCL, forced
     e, r, losses, _ = _reference(1, steps, neg=25)
     np.testing.assert_allclose(loss, sum(losses), rtol=2e-6)
@@ -574,23 +511,15 @@ def test_native_step_loop_over_rccl_entry_points(chunks, em, overlap):
     assert clean
 
 
-def _rccl_epoch_worker(ret, forced):
-    import tempfile
-    import torch.distributed as dist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
+def _rccl_epoch_worker(rank, world, forced):
     if forced:
         os.environ["MKE_OC_FORCE_COLLECTIVES"] = "1"
-    dist.init_process_group("nccl", init_method="file://" + tempfile.mktemp(prefix="mke_rdv_"), rank=0, world_size=1,
-                            device_id=torch.device("cuda", 0))
-    try:
-        tr = _make(0, 1, neg=25, em=True)          # prefetch on (the default): the next epoch's plan is staged while this one trains
-        n = 2 * tr.steps + 3
-        tr.run(0, n)
-        torch.cuda.synchronize()
-        ret.put((type(tr.comm).__name__, bool(tr.force_collectives), tr.ent.cpu().numpy(), tr.ent_acc.cpu().numpy(), tr.rel.cpu().numpy(),
-                 tr.loss_ring.cpu().numpy(), n))
-    finally:
-        dist.destroy_process_group()
+    tr = _make(0, 1, neg=25, em=True)          # prefetch on (the default): the next epoch's plan is staged while this one trains
+    n = 2 * tr.steps + 3
+    tr.run(0, n)
+    torch.cuda.synchronize()
+    return (type(tr.comm).__name__, bool(tr.force_collectives), tr.ent.cpu().numpy(), tr.ent_acc.cpu().numpy(), tr.rel.cpu().numpy(),
+            tr.loss_ring.cpu().numpy(), n)
 
 
 @pytest.mark.timeout(600)
@@ -600,16 +529,7 @@ def test_rccl_step_loop_across_epoch_boundaries_with_prefetch():
     communicator at its fixed point of the step sequence (at one rank the sampling / gather / lists split is taken only when the
     collectives are forced: the split plan, its events and the hand-over are exercised).  Every collective is the identity at one
     rank and the step has no atomics, so the tables, accumulators and losses must equal, BIT FOR BIT, a run without any collective."""
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
-    out = []
-    for forced in (True, False):
-        ret = ctx.Queue()
-        p = ctx.Process(target=_rccl_epoch_worker, args=(ret, forced))
-        p.start()
-        out.append(ret.get(timeout=500))
-        p.join(120)
-        assert p.exitcode == 0
+    out = [ranks.run_ranks(1, _rccl_epoch_worker, (forced,), limit=500, backend="nccl")[0] for forced in (True, False)]
     assert out[0][0] == "OcRcclComm" and out[0][1] and not out[1][1] and out[0][6] == out[1][6]
     for a, b in zip(out[0][2:6], out[1][2:6]):
         assert np.array_equal(a, b)
@@ -677,22 +597,16 @@ def test_one_rank_cross_kg_positive_steps_equal_dense_oracle(weighted):
     assert tr.scratch_clean()
 
 
-def _ck_two_rank_worker(rank, world, port, ret, steps, weighted):
-    import torch.distributed as dist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    dist.init_process_group("gloo", init_method=f"file://{port}", rank=rank, world_size=world)
-    try:
-        from multike_amd.distributed_oc import OcHostStagedComm
-        torch.cuda.set_device(0)
-        tr = _ck_trainer(rank, world, comm=OcHostStagedComm(), weighted=weighted)
-        for i in range(steps):
-            tr.step(i)
-        full = tr.gather_entity_table().cpu().numpy()
-        loss = tr.epoch_loss()
-        if rank == 0:
-            ret.put((full, tr.rel[:, :DIM].cpu().numpy().copy(), loss))
-    finally:
-        dist.destroy_process_group()
+def _ck_two_rank_worker(rank, world, steps, weighted):
+    from multike_amd.distributed_oc import OcHostStagedComm
+    torch.cuda.set_device(0)
+    tr = _ck_trainer(rank, world, comm=OcHostStagedComm(), weighted=weighted)
+    for i in range(steps):
+        tr.step(i)
+    full = tr.gather_entity_table().cpu().numpy()
+    loss = tr.epoch_loss()
+    if rank == 0:
+        return full, tr.rel[:, :DIM].cpu().numpy().copy(), loss
 
 
 @pytest.mark.timeout(600)
@@ -700,19 +614,8 @@ def _ck_two_rank_worker(rank, world, port, ret, steps, weighted):
 def test_two_ranks_cross_kg_positive_steps_equal_dense_oracle(weighted):
     """Two ranks sharing the GPU: heads / tails of the sampled cross-KG triples live on either rank; 2 vectors per positive
     each way, nothing else."""
-    import torch.multiprocessing as mp
-    import tempfile
-    port = tempfile.mktemp(prefix="mke_rdv_")
     world, steps = 2, 5
-    ctx = mp.get_context("spawn")
-    ret = ctx.Queue()
-    procs = [ctx.Process(target=_ck_two_rank_worker, args=(r, world, port, ret, steps, weighted)) for r in range(world)]
-    for p in procs:
-        p.start()
-    full, rel, loss = ret.get(timeout=480)
-    for p in procs:
-        p.join(120)
-        assert p.exitcode == 0
+    full, rel, loss = ranks.run_ranks(world, _ck_two_rank_worker, (steps, weighted), limit=480)[0]
     e, r, losses, _ = _ck_reference(steps, weighted)
     np.testing.assert_allclose(loss, sum(losses[2:]), rtol=2e-6)
     np.testing.assert_allclose(full, e, rtol=2e-4, atol=2e-6)
@@ -816,30 +719,19 @@ def _c5_full_size(rank, world, comm, steps=2):
 @pytest.mark.timeout(900)
 def test_full_size_c5_owner_computes_one_rank_over_rccl():
     """configs[4] per-GPU shape at full size on the SHARDED path, G = 1, the communicator a real 1-rank RCCL group."""
-    import tempfile
-    import torch.distributed as dist
     from multike_amd.distributed_oc import OcComm
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    dist.init_process_group("nccl", init_method="file://" + tempfile.mktemp(prefix="mke_rdv_"), rank=0, world_size=1,
-                            device_id=torch.device("cuda", 0))
     try:
-        out = _c5_full_size(0, 1, OcComm())
-        assert out["used"] > 500_000 and out["owned"] == out["used"]     # 2 steps x ~300K distinct rows of 2M
+        with ranks.one_rank_group():
+            out = _c5_full_size(0, 1, OcComm())
+            assert out["used"] > 500_000 and out["owned"] == out["used"]     # 2 steps x ~300K distinct rows of 2M
     finally:
-        dist.destroy_process_group()
         torch.cuda.empty_cache()
 
 
-def _c5_worker(rank, world, port, ret):
-    import torch.distributed as dist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    dist.init_process_group("gloo", init_method=f"file://{port}", rank=rank, world_size=world)
-    try:
-        from multike_amd.distributed_oc import OcHostStagedComm
-        torch.cuda.set_device(0)
-        ret.put(_c5_full_size(rank, world, OcHostStagedComm()))
-    finally:
-        dist.destroy_process_group()
+def _c5_worker(rank, world):
+    from multike_amd.distributed_oc import OcHostStagedComm
+    torch.cuda.set_device(0)
+    return _c5_full_size(rank, world, OcHostStagedComm())
 
 
 @pytest.mark.timeout(1500)
@@ -847,18 +739,7 @@ def test_full_size_c5_owner_computes_two_ranks_on_one_gpu():
     """The same at world 2 (two ranks sharing the GPU, 1M-row shards, 10,000 positives / 650K scored triples per global step,
     collectives staged through gloo): each rank scores, for all positives, the negatives whose corrupt entity it owns; 2 x
     10.5K x 256 floats cross the ranks each way per step."""
-    import tempfile
-    import torch.multiprocessing as mp
-    port = tempfile.mktemp(prefix="mke_rdv_")
-    ctx = mp.get_context("spawn")
-    ret = ctx.Queue()
-    procs = [ctx.Process(target=_c5_worker, args=(r, 2, port, ret)) for r in range(2)]
-    for p in procs:
-        p.start()
-    outs = [ret.get(timeout=1400) for _ in range(2)]
-    for p in procs:
-        p.join(120)
-        assert p.exitcode == 0
+    outs = list(ranks.run_ranks(2, _c5_worker, limit=1400).values())
     assert sorted(o["rank"] for o in outs) == [0, 1]
     assert outs[0]["used"] == outs[1]["used"] and outs[0]["owned"] + outs[1]["owned"] == outs[0]["used"]
     assert abs(outs[0]["loss"] - outs[1]["loss"]) <= 1e-9 * abs(outs[0]["loss"])

@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+import ranks
+
 pytestmark = pytest.mark.gpu
 
 DIM = 24
@@ -64,20 +66,14 @@ def test_one_rank_runs_the_whole_schedule(method):
     np.testing.assert_allclose(res["rv"], mrr, rtol=1e-6)
 
 
-def _worker(rank, world, port, ret, method, itc_lr):
-    import torch.distributed as dist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    dist.init_process_group("gloo", init_method=f"file://{port}", rank=rank, world_size=world)
-    try:
-        from multike_amd.distributed_oc import OcHostStagedComm
-        from multike_amd.distributed_views import HostStagedViewComm
-        torch.cuda.set_device(0)
-        model, res, log = _run(method, rank, world, OcHostStagedComm(), HostStagedViewComm(), itc_lr)
-        tables = model.m.gather()
-        if rank == 0:
-            ret.put((res, {k: np.asarray(tables[k]) for k in ("ent", "rv", "av", "rel", "attr")}, log))
-    finally:
-        dist.destroy_process_group()
+def _worker(rank, world, method, itc_lr):
+    from multike_amd.distributed_oc import OcHostStagedComm
+    from multike_amd.distributed_views import HostStagedViewComm
+    torch.cuda.set_device(0)
+    model, res, log = _run(method, rank, world, OcHostStagedComm(), HostStagedViewComm(), itc_lr)
+    tables = model.m.gather()
+    if rank == 0:
+        return res, {k: np.asarray(tables[k]) for k in ("ent", "rv", "av", "rel", "attr")}, log
 
 
 @pytest.mark.timeout(900)
@@ -92,20 +88,9 @@ def test_two_ranks_equal_one_rank(method, itc_lr, elementwise):
     (row, element) pairs (tests/test_schedule_trace_gpu.py has the derivation and the float64 finite-difference evidence is in
     profiles/r04_parity_noise.log) — two fp32 runs that differ in summation order then differ there by construction, so that
     variant asserts the statistics (mean error, metrics), not a maximum."""
-    import tempfile
-    import torch.multiprocessing as mp
     m1, r1, _ = _run(method, 0, 1, itc_lr=itc_lr)
     ref = m1.m.gather()
-    port = tempfile.mktemp(prefix="mke_rdv_")
-    ctx = mp.get_context("spawn")
-    ret = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, ret, method, itc_lr)) for r in range(2)]
-    for p in procs:
-        p.start()
-    r2, got, log = ret.get(timeout=800)
-    for p in procs:
-        p.join(120)
-        assert p.exitcode == 0
+    r2, got, log = ranks.run_ranks(2, _worker, (method, itc_lr), limit=800)[0]
     for k in r1:
         assert abs(r2[k] - r1[k]) <= (2e-3 if elementwise else 1e-2), (k, r2[k], r1[k])   # MRR over ~500 test pairs
     for k in ("ent", "rv", "av", "rel", "attr"):

@@ -1,13 +1,11 @@
 """The sharded attribute view / common-space step with the HIP kernels (mke_attr_step_phases, mke_align_*): two ranks
 SHARING the one GPU of the test box (collectives staged through gloo) against the float64 dense oracle on the same global
 batches; the exchange logic itself is covered under gloo in tests/test_distributed_views_cpu.py."""
-import os
-import socket
-
 import numpy as np
 import pytest
 import torch
 
+import ranks
 from oracle import attr_cnn_oracle as ao
 from oracle import multike_oracle as mo
 
@@ -34,50 +32,28 @@ def _attr_data():
     return ent, attr, lit, P, batches
 
 
-def _attr_worker(rank, world, port, ret, mode="parallel"):
+def _attr_worker(rank, world, mode="parallel"):
     import torch.distributed as dist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    dist.init_process_group("gloo", init_method=f"file://{port}", rank=rank, world_size=world)   # `port`: a rendezvous FILE (no TCP port to collide on)
-    try:
-        from multike_amd.distributed_views import HostStagedViewComm, ShardedAttributeView
-        torch.cuda.set_device(0)
-        ent, attr, lit, P, batches = _attr_data()
-        v = ShardedAttributeView(ent, attr, lit, P, rank, world, lr=0.01, comm=HostStagedViewComm(), mode=mode)
-        for (ih, ia, iv, w) in batches:
-            v.step(ih, ia, iv, w, scale=2.0)
-        loss = v.epoch_loss()
-        full, a, p = v.gather()
-        # replicated state must be BIT-identical on the two ranks (rank 0's gradients are everybody's in "replicated" mode;
-        # all-reduced sums in "parallel" mode)
-        import torch.distributed as dist2
-        mine = torch.cat([v.backend.cnn.params.detach().reshape(-1), v.backend.attr.data.reshape(-1)]).cpu()
-        other = mine.clone()
-        dist2.broadcast(other, 0)
-        same = torch.tensor([1 if torch.equal(mine, other) else 0])
-        dist2.all_reduce(same, op=dist2.ReduceOp.MIN)
-        assert int(same) == 1, "replicated parameters differ between the ranks"
-        ok = float(v.backend.cnn.grads.abs().max()) == 0.0 and float(v.backend.attr.grad.abs().max()) == 0.0 and \
-            float(v.backend.ent.grad.abs().max()) == 0.0
-        if rank == 0:
-            ret.put((full, a, p, loss, ok))
-    finally:
-        dist.destroy_process_group()
-
-
-def _run(worker, world=2, extra=()):
-    import torch.multiprocessing as mp
-    import tempfile
-    port = tempfile.mktemp(prefix="mke_rdv_")   # rendezvous file (init_method="file://..."): no TCP port to collide on
-    ctx = mp.get_context("spawn")
-    ret = ctx.Queue()
-    procs = [ctx.Process(target=worker, args=(r, world, port, ret) + tuple(extra)) for r in range(world)]
-    for p in procs:
-        p.start()
-    out = ret.get(timeout=480)
-    for p in procs:
-        p.join(120)
-        assert p.exitcode == 0
-    return out
+    from multike_amd.distributed_views import HostStagedViewComm, ShardedAttributeView
+    torch.cuda.set_device(0)
+    ent, attr, lit, P, batches = _attr_data()
+    v = ShardedAttributeView(ent, attr, lit, P, rank, world, lr=0.01, comm=HostStagedViewComm(), mode=mode)
+    for (ih, ia, iv, w) in batches:
+        v.step(ih, ia, iv, w, scale=2.0)
+    loss = v.epoch_loss()
+    full, a, p = v.gather()
+    # replicated state must be BIT-identical on the two ranks (rank 0's gradients are everybody's in "replicated" mode;
+    # all-reduced sums in "parallel" mode)
+    mine = torch.cat([v.backend.cnn.params.detach().reshape(-1), v.backend.attr.data.reshape(-1)]).cpu()
+    other = mine.clone()
+    dist.broadcast(other, 0)
+    same = torch.tensor([1 if torch.equal(mine, other) else 0])
+    dist.all_reduce(same, op=dist.ReduceOp.MIN)
+    assert int(same) == 1, "replicated parameters differ between the ranks"
+    ok = float(v.backend.cnn.grads.abs().max()) == 0.0 and float(v.backend.attr.grad.abs().max()) == 0.0 and \
+        float(v.backend.ent.grad.abs().max()) == 0.0
+    if rank == 0:
+        return full, a, p, loss, ok
 
 
 @pytest.mark.timeout(600)
@@ -86,7 +62,7 @@ def test_two_ranks_attribute_view_equals_dense_oracle(mode):
     """mode "replicated": every rank computes the whole step on the gathered head rows (1 all-reduce + 1 broadcast per step
     instead of 4 all-reduces), applies the heads it owns; a rank that owns none of a step's heads still updates the replicated
     state identically."""
-    full, a, p, loss, ok = _run(_attr_worker, extra=(mode,))
+    full, a, p, loss, ok = ranks.run_ranks(2, _attr_worker, (mode,), limit=480)[0]
     ent, attr, lit, P, batches = _attr_data()
     p64 = {k: v.astype(np.float64) for k, v in P.items()}
     acc = {k: np.full_like(v, 0.1) for k, v in p64.items()}
@@ -114,28 +90,22 @@ def _cs_data():
     return ent, name, rv, av, batches
 
 
-def _cs_worker(rank, world, port, ret):
-    import torch.distributed as dist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    dist.init_process_group("gloo", init_method=f"file://{port}", rank=rank, world_size=world)   # `port`: a rendezvous FILE (no TCP port to collide on)
-    try:
-        from multike_amd.distributed_views import HostStagedViewComm, ShardedCommonSpace
-        torch.cuda.set_device(0)
-        ent, name, rv, av, batches = _cs_data()
-        v = ShardedCommonSpace(ent, name, rv, av, rank, world, lr=0.02, cv_name_weight=0.7, cv_weight=1.3, comm=HostStagedViewComm())
-        for ids in batches:
-            v.step(ids)
-        loss = v.epoch_loss()
-        out = v.gather()
-        if rank == 0:
-            ret.put((out, loss))
-    finally:
-        dist.destroy_process_group()
+def _cs_worker(rank, world):
+    from multike_amd.distributed_views import HostStagedViewComm, ShardedCommonSpace
+    torch.cuda.set_device(0)
+    ent, name, rv, av, batches = _cs_data()
+    v = ShardedCommonSpace(ent, name, rv, av, rank, world, lr=0.02, cv_name_weight=0.7, cv_weight=1.3, comm=HostStagedViewComm())
+    for ids in batches:
+        v.step(ids)
+    loss = v.epoch_loss()
+    out = v.gather()
+    if rank == 0:
+        return out, loss
 
 
 @pytest.mark.timeout(600)
 def test_two_ranks_common_space_equals_dense_oracle():
-    out, loss = _run(_cs_worker)
+    out, loss = ranks.run_ranks(2, _cs_worker, limit=480)[0]
     ent, name, rv, av, batches = (x.astype(np.float64) if isinstance(x, np.ndarray) else x for x in _cs_data())
     accs = [np.full_like(ent, 0.1) for _ in range(3)]
     tot = sum(mo.common_space_step_dense(ent, name, rv, av, accs[0], accs[1], accs[2], ids, 0.02, 0.7, 1.3) for ids in batches)
@@ -154,24 +124,18 @@ def _sm_data():
     return ent, views, mats, batches
 
 
-def _sm_worker(rank, world, port, ret):
-    import torch.distributed as dist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    dist.init_process_group("gloo", init_method=f"file://{port}", rank=rank, world_size=world)   # `port`: a rendezvous FILE (no TCP port to collide on)
-    try:
-        from multike_amd.distributed_views import HostStagedViewComm, ShardedSpaceMapping
-        torch.cuda.set_device(0)
-        ent, views, mats, batches = _sm_data()
-        v = ShardedSpaceMapping(ent, views, mats, rank, world, lr=0.01, orthogonal_weight=2.0, comm=HostStagedViewComm())
-        for ids in batches:
-            v.step(ids)
-        loss = v.epoch_loss()
-        full, M = v.gather()
-        ok = float(v.backend.state.gM.abs().max()) == 0.0 and float(v.backend.ent.grad.abs().max()) == 0.0
-        if rank == 0:
-            ret.put((full, M, loss, ok))
-    finally:
-        dist.destroy_process_group()
+def _sm_worker(rank, world):
+    from multike_amd.distributed_views import HostStagedViewComm, ShardedSpaceMapping
+    torch.cuda.set_device(0)
+    ent, views, mats, batches = _sm_data()
+    v = ShardedSpaceMapping(ent, views, mats, rank, world, lr=0.01, orthogonal_weight=2.0, comm=HostStagedViewComm())
+    for ids in batches:
+        v.step(ids)
+    loss = v.epoch_loss()
+    full, M = v.gather()
+    ok = float(v.backend.state.gM.abs().max()) == 0.0 and float(v.backend.ent.grad.abs().max()) == 0.0
+    if rank == 0:
+        return full, M, loss, ok
 
 
 def _sm_reference():
@@ -188,7 +152,7 @@ def _sm_reference():
 def test_two_ranks_space_mapping_equals_dense_oracle():
     """mke_mapping_step_phases on two ranks sharing the GPU: per view the batch-wide sums and the matrix gradients travel
     through the (host-staged) all-reduces; a step in which rank 1 owns nothing."""
-    full, M, loss, ok = _run(_sm_worker)
+    full, M, loss, ok = ranks.run_ranks(2, _sm_worker, limit=480)[0]
     e64, m64, tot = _sm_reference()
     assert ok
     np.testing.assert_allclose(loss, tot, rtol=2e-5)
@@ -238,24 +202,18 @@ def _ae_reference(active):
     return p, tot
 
 
-def _ae_worker(rank, world, port, ret):
-    import torch.distributed as dist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    dist.init_process_group("gloo", init_method=f"file://{port}", rank=rank, world_size=world)
-    try:
-        from multike_amd.distributed_views import HostStagedViewComm, ShardedAutoEncoder
-        torch.cuda.set_device(0)
-        p, batches = _ae_data()
-        v = ShardedAutoEncoder(p, AE_DIMS, rank, world, lr=AE_LR, active="tanh", normalize=True, comm=HostStagedViewComm())
-        for x in batches:
-            v.step(x)
-        loss = v.epoch_loss()
-        m = v.backend.model
-        ok = float(m.grads.abs().max()) == 0.0 and float(m._partials.abs().max()) == 0.0
-        if rank == 0:
-            ret.put((v.params(), loss, ok))
-    finally:
-        dist.destroy_process_group()
+def _ae_worker(rank, world):
+    from multike_amd.distributed_views import HostStagedViewComm, ShardedAutoEncoder
+    torch.cuda.set_device(0)
+    p, batches = _ae_data()
+    v = ShardedAutoEncoder(p, AE_DIMS, rank, world, lr=AE_LR, active="tanh", normalize=True, comm=HostStagedViewComm())
+    for x in batches:
+        v.step(x)
+    loss = v.epoch_loss()
+    m = v.backend.model
+    ok = float(m.grads.abs().max()) == 0.0 and float(m._partials.abs().max()) == 0.0
+    if rank == 0:
+        return v.params(), loss, ok
 
 
 @pytest.mark.timeout(600)
@@ -263,7 +221,7 @@ def test_two_ranks_auto_encoder_equals_dense_oracle():
     """mke_ae_step_phases on two ranks sharing the GPU (rows r, r + 2, ... of every batch each): the two batch-wide sums of the
     whole-matrix normalisation of the code and the packed gradient travel through the (host-staged) all-reduces; a batch in
     which rank 1 has no row."""
-    got, loss, ok = _run(_ae_worker)
+    got, loss, ok = ranks.run_ranks(2, _ae_worker, limit=480)[0]
     p64, tot = _ae_reference("tanh")
     assert ok
     np.testing.assert_allclose(loss, tot, rtol=2e-5)

@@ -8,89 +8,80 @@ The oracle backend has the atomics form only (no entity-major plan), and `owner`
 here too — so no epoch is trained on this backend: the PLAN equality is what this file checks; the entity-major epochs of the two
 forms are compared bit for bit on the GPU (tests/test_oc_owned_codes_gpu.py)."""
 import os
-import tempfile
 
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
+
+import ranks
 
 N_REL, DIM, B, NEG, SEED = 12, 20, 64, 5, 7
 
 
-def _worker(rank, world, rdv, ret, n_ent, small_cap):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
+def _worker(rank, world, n_ent, small_cap):
     os.environ.pop("MKE_OC_CODES", None)
-    dist.init_process_group("gloo", init_method=f"file://{rdv}", rank=rank, world_size=world)
+    from oracle import multike_oracle as mo
+    from multike_amd import _lib
+    from multike_amd.distributed_oc import OwnerComputesTrainer
+    from multike_amd.synthetic import SyntheticKGs
+    from oracle_backend import OcOracleBackend
+    import oc_owned_util as U
+    kgs = SyntheticKGs(n_ent=n_ent, n_rel=N_REL, seed=SEED)
+    rng = np.random.default_rng(SEED)
+    ent0 = mo.xavier_truncated_normal((n_ent, DIM), rng).astype(np.float64)
+    rel0 = mo.xavier_truncated_normal((N_REL, DIM), rng).astype(np.float64)
+    mk = lambda **kw: OwnerComputesTrainer(kgs, ent0, rel0, B, NEG, rank, world, seed=SEED, lr=0.05, backend=OcOracleBackend(),
+                                           device="cpu", dtype=torch.float64, **kw)
+    refused = False
     try:
-        from oracle import multike_oracle as mo
-        from multike_amd import _lib
-        from multike_amd.distributed_oc import OwnerComputesTrainer
-        from multike_amd.synthetic import SyntheticKGs
-        from oracle_backend import OcOracleBackend
-        import oc_owned_util as U
-        kgs = SyntheticKGs(n_ent=n_ent, n_rel=N_REL, seed=SEED)
-        rng = np.random.default_rng(SEED)
-        ent0 = mo.xavier_truncated_normal((n_ent, DIM), rng).astype(np.float64)
-        rel0 = mo.xavier_truncated_normal((N_REL, DIM), rng).astype(np.float64)
-        mk = lambda **kw: OwnerComputesTrainer(kgs, ent0, rel0, B, NEG, rank, world, seed=SEED, lr=0.05, backend=OcOracleBackend(),
-                                               device="cpu", dtype=torch.float64, **kw)
-        refused = False
-        try:
-            mk(codes="owner")
-        except _lib.MultiKEHipError as e:
-            refused = "entity-major" in str(e) and "owner" in str(e)
-        tr = mk()
-        assert not tr.em and tr.check()["codes"] == "gather" and tr.check()["code_bytes_received_per_epoch"] == 4 * world * -(-tr._n_all // world) * NEG
-        b = tr.bat
-        pos, n_all, G = (b.pos_h, b.pos_r, b.pos_t), tr._n_all, world
-        g = tr._compute_plan(pos, b.rng_stream, 1)                    # the all-gathered codes, in the spare buffer set
-        codes = g.codes[:n_all * NEG].numpy().astype(np.int64) & 0xFFFFFFFF
-        slots = [s[:n_all].clone() for s in g.slot]
-        owns = [o[:n_all].clone() for o in g.own]
-        cnt = g.cnt_host.clone()
-        # the owner plan of the same epoch order by the same trainer (construction would refuse the form with this backend)
-        tr.codes_form = "owner"
-        if small_cap:
-            tr._own_cap = 9                                           # every pair overflows: bucket + exchange + plan are redone
-        o = tr._compute_plan(pos, b.rng_stream, 1)
-        n_per = -(-n_all // G)
-        table = o.cnt_all.view(G, G).numpy().copy()
-        want_table = np.zeros((G, G), dtype=np.int64)
-        for src in range(G):
-            lo, hi = min(n_all, src * n_per), min(n_all, (src + 1) * n_per)
-            _, per_dest = U.np_bucket(codes[lo * NEG:hi * NEG], hi - lo, NEG, lo, G)
-            want_table[src] = [len(x) for x in per_dest]
-        assert (table == want_table).all(), (table, want_table)
-        if small_cap:
-            assert table.max() > o.own_cap == 9
-        tr._finish_plan(o)                                            # reads the table; redoes the plan when a pair overflowed
-        assert tr.owner_replans == (1 if small_cap else 0)
-        assert tr._own_cap == (int(want_table.max()) if small_cap else int(1.06 * n_per * NEG / G) + 4096)
-        recs, off = U.np_owned(codes, n_all, NEG, G, rank)
-        assert int(tr._own_off[n_all]) == len(recs)
-        np.testing.assert_array_equal(tr._own_rec[:3 * len(recs)].numpy().reshape(-1, 3), recs)
-        np.testing.assert_array_equal(tr._own_off[:n_all + 1].numpy(), off)
-        np.testing.assert_array_equal(o.need_all[:n_all].numpy().astype(np.int64) & 0xFFFFFFFF, codes[::NEG] & U.NEED)
-        for x in range(2):
-            assert torch.equal(tr._slot[x][:n_all], slots[x])
-            lo_hi = [(lo, int(tr._own_cnt[x][k])) for k, (_, lo, _) in enumerate(tr._parts)]
-            for lo, n in lo_hi:
-                assert torch.equal(tr._own[x][lo:lo + n], owns[x][lo:lo + n])
-        assert torch.equal(o.cnt_host, cnt)
-        info = tr.check()
-        assert info["codes"] == "owner" and info["owner_code_capacity_per_pair"] == tr._own_cap
-        assert info["code_bytes_received_per_epoch"] == 12 * G * tr._own_cap + 4 * G * n_per + 4 * G * G
-        st = tr._build_part_step(len(tr._parts) - 1, 1)               # the step fields of the last part: its offsets into the list
-        _, lo, hi = tr._parts[-1]
-        assert st.own_rec is tr._own_rec and torch.equal(st.own_off, tr._own_off[lo:hi + 1])
-        ret.put((rank, refused))
-    except Exception as e:      # noqa: BLE001 — reported to the parent, which fails the test
-        import traceback
-        ret.put((rank, "".join(traceback.format_exception(e))))
-    finally:
-        dist.destroy_process_group()
+        mk(codes="owner")
+    except _lib.MultiKEHipError as e:
+        refused = "entity-major" in str(e) and "owner" in str(e)
+    tr = mk()
+    assert not tr.em and tr.check()["codes"] == "gather" and tr.check()["code_bytes_received_per_epoch"] == 4 * world * -(-tr._n_all // world) * NEG
+    b = tr.bat
+    pos, n_all, G = (b.pos_h, b.pos_r, b.pos_t), tr._n_all, world
+    g = tr._compute_plan(pos, b.rng_stream, 1)                    # the all-gathered codes, in the spare buffer set
+    codes = g.codes[:n_all * NEG].numpy().astype(np.int64) & 0xFFFFFFFF
+    slots = [s[:n_all].clone() for s in g.slot]
+    owns = [o[:n_all].clone() for o in g.own]
+    cnt = g.cnt_host.clone()
+    # the owner plan of the same epoch order by the same trainer (construction would refuse the form with this backend)
+    tr.codes_form = "owner"
+    if small_cap:
+        tr._own_cap = 9                                           # every pair overflows: bucket + exchange + plan are redone
+    o = tr._compute_plan(pos, b.rng_stream, 1)
+    n_per = -(-n_all // G)
+    table = o.cnt_all.view(G, G).numpy().copy()
+    want_table = np.zeros((G, G), dtype=np.int64)
+    for src in range(G):
+        lo, hi = min(n_all, src * n_per), min(n_all, (src + 1) * n_per)
+        _, per_dest = U.np_bucket(codes[lo * NEG:hi * NEG], hi - lo, NEG, lo, G)
+        want_table[src] = [len(x) for x in per_dest]
+    assert (table == want_table).all(), (table, want_table)
+    if small_cap:
+        assert table.max() > o.own_cap == 9
+    tr._finish_plan(o)                                            # reads the table; redoes the plan when a pair overflowed
+    assert tr.owner_replans == (1 if small_cap else 0)
+    assert tr._own_cap == (int(want_table.max()) if small_cap else int(1.06 * n_per * NEG / G) + 4096)
+    recs, off = U.np_owned(codes, n_all, NEG, G, rank)
+    assert int(tr._own_off[n_all]) == len(recs)
+    np.testing.assert_array_equal(tr._own_rec[:3 * len(recs)].numpy().reshape(-1, 3), recs)
+    np.testing.assert_array_equal(tr._own_off[:n_all + 1].numpy(), off)
+    np.testing.assert_array_equal(o.need_all[:n_all].numpy().astype(np.int64) & 0xFFFFFFFF, codes[::NEG] & U.NEED)
+    for x in range(2):
+        assert torch.equal(tr._slot[x][:n_all], slots[x])
+        lo_hi = [(lo, int(tr._own_cnt[x][k])) for k, (_, lo, _) in enumerate(tr._parts)]
+        for lo, n in lo_hi:
+            assert torch.equal(tr._own[x][lo:lo + n], owns[x][lo:lo + n])
+    assert torch.equal(o.cnt_host, cnt)
+    info = tr.check()
+    assert info["codes"] == "owner" and info["owner_code_capacity_per_pair"] == tr._own_cap
+    assert info["code_bytes_received_per_epoch"] == 12 * G * tr._own_cap + 4 * G * n_per + 4 * G * G
+    st = tr._build_part_step(len(tr._parts) - 1, 1)               # the step fields of the last part: its offsets into the list
+    _, lo, hi = tr._parts[-1]
+    assert st.own_rec is tr._own_rec and torch.equal(st.own_off, tr._own_off[lo:hi + 1])
+    return refused
 
 
 @pytest.mark.timeout(300)
@@ -98,24 +89,10 @@ def _worker(rank, world, rdv, ret, n_ent, small_cap):
 def test_owner_plan_lists_equal_the_gather_plan(world, n_ent, small_cap):
     """world 3 with 602 entities: ragged shares (the last home rank's is shorter); 80 entities: a sixth of the positives need both
     vectors; small_cap: a pair capacity of 9 records, so the first exchange overflows everywhere and is redone at the exact maximum."""
-    ctx = mp.get_context("spawn")
-    ret = ctx.Queue()
-    rdv = tempfile.mktemp(prefix="mke_rdv_")
-    procs = [ctx.Process(target=_worker, args=(r, world, rdv, ret, n_ent, small_cap)) for r in range(world)]
-    for p in procs:
-        p.start()
-    try:
-        for _ in range(world):
-            rank, out = ret.get(timeout=240)
-            assert out is True, f"rank {rank}: {out}"
-        for p in procs:
-            p.join(60)
-            assert p.exitcode == 0
-    finally:
-        for p in procs:
-            if p.is_alive():
-                p.terminate()
-                p.join(10)
+    got = ranks.run_ranks(world, _worker, (n_ent, small_cap), limit=240)
+    assert sorted(got) == list(range(world))
+    for rank, out in got.items():
+        assert out is True, f"rank {rank}: {out}"
 
 
 def test_the_new_entry_points_validate_without_a_gpu():

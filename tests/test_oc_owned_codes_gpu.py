@@ -6,14 +6,13 @@ scan (coefficients, gradient-vector slots and loss partials, bit for bit), and t
 No multi-GPU link is exercised anywhere here: beyond one rank the collectives run host-staged only."""
 import ctypes as C
 import os
-import tempfile
-import time
 
 import numpy as np
 import pytest
 import torch
 
 import oc_owned_util as U
+import ranks
 from multike_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -285,72 +284,33 @@ def _run_pair(rank, world, comm, kw, native, kgs=None):
     return bad, info
 
 
-def _trainer_worker(rank, world, rdv, ret, what):
-    import torch.distributed as dist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
+def _trainer_worker(rank, world, what):
+    """One rank (sharing the GPU with the others) with the whole job of `what`; "rccl": in a one-rank RCCL group."""
     os.environ.pop("MKE_OC_CODES", None)
     rccl = what == "rccl"
     if world == 1:
         os.environ["MKE_OC_FORCE_COLLECTIVES"] = "1"
-    try:
-        if rccl:
-            dist.init_process_group("nccl", init_method=f"file://{rdv}", rank=0, world_size=1, device_id=torch.device("cuda", 0))
-        else:
-            dist.init_process_group("gloo", init_method=f"file://{rdv}", rank=rank, world_size=world)
-        from multike_amd.distributed_oc import OcHostStagedComm
-        torch.cuda.set_device(0)
-        comm = None if rccl else OcHostStagedComm()
-        out = []
-        if what == "peer":
-            # the peer-direct transport of the entity-major form (IPC-mapped send blocks and inboxes, Python step loop, one part):
-            # the mirror instantiations of the score kernels on owned lists
-            for zipf in (0.0, 1.0):
-                kw = dict(n_ent=600, dim=75, neg=8, b=max(1, 700 // world), zipf=zipf, peer_direct=True)
-                out.append(_run_pair(rank, world, comm, kw, False))
-        elif what == "overflow":
-            # nine tenths of the corrupt entities belong to rank 0: the pair capacity 1.06 n_per N / 2 + 4096 does not hold them
-            kw = dict(n_ent=400, dim=20, neg=25, b=700)
-            bad, info = _run_pair(rank, world, comm, kw, True, kgs=U.SkewKGs())
+    from multike_amd.distributed_oc import OcHostStagedComm
+    torch.cuda.set_device(0)
+    comm = None if rccl else OcHostStagedComm()
+    out = []
+    if what == "peer":
+        # the peer-direct transport of the entity-major form (IPC-mapped send blocks and inboxes, Python step loop, one part):
+        # the mirror instantiations of the score kernels on owned lists
+        for zipf in (0.0, 1.0):
+            kw = dict(n_ent=600, dim=75, neg=8, b=max(1, 700 // world), zipf=zipf, peer_direct=True)
+            out.append(_run_pair(rank, world, comm, kw, False))
+    elif what == "overflow":
+        # nine tenths of the corrupt entities belong to rank 0: the pair capacity 1.06 n_per N / 2 + 4096 does not hold them
+        kw = dict(n_ent=400, dim=20, neg=25, b=700)
+        bad, info = _run_pair(rank, world, comm, kw, True, kgs=U.SkewKGs())
+        out.append((bad, info))
+    else:
+        for cfg in (CONFIGS[:1] if rccl else CONFIGS):
+            kw = dict(n_ent=600, dim=75, neg=8, b=max(1, 700 // world), zipf=cfg["zipf"], chunks=2 if cfg["zipf"] else 1)
+            bad, info = _run_pair(rank, world, comm, kw, cfg["native"])
             out.append((bad, info))
-        else:
-            for cfg in (CONFIGS[:1] if rccl else CONFIGS):
-                kw = dict(n_ent=600, dim=75, neg=8, b=max(1, 700 // world), zipf=cfg["zipf"], chunks=2 if cfg["zipf"] else 1)
-                bad, info = _run_pair(rank, world, comm, kw, cfg["native"])
-                out.append((bad, info))
-        ret.put((rank, out))
-    except Exception as e:      # noqa: BLE001 — reported to the parent, which fails the test
-        import traceback
-        ret.put((rank, "".join(traceback.format_exception(e))))
-    finally:
-        if dist.is_initialized():
-            dist.destroy_process_group()
-
-
-def _spawn(world, what, limit):
-    """`world` rank processes sharing the GPU, each with the whole job; every rank's answer within `limit` seconds, the processes
-    joined (ended, if one is still there) whatever happened."""
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
-    ret = ctx.Queue()
-    rdv = tempfile.mktemp(prefix="mke_rdv_")
-    procs = [ctx.Process(target=_trainer_worker, args=(r, world, rdv, ret, what)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got, end = {}, time.monotonic() + limit
-    try:
-        while len(got) < world:
-            rank, out = ret.get(timeout=max(1.0, end - time.monotonic()))
-            assert not isinstance(out, str), f"rank {rank}:\n{out}"
-            got[rank] = out
-        for p in procs:
-            p.join(60)
-            assert p.exitcode == 0
-    finally:
-        for p in procs:
-            if p.is_alive():
-                p.terminate()
-                p.join(10)
-    return got
+    return out
 
 
 @pytest.mark.timeout(420)
@@ -359,7 +319,7 @@ def test_owner_trainer_is_the_gather_trainer_bit_for_bit(world):
     """Two epochs and a step, plans prefetched, native step loop and Python loop, uniform triples (one part per step) and Zipf(1.0)
     triples (hub entities: long rows; two parts per step): entity shard, Adagrad slot, relation table, the loss ring and the epoch
     loss are bit-identical between the two forms on every rank.  World 1 forces the collectives (host-staged)."""
-    got = _spawn(world, "staged", 360)
+    got = ranks.run_ranks(world, _trainer_worker, ("staged",), limit=360)
     for rank, out in got.items():
         assert len(out) == len(CONFIGS)
         for cfg, (bad, info) in zip(CONFIGS, out):
@@ -373,7 +333,7 @@ def test_owner_trainer_is_the_gather_trainer_bit_for_bit(world):
 def test_owner_trainer_over_a_one_rank_rccl_communicator():
     """World 1 with the collectives forced over the real one-rank RCCL communicator (the flags' and counts' all-gathers and the
     all-to-all issued for real, at the plan's fixed point of the step sequence, native step loop): bit-identical to `gather`."""
-    got = _spawn(1, "rccl", 240)
+    got = ranks.run_ranks(1, _trainer_worker, ("rccl",), limit=240, backend="nccl")
     (bad, info), = got[0]
     assert not bad, bad
     assert info["communicator"] == "OcRcclComm" and info["codes"] == "owner" and info["native_step_loop"]
@@ -383,7 +343,7 @@ def test_owner_trainer_over_a_one_rank_rccl_communicator():
 def test_owner_trainer_on_the_peer_direct_transport():
     """Two ranks, `peer_direct=True, entity_major=True`: the score launch reads the owners' send blocks, mirrors them and writes
     the owners' inboxes — on owned lists (the same kernels with both flags): bit-identical to `gather` on that transport."""
-    got = _spawn(2, "peer", 240)
+    got = ranks.run_ranks(2, _trainer_worker, ("peer",), limit=240)
     for rank, out in got.items():
         assert len(out) == 2
         for bad, info in out:
@@ -397,7 +357,7 @@ def test_owner_plan_is_redone_once_when_a_pair_overflows():
     """Two ranks, a KG pair whose corrupt entities are nine tenths rank 0's: the default pair capacity overflows in the first plan,
     every rank sees it in the same counts table and buckets, exchanges and plans again, in line, at the exact maximum (kept for
     the epochs that follow) — and the result is `gather`'s bit for bit."""
-    got = _spawn(2, "overflow", 240)
+    got = ranks.run_ranks(2, _trainer_worker, ("overflow",), limit=240)
     for rank, out in got.items():
         (bad, info), = out
         assert not bad, (rank, bad)

@@ -10,15 +10,11 @@ with the collective entity-major form at two ranks (the forms differ only in whe
 and a + b is one float whatever the order), an epoch boundary with the peer blocks mapped again, and three ranks (the
 division form of the owner arithmetic, three writers per inbox: the rank order of the sum is what makes two runs agree)."""
 import functools
-import os
-import queue
-import tempfile
-import traceback
-from datetime import timedelta
 
 import numpy as np
 import pytest
 
+import ranks
 from test_distributed_oc_gpu import B, DIM, N_ENT, N_REL, NEG, SEED, _make, _reference
 
 pytestmark = pytest.mark.gpu
@@ -43,90 +39,44 @@ def _trainer(rank, world, comm, form, cfg):
                                 entity_major=True, tuning=cfg["tuning"])
 
 
-def _worker(rank, world, rdv, ret, forms, cfg):
+def _worker(rank, world, forms, cfg):
     """One rank: every form of `forms` in turn on the same inputs (one process group); rank 0 reports."""
     import torch
-    import torch.distributed as dist
-    try:
-        os.environ["MASTER_ADDR"] = "127.0.0.1"
-        # a rank that dies must not leave its peers in a collective for long
-        dist.init_process_group("gloo", init_method=f"file://{rdv}", rank=rank, world_size=world, timeout=timedelta(seconds=120))
-        try:
-            from multike_amd.distributed_oc import OcHostStagedComm
-            torch.cuda.set_device(0)
-            out = {}
-            for form in forms:
-                tr = _trainer(rank, world, OcHostStagedComm(), form, cfg)
-                chk = tr.check()
-                assert tr.em and chk["entity_major"]
-                assert bool(tr.peer_direct) == (form == PEER) == chk["peer_direct"]
-                assert not chk["native_step_loop"] or form == COLL
-                steps = cfg["steps"] if cfg["steps"] > 0 else tr.steps - cfg["steps"]      # -k: an epoch and k steps
-                if cfg.get("max_epoch"):
-                    assert tr.steps <= cfg["max_epoch"], tr.steps
-                remapped = False
-                ring = []
-                for i in range(steps):
-                    if form == PEER and cfg.get("remap") and i == tr.steps:
-                        # the capacity "grows" at the boundary: every exchange buffer is allocated and the peers' blocks mapped again
-                        old, tr.C = tr._inbox, 0
-                    tr.step(i)
-                    if form == PEER and cfg.get("remap") and i == tr.steps:
-                        remapped = tr._inbox is not old and tr.C > 0
-                    ring.append(tr.loss_ring[(i % tr.steps) * tr.chunks].cpu().numpy().copy())     # this rank's partials of the step, raw
-                torch.cuda.synchronize()
-                kernel_q = bool(cfg.get("tuning", {}).get("oc_score_quarter", 0))
-                res = dict(full=tr.gather_entity_table().cpu().numpy(), rel=tr.rel[:, :tr.dim].cpu().numpy().copy(), ring=np.stack(ring),
-                           clean=tr.scratch_clean(), check=tr.check(), spe=tr.steps, steps=steps, remapped=remapped, quarter=kernel_q)
-                res["loss"] = tr.epoch_loss()
-                res["long_rows"] = tr.comm.all_gather_object(res["check"]["long_rows_per_global_step"])     # every rank's
-                out[form] = res
-                del tr
-            if rank == 0:
-                ret.put(("ok", out))
-        finally:
-            dist.destroy_process_group()
-    except Exception:   # noqa: BLE001 — reported to the test, which fails with the text
-        ret.put(("error", f"rank {rank}: {traceback.format_exc()}"))
-        raise
+    from multike_amd.distributed_oc import OcHostStagedComm
+    torch.cuda.set_device(0)
+    out = {}
+    for form in forms:
+        tr = _trainer(rank, world, OcHostStagedComm(), form, cfg)
+        chk = tr.check()
+        assert tr.em and chk["entity_major"]
+        assert bool(tr.peer_direct) == (form == PEER) == chk["peer_direct"]
+        assert not chk["native_step_loop"] or form == COLL
+        steps = cfg["steps"] if cfg["steps"] > 0 else tr.steps - cfg["steps"]      # -k: an epoch and k steps
+        if cfg.get("max_epoch"):
+            assert tr.steps <= cfg["max_epoch"], tr.steps
+        remapped = False
+        ring = []
+        for i in range(steps):
+            if form == PEER and cfg.get("remap") and i == tr.steps:
+                # the capacity "grows" at the boundary: every exchange buffer is allocated and the peers' blocks mapped again
+                old, tr.C = tr._inbox, 0
+            tr.step(i)
+            if form == PEER and cfg.get("remap") and i == tr.steps:
+                remapped = tr._inbox is not old and tr.C > 0
+            ring.append(tr.loss_ring[(i % tr.steps) * tr.chunks].cpu().numpy().copy())     # this rank's partials of the step, raw
+        torch.cuda.synchronize()
+        kernel_q = bool(cfg.get("tuning", {}).get("oc_score_quarter", 0))
+        res = dict(full=tr.gather_entity_table().cpu().numpy(), rel=tr.rel[:, :tr.dim].cpu().numpy().copy(), ring=np.stack(ring),
+                   clean=tr.scratch_clean(), check=tr.check(), spe=tr.steps, steps=steps, remapped=remapped, quarter=kernel_q)
+        res["loss"] = tr.epoch_loss()
+        res["long_rows"] = tr.comm.all_gather_object(res["check"]["long_rows_per_global_step"])     # every rank's
+        out[form] = res
+        del tr
+    if rank == 0:
+        return out
 
 
-def _run_ranks(world, forms, cfg, limit=240):
-    """Spawn the ranks, return rank 0's report; fails as soon as a rank has died, and leaves no process behind."""
-    import time
-    import torch.multiprocessing as mp
-    assert world <= 3
-    rdv = tempfile.mktemp(prefix="mke_rdv_")     # rendezvous FILE: no TCP port to collide on
-    ctx = mp.get_context("spawn")
-    ret = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, world, rdv, ret, forms, cfg)) for r in range(world)]
-    try:
-        for p in procs:
-            p.start()
-        t_end = time.monotonic() + limit
-        got = None
-        while got is None:
-            try:
-                got = ret.get(timeout=1.0)
-            except queue.Empty:
-                dead = [p.exitcode for p in procs if p.exitcode not in (None, 0)]
-                assert not dead, f"a rank exited with {dead} before reporting"
-                assert time.monotonic() < t_end, "the ranks did not report in time"
-        assert got[0] == "ok", got[1]
-        for p in procs:
-            p.join(60)
-            assert p.exitcode == 0, p.exitcode
-        return got[1]
-    finally:
-        for p in procs:
-            if p.is_alive():
-                p.terminate()
-                p.join(10)
-            if p.is_alive():
-                p.kill()
-                p.join(10)
-        if os.path.exists(rdv):
-            os.unlink(rdv)
+RUN = dict(limit=240, group_timeout=120)     # collectives limited to 120 s: a rank that dies must not leave its peers in one for long
 
 
 @functools.lru_cache(maxsize=None)
@@ -155,7 +105,7 @@ def _assert_same_bits(a, b):
 def test_two_ranks_equal_dense_oracle(neg):
     """World 2, 7 steps: owner = id & 1 (the shift / mask instantiation), each rank's score launch mirrors all 600 positives'
     vectors and sums two writer slices per owned slot."""
-    res = _run_ranks(2, (PEER,), dict(steps=7, neg=neg))[PEER]
+    res = ranks.run_ranks(2, _worker, ((PEER,), dict(steps=7, neg=neg)), **RUN)[0][PEER]
     _assert_oracle(res, 2, neg)
 
 
@@ -172,7 +122,7 @@ def test_two_ranks_equal_collective_form_bit_for_bit(name, cfg):
     """The same inputs through the peer-direct and the collective (host-staged all-gather / reduce-scatter) entity-major forms:
     the mirror holds what the all-gather would have delivered, the summed block what the reduce-scatter would have (two writers:
     a + b either way), the second pass is the same launch — tables and every step's loss partials equal as raw floats."""
-    out = _run_ranks(2, (PEER, COLL), cfg)
+    out = ranks.run_ranks(2, _worker, ((PEER, COLL), cfg), **RUN)[0]
     _assert_same_bits(out[PEER], out[COLL])
     assert out[PEER]["clean"] and out[COLL]["clean"]
     if name == "zipf":
@@ -184,7 +134,7 @@ def test_two_ranks_equal_collective_form_bit_for_bit(name, cfg):
 def test_two_ranks_across_an_epoch_boundary_equal_collective_form():
     """An epoch of at most 4 global steps, then two more: the shuffle, the prefetched plan and — forced here by dropping the
     capacity at the boundary — new exchange buffers with the peers' blocks mapped a second time (`_map_peers`)."""
-    out = _run_ranks(2, (PEER, COLL), dict(steps=-2, n_ent=500, max_epoch=4, remap=True))
+    out = ranks.run_ranks(2, _worker, ((PEER, COLL), dict(steps=-2, n_ent=500, max_epoch=4, remap=True)), **RUN)[0]
     assert out[PEER]["remapped"] and out[PEER]["steps"] == out[PEER]["spe"] + 2 == out[COLL]["steps"]
     _assert_same_bits(out[PEER], out[COLL])
 
@@ -194,6 +144,6 @@ def test_three_ranks_equal_dense_oracle_and_repeat_bit_for_bit():
     """World 3: owner = id % 3 by division, three writer slices per inbox summed as (s0 + s1) + s2 on every run — two runs in
     fresh process groups agree to the bit (with the collective form gloo's own summation order decides, so that form is not the
     yardstick here); the float64 oracle is."""
-    runs = [_run_ranks(3, (PEER,), dict(steps=5))[PEER] for _ in range(2)]
+    runs = [ranks.run_ranks(3, _worker, ((PEER,), dict(steps=5)), **RUN)[0][PEER] for _ in range(2)]
     _assert_oracle(runs[0], 3, NEG)
     _assert_same_bits(runs[0], runs[1])

@@ -7,26 +7,22 @@ the GPU (tests/test_distributed_oc_gpu.py)."""
 import os
 import subprocess
 import sys
-import tempfile
 
 import numpy as np
 import pytest
 import torch
+
+import ranks
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def one_rank_group():
+    import contextlib
     import torch.distributed as dist
-    created = False
-    if not dist.is_initialized():
-        dist.init_process_group("nccl", init_method="file://" + tempfile.mktemp(prefix="mke_rdv_"), rank=0, world_size=1,
-                                device_id=torch.device("cuda", 0))
-        created = True
-    yield dist
-    if created:
-        dist.destroy_process_group()
+    with contextlib.nullcontext() if dist.is_initialized() else ranks.one_rank_group():
+        yield dist
 
 
 def test_collectives_on_the_compute_stream(one_rank_group):
