@@ -14,7 +14,7 @@ from . import _lib
 from .base import bootstrap as boot
 from .base import evaluation as eva
 from .base.alignment import assignment_alignment, mutual_alignment, stable_alignment
-from .base.batch import neighbour_table
+from .base.batch import neighbour_table, refresh_seed
 from .base.bootstrap import bootstrap_options
 from .base.kgs import TripleArray
 from .MultiKE_model import MultiKE
@@ -461,19 +461,23 @@ class _ScheduledMultiKE(MultiKE):
             return
         t1 = time.time()
         assert 0.0 < a.truncated_epsilon < 1.0
+        cap = int(getattr(a, "truncated_cap", 0) or 0)     # > 0: capped tables; 0: the call made without it
         out = []
         for kg, useful in ((kgs.kg1, kgs.useful_entities_list1), (kgs.kg2, kgs.useful_entities_list2)):
             k = int((1 - a.truncated_epsilon) * kg.entities_num)
             # the reference's random.sample(candidates, neg_triple_num) raises ValueError on a shorter list
             # (code/base/batch.py:96-99); say so before the kernels see it
-            if k < a.neg_triple_num or k > len(useful):
+            if min(k, cap or k) < a.neg_triple_num or k > len(useful):
                 raise ValueError(f"truncated sampling: {k} neighbours per entity (int((1 - truncated_epsilon) * "
-                                 f"{kg.entities_num})) must be >= neg_triple_num ({a.neg_triple_num}) and <= the "
+                                 f"{kg.entities_num}))" + (f", capped to truncated_cap = {cap}," if cap else "") +
+                                 f" must be >= neg_triple_num ({a.neg_triple_num}) and <= the "
                                  f"{len(useful)} useful entities of the KG")
             emb = self.rv_ent_embeds.lookup(self._ids(useful))
-            out.append(neighbour_table(emb, useful, k, kgs.entities_num, device=self.device))
+            capped = dict(cap=cap, seed=refresh_seed(getattr(a, "seed", 0), i, len(out))) if cap else {}
+            out.append(neighbour_table(emb, useful, k, kgs.entities_num, device=self.device, **capped))
         self._neighbors = tuple(out)
-        print("generating neighbors of {} entities costs {:.3f} s.".format(len(self._entity_list), time.time() - t1))
+        print("generating neighbors of {} entities costs {:.3f} s.".format(len(self._entity_list), time.time() - t1) +
+              (" (tables capped to {} of the neighbours)".format(cap) if cap else ""))
 
     def _ids(self, lst):
         import torch

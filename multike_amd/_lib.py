@@ -378,6 +378,43 @@ def topk_long(vals: torch.Tensor, k: int, id_map=None) -> torch.Tensor:
     return out
 
 
+THIN_SO_PATH = os.path.join(_HERE, "libmultike_thin.so")     # include/multike_thin.h: a library and a generated module of its own
+_thin = None
+
+
+def thin_lib():
+    """Load libmultike_thin.so (once), typed from _abi_thin.py as lib() is from _abi.py.  Raises if it has not been built."""
+    global _thin
+    if _thin is None:
+        from . import _abi_thin
+        if not os.path.exists(THIN_SO_PATH):
+            raise MultiKEHipError(f"{THIN_SO_PATH} not found: build it with `make -C multike_amd/csrc`.  multike_amd has no CPU fallback.")
+        L = C.CDLL(THIN_SO_PATH)
+        for name, (restype, argtypes) in _abi_thin.FUNCTIONS.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _thin = L
+    return _thin
+
+
+def idlist_thin(ids: torch.Tensor, m: int, seed: int, row_ids=None) -> torch.Tensor:
+    """mke_idlist_thin over the id lists ids int32 [rows, k] (unit column stride) -> int32 [rows, m]: the keyed m-subset of
+    every row, in list order.  row_ids int32 [rows]: the entity id that keys each row (None: the row number)."""
+    if ids.dim() != 2 or ids.stride(1) != 1:
+        raise MultiKEHipError("idlist_thin: ids must be [rows, k] with unit column stride")
+    rows, k = ids.shape
+    if row_ids is not None and row_ids.numel() != rows:
+        raise MultiKEHipError("idlist_thin: one row id per row")
+    out = torch.empty(rows, max(0, int(m)), dtype=torch.int32, device=ids.device)
+    L = thin_lib()
+    rc = L.mke_idlist_thin(ids.data_ptr() if ids.is_cuda and ids.dtype == torch.int32 else ptr(ids, torch.int32, "ids"),
+                           rows, k, ids.stride(0) if rows > 1 else k, ptr(row_ids, torch.int32, "row_ids"), int(m),
+                           int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(out, torch.int32, "out"), _stream())
+    if rc != 0:
+        raise MultiKEHipError(f"mke_idlist_thin failed (code {rc}): {L.mke_thin_last_error().decode('utf-8', 'replace')}")
+    return out
+
+
 def mapping_scratch_floats(n: int, dim: int) -> int:
     return int(lib().mke_mapping_scratch_floats(n, dim))
 

@@ -104,11 +104,11 @@ def generate_relation_triple_batch_queue(triple_list1, triple_list2, triple_set1
 
 
 def neighbour_table(entity_embeds, entity_list, neighbors_num, n_ent_total, device="cuda", block_rows=4096,
-                    rows_per_launch=None, part=None):
+                    rows_per_launch=None, part=None, *, cap=None, seed=0, round_floats=None):
     """Truncated-sampling k-NN refresh on the device (code/base/batch.py:119-150): inner product of the (already
     row-normalised) relation-view rows of one KG's useful entities, top `neighbors_num` per row INCLUDING the entity
-    itself, unordered.  Returns (cand_table [n_ent_total, k] int32, cand_valid [n_ent_total] uint8) for
-    `KGSide.set_neighbours`.
+    itself, unordered.  Returns (cand_table [n_ent_total, k] int32 — [n_ent_total, cap] when capped, below —, cand_valid
+    [n_ent_total] uint8) for `KGSide.set_neighbours`.
 
     When k is a small share of a long row the n x n similarity matrix is never built: a per-row threshold a bit below
     the k-th largest value is estimated from a fixed column sample (`mke_sim_sample` + `mke_topk_rows`),
@@ -119,17 +119,33 @@ def neighbour_table(entity_embeds, entity_list, neighbors_num, n_ent_total, devi
 
     part = (r, G): compute only the r-th of G contiguous slices of the rows (in the function's own working order) — the
     multi-GPU refresh: every rank holds all rows, ranks the slice it is given against all columns and the slices are
-    all-gathered.  Returns (table, valid, ids_of_the_slice) with only those rows filled."""
+    all-gathered.  Returns (table, valid, ids_of_the_slice) with only those rows filled.
+
+    cap (keyword only; None or >= k: off, today's table): the table is [n_ent_total, cap] — row e holds a uniform random
+    cap-subset of e's exact top-k set, `mke_idlist_thin` of the list the uncapped call would have written, keyed by (seed, e)
+    and applied to every block's [rows, k] list before it is scattered, so that no k-wide array outlives one launch or one
+    round.  The kept set is a function of (seed, e, the top-k set) alone: the same whatever the path, the blocking or the
+    slice.  round_floats (keyword only; default 2^28 floats = 1 GiB): the whole-row path ranks at most
+    max(1, round_floats // n) rows at a time instead of `block_rows` — only when cap or round_floats is given; results
+    never depend on it."""
     from .. import _lib
+    k = int(neighbors_num)
+    if cap is not None and int(cap) < 1:
+        raise _lib.MultiKEHipError(f"neighbour_table: cap must be >= 1 (or None = uncapped), got {cap}")
+    if round_floats is not None and int(round_floats) < 1:
+        raise _lib.MultiKEHipError(f"neighbour_table: round_floats must be >= 1, got {round_floats}")
+    bounded = cap is not None or round_floats is not None     # whole-row rounds sized by round_floats, not block_rows
+    width = int(cap) if cap is not None and int(cap) < k else k
     e = (entity_embeds.to(device).float() if isinstance(entity_embeds, torch.Tensor)
          else torch.as_tensor(np.asarray(entity_embeds), dtype=torch.float32, device=device))
     ids = torch.as_tensor(np.asarray(entity_list), dtype=torch.int64, device=device)
     n, d = e.shape
-    k = int(neighbors_num)
-    table = torch.zeros(n_ent_total, k, dtype=torch.int32, device=device)
+    table = torch.zeros(n_ent_total, width, dtype=torch.int32, device=device)
     valid = torch.zeros(n_ent_total, dtype=torch.uint8, device=device)
-    n_samp, cap = 4096, _pow2_at_least(int(1.4 * k) + 64)
-    short = n >= 8 * n_samp and cap * 4 <= n and cap <= 4096
+    n_samp, slots = 4096, _pow2_at_least(int(1.4 * k) + 64)
+    short = n >= 8 * n_samp and slots * 4 <= n and slots <= 4096
+    if bounded:
+        block_rows = max(1, int(2 ** 28 if round_floats is None else round_floats) // max(n, 1))
     if d > _lib.SIM_SELECT_KPADS[-1]:     # wider than the widest table the package supports (MKE_MAX_STRIDE): no second backend
         raise _lib.MultiKEHipError(f"neighbour_table: rows of {d} floats exceed the widest k_sim_select instantiation "
                                    f"({_lib.SIM_SELECT_KPADS[-1]} = MKE_MAX_STRIDE)")
@@ -144,6 +160,15 @@ def neighbour_table(entity_embeds, entity_list, neighbors_num, n_ent_total, devi
         sim = _lib.sim_sample(src, kpad, 0, int(src.shape[0]), cols)
         return _lib.topk_long(sim, k).long()          # exact top k of whole rows: radix select in the package's own kernel
 
+    def put(rows, lists=None):
+        """scatter the [rows, k] entity-id lists of the working rows `rows` into the table — through the thinning kernel, keyed
+        by the rows' entity ids, when the table is capped.  lists None: whole-row top k of those rows."""
+        if lists is None:
+            lists = ids[full_width(rows)].to(torch.int32)
+        if width < k:
+            lists = _lib.idlist_thin(lists, width, seed, row_ids=ids[rows].to(torch.int32))
+        table[ids[rows]] = lists
+
     def _padded(x):
         out = torch.zeros(x.shape[0], kpad, dtype=torch.float32, device=device)
         out[:, :d] = x
@@ -155,7 +180,7 @@ def neighbour_table(entity_embeds, entity_list, neighbors_num, n_ent_total, devi
         ep = _padded(e)
         for lo in range(p_lo, p_hi, block_rows):
             hi = min(p_hi, lo + block_rows)
-            table[ids[lo:hi]] = ids[full_width(slice(lo, hi))].to(torch.int32)
+            put(slice(lo, hi))
         valid[ids[p_lo:p_hi]] = 1
         return (table, valid) if part is None else (table, valid, ids[p_lo:p_hi])
 
@@ -181,7 +206,7 @@ def neighbour_table(entity_embeds, entity_list, neighbors_num, n_ent_total, devi
     samp = keyed_perm(0x1B873593)[:n_samp]
     es = ep[samp].contiguous()
     m = min(n_samp, int(math.ceil(1.4 * k * n_samp / n)) + 8)
-    chunk = (1 << 29) // cap - 128                        # rows per launch: 2^29 candidate slots (8 bytes each) at most
+    chunk = (1 << 29) // slots - 128                      # rows per launch: 2^29 candidate slots (8 bytes each) at most
     if rows_per_launch:
         chunk = min(chunk, int(rows_per_launch))
     for lo in range(p_lo, p_hi, chunk):
@@ -195,17 +220,22 @@ def neighbour_table(entity_embeds, entity_list, neighbors_num, n_ent_total, devi
             b = min(hi, a + 16384)
             _, kth, _ = _lib.topk_rows(_lib.sim_sample(ep, kpad, a, b, es), m, want_idx=False, want_kth=True)
             tau[a - lo:b - lo] = kth
-        cand, cnt = _lib.sim_select(ep, kpad, lo, hi, tau, n_seg, cap // n_seg)
+        cand, cnt = _lib.sim_select(ep, kpad, lo, hi, tau, n_seg, slots // n_seg)
         out, status = _lib.topk_candidates(cand, cnt, k, id_map=ids32)
-        table[ids[lo:hi]] = out
+        put(slice(lo, hi), out)                           # rows with status != 0 hold no list yet: redone below
         bad = torch.nonzero(status).reshape(-1)
         if bad.numel():
             rows = bad + lo
             for a in range(0, rows.numel(), block_rows):
-                r = rows[a:a + block_rows]
-                table[ids[r]] = ids[full_width(r)].to(torch.int32)
+                put(rows[a:a + block_rows])
     valid[ids[p_lo:p_hi]] = 1
     return (table, valid) if part is None else (table, valid, ids[p_lo:p_hi])
+
+
+def refresh_seed(seed, epoch: int, kg_index: int) -> int:
+    """The 64-bit seed of a capped refresh (`neighbour_table(cap=, seed=)`): a pure function of the run's seed, the epoch of
+    the refresh and the KG (0 / 1) — the same on every rank, another subset at every refresh."""
+    return ((int(seed) & 0xFFFFFFFF) << 32) | ((int(epoch) & 0x7FFFFFFF) << 1) | (int(kg_index) & 1)
 
 
 def _pow2_at_least(x: int) -> int:

@@ -29,7 +29,7 @@ import torch.distributed as dist
 from . import _lib
 from .attr_cnn import AttrCNN
 from .base.alignment import alignment_counts, csls_means, prepare_operands, print_results, tie_aware_metrics
-from .base.batch import neighbour_table
+from .base.batch import neighbour_table, refresh_seed
 from .distributed_model import ShardedITC
 from .MultiKE_CSL import MultiKE_CV
 from .MultiKE_Late import MultiKE_Late, _compute_weight
@@ -281,19 +281,23 @@ class _ShardedMixin:
         if a.neg_sampling != 'truncated' or i % a.truncated_freq != 0:
             return
         t1 = time.time()
+        cap = int(getattr(a, "truncated_cap", 0) or 0)     # > 0: capped tables; 0: the calls made without it
         out = []
         for kg, useful in ((kgs.kg1, kgs.useful_entities_list1), (kgs.kg2, kgs.useful_entities_list2)):
             k = int((1 - a.truncated_epsilon) * kg.entities_num)
-            if k < a.neg_triple_num or k > len(useful):
-                raise ValueError(f"truncated sampling: {k} neighbours per entity must be >= neg_triple_num ({a.neg_triple_num}) "
+            if min(k, cap or k) < a.neg_triple_num or k > len(useful):
+                raise ValueError(f"truncated sampling: {k} neighbours per entity" + (f", capped to truncated_cap = {cap}," if cap else "") +
+                                 f" must be >= neg_triple_num ({a.neg_triple_num}) "
                                  f"and <= the {len(useful)} useful entities of the KG")
             emb = self.rows("rv", useful)
+            # the same seed on every rank: a row's kept set does not depend on the slice that computes it
+            capped = dict(cap=cap, seed=refresh_seed(getattr(a, "seed", 0), i, len(out))) if cap else {}
             if G == 1:
-                out.append(neighbour_table(emb, useful, k, kgs.entities_num, device=self.device))
+                out.append(neighbour_table(emb, useful, k, kgs.entities_num, device=self.device, **capped))
                 continue
-            table, valid, ids = neighbour_table(emb, useful, k, kgs.entities_num, device=self.device, part=(self.rank, G))
+            table, valid, ids = neighbour_table(emb, useful, k, kgs.entities_num, device=self.device, part=(self.rank, G), **capped)
             pad = -(-len(useful) // G)
-            rows = torch.zeros(pad, k, dtype=torch.int32, device=self.device)
+            rows = torch.zeros(pad, table.shape[1], dtype=torch.int32, device=self.device)
             idp = torch.full((pad,), -1, dtype=torch.int64, device=self.device)
             rows[:ids.numel()] = table[ids]
             idp[:ids.numel()] = ids
@@ -308,7 +312,8 @@ class _ShardedMixin:
             out.append((table, valid))
         self._neighbors = tuple(out)
         if self.rank == 0:
-            print("generating neighbors of {} entities costs {:.3f} s.".format(len(self._entity_list), time.time() - t1))
+            print("generating neighbors of {} entities costs {:.3f} s.".format(len(self._entity_list), time.time() - t1) +
+                  (" (tables capped to {} of the neighbours)".format(cap) if cap else ""))
 
     def save(self):
         full = self.m.gather()                       # collective: every rank takes part, rank 0 writes

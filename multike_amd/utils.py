@@ -38,6 +38,10 @@ def default_args(**over):
         max_epoch=200, shared_learning_max_epoch=200, batch_size=5000, entity_batch_size=5000, attribute_batch_size=5000,
         # negative sampling
         neg_triple_num=10, neg_sampling="truncated", truncated_epsilon=0.98, truncated_freq=20,
+        # capped neighbour tables of the truncated sampler (0 = off, the reference's tables): every refresh keeps a uniform random
+        # `truncated_cap`-subset of each entity's exact int((1 - truncated_epsilon) * |E_kg|) neighbours, so the two tables grow
+        # with |E| * cap instead of |E|^2; every negative is still uniform over the exact neighbour set
+        truncated_cap=0,
         # host-side worker counts of the reference (accepted, unused: batches are produced on the device)
         batch_threads_num=4, test_threads_num=8,
         # validation / early stopping

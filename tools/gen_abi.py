@@ -2,6 +2,7 @@
 """Generate multike_amd/_abi.py, the ctypes view of the C-ABI, from include/multike_hip.h.
 
     python tools/gen_abi.py [header [output]]
+    python tools/gen_abi.py include/multike_thin.h multike_amd/_abi_thin.py      (libmultike_thin.so, a header of its own)
 
 The header is the only place a struct, a prototype or a constant is typed; this script turns its small vocabulary (fixed-width
 scalars, pointers, arrays sized by literals or MKE_* constants, structs by value, integer #defines) into ctypes and stops at
@@ -110,10 +111,10 @@ def parse(header):
     return constants, structs, functions
 
 
-def generate(header):
-    """The text of multike_amd/_abi.py for the text of the header."""
+def generate(header, source="include/multike_hip.h"):
+    """The text of multike_amd/_abi.py for the text of the header (`source`: the header's name in the module's first line)."""
     constants, structs, functions = parse(header)
-    out = ['"""generated from include/multike_hip.h by tools/gen_abi.py — do not edit',
+    out = [f'"""generated from {source} by tools/gen_abi.py — do not edit',
            "",
            "The C-ABI as ctypes: every integer #define (MKE_X as X), every struct under its C name with its members in header order,",
            "and FUNCTIONS = {name: (restype, argtypes)} in header order.  Pointers inside structs are plain addresses (c_void_p).",
@@ -136,7 +137,7 @@ def main(argv):
     header = argv[0] if argv else HEADER
     output = argv[1] if len(argv) > 1 else OUTPUT
     with open(header, encoding="utf-8") as f:
-        text = generate(f.read())
+        text = generate(f.read(), os.path.relpath(os.path.abspath(header), ROOT).replace(os.sep, "/"))
     with open(output, "w", encoding="utf-8") as f:
         f.write(text)
 
