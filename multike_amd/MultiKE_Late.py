@@ -474,6 +474,8 @@ class _ScheduledMultiKE(MultiKE):
                                  f"{len(useful)} useful entities of the KG")
             emb = self.rv_ent_embeds.lookup(self._ids(useful))
             capped = dict(cap=cap, seed=refresh_seed(getattr(a, "seed", 0), i, len(out))) if cap else {}
+            if getattr(a, "truncated_keyed", None) is not None:      # unset: neighbour_table's automatic rule
+                capped["keyed"] = bool(int(a.truncated_keyed))
             out.append(neighbour_table(emb, useful, k, kgs.entities_num, device=self.device, **capped))
         self._neighbors = tuple(out)
         print("generating neighbors of {} entities costs {:.3f} s.".format(len(self._entity_list), time.time() - t1) +

@@ -415,6 +415,82 @@ def idlist_thin(ids: torch.Tensor, m: int, seed: int, row_ids=None) -> torch.Ten
     return out
 
 
+KEYED_SO_PATH = os.path.join(_HERE, "libmultike_keyed.so")   # include/multike_keyed.h: a library and a generated module of its own
+# instantiations of k_sim_select_keyed.  224 is there for the kernel tests alone (the first width with 32-column tiles, next to
+# 208, the last with 64): k_sim_sample has no 224, so neighbour_table takes its kpad from SIM_SELECT_KPADS on every path and rows
+# of 209 .. 224 floats run at 256 as they always have
+KEYED_KPADS = tuple(sorted(SIM_SELECT_KPADS + (224,)))
+_keyed = None
+
+
+def keyed_lib():
+    """Load libmultike_keyed.so (once), typed from _abi_keyed.py as lib() is from _abi.py.  Raises if it has not been built."""
+    global _keyed
+    if _keyed is None:
+        from . import _abi_keyed
+        if not os.path.exists(KEYED_SO_PATH):
+            raise MultiKEHipError(f"{KEYED_SO_PATH} not found: build it with `make -C multike_amd/csrc`.  multike_amd has no CPU fallback.")
+        L = C.CDLL(KEYED_SO_PATH)
+        for name, (restype, argtypes) in _abi_keyed.FUNCTIONS.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _keyed = L
+    return _keyed
+
+
+def _keyed_check(rc: int, what: str):
+    if rc != 0:
+        raise MultiKEHipError(f"{what} failed (code {rc}): {keyed_lib().mke_keyed_last_error().decode('utf-8', 'replace')}")
+
+
+def _keyed_candidates(cand: torch.Tensor):
+    from . import _abi_keyed
+    return C.cast(ptr(cand, torch.int32, "cand"), C.POINTER(_abi_keyed.mke_keyed_candidate))
+
+
+def sim_select_keyed(emb: torch.Tensor, kpad: int, row_lo: int, row_hi: int, tau_lo: torch.Tensor, tau_hi: torch.Tensor,
+                     col_ids: torch.Tensor, seed: int, key_below: int, n_seg: int, seg_cap: int):
+    """mke_sim_select_keyed -> (cand int32 [rows, n_seg, seg_cap, 2] = (column, similarity bits) pairs, seg_count int32
+    [rows, n_seg], seg_sure int32 [rows, n_seg]).  col_ids int32 [n]: the entity id of every working row / column."""
+    if emb.dim() != 2 or emb.stride(1) != 1 or emb.dtype != torch.float32:
+        raise MultiKEHipError("sim_select_keyed: emb must be a row-major float32 matrix")
+    rows = row_hi - row_lo
+    if tau_lo.numel() != rows or tau_hi.numel() != rows:
+        raise MultiKEHipError("sim_select_keyed: one pair of thresholds per row")
+    if col_ids.numel() != emb.shape[0]:
+        raise MultiKEHipError("sim_select_keyed: one id per row of emb")
+    cand = torch.empty(rows, n_seg, seg_cap, 2, dtype=torch.int32, device=emb.device)
+    cnt = torch.empty(rows, n_seg, dtype=torch.int32, device=emb.device)
+    sure = torch.empty(rows, n_seg, dtype=torch.int32, device=emb.device)
+    rc = keyed_lib().mke_sim_select_keyed(emb.data_ptr(), emb.stride(0), kpad, emb.shape[0], row_lo, row_hi,
+                                          ptr(tau_lo, torch.float32, "tau_lo"), ptr(tau_hi, torch.float32, "tau_hi"),
+                                          ptr(col_ids, torch.int32, "col_ids"), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                          int(key_below) & 0xFFFFFFFFFFFFFFFF, n_seg, seg_cap, _keyed_candidates(cand),
+                                          ptr(cnt, torch.int32, "seg_count"), ptr(sure, torch.int32, "seg_sure"), _stream())
+    _keyed_check(rc, "mke_sim_select_keyed")
+    return cand, cnt, sure
+
+
+def keyed_finish(cand: torch.Tensor, seg_count: torch.Tensor, seg_sure: torch.Tensor, tau_hi: torch.Tensor, row_ids: torch.Tensor,
+                 col_ids: torch.Tensor, k: int, m: int, seed: int, key_below: int, out=None):
+    """mke_keyed_finish over sim_select_keyed's lists -> (out int32 [rows, m], status int32 [rows]); rows whose status is not 0
+    are not written (`out`: a tensor to write into, e.g. to see that)."""
+    rows, n_seg, seg_cap, _ = cand.shape
+    if tau_hi.numel() != rows or row_ids.numel() != rows:
+        raise MultiKEHipError("keyed_finish: one threshold and one row id per row")
+    if out is None:
+        out = torch.empty(rows, max(0, int(m)), dtype=torch.int32, device=cand.device)
+    status = torch.empty(rows, dtype=torch.int32, device=cand.device)
+    rc = keyed_lib().mke_keyed_finish(_keyed_candidates(cand), ptr(seg_count, torch.int32, "seg_count"),
+                                      ptr(seg_sure, torch.int32, "seg_sure"), rows, n_seg, seg_cap,
+                                      ptr(tau_hi, torch.float32, "tau_hi"), ptr(row_ids, torch.int32, "row_ids"),
+                                      ptr(col_ids, torch.int32, "col_ids"), int(k), int(m), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                      int(key_below) & 0xFFFFFFFFFFFFFFFF, ptr(out, torch.int32, "out"),
+                                      ptr(status, torch.int32, "status"), _stream())
+    _keyed_check(rc, "mke_keyed_finish")
+    return out, status
+
+
 def mapping_scratch_floats(n: int, dim: int) -> int:
     return int(lib().mke_mapping_scratch_floats(n, dim))
 

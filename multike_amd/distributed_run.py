@@ -292,6 +292,8 @@ class _ShardedMixin:
             emb = self.rows("rv", useful)
             # the same seed on every rank: a row's kept set does not depend on the slice that computes it
             capped = dict(cap=cap, seed=refresh_seed(getattr(a, "seed", 0), i, len(out))) if cap else {}
+            if getattr(a, "truncated_keyed", None) is not None:      # unset: neighbour_table's automatic rule, the same on every rank
+                capped["keyed"] = bool(int(a.truncated_keyed))
             if G == 1:
                 out.append(neighbour_table(emb, useful, k, kgs.entities_num, device=self.device, **capped))
                 continue

@@ -42,6 +42,9 @@ def default_args(**over):
         # `truncated_cap`-subset of each entity's exact int((1 - truncated_epsilon) * |E_kg|) neighbours, so the two tables grow
         # with |E| * cap instead of |E|^2; every negative is still uniform over the exact neighbour set
         truncated_cap=0,
+        # the matrix-free selection of a capped refresh (`neighbour_table(keyed=)`): None = automatic (large KGs whose k is beyond
+        # the thresholded sweep), 0 / 1 = never / always (1 needs truncated_cap below the neighbour count)
+        truncated_keyed=None,
         # host-side worker counts of the reference (accepted, unused: batches are produced on the device)
         batch_threads_num=4, test_threads_num=8,
         # validation / early stopping
