@@ -238,11 +238,17 @@ class _ScheduledMultiKE(MultiKE):
         + test entities of each KG, in that order on both sides; no gold link is read to choose pairs (the precision printed
         is a diagnostic: gold = the same index, which the pairing kernel counts anyway).  Decode, link table, both swaps and the
         weight table are enqueued without waiting; one read-back (the two list lengths and the two counters) ends the refresh.
+        `bootstrap_accumulate` > 0: the links live across refreshes (`base.bootstrap.edit_links` on the decode's own operands: a
+        new pair always wins, an old link with an end in a new pair is displaced, any other old link stays while its value today
+        is >= `bootstrap_retain`).  Table, swaps, weights (a kept link's: its value today) and `bootstrap_links` then come from
+        the edited set, the seven counters of the edit ride in the same single read-back, and the line ends in ", kept K,
+        displaced D, expired X".
         Not done: the sampler's known-triple filter does not grow by the bootstrapped triples, and `kg.add_sup_*` is not called."""
         opt = bootstrap_options(self.args)
         if opt is None:
             return
-        freq, start, threshold, csls_k, view, weighted = opt
+        freq, start, threshold, csls_k, view, weighted = opt[:6]
+        accumulate = len(opt) > 6
         if i < start or (i - start) % freq != 0 or i >= self.args.max_epoch:
             return
         import torch
@@ -256,7 +262,12 @@ class _ScheduledMultiKE(MultiKE):
             raise _lib.MultiKEHipError("bootstrap_freq > 0: the tables of this model are not device tables")
         e2 = _view_rows(self, choice, w, ids2)
         src = self._bootstrap_sources()
-        partner, match, counts, score = boot.bootstrap_links(e1, e2, ids1, ids2, k.entities_num, threshold, csls_k, scores=True)
+        if accumulate:
+            store = self.__dict__.setdefault("_boot_store", boot.LinkStore())
+            partner, match, counts, score = boot.bootstrap_links(e1, e2, ids1, ids2, k.entities_num, threshold, csls_k, scores=True,
+                                                                 store=store, retain=opt[7])
+        else:
+            partner, match, counts, score = boot.bootstrap_links(e1, e2, ids1, ids2, k.entities_num, threshold, csls_k, scores=True)
         weight = None
         if weighted:
             # weight[e] = clamp(score of e's pair, 0, 1) for both entities of a pair; unmatched rows write a spare last word
@@ -270,14 +281,16 @@ class _ScheduledMultiKE(MultiKE):
             weight = weight[:n]
         rel = boot._swap_launch(src["rel"], partner, False, weight)
         attr = boot._swap_launch(src["attr"], partner, True, weight)
-        n_rel, n_attr, pairs, gold = torch.cat([rel[-1], attr[-1], counts.long()]).cpu().tolist()      # the one read-back
+        n_rel, n_attr, pairs, gold, *edit = torch.cat([rel[-1], attr[-1], counts.long()]).cpu().tolist()      # the one read-back
         lists = (boot._swap_finish(rel, n_rel), boot._swap_finish(attr, n_attr))
         self._ckge_rel_triples, self._ckge_attr_triples = (
             new if seed is None else seed + new for seed, new in zip(self._bootstrap_seeds(weighted), lists))
         self.bootstrap_links = boot.BootstrapLinks(match, ids1, ids2, pairs)
         self._bootstrap_partner = partner
         print("bootstrapping after epoch {}: {} pairs, precision = {:.3f}%, {} relation triples, {} attribute triples, "
-              "time = {:.3f} s".format(i, pairs, gold / pairs * 100 if pairs else 0.0, n_rel, n_attr, time.time() - t0))
+              "time = {:.3f} s".format(i, pairs, gold / pairs * 100 if pairs else 0.0, n_rel, n_attr, time.time() - t0) +
+              (", kept {}, displaced {}, expired {}".format(*edit[2:5]) if accumulate else ""))
+        self._bootstrap_edit = tuple(edit) if accumulate else None      # (new, re-found, kept, displaced, expired) of this refresh
 
     def _bootstrap_sources(self):
         """Device columns of the KG1 ++ KG2 local (pre-supervision) relation and attribute id-triples: uploaded once per model."""

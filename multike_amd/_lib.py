@@ -491,6 +491,59 @@ def keyed_finish(cand: torch.Tensor, seg_count: torch.Tensor, seg_sure: torch.Te
     return out, status
 
 
+LINKS_SO_PATH = os.path.join(_HERE, "libmultike_links.so")   # include/multike_links.h: a library and a generated module of its own
+_links = None
+
+
+def links_lib():
+    """Load libmultike_links.so (once), typed from _abi_links.py as lib() is from _abi.py.  Raises if it has not been built."""
+    global _links
+    if _links is None:
+        from . import _abi_links
+        if not os.path.exists(LINKS_SO_PATH):
+            raise MultiKEHipError(f"{LINKS_SO_PATH} not found: build it with `make -C multike_amd/csrc`.  multike_amd has no CPU fallback.")
+        L = C.CDLL(LINKS_SO_PATH)
+        for name, (restype, argtypes) in _abi_links.FUNCTIONS.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _links = L
+    return _links
+
+
+def links_edit(held, match, a, b, kpad, metric=METRIC_INNER, sq_a=None, sq_b=None, csls_row=None, csls_col=None,
+               retain=float("-inf"), new_score=None, want_score=True, out=None):
+    """mke_links_edit over the link set held int32 [n_a], this refresh's match int32 [n_a] and the decode's operands (row-major
+    padded a [n_a, lda] / b [n_b, ldb], as align_mutual takes them) -> (out int32 [n_a], score float32 [n_a] or None, counts
+    int32 [7]).  `out` = (out, score or None, inv int32 [n_b], counts) to write into instead of fresh tensors.  Nothing is read
+    back here."""
+    from . import _abi_links
+    n_a, n_b = a.shape[0], b.shape[0]
+    if held.numel() != n_a or match.numel() != n_a:
+        raise MultiKEHipError(f"links_edit: held has {held.numel()} rows, match {match.numel()}, a {n_a}")
+    dev = a.device
+    if out is None:
+        out = (torch.empty(n_a, dtype=torch.int32, device=dev), torch.empty(n_a, dtype=torch.float32, device=dev) if want_score else None,
+               torch.empty(n_b, dtype=torch.int32, device=dev), torch.empty(_abi_links.LINKS_COUNTS, dtype=torch.int32, device=dev))
+    o, score, inv, counts = out
+    if o.numel() < n_a or inv.numel() < n_b or (score is not None and score.numel() < n_a) or counts.numel() < _abi_links.LINKS_COUNTS:
+        raise MultiKEHipError("links_edit: out is shorter than the link set")
+    if n_a > 0 and n_b == 0:                # the call zeroes the counters and nothing else: no column, no link
+        o[:n_a] = -1
+        if score is not None:
+            score[:n_a] = 0.0
+    args = _abi_links.mke_links_args(ptr(held, torch.int32, "held"), ptr(match, torch.int32, "match"), n_a, n_b,
+                                     ptr(a, torch.float32, "a"), a.stride(0), ptr(b, torch.float32, "b"), b.stride(0), kpad, metric,
+                                     ptr(sq_a, torch.float32, "sq_a"), ptr(sq_b, torch.float32, "sq_b"),
+                                     ptr(csls_row, torch.float32, "csls_row"), ptr(csls_col, torch.float32, "csls_col"),
+                                     float(retain), ptr(new_score, torch.float32, "new_score"), ptr(inv, torch.int32, "inv"),
+                                     ptr(o, torch.int32, "out"), ptr(score, torch.float32, "score"), ptr(counts, torch.int32, "counts"))
+    L = links_lib()
+    rc = L.mke_links_edit(C.byref(args), _stream())
+    if rc != 0:
+        raise MultiKEHipError(f"mke_links_edit failed (code {rc}): {L.mke_links_last_error().decode('utf-8', 'replace')}")
+    return o, score, counts
+
+
 def mapping_scratch_floats(n: int, dim: int) -> int:
     return int(lib().mke_mapping_scratch_floats(n, dim))
 

@@ -315,9 +315,21 @@ def mutual_pairs(embed1, embed2, metric="inner", normalize=True, csls_k=0, thres
 
 def _mutual(embed1, embed2, metric, normalize, csls_k, threshold, sinkhorn):
     """(match, counts, row_best) of the checked arguments: the operand path of the other decoders, one sweep, one pairing."""
+    return _mutual_decode(_mutual_operands(embed1, embed2, metric, normalize, csls_k, sinkhorn), threshold)
+
+
+def _mutual_operands(embed1, embed2, metric, normalize, csls_k, sinkhorn):
+    """prepare_operands' tuple + (the re-scoring terms or None,): everything the mutual sweep reads.  Whoever re-scores single
+    pairs of the same decode afterwards (base.bootstrap.edit_links) takes this tuple, not a second preparation."""
     operands = prepare_operands(embed1, embed2, metric, normalize, "cuda")
-    a, b, kpad, code, sq1, sq2 = operands
+    a, b = operands[:2]
     terms = _rescoring_terms(operands, csls_k, sinkhorn) if min(a.shape[0], b.shape[0]) > 0 else None
+    return operands + (terms,)
+
+
+def _mutual_decode(operands, threshold):
+    """(match, counts, row_best) of _mutual_operands' tuple: one sweep, one pairing."""
+    a, b, kpad, code, sq1, sq2, terms = operands
     row_best, col_best = _lib.align_mutual(a, b, kpad, code, sq1, sq2, *(terms or (None, None)))
     match, counts = _lib.mutual_pairs(row_best, col_best, float("-inf") if threshold is None else float(threshold))
     return match, counts, row_best

@@ -8,6 +8,8 @@ mutual nearest-neighbour decoder finds among the unlabelled entities:
     partner_table     a decoder's `match` + the entity ids of its rows and columns -> partner[e] (int32 [n_entities], -1 = none)
     swap_triples      triple columns + partner -> the swapped list, a `TripleArray` whose columns live on the device
     bootstrap_links   embeddings of the candidate rows -> (partner, match, counts): one mutual decode, then partner_table
+    edit_links        a link set kept across refreshes + this refresh's match + the decode's operands -> the edited link set
+                      (`mke_links_edit`, include/multike_links.h); `LinkStore` holds the set of a model
 
 Tensors or NumPy go in, as with the decoders of base/alignment.py; what cannot be right is refused with `MultiKEHipError`
 before the device is touched.  `swap_host` is the same walk in NumPy: the `host()` form of the device-built lists.
@@ -21,7 +23,8 @@ from .. import _lib
 from . import alignment
 from .kgs import TripleArray
 
-__all__ = ["partner_table", "swap_triples", "bootstrap_links", "bootstrap_options", "swap_host", "BootstrapLinks"]
+__all__ = ["partner_table", "swap_triples", "bootstrap_links", "bootstrap_options", "swap_host", "BootstrapLinks", "edit_links",
+           "LinkStore"]
 
 
 def _i32(x, name, device="cuda"):
@@ -128,12 +131,62 @@ def swap_triples(cols, partner, heads_only=False, weight=None):
     return _swap_finish(state, n), n
 
 
-def bootstrap_links(embeds1, embeds2, ids1, ids2, n_entities, threshold=None, csls_k=0, sinkhorn=None, *, scores=False):
+def edit_links(held, match, operands, retain=None, new_score=None):
+    """One edit of a link set that lives across refreshes -> (out int32 [n1], score float32 [n1], counts int32 [7]), all on the
+    device.  `held` [n1]: the column every row is linked to or -1 (the `out` of the edit before; all -1 at the start); `match`
+    [n1]: this refresh's one-to-one decode; `operands`: what the decode swept, alignment.prepare_operands' tuple followed by the
+    re-scoring terms (alignment._rescoring_terms' pair, or None) — the tuple of alignment._mutual_operands, prepared ONCE for the
+    decode and for this.  Per row, the first rule that applies (include/multike_links.h):
+        a new pair always wins (nothing is compared: for the mutual decoder each of a new pair's ends is the other's best on the
+        same values, so no old link at either end has a larger value; the rule is the same for any other decoder's match);
+        an old link one of whose ends is in a new pair is displaced;
+        an old link is kept while its value today — metric and re-scoring of the decode, so CSLS units with CSLS — is >= `retain`
+        (None: no retention threshold, every undisplaced link is kept; NaN is refused), and expires otherwise.
+    score: a kept link's value today, `new_score` (float32 [n1], e.g. the decode's row-best value) copied for a new pair, 0
+    elsewhere.  counts = (links, links with out[i] == i, new, re-found, kept, displaced, expired).  Nothing is read back."""
+    if retain is not None and np.isnan(float(retain)):
+        raise _lib.MultiKEHipError("edit_links: retain is NaN (None = no retention threshold)")
+    a, b, kpad, code, sq_a, sq_b = operands[:6]
+    terms = operands[6] if len(operands) > 6 else None
+    held, match = _i32(held, "held", a.device), _i32(match, "match", a.device)
+    return _lib.links_edit(held, match, a, b, kpad, code, sq_a, sq_b, *(terms or (None, None)),
+                           retain=float("-inf") if retain is None else float(retain), new_score=new_score)
+
+
+class LinkStore:
+    """The link set of a model between two refreshes: `held(n)` is the int32 device vector edit_links takes (all -1 before the
+    first refresh), `update(out)` keeps an edit's result.  The candidates of a model are fixed, so a set of another length is
+    refused."""
+
+    def __init__(self):
+        self._held = None
+
+    def held(self, n, device="cuda"):
+        if self._held is None:
+            self._held = torch.full((int(n),), -1, dtype=torch.int32, device=device)
+        if self._held.numel() != int(n):
+            raise _lib.MultiKEHipError(f"LinkStore: the link set has {self._held.numel()} rows, this refresh {int(n)}")
+        return self._held
+
+    def update(self, out):
+        if self._held is not None and self._held.numel() != out.numel():
+            raise _lib.MultiKEHipError(f"LinkStore: the link set has {self._held.numel()} rows, the edit {out.numel()}")
+        self._held = out
+
+    def __len__(self):
+        return 0 if self._held is None else self._held.numel()
+
+
+def bootstrap_links(embeds1, embeds2, ids1, ids2, n_entities, threshold=None, csls_k=0, sinkhorn=None, *, scores=False, store=None,
+                    retain=None):
     """One label-free decode of the candidate rows -> (partner, match, counts), all on the device: the mutual nearest-neighbour
     pairs of `embeds1` [n1, d] and `embeds2` [n2, d] (inner product of unit rows, CSLS or Sinkhorn re-scored on request, at or
     above `threshold` in units of the value compared), as base.alignment.mutual_pairs finds them, and their link table over the
     entity ids `ids1` / `ids2`.  counts int32 [2] = (pairs, pairs with match[i] == i).  scores=True appends the float32 [n1]
-    value of every row's best column (mutual_pairs' `score`)."""
+    value of every row's best column (mutual_pairs' `score`).
+    store = a LinkStore: the links accumulate.  The decode's match is edited against the store's set (edit_links, on the
+    decode's own operands, `retain` as there), the store keeps the result, and what is returned — `match`, the table made of it,
+    counts int32 [7] as edit_links', and with scores=True edit_links' `score` — is the edited set."""
     n_entities = _check_entities(n_entities, "bootstrap_links")
     csls_k, sinkhorn = alignment._check_rescoring(csls_k, sinkhorn)
     if threshold is not None and np.isnan(float(threshold)):
@@ -141,14 +194,25 @@ def bootstrap_links(embeds1, embeds2, ids1, ids2, n_entities, threshold=None, cs
     if len(embeds1) != len(ids1) or len(embeds2) != len(ids2):
         raise _lib.MultiKEHipError(f"bootstrap_links: {len(embeds1)} / {len(embeds2)} rows, {len(ids1)} / {len(ids2)} entity ids")
     ids1, ids2 = _i32(ids1, "ids1"), _i32(ids2, "ids2")
-    match, counts, row_best = alignment._mutual(embeds1, embeds2, "inner", True, csls_k, threshold, sinkhorn)
-    partner = _lib.boot_partner(match, ids1, ids2, n_entities)
-    return (partner, match, counts) + ((alignment._best_value(row_best),) if scores else ())
+    if store is None:
+        match, counts, row_best = alignment._mutual(embeds1, embeds2, "inner", True, csls_k, threshold, sinkhorn)
+        partner = _lib.boot_partner(match, ids1, ids2, n_entities)
+        return (partner, match, counts) + ((alignment._best_value(row_best),) if scores else ())
+    if retain is not None and np.isnan(float(retain)):
+        raise _lib.MultiKEHipError("bootstrap_links: retain is NaN (None = no retention threshold)")
+    operands = alignment._mutual_operands(embeds1, embeds2, "inner", True, csls_k, sinkhorn)
+    match, _, row_best = alignment._mutual_decode(operands, threshold)
+    out, score, counts = edit_links(store.held(match.numel(), match.device), match, operands, retain, alignment._best_value(row_best))
+    store.update(out)
+    partner = _lib.boot_partner(out, ids1, ids2, n_entities)
+    return (partner, out, counts) + ((score,) if scores else ())
 
 
 def bootstrap_options(args):
     """The checked `bootstrap_*` hyper-parameters -> None when self-training is off (`bootstrap_freq` absent or 0), else
-    (freq, start, threshold, csls_k, view, weighted)."""
+    (freq, start, threshold, csls_k, view, weighted); with `bootstrap_accumulate` > 0 (links kept across refreshes, edit_links)
+    two more: (.., True, retain), retain = `bootstrap_retain`, or the threshold when that is None (None = no retention
+    threshold), in the units of the decode.  `bootstrap_accumulate` without `bootstrap_freq` is ignored."""
     freq = int(getattr(args, "bootstrap_freq", 0) or 0)
     if freq <= 0:
         return None
@@ -166,7 +230,13 @@ def bootstrap_options(args):
                                    "pair's raw similarity clamped to [0, 1], and CSLS re-scored values are in other units")
     if view not in (None, "nv", "rv", "av", "avg", "final"):
         raise _lib.MultiKEHipError(f"bootstrap_view {view!r}: one of 'nv', 'rv', 'av', 'avg', 'final' or None")
-    return freq, start, None if threshold is None else float(threshold), csls_k, view, weighted
+    threshold = None if threshold is None else float(threshold)
+    retain = getattr(args, "bootstrap_retain", None)
+    if retain is not None and np.isnan(float(retain)):
+        raise _lib.MultiKEHipError("bootstrap_retain is NaN (None = bootstrap_threshold)")
+    if int(getattr(args, "bootstrap_accumulate", 0) or 0) <= 0:
+        return freq, start, threshold, csls_k, view, weighted
+    return freq, start, threshold, csls_k, view, weighted, True, threshold if retain is None else float(retain)
 
 
 class BootstrapLinks:

@@ -68,7 +68,11 @@ def default_args(**over):
         # `bootstrap_csls` > 0 decodes on CSLS re-scored values (the threshold is then in those units); `bootstrap_view` names the
         # embedding decoded (None = the one the driver validates on: 'final' for ITC, 'avg' for SSL); `bootstrap_weighted` = 1
         # weights a bootstrapped triple by its pair's similarity clamped to [0, 1] (seed triples 1.0; not with `bootstrap_csls`)
+        # `bootstrap_accumulate` = 1 keeps the links across refreshes instead: a refresh's new pairs always win, an old link with
+        # an end in a new pair is dropped, and any other old link stays while its value today is >= `bootstrap_retain` (None =
+        # `bootstrap_threshold`; both None = no retention threshold; in the units of the decode, CSLS units with `bootstrap_csls`)
         bootstrap_freq=0, bootstrap_start=10, bootstrap_threshold=None, bootstrap_csls=0, bootstrap_view=None, bootstrap_weighted=0,
+        bootstrap_accumulate=0, bootstrap_retain=None,
         # view combination and predicate soft alignment
         orthogonal_weight=2, cv_name_weight=1, cv_weight=1, start_predicate_soft_alignment=10, predicate_soft_sim=0.85,
         predicate_init_sim=0.90)

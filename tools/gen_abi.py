@@ -4,6 +4,7 @@
     python tools/gen_abi.py [header [output]]
     python tools/gen_abi.py include/multike_thin.h multike_amd/_abi_thin.py      (libmultike_thin.so, a header of its own)
     python tools/gen_abi.py include/multike_keyed.h multike_amd/_abi_keyed.py    (libmultike_keyed.so, likewise)
+    python tools/gen_abi.py include/multike_links.h multike_amd/_abi_links.py    (libmultike_links.so, likewise)
 
 The header is the only place a struct, a prototype or a constant is typed; this script turns its small vocabulary (fixed-width
 scalars, pointers, arrays sized by literals or MKE_* constants, structs by value, integer #defines) into ctypes and stops at

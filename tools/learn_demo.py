@@ -1,8 +1,10 @@
 """End-to-end sanity run: a synthetic dataset FOLDER whose two KGs share structure -> DataModel -> ITC training ->
 Hits@k per view over the epochs.  python tools/learn_demo.py [n_pairs] [epochs] [shared] [bootstrap_freq] [threshold] [weighted]
+[accumulate] [retain]
 
 bootstrap_freq > 0 switches self-training on (from epoch 10, every bootstrap_freq epochs; `threshold` = bootstrap_threshold,
-'none' or absent = none; `weighted` = bootstrap_weighted) and prints every refresh's line; absent or 0, the run is as before."""
+'none' or absent = none; `weighted` = bootstrap_weighted; `accumulate` = bootstrap_accumulate, the links kept across refreshes,
+`retain` = bootstrap_retain, 'none' or absent = the threshold) and prints every refresh's line; absent or 0, the run is as before."""
 import os, sys, tempfile, contextlib, io
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from multike_amd.data_model import DataModel
@@ -19,6 +21,8 @@ if len(sys.argv) > 4 and int(sys.argv[4]) > 0:
     boot = dict(bootstrap_freq=int(sys.argv[4]), bootstrap_start=10,
                 bootstrap_threshold=float(sys.argv[5]) if len(sys.argv) > 5 and sys.argv[5].lower() != "none" else None,
                 bootstrap_weighted=int(sys.argv[6]) if len(sys.argv) > 6 else 0)
+    if len(sys.argv) > 7 and int(sys.argv[7]) > 0:
+        boot.update(bootstrap_accumulate=1, bootstrap_retain=float(sys.argv[8]) if len(sys.argv) > 8 and sys.argv[8].lower() != "none" else None)
 folder = tempfile.mkdtemp() + "/"
 wf = write_dataset_folder(folder, n_pairs=n_pairs, n_extra=n_pairs // 10, n_rel=40, n_attr=30, triples_per_entity=5.0, shared_structure=shared)
 args = synthetic_args(training_data=folder, output=folder + "out/", word2vec_path=wf, dataset_division="631/", encoder_epoch=5,
