@@ -98,6 +98,10 @@ int mke_tuning_init(mke_tuning* t);   /* every field = MKE_TUNE_DEFAULT */
  *                     themselves (mke_neg_sample without neg_r / neg_t), the bake adds MKE_CODE_EXCL in place (mke_neg_codes without
  *                     id arrays) and the training kernel runs without id arrays: neg_h / neg_r / neg_t are not written
  *                     (mke_relation_plan.ids_stale); 0 = three id arrays, then mke_neg_codes.  No effect on any other path
+ *   "code_flags"        : 1 (default) = a step of mke_relation_steps that runs the code-word form stores no entity touched flags
+ *                     (mke_score_args.touched_ent == NULL) and its update launch finds the rows in the step's row of the bake's
+ *                     bitmap and the step's positives (mke_update_table.bits): ent_touched is left as it was by such steps;
+ *                     0 = flags stored and scanned, as in every other path.  Process-wide only (no mke_tuning field)
  * Returns the previous value through *old_value when it is not NULL. */
 int mke_set_option(const char* name, int value, int* old_value);
 
@@ -207,7 +211,9 @@ typedef struct mke_score_args {
   float scale;
   /* gradient scratch: grad_ent == NULL = forward only */
   float* grad_ent; float* grad_rel /*nullable iff grad_ent is*/; int grad_rel_copies;
-  int32_t* touched_ent; int32_t* touched_rel; int32_t tag;
+  int32_t* touched_ent; int32_t* touched_rel; int32_t tag;   /* touched_ent == NULL: only where the code-word form runs (neg_code):
+                                                                no entity flag is stored, the update launch reads the bake's
+                                                                bitmap instead (mke_update_table.bits); relation flags stay */
   /* exclusive-row path: ref_count == NULL = off */
   int32_t* ref_count; float* ent_acc /*nullable for SGD*/; int optimizer; float lr;
   const mke_count_job* next_count;   /* host pointer, NULL = no rider */
@@ -320,6 +326,15 @@ typedef struct mke_update_table {
   int64_t capacity;
   /* version 103: hub rows of this table (see mke_hot_rows; slot == NULL: none) */
   mke_hot_rows hot;
+  /* code-word steps (section (1c); added behind `hot` within version 107, as neg_code was to mke_score_args: a caller that
+   * zero-fills the struct gets the flag form).  bits != NULL: the rows are found in the step's row of the bake's bitmap
+   * (mke_neg_codes: two bits per row, word row >> 4) and `touched` is not read (it may be NULL).  Visited are the rows with
+   * pair 11, and the rows with pair 01 that pos_h[0, n_pos) or pos_t[0, n_pos), the step's positives, name: those took
+   * contributions in the gradient scratch; a row with pair 01 that only a negative names was finished by the score launch.
+   * (bits, pos_h, pos_t) must be the bitmap row and the positives of the step whose score launch filled `grad`.  Hub rows
+   * work as with flags; slot_of and grad_copies > 1 -> MKE_E_UNSUPPORTED, as is a second bitmap table in one call. */
+  const uint32_t* bits;
+  const int32_t* pos_h; const int32_t* pos_t; int64_t n_pos;
 } mke_update_table;
 int mke_rows_update_multi(const mke_update_table* tables, int n_tables, int32_t tag, int stride, int dim,
                           int optimizer, float lr, void* stream);
@@ -531,7 +546,8 @@ typedef struct mke_relation_plan {
   float* ent_acc; float* rel_acc;            /* this optimizer's Adagrad slots (NULL for SGD) */
   float* ent_grad; float* rel_grad;          /* zero-invariant gradient scratch; rel_grad is [rel_grad_copies][n_rel][stride] */
   int rel_grad_copies;
-  int32_t* ent_touched; int32_t* rel_touched;
+  int32_t* ent_touched; int32_t* rel_touched; /* steps that run the code-word form leave ent_touched as it was ("code_flags"):
+                                                their update launch reads the step's row of code_bits and the step's positives */
   int32_t* ent_ref_count;                    /* nullable: enables the exclusive-row fast path (zero-invariant scratch),
                                                 int32 [2][n_ent]: steps alternate between the two halves so that the
                                                 counting of step s+1 can ride in the update launch of step s */

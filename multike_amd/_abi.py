@@ -166,6 +166,10 @@ class mke_update_table(C.Structure):
         ("n_ranks", C.c_int),
         ("capacity", C.c_int64),
         ("hot", mke_hot_rows),
+        ("bits", C.c_void_p),
+        ("pos_h", C.c_void_p),
+        ("pos_t", C.c_void_p),
+        ("n_pos", C.c_int64),
     ]
 
 

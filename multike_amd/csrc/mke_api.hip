@@ -35,7 +35,8 @@ int g_count_in_score = 1;    // runner: the next step's reference counting rides
 int g_score_lane_ids = 1;    // training kernel: a group's ids and reference counts fetched once, one negative per lane (mke_score.hip)
 int g_neg_codes = 1;         // runner: one code word per negative baked when a chunk is sampled, code-word form of the training kernel (0: reference counts per step)
 int g_sampler_codes = 1;     // runner, code-word chunks: the sampler writes code words, the bake runs on them in place, no id arrays (0: ids, then mke_neg_codes)
-int g_update_chunk = 0;      // rows per wavefront of the row-update kernel on large tables: 0 = by table size, 16, 64
+int g_code_flags = 1;        // runner, code-word steps: no entity touched flags, the update launch reads the bake's bitmap row and the step's positives (0: flags)
+int g_update_chunk = 0;     // rows per wavefront of the row-update kernel on large tables: 0 = by table size, 16, 64
 int g_deterministic = 0;     // fixed-order gradient reduction (parity / debugging mode)
 int g_attr_fused_bwd = 1;    // mke_attr_cnn.hip: dflat product inside the convolution-backward launch, dW on rider blocks (every dim <= 80)
 int g_oc_em_keys64 = 0;      // mke_oc_em.hip: sort the epoch's (step, row) keys as 64-bit words even when they fit 32 bits (the path large KGs take)
@@ -85,6 +86,11 @@ extern "C" int mke_set_option(const char* name, int value, int* old_value) {
   if (!strcmp(name, "sampler_codes")) {
     if (old_value) *old_value = mke::g_sampler_codes;
     mke::g_sampler_codes = value != 0;
+    return MKE_OK;
+  }
+  if (!strcmp(name, "code_flags")) {
+    if (old_value) *old_value = mke::g_code_flags;
+    mke::g_code_flags = value != 0;
     return MKE_OK;
   }
   if (!strcmp(name, "update_chunk")) {

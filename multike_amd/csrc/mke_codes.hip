@@ -13,6 +13,8 @@
 // words save — and is kept for rows that do not fit (k_code_mark, k_code_bake: one launch each per chunk, grid.y = step).
 // Where the sampler itself wrote the words (its code-word form: everything but the exclusive bit), the same workgroup per step
 // marks from and bakes into that one array (k_code_step_inplace).
+// The row written out is read again: the update launch of a code-word step finds its rows in it (mke_update_table.bits — pair 11,
+// and pair 01 where a positive names the row) instead of in touched flags that the score launch would have to store.
 #include "mke_common.h"
 
 namespace mke {

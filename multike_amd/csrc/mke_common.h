@@ -136,7 +136,7 @@ struct TuningScope {
   ~TuningScope() { tl_tuning = prev; }
 };
 extern int g_score_splits, g_score_half_max, g_score_o32, g_score_lane_ids, g_count_in_score, g_update_chunk, g_oc_score_quarter,
-    g_attr_fused_bwd, g_neg_codes, g_sampler_codes;
+    g_attr_fused_bwd, g_neg_codes, g_sampler_codes, g_code_flags;
 #define MKE_TUNE(field, dflt) ((mke::tl_tuning && mke::tl_tuning->field != MKE_TUNE_DEFAULT) ? mke::tl_tuning->field : (dflt))
 inline int tune_score_splits() { const int v = MKE_TUNE(score_splits, g_score_splits); return v < 0 ? 0 : v; }
 inline int tune_score_half_max() { const int v = MKE_TUNE(score_half_groups, g_score_half_max); return v < 0 ? -1 : (v > 64 ? 64 : v); }
@@ -160,6 +160,8 @@ int launch_neg_codes(const int32_t* pos_h, const int32_t* pos_r, const int32_t* 
 bool neg_codes_in_lds(int64_t n_ent);   // the bake is one launch, a step's bitmap row in the LDS (else device-scope atomics: slower than what it saves)
 // runner, code-word chunks only: the sampler writes the code words themselves and the bake works on them in place
 inline int tune_sampler_codes() { return MKE_TUNE(sampler_codes, g_sampler_codes) != 0; }
+// runner, code-word steps only: no entity touched flags, the update launch reads the step's bitmap row (process-wide, no mke_tuning field)
+inline int tune_code_flags() { return g_code_flags != 0; }
 // mke_codes.hip: the same rows and MKE_CODE_EXCL from the words the sampler's code-word form left in neg_code (rows in the LDS only)
 int launch_neg_codes_inplace(const int32_t* pos_h, const int32_t* pos_t, const int64_t* step_off_dev, int step_begin, int step_end,
                              int64_t pos_begin, int64_t pos_end, int neg_per_pos, int64_t n_ent, uint32_t* bits, int32_t* neg_code,

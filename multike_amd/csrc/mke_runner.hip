@@ -2,7 +2,8 @@
 // (code/MultiKE_model.py:302-312: batch_queue.get() -> session.run) expressed as a C++ loop that only enqueues
 // kernels.  Per step: [sampler for the next `sample_chunk` steps when the previous chunk is used up] ->
 // fused triple step -> one update launch covering the relation and the entity table.  A chunk that runs the code-word form is
-// sampled straight into code words and baked in place ("sampler_codes"): its three id arrays are never written.
+// sampled straight into code words and baked in place ("sampler_codes"): its three id arrays are never written; its steps store
+// no entity touched flags, their update launches read the step's row of the bake's bitmap and the step's positives ("code_flags").
 #include "mke_common.h"
 
 namespace mke {
@@ -156,6 +157,7 @@ extern "C" int mke_relation_steps(const mke_relation_plan* pl, int step_begin, i
   bool codes = false;    // the current chunk has code words
   bool no_ids = false;   // ... written by the sampler itself: neg_h / neg_r / neg_t do not hold the chunk
   int64_t chunk_lo = 0;  // first positive (epoch position) whose negatives sit at neg_*[0]
+  int chunk_first = step_begin;  // first step of the current chunk: row 0 of code_bits is its row
   int chunk_end = step_begin;  // steps < chunk_end are sampled
   bool counted_ahead = false;  // the current step's references were counted by the previous step's update launch
   for (int s = step_begin; s < step_end; ++s) {
@@ -167,6 +169,7 @@ extern "C" int mke_relation_steps(const mke_relation_plan* pl, int step_begin, i
     if (N > 0 && s >= chunk_end) {
       chunk_end = s + pl->sample_chunk < step_end ? s + pl->sample_chunk : step_end;
       chunk_lo = lo;
+      chunk_first = s;
       const int64_t n = pl->step_off[chunk_end] - lo;
       codes = codes_ok && chunk_end - s <= 65535 && (int64_t)(chunk_end - s) * mke_neg_code_row_words(pl->n_ent) <= pl->code_bits_words;
       // sampler_codes: the sampler writes the chunk's code words (all but MKE_CODE_EXCL) straight into neg_code, the bake adds the
@@ -220,6 +223,12 @@ extern "C" int mke_relation_steps(const mke_relation_plan* pl, int step_begin, i
     if (no_ids) sa.neg_h = sa.neg_r = sa.neg_t = nullptr;
     sa.next_count = in_score ? cjp : nullptr;
     sa.neg_code = codes ? pl->neg_code + no : nullptr;
+    // code_flags: a code-word step stores no entity flags; its update launch finds the rows in the step's row of the bake's bitmap
+    // (pair 11) and among the step's positives (pair 01).  ent_touched is left as it was.  Every other step: flags, as ever
+    const bool bitmap = codes && tune_code_flags();
+    sa.touched_ent = bitmap ? nullptr : pl->ent_touched;
+    ut[1].bits = bitmap ? pl->code_bits + (int64_t)(s - chunk_first) * mke_neg_code_row_words(pl->n_ent) : nullptr;
+    ut[1].pos_h = bitmap ? pl->pos_h + lo : nullptr; ut[1].pos_t = bitmap ? pl->pos_t + lo : nullptr; ut[1].n_pos = bitmap ? hi - lo : 0;
     rc = mke_triple_score_step(&sa, stream);
     if (rc) return rc;
     ut[1].ref_count = refc;

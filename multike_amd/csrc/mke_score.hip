@@ -93,7 +93,9 @@ __device__ __forceinline__ void atomic_add_at(float* __restrict__ q, int dim, in
 }
 
 // one gradient-row contribution: atomic add + touched flag, or (deterministic mode) a plain store into its slot
-template <int FPL, bool DET = false, bool O32 = false>
+// NF (the code-word instantiations' entity rows only): `touched` may be NULL — the update launch then finds the rows in the
+// bake's bitmap (mke_update_table.bits) and no flag is stored; a wave-uniform test of a kernel argument
+template <int FPL, bool DET = false, bool O32 = false, bool NF = false>
 __device__ __forceinline__ void emit_row(const ScoreParams& p, bool is_rel, float* __restrict__ table_grad, int32_t* __restrict__ touched,
                                          int row, int64_t slot, int j, const float (&v)[FPL], float sgn, int grad_row = -1) {
   if (DET) {
@@ -104,7 +106,7 @@ __device__ __forceinline__ void emit_row(const ScoreParams& p, bool is_rel, floa
   } else {
     // grad_row >= 0: a hub row's private copy takes the sum; the flag stays with the row itself
     atomic_add_at<FPL>(row_at<FPL, O32>(table_grad, grad_row >= 0 ? grad_row : row, p.stride, j), p.dim, j, v, sgn);
-    if (j == 0) touched[row] = p.tag;
+    if (j == 0 && (!NF || touched != nullptr)) touched[row] = p.tag;
   }
 }
 
@@ -117,7 +119,7 @@ __device__ __forceinline__ int hot_copy_row(const ScoreParams& p, int e, int64_t
   return s >= 0 ? p.hot_row0 + (int)((uint32_t)k % (uint32_t)p.hot_copies) * p.n_hot + s : -1;   // k < 2^32 (the launcher checks the item count)
 }
 
-template <int FPL, bool DET = false>
+template <int FPL, bool DET = false, bool NF = false>
 __device__ __forceinline__ float independent_triple(const ScoreParams& p, float* __restrict__ grel, int j, int h, int r,
                                                     int t, float w, float sign, int64_t slot0) {
   float H[FPL], R[FPL], T[FPL];
@@ -142,9 +144,9 @@ __device__ __forceinline__ float independent_triple(const ScoreParams& p, float*
     for (int k = 0; k < FPL; ++k) H[k] *= c;
     // positives-only steps (the cross-KG loops) score every triple here: a hub entity's row takes its private copy (slot0 / 3 = the
     // triple's index spreads the copies)
-    emit_row<FPL, DET>(p, false, p.gent, p.tent, h, slot0, j, H, 1.0f, hot_copy_row<DET>(p, h, slot0 / 3));
+    emit_row<FPL, DET, false, NF>(p, false, p.gent, p.tent, h, slot0, j, H, 1.0f, hot_copy_row<DET>(p, h, slot0 / 3));
     emit_row<FPL, DET>(p, true, grel, p.trel, r, slot0 + 1, j, H, 1.0f);
-    emit_row<FPL, DET>(p, false, p.gent, p.tent, t, slot0 + 2, j, H, -1.0f, hot_copy_row<DET>(p, t, slot0 / 3));
+    emit_row<FPL, DET, false, NF>(p, false, p.gent, p.tent, t, slot0 + 2, j, H, -1.0f, hot_copy_row<DET>(p, t, slot0 / 3));
   }
   return l;
 }
@@ -414,7 +416,7 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_triple_score(const ScoreParams p)
                 }
                 if constexpr (!CW) { if (j == 0) p.refcount[e[u]] = 0; }
               } else {
-                emit_row<FPL, DET, O32>(p, false, p.gent, p.tent, e[u], stage_slot(g, npp, n0 + QPG * u, sideH[u] ? 0 : 2), j, d,
+                emit_row<FPL, DET, O32, CW>(p, false, p.gent, p.tent, e[u], stage_slot(g, npp, n0 + QPG * u, sideH[u] ? 0 : 2), j, d,
                               sideH[u] ? 1.0f : -1.0f);
               }
             }
@@ -439,7 +441,7 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_triple_score(const ScoreParams p)
             if (p.neg_code[idx] & MKE_CODE_FAST) continue;
             const bool ids = p.nh != nullptr;
             const int nh = ids ? p.nh[idx] : ph, nr = ids ? p.nr[idx] : pr, nt = ids ? p.nt[idx] : pt;
-            loss += independent_triple<FPL, DET>(p, grel, j, nh, nr, nt, p.nw ? p.nw[idx] : 1.0f, -1.0f, stage_slot(g, npp, n, 0));
+            loss += independent_triple<FPL, DET, true>(p, grel, j, nh, nr, nt, p.nw ? p.nw[idx] : 1.0f, -1.0f, stage_slot(g, npp, n, 0));
           }
         }
       }
@@ -469,7 +471,7 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_triple_score(const ScoreParams p)
             for (int k = 0; k < FPL; ++k) v[k] = q == 0 ? gH[k] : (q == 1 ? gR[k] : -gT[k]);
             float* __restrict__ base = q == 1 ? grel : p.gent;
             const int row = q == 0 ? ph : (q == 1 ? pr : pt);
-            if (q < 3) emit_row<FPL, DET>(p, q == 1, base, q == 1 ? p.trel : p.tent, row, stage_slot(g, npp, npp, q), j, v, 1.0f,
+            if (q < 3) emit_row<FPL, DET, false, CW>(p, q == 1, base, q == 1 ? p.trel : p.tent, row, stage_slot(g, npp, npp, q), j, v, 1.0f,
                                           q == 0 ? hot_h : (q == 2 ? hot_t : -1));
           } else {
             // two quarter-waves per group: quarter 0 -> h, quarter 1 -> t, then quarter 0 -> r
@@ -477,7 +479,7 @@ __global__ __launch_bounds__(MKE_BLOCK) void k_triple_score(const ScoreParams p)
 #pragma unroll
             for (int k = 0; k < FPL; ++k) v[k] = q == 0 ? gH[k] : -gT[k];
             const int row = q == 0 ? ph : pt;
-            emit_row<FPL, DET>(p, false, p.gent, p.tent, row, stage_slot(g, npp, npp, q == 0 ? 0 : 2), j, v, 1.0f, q == 0 ? hot_h : hot_t);
+            emit_row<FPL, DET, false, CW>(p, false, p.gent, p.tent, row, stage_slot(g, npp, npp, q == 0 ? 0 : 2), j, v, 1.0f, q == 0 ? hot_h : hot_t);
             if (q == 0) emit_row<FPL, DET>(p, true, grel, p.trel, pr, stage_slot(g, npp, npp, 1), j, gR, 1.0f);
           }
         }
@@ -565,7 +567,7 @@ static int score_impl(const mke_score_args& a, void* stream) {
     return MKE_E_SHAPE;
   }
   if ((a.grad_ent == nullptr) != (a.grad_rel == nullptr)) { set_error("grad_ent and grad_rel must both be given or both NULL"); return MKE_E_NULL; }
-  if (a.grad_ent && (!a.touched_ent || !a.touched_rel)) { set_error("NULL touched array"); return MKE_E_NULL; }
+  if (a.grad_ent && !a.touched_rel) { set_error("NULL touched array"); return MKE_E_NULL; }   // touched_ent: with the form, below
   const int grad_rel_copies = det ? 1 : a.grad_rel_copies;   // deterministic mode: one flush slot per group
   if (a.grad_ent && (grad_rel_copies < 1 || grad_rel_copies > 64)) { set_error("grad_rel_copies must be in [1,64]"); return MKE_E_SHAPE; }
 
@@ -621,6 +623,8 @@ static int score_impl(const mke_score_args& a, void* stream) {
   const bool cw = a.neg_code != nullptr && neg_per_pos > 0 && !det && score_codes_legal(a.n_ent, code_rows, a.n_rel, stride);
   if (a.neg_code && neg_per_pos > 0 && !cw && !a.ref_count) { set_error("neg_code: the code-word form needs 32-bit offsets, lane ids and n_ent <= 2^%d (or give ref_count)", MKE_CODE_ENT_BITS); return MKE_E_UNSUPPORTED; }
   if (no_ids && !cw) { set_error("neg_code without neg_h / neg_r / neg_t: only where the code-word form is legal (grouped negatives, 32-bit offsets, lane ids, n_ent <= 2^%d, not deterministic)", MKE_CODE_ENT_BITS); return MKE_E_UNSUPPORTED; }
+  // the code-word form alone runs without entity flags (the update launch reads the bake's bitmap: mke_update_table.bits)
+  if (a.grad_ent && !a.touched_ent && !cw) { set_error("NULL touched array"); return MKE_E_NULL; }
   const bool excl = (a.ref_count != nullptr || cw) && neg_per_pos > 0;   // (a training step: checked above)
   p.refcount = excl && !cw ? a.ref_count : nullptr; p.ent_w = a.ent_table;
   p.neg_code = cw ? a.neg_code : nullptr;
