@@ -251,6 +251,10 @@ int mke_count_entity_refs(const int32_t* pos_h, const int32_t* pos_t, int64_t n_
  *   Without id arrays (neg_h == neg_r == neg_t == NULL beside neg_code): every negative without MKE_CODE_FAST is scored as the
  *   positive's own triple (h, r, t) — what such a word means when the sampler wrote it.  Legal only where the code-word form is
  *   (grouped negatives, not deterministic); anywhere else MKE_E_UNSUPPORTED before anything is launched.
+ *   Without entity flags (mke_score_args.touched_ent == NULL) the update launch finds the rows in `bits` and the step's positives
+ *   (mke_update_table.bits).  That is complete only when every word of the step without MKE_CODE_FAST stands for the positive
+ *   itself, as mke_neg_sample writes it: with id arrays whose slow negatives name other entities, pass touched_ent and update
+ *   by flags (the precondition is spelled out at mke_update_table.bits).
  *
  *   The sampler's own words.  mke_neg_sample holds, for every negative it keeps, the drawn entity, the side and whether the
  *   draw differs from the id it replaces, so it can store the word instead of three ids (two of which copy the positive).
@@ -332,7 +336,12 @@ typedef struct mke_update_table {
    * pair 11, and the rows with pair 01 that pos_h[0, n_pos) or pos_t[0, n_pos), the step's positives, name: those took
    * contributions in the gradient scratch; a row with pair 01 that only a negative names was finished by the score launch.
    * (bits, pos_h, pos_t) must be the bitmap row and the positives of the step whose score launch filled `grad`.  Hub rows
-   * work as with flags; slot_of and grad_copies > 1 -> MKE_E_UNSUPPORTED, as is a second bitmap table in one call. */
+   * work as with flags; slot_of and grad_copies > 1 -> MKE_E_UNSUPPORTED, as is a second bitmap table in one call.
+   * PRECONDITION: every code word of that step without MKE_CODE_FAST stands for the positive itself (h, r, t), which is what
+   * mke_neg_sample writes and all mke_relation_steps ever bakes.  A negative without MKE_CODE_FAST scored from other ids
+   * (both sides replaced; another relation and another head) adds to the scratch rows of ITS entities; one of those referenced
+   * once in the step and by no positive has pair 01 and no list entry, so this form never visits it: its gradient is lost and
+   * the scratch row stays non-zero for the next step.  Steps with such ids take the flag form (`touched`, bits == NULL). */
   const uint32_t* bits;
   const int32_t* pos_h; const int32_t* pos_t; int64_t n_pos;
 } mke_update_table;

@@ -62,6 +62,13 @@ MUTANTS = ("gR_keeps_gP", "cH_cT_swapped", "skip_fourth", "skip_past_first_block
 # that is ADDED adds c * 0 (the tables' pad columns are 0 by the ABI).  test_score_cases.py asserts both equalities;
 # "ragged_guard" is the guard failing the other way (the last live column of a ragged dim skipped).
 SILENT_MUTANTS = ("empty_slice_flushes", "pad_added")
+# The code-word forms (section (1c) of the header).  Mutants of the routing by words; the last one is a mutant of the REFERENCE
+# (it lists entity flags although touched_ent is NULL) and must fail against the unmutated model.
+CODE_ENT_BITS = 26
+CODE_HEAD, CODE_FAST, CODE_EXCL = 1 << 26, 1 << 27, 1 << 28
+CODE_ENT_MASK = (1 << CODE_ENT_BITS) - 1
+CW_MUTANTS = ("cw_excl_ignored", "cw_excl_without_fast", "cw_head_inverted", "cw_slow_skipped", "cw_slow_entity_head", "cw_mask16",
+              "cw_flags_listed")
 
 
 class Form(NamedTuple):
@@ -72,10 +79,18 @@ class Form(NamedTuple):
     lid: int = 1
     half: int = -1          # score_half_groups
     splits: int = 0         # score_splits (0 = auto)
+    cw: int = 0             # neg_code given and no ref_count: the code-word instantiation (only det=0, x=1, o32=1, lid=1, npp > 0)
+    ids: int = 1            # cw: neg_h / neg_r / neg_t given (0: all three NULL, "own" batches only)
+    flags: int = 1          # cw: touched_ent given (0: NULL)
 
     @property
     def id(self):
-        return f"{'det' if self.det else 'atm'}-x{self.x}-o{self.o32}-l{self.lid}-h{self.half}-s{self.splits}"
+        s = f"{'det' if self.det else 'atm'}-x{self.x}-o{self.o32}-l{self.lid}-h{self.half}-s{self.splits}"
+        return s + (f"-cw-i{self.ids}-f{self.flags}" if self.cw else "")
+
+    @property
+    def legal(self):
+        return not self.cw and self.ids == 1 and self.flags == 1 or bool(self.cw and not self.det and self.x and self.o32 and self.lid)
 
 
 def forms12(npp_max=1000):
@@ -87,6 +102,11 @@ def forms12(npp_max=1000):
     return out
 
 
+def forms_cw(npp_max=1000):
+    """The code-word forms of a width: two and one group per wavefront, with and without id arrays, with and without entity flags."""
+    return [Form(0, 1, 1, 1, half, 1, 1, ids, flags) for half in (npp_max, 0) for ids in (1, 0) for flags in (1, 0)]
+
+
 class SCase(NamedTuple):
     stride: int
     dim: int
@@ -94,7 +114,7 @@ class SCase(NamedTuple):
     npp: int = 0            # negatives per positive; 0: ungrouped
     n_neg0: int = 0         # ungrouped negatives
     tier: int = 1
-    kinds: str = "fast"     # fast | mixed | slow2nd | unique | dup
+    kinds: str = "fast"     # fast | mixed | slow2nd | unique | dup | own (the sampler's shape of a batch: see own_positions)
     weights: str = "none"   # none | pos | both
     scale: float = 1.0
     copies: int = 1
@@ -161,8 +181,11 @@ def excl_of(c: SCase, f: Form) -> bool:
 
 
 def instantiation(c: SCase, f: Form):
-    """(FPL, family, flag, QPG): the template arguments launch_score() picks."""
+    """(FPL, family, flag, QPG): the template arguments launch_score() picks; (FPL, "cw", QPG) for the code-word instantiation."""
     x = excl_of(c, f)
+    if f.cw:
+        assert f.legal and x
+        return (c.fpl, "cw", qpg_of(c, f))
     if f.det:
         fam = ("det", x)
     elif x and f.o32:
@@ -174,6 +197,10 @@ def instantiation(c: SCase, f: Form):
 
 def all_instantiations():
     return {(fpl, fam, flag, q) for fpl in FPLS for fam in ("det", "o32", "plain") for flag in (False, True) for q in (2, 4)}
+
+
+def cw_instantiations():
+    return {(fpl, "cw", q) for fpl in FPLS for q in (2, 4)}
 
 
 def count_blocks(c: SCase) -> int:
@@ -210,14 +237,28 @@ def _rng(c: SCase, salt=0):
 
 def sizes(c: SCase):
     """(n_ent, n_rel): a collision-free batch needs a row of its own for every id."""
-    if c.kinds == "unique":
+    if collision_free(c):
         return c.n_pos * (2 + c.npp) + 3, c.n_pos
     return c.n_ent, c.n_rel
 
 
+def collision_free(c: SCase) -> bool:
+    """Every id names a row of its own ("own" with the tag "free": the positive drawn as its own negative apart, which gives its
+    three rows a second add -- two adds to a zero row commute, so device runs still agree bit for bit)."""
+    return c.kinds == "unique" or (c.kinds == "own" and c.tag == "free")
+
+
+def own_positions(npp: int, n_neg: int):
+    """The negatives of an "own" batch that equal their positive (mke_neg_sample keeps the positive when the last round draws
+    the replaced id): the last of an even group (with slices: not slice 0; npp = 1: the group's only negative), the first of an
+    odd group (the first id block) and negative 70 of every group that has one (the second id block, 32 or 64 lanes long)."""
+    g, n = np.arange(n_neg) // npp, np.arange(n_neg) % npp
+    return ((g % 2 == 0) & (n == npp - 1)) | ((g % 2 == 1) & (n == 0) & (npp > 1)) | (n == 70)
+
+
 def _ids(c: SCase, rng, n_ent, n_rel):
     P, N = c.n_pos, c.n_neg
-    if c.kinds == "unique":
+    if collision_free(c):
         perm = rng.permutation(n_ent - 3) + 3 if c.special else rng.permutation(n_ent)
         ph, pt, e = perm[:P], perm[P:2 * P], perm[2 * P:2 * P + N]
         if c.special and N >= 3:
@@ -225,7 +266,8 @@ def _ids(c: SCase, rng, n_ent, n_rel):
         pr = rng.permutation(n_rel)[:P]
         g = np.arange(N) // max(c.npp, 1)
         head = rng.integers(0, 2, N).astype(bool)
-        nh, nt = np.where(head, e, ph[g]), np.where(head, pt[g], e)
+        own = own_positions(c.npp, N) if c.kinds == "own" else np.zeros(N, bool)
+        nh, nt = np.where(head & ~own, e, ph[g]), np.where(head | own, pt[g], e)
         return ph, pr, pt, nh, pr[g].copy(), nt
     ph, pt = rng.integers(0, n_ent, P), rng.integers(0, n_ent, P)
     pr = rng.integers(0, n_rel, P)
@@ -236,6 +278,11 @@ def _ids(c: SCase, rng, n_ent, n_rel):
         return ph, pr, pt, nh, nr, nt
     g = np.arange(N) // c.npp
     n = np.arange(N) % c.npp
+    if c.kinds == "own":                                             # one side replaced by a draw that differs from it, or the positive itself
+        lo = 65536 if n_ent > 65536 else 0                           # a table past 2^16 rows: every draw needs more than 16 bits
+        draw = lambda a: lo + (a - lo + 1 + rng.integers(0, n_ent - lo - 1, len(a))) % (n_ent - lo)
+        head, own = (n + g) % 2 == 0, own_positions(c.npp, N)
+        return ph, pr, pt, np.where(head & ~own, draw(ph[g]), ph[g]), pr[g].copy(), np.where(~head & ~own, draw(pt[g]), pt[g])
     other = lambda a: (a + 1 + rng.integers(0, n_ent - 1, len(a))) % n_ent          # an entity different from a
     kind = np.where((n + g) % 2 == 0, 0, 1)                          # fast: corrupted head / tail in turn
     if c.kinds == "mixed":
@@ -276,6 +323,58 @@ def count_refs(ph, pt, nh, nt, npp, n_neg, n_ent):
         np.add.at(out, nh[:n_neg][nh[:n_neg] != ph[g]], 1)
         np.add.at(out, nt[:n_neg][nt[:n_neg] != pt[g]], 1)
     return out
+
+
+def step_counts(ph, pt, nh, nt, npp, n_ent):
+    """mke_count_entity_refs of one step."""
+    cnt = np.zeros(n_ent, dtype=np.int64)
+    np.add.at(cnt, ph, 1)
+    np.add.at(cnt, pt, 1)
+    g = np.arange(len(nh)) // npp
+    np.add.at(cnt, nh[nh != ph[g]], 1)
+    np.add.at(cnt, nt[nt != pt[g]], 1)
+    return cnt
+
+
+def define(pos, neg, off, s0, s1, npp, n_ent):
+    """Section (1c) of the header in NumPy: (codes of the negatives of steps [s0, s1), bitmap rows [s1 - s0, row_words])."""
+    ph, pr, pt = pos
+    nh, nr, nt = neg                                   # laid out from off[s0]
+    words = (n_ent + 15) // 16
+    codes = np.zeros((off[s1] - off[s0]) * npp, dtype=np.int64)
+    bits = np.zeros((s1 - s0, words), dtype=np.uint32)
+    for s in range(s0, s1):
+        lo, hi = off[s], off[s + 1]
+        a, b = (lo - off[s0]) * npp, (hi - off[s0]) * npp
+        cnt = step_counts(ph[lo:hi], pt[lo:hi], nh[a:b], nt[a:b], npp, n_ent)
+        g = lo + np.arange(b - a) // npp
+        dh, dt = nh[a:b] != ph[g], nt[a:b] != pt[g]
+        e = np.where(dh, nh[a:b], nt[a:b]).astype(np.int64)
+        fast = (nr[a:b] == pr[g]) & (dh != dt)
+        codes[a:b] = e | np.where(dh, CODE_HEAD, 0) | np.where(fast, CODE_FAST, 0) | np.where(cnt[e] == 1, CODE_EXCL, 0)
+        two = np.where(cnt == 0, 0, np.where(cnt == 1, 1, 3)).astype(np.uint32)
+        ent = np.arange(n_ent)
+        np.bitwise_or.at(bits[s - s0], ent >> 4, two << ((ent & 15) * 2).astype(np.uint32))
+    return codes.astype(np.int32), bits
+
+
+def codes_of(c: SCase) -> np.ndarray:
+    """The baked code words of the case's one step."""
+    return step_codes(c)[0]
+
+
+def step_codes(c: SCase):
+    """(words [n_neg], bitmap row [(n_ent + 15) // 16]) of the case's one step; `sampler_words` are the words before the bake."""
+    o = ops(c)
+    n_ent, _ = sizes(c)
+    codes, bits = define((o.ph, o.pr, o.pt), (o.nh[:c.n_neg], o.nr[:c.n_neg], o.nt[:c.n_neg]), np.array([0, c.n_pos]), 0, 1, c.npp, n_ent)
+    return codes, bits[0]
+
+
+def sampler_words(c: SCase) -> np.ndarray:
+    """What mke_neg_sample writes for an "own" batch: draw | HEAD | FAST, or pos_t without flags for the positive itself."""
+    assert c.kinds == "own"
+    return codes_of(c) & ~np.int32(CODE_EXCL)
 
 
 def tier2_shift(dim: int) -> int:
@@ -527,6 +626,24 @@ def _reference(c, f, mode, mutant):
         if mutant == "equal_as_fast":
             fast = fast | ((nr == o.pr[g]) & ~dh & ~dt)
         e = np.where(dh, nh, nt)
+        xbit = o.ref_count[:n_ent][e] == 1                           # MKE_CODE_EXCL of the negative's word
+        if f.cw:
+            # the kernel sees the WORD (entity, HEAD, FAST, EXCL) and, for a word without FAST, the id arrays or -- without
+            # them -- the positive's own triple; only the sampler's shape of a batch may come without ids
+            assert f.legal and (f.ids or c.kinds == "own") and not c.fwd_only, (c.id, f.id)
+            w = codes_of(c)                                          # the routing below is the NumPy statement of section (1c)
+            assert np.array_equal(w & CODE_ENT_MASK, e) and np.array_equal((w & CODE_HEAD) != 0, dh), c.id
+            assert np.array_equal((w & CODE_FAST) != 0, fast) and np.array_equal((w & CODE_EXCL) != 0, xbit), c.id
+            if mutant == "cw_head_inverted":
+                dh = np.where(fast, ~dh, dh)
+            if mutant == "cw_mask16":
+                e = e & 0xFFFF
+            sh, sr, st_ = (nh, nr, nt) if f.ids else (o.ph[g], o.pr[g], o.pt[g])
+            if mutant == "cw_slow_entity_head" and not f.ids:
+                sh = e
+            nh, nr, nt = np.where(fast, np.where(dh, e, o.ph[g]), sh), np.where(fast, o.pr[g], sr), np.where(fast, np.where(dh, o.pt[g], e), st_)
+            if mutant == "cw_slow_skipped" and not f.ids:
+                live_neg &= fast
         lpg = 64 if qpg == 4 else 32
         if mutant == "skip_fourth":
             live_neg &= (n - s * per) % 4 != 3
@@ -558,6 +675,8 @@ def _reference(c, f, mode, mutant):
             ip = np.zeros(N, bool)
             if excl:
                 ip[fi] = (cnt[e[fi]] == 1) | ((cnt[e[fi]] == 2) if mutant == "inplace_at_2" else False)
+            if f.cw:                                                  # in-place rows are exactly the words with FAST and EXCL
+                ip[fi] = xbit[fi] & (mutant != "cw_excl_ignored")
             a, b = fi[~ip[fi]], fi[ip[fi]]
             # a fast negative's own row, then its share of the flush of its work item (group g, slice s)
             swap = mutant == "cH_cT_swapped"
@@ -570,9 +689,12 @@ def _reference(c, f, mode, mutant):
             # slow negatives: three rows each
             gs, ns = g[si], n[si]
             k3 = gs * (npp + 1) + ns
-            E.add(0, hub(nh[si], k3), nh[si], stage_slot(gs, npp, ns, 0), P + si, 1)
+            kh = kt = np.ones(len(si), bool)
+            if mutant == "cw_excl_without_fast" and f.cw:             # the word's entity row left to an in-place update that never comes
+                kh, kt = ~(xbit[si] & dh[si]), ~(xbit[si] & ~dh[si])
+            E.add(0, hub(nh[si], k3)[kh], nh[si][kh], stage_slot(gs, npp, ns, 0)[kh], P + si[kh], 1)
             E.add(1, relcopy(s[si] * P + gs) * n_rel + nr[si], nr[si], stage_slot(gs, npp, ns, 1), P + si, 1)
-            E.add(0, hub(nt[si], k3), nt[si], stage_slot(gs, npp, ns, 2), P + si, -1)
+            E.add(0, hub(nt[si], k3)[kt], nt[si][kt], stage_slot(gs, npp, ns, 2)[kt], P + si[kt], -1)
             # the positive (slice 0), and the zero every flushing work item adds to its three rows
             gg = np.nonzero(groups)[0]
             E.add(0, hub(o.ph[gg], gg), o.ph[gg], stage_slot(gg, npp, npp, 0), gg, 1)
@@ -698,6 +820,11 @@ def _assemble(c, f, o, ar, E, Dval, Derr, Lval, Lerr, inpl, mutant, K, det, excl
     out["acc"] = (acc.astype(f32), None) if lossless else (acc, acc_err)
     out["ref_count"] = rcnt
     out["in_place_rows"] = rows
+    if f.cw:                                                         # neither reads nor resets ref_count; no entity flag without touched_ent
+        out["cw"] = True
+        del out["ref_count"]
+        if not f.flags and mutant != "cw_flags_listed":
+            del out["touched_ent"]
     return out
 
 
@@ -773,6 +900,8 @@ def compare(got: dict, want: dict):
     for name in ("touched_ent", "touched_rel", "ref_count", "stage_keys"):
         if name in got and name in want and not np.array_equal(got[name], want[name]):
             problems.append(f"{name}: differs from the reference")
+    if want.get("cw") and "touched_ent" in want and "touched_ent" not in got:
+        problems.append("touched_ent: the reference lists entity flags, the launch had no flag array")
     return problems, ratios
 
 
@@ -903,6 +1032,44 @@ def _build():
 
 
 RUNS = _build()
+
+
+def _build_cw():
+    """The runs of the code-word forms (beside RUNS, which they leave as it is).  Per width: every group length on "own" batches in
+    tier 1, the eight forms in rotation; in tier 2 all eight forms on "own" batches with collisions (normalised tables, hub rows,
+    a second id block), the forms with ids on "mixed" batches, slices, and the collision-free batches of tier E."""
+    runs = []
+    add = lambda case, form: runs.append(Run(case, form))
+    F = forms_cw()
+    for si, stride in enumerate(STRIDES):
+        dims = table_dims(stride)
+        for ni, npp in enumerate(NPPS):
+            k = ni + si
+            add(SCase(stride, dims[k % len(dims)], (3, 4, 2)[k % 3], npp, kinds="own", weights=("none", "pos", "both")[k % 3], scale=(1.0, 0.25)[k % 2],
+                      copies=REL_COPIES[k % 4], opt=("sgd", "adagrad")[(k // 2) % 2], n_ent=40), F[k % 8])
+        dim = dims[si % len(dims)]
+        t2 = (SCase(stride, dim, 4, 9, tier=2, kinds="own", weights="both", copies=2, ent_norm=1, rel_norm=1, opt="adagrad", n_ent=40),
+              SCase(stride, dims[(si + 1) % len(dims)], 3, 65, tier=2, kinds="own", weights="both", copies=8, opt="sgd", n_hot=5, hot_copies=3, n_ent=60),
+              SCase(stride, dim, 5, 1, tier=2, kinds="own", weights="pos", ent_norm=1, opt="sgd", n_hot=1, hot_copies=2, n_ent=12))
+        for c in t2:
+            for form in F:
+                add(c, form)
+        for form in F:
+            if form.ids:                                             # words without FAST that stand for other ids than the positive's
+                add(SCase(stride, dim, 3, 9, tier=2, kinds="mixed", weights="both", copies=2, ent_norm=1, rel_norm=1, opt="adagrad", n_ent=60), form)
+            if form.half == 0:                                       # slices: the positive as its own negative outside slice 0
+                add(SCase(stride, dim, 2, 10, tier=2, kinds="own", weights="both", copies=2, ent_norm=1, opt="adagrad", n_ent=40, tag="slices"),
+                    form._replace(splits=3))
+        for en, opt in ((1, "adagrad"), (0, "sgd")):                 # tier E (every form runs them, see the GPU test)
+            add(SCase(stride, dim, 4, 9, tier=2, kinds="own", weights="both", ent_norm=en, rel_norm=en, opt=opt, special=bool(en), tag="free"), F[0])
+    for form in F:                                                   # entities past 2^16: a 16-bit entity mask shows
+        add(SCase(16, 16, 3, 9, tier=2, kinds="own", weights="both", n_ent=70000, tag="mask"), form)
+    assert len({r.id for r in runs}) == len(runs) and all(r.form.legal and r.case.npp > 0 for r in runs)
+    assert all(r.form.ids or r.case.kinds == "own" for r in runs)
+    return runs
+
+
+CW_RUNS = _build_cw()
 
 
 def runs_of(**kw):

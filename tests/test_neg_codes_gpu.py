@@ -44,38 +44,7 @@ def sync():
 
 
 # ----------------------------------------------------------------------------------------------------- the definition
-def step_counts(ph, pt, nh, nt, npp, n_ent):
-    """mke_count_entity_refs of one step."""
-    cnt = np.zeros(n_ent, dtype=np.int64)
-    np.add.at(cnt, ph, 1)
-    np.add.at(cnt, pt, 1)
-    g = np.arange(len(nh)) // npp
-    np.add.at(cnt, nh[nh != ph[g]], 1)
-    np.add.at(cnt, nt[nt != pt[g]], 1)
-    return cnt
-
-
-def define(pos, neg, off, s0, s1, npp, n_ent):
-    """(codes of the negatives of steps [s0, s1), bitmap rows [s1 - s0, row_words])."""
-    from multike_amd import _lib
-    ph, pr, pt = pos
-    nh, nr, nt = neg                                   # laid out from off[s0]
-    words = (n_ent + 15) // 16
-    codes = np.zeros((off[s1] - off[s0]) * npp, dtype=np.int64)
-    bits = np.zeros((s1 - s0, words), dtype=np.uint32)
-    for s in range(s0, s1):
-        lo, hi = off[s], off[s + 1]
-        a, b = (lo - off[s0]) * npp, (hi - off[s0]) * npp
-        cnt = step_counts(ph[lo:hi], pt[lo:hi], nh[a:b], nt[a:b], npp, n_ent)
-        g = lo + np.arange(b - a) // npp
-        dh, dt = nh[a:b] != ph[g], nt[a:b] != pt[g]
-        e = np.where(dh, nh[a:b], nt[a:b]).astype(np.int64)
-        fast = (nr[a:b] == pr[g]) & (dh != dt)
-        codes[a:b] = e | np.where(dh, _lib.CODE_HEAD, 0) | np.where(fast, _lib.CODE_FAST, 0) | np.where(cnt[e] == 1, _lib.CODE_EXCL, 0)
-        two = np.where(cnt == 0, 0, np.where(cnt == 1, 1, 3)).astype(np.uint32)
-        ent = np.arange(n_ent)
-        np.bitwise_or.at(bits[s - s0], ent >> 4, two << ((ent & 15) * 2).astype(np.uint32))
-    return codes.astype(np.int32), bits
+from score_cases import define, step_counts          # noqa: E402  (the NumPy statement of section (1c): one definition, in the case module)
 
 
 def bake(pos, neg, off, s0, s1, npp, n_ent, extra_rows=2):

@@ -38,6 +38,19 @@ two-kernel path is NOT bit-identical to the in-place rows: of 52 collision-free 
 the last bit of 1 to 59 table elements and one (stride 320, Adagrad, entity table not normalised) in 1225 of 8640, never in the
 accumulator: mke_rows_update associates the Jacobian differently and w - lr g s is not contracted alike at every width.  Both
 sit inside the counted bound, and the header says so now.
+
+The code-word forms (k_triple_score<..., CW>: neg_code instead of ref_count; score_cases.CW_RUNS) run the same way: neg_code with
+a poisoned pad behind it, neg_h / neg_r / neg_t NULL when ids = 0, touched_ent NULL when flags = 0, a poisoned ref_count that must
+come back untouched.  Tier 1 matched bit for bit in all 26 instantiations and all four (ids, flags) combinations; tier E found
+the code-word form equal to the ref_count form, ids = 0 equal to ids = 1 and flags = 0 equal to flags = 1 in every buffer they
+share.  Worst error / bound, tier 2 (the same for q2 and q4 and for flags = 0 / 1 unless two figures are given):
+
+  form                              loss     grad_ent  grad_rel          in-place w  in-place acc
+  code words with ids               0.0550   0.2340    0.1944            0.4921      0.4545
+  code words without ids            0.0550   0.1797    0.0653 / 0.0675   0.4921      0.4545
+
+(with ids the "mixed" batches run as well, hence the larger gradient figures).  test_score_cases.py shows that seven kinds of
+kernel that route the words wrongly fail these comparisons.
 """
 import ctypes as C
 
@@ -79,6 +92,12 @@ def sync():
         pytest.exit(f"device error: {e}", returncode=3)
 
 
+RC_POISON = 0x5A5A5A5A
+CODE_PAD = 64
+# what the pad behind neg_code holds: read as a word it would finish row 0 in place (seen by the comparisons) and never leave the tables
+CODE_POISON = sc.CODE_FAST | sc.CODE_HEAD | sc.CODE_EXCL
+
+
 def sentinel(rows, stride):
     return np.full((rows + 1, stride), SENTINEL, dtype=f32)
 
@@ -93,8 +112,15 @@ def launch(c, f, want):
     d = {k: dev(getattr(o, k)) for k in ("ent", "rel", "ph", "pr", "pt", "pw", "nh", "nr", "nt", "nw", "hot_slot")}
     d["acc"] = dev(o.acc) if c.opt == "adagrad" else None
     d["ref_count"] = dev(o.ref_count) if (f.x and bwd) else None
+    if f.cw:                                                          # the word array with its poisoned pad, a poisoned ref_count
+        d["ref_count"] = dev(np.full(n_ent + 1, RC_POISON, np.int32))
+        d["neg_code"] = dev(np.concatenate([sc.codes_of(c), np.full(CODE_PAD, CODE_POISON, np.int32)]))
+        if not f.ids:
+            d["nh"] = d["nr"] = d["nt"] = None
     d["partials"] = dev(np.full(sc.LOSS_PARTIALS, np.nan))
     d["touched_ent"], d["touched_rel"] = dev(np.full(n_ent + 64, OLD_TAG, np.int32)), dev(np.full(n_rel + 64, OLD_TAG, np.int32))
+    if f.cw and not f.flags:
+        d["touched_ent"] = None
     n_gent = n_ent + (c.hot_copies * c.n_hot if c.n_hot else 0)
     if bwd:
         d["grad_ent"] = dev(sc.initial("grad_ent", want) if "grad_ent" in want else sentinel(n_gent, st))
@@ -104,7 +130,8 @@ def launch(c, f, want):
                        pos_w=addr(d["pw"]), n_pos=c.n_pos, neg_h=addr(d["nh"]), neg_r=addr(d["nr"]), neg_t=addr(d["nt"]), neg_w=addr(d["nw"]),
                        n_neg=c.n_neg, neg_per_pos=c.npp, scale=c.scale, grad_ent=addr(d.get("grad_ent")), grad_rel=addr(d.get("grad_rel")),
                        grad_rel_copies=c.copies, touched_ent=addr(d["touched_ent"]), touched_rel=addr(d["touched_rel"]), tag=TAG,
-                       ref_count=addr(d["ref_count"]), ent_acc=addr(d["acc"]), optimizer=opt_code(c), lr=c.lr, loss_partials=addr(d["partials"]))
+                       ref_count=addr(d["ref_count"]), ent_acc=addr(d["acc"]), optimizer=opt_code(c), lr=c.lr, loss_partials=addr(d["partials"]),
+                       neg_code=addr(d.get("neg_code")))
     if c.n_hot:
         a.hot = _lib.HotRowsStruct(addr(d["hot_slot"]), c.n_hot, c.hot_copies, n_ent)
     if f.det:
@@ -128,6 +155,9 @@ def launch(c, f, want):
                                                                       "touched_rel", "ent", "acc", "ref_count", "rel")}
     if c.rider:
         got["counted"] = host(keep[4])
+    if f.cw:                                                          # neither reads nor resets ref_count; the words and their pad stay
+        assert (got.pop("ref_count") == RC_POISON).all(), (c.id, f.id, "ref_count was written")
+        assert np.array_equal(host(d["neg_code"]), np.concatenate([sc.codes_of(c), np.full(CODE_PAD, CODE_POISON, np.int32)]))
     got["_dev"] = d
     return got
 
@@ -150,8 +180,9 @@ def reduce_staged(c, got, want):
 
 def report(ratios, r):
     inst = sc.instantiation(r.case, r.form)
+    fam = f"cw-i{r.form.ids}f{r.form.flags}-q{inst[2]}" if r.form.cw else f"{inst[1]}{int(inst[2])}-q{inst[3]}"
     for name, v in ratios.items():
-        print(f"RATIO score:{inst[1]}{int(inst[2])}-q{inst[3]}:{name} {v:.4f} {r.id}")
+        print(f"RATIO score:{fam}:{name} {v:.4f} {r.id}")
 
 
 def run(r):
@@ -163,7 +194,7 @@ def run(r):
     o = sc.ops(c)
     if not np.array_equal(got["rel"].view(np.int32), o.rel.view(np.int32)):
         problems.append("rel_table changed")
-    if "ref_count" not in got and not np.array_equal(got["ent"].view(np.int32), o.ent.view(np.int32)):
+    if "ref_count" not in got and not f.cw and not np.array_equal(got["ent"].view(np.int32), o.ent.view(np.int32)):
         problems.append("ent_table changed without the exclusive path")
     if c.fwd_only and not ((got["touched_ent"] == OLD_TAG).all() and (got["touched_rel"] == OLD_TAG).all()):
         problems.append("forward only: a flag was set")
@@ -321,6 +352,153 @@ def test_count_entity_refs_alone(total):
     assert code == 0, _lib.lib().mke_last_error()
     sync()
     assert np.array_equal(host(d[4]), uc.count_reference(cc))
+
+
+# ----------------------------------------------------------------------------------------------------- the code-word forms
+def select_cw(stride, **kw):
+    return [r for r in sc.CW_RUNS if r.case.stride == stride and all(getattr(r.case, k) == v for k, v in kw.items())]
+
+
+def test_code_constants():
+    from multike_amd import _lib
+    assert (sc.CODE_ENT_BITS, sc.CODE_HEAD, sc.CODE_FAST, sc.CODE_EXCL) == (_lib.CODE_ENT_BITS, _lib.CODE_HEAD, _lib.CODE_FAST, _lib.CODE_EXCL)
+
+
+@pytest.mark.parametrize("stride", STRIDES)
+def test_cw_tier1(stride):
+    """k_triple_score<..., CW> bit for bit on the sampler's shape of a batch: with and without id arrays, with and without
+    touched_ent, two and one group per wavefront, every group length."""
+    seen = set()
+    for r in select_cw(stride, tier=1):
+        run(r)
+        seen.add(sc.instantiation(r.case, r.form) + (r.form.ids, r.form.flags))
+    assert {i[:3] for i in seen} == {(stride // 16, "cw", q) for q in (2, 4)} and len(seen) == 8, sorted(seen)
+
+
+@pytest.mark.parametrize("stride", STRIDES)
+def test_cw_tier2(stride):
+    """The same against float64 within the derived bound: collisions, rows finished in place by MKE_CODE_EXCL, hub rows, slices,
+    the second id block, words without MKE_CODE_FAST with and without ids; at stride 16 a table of 70,000 rows."""
+    seen = set()
+    for r in select_cw(stride, tier=2):
+        run(r)
+        seen.add((sc.qpg_of(r.case, r.form), r.form.ids, r.form.flags))
+    assert len(seen) == 8
+
+
+def same_bits(a, b):
+    return np.array_equal(a.view(np.int32 if a.itemsize == 4 else np.int64), b.view(np.int32 if b.itemsize == 4 else np.int64))
+
+
+@pytest.mark.parametrize("stride", STRIDES)
+def test_cw_tier_e(stride):
+    """Collision-free batches (a row takes one add, or the two of a positive drawn as its own negative, which commute): the
+    code-word form against the ref_count form of the same grouping in every buffer both leave, ids = 0 against ids = 1 in every
+    buffer, flags = 0 against flags = 1 in every buffer but the entity flags."""
+    cases = [r.case for r in select_cw(stride, tag="free")]
+    assert len(cases) == 2
+    for c in cases:
+        for half in (1000, 0):
+            base_f = sc.Form(0, 1, 1, 1, half, 1)
+            base = launch(c, base_f, sc.reference(c, base_f))
+            got = {}
+            for f in (f for f in sc.forms_cw() if f.half == half):
+                got[f.ids, f.flags] = run(sc.Run(c, f))
+            for k in ("partials", "ent", "acc", "rel", "grad_ent", "grad_rel", "touched_ent", "touched_rel"):
+                if k in base:
+                    assert same_bits(base[k], got[1, 1][k]), (c.id, half, k, "code words against ref_count")
+                for ids, flags in ((0, 1), (1, 0), (0, 0)):
+                    if k in base and not (k == "touched_ent" and not flags):
+                        assert same_bits(got[1, 1][k], got[ids, flags][k]), (c.id, half, k, ids, flags)
+            assert "touched_ent" not in got[1, 0] and "touched_ent" not in got[0, 0]
+            assert not base["ref_count"][sc.reference(c, base_f)["in_place_rows"]].any()
+
+
+def refusal_args(c, d, **kw):
+    from multike_amd import _lib
+    n_ent, n_rel = sc.sizes(c)
+    return _lib.ScoreArgs(ent_table=addr(d["ent"]), n_ent=n_ent, ent_normalize=c.ent_norm, rel_table=addr(d["rel"]), n_rel=n_rel,
+                          rel_normalize=c.rel_norm, stride=c.stride, dim=c.dim, pos_h=addr(d["ph"]), pos_r=addr(d["pr"]), pos_t=addr(d["pt"]),
+                          pos_w=addr(d["pw"]), n_pos=c.n_pos, neg_h=addr(d["nh"]), neg_r=addr(d["nr"]), neg_t=addr(d["nt"]), neg_w=addr(d["nw"]),
+                          n_neg=c.n_neg, neg_per_pos=c.npp, scale=c.scale, grad_ent=addr(d["grad_ent"]), grad_rel=addr(d["grad_rel"]),
+                          grad_rel_copies=c.copies, touched_ent=addr(d["touched_ent"]), touched_rel=addr(d["touched_rel"]), tag=TAG,
+                          ref_count=addr(d["ref_count"]), ent_acc=addr(d["acc"]), optimizer=opt_code(c), lr=c.lr,
+                          loss_partials=addr(d["partials"]), neg_code=addr(d["neg_code"]), **kw)
+
+
+def test_cw_refusals_and_fallbacks():
+    """Where the code-word form is not legal -- 64-bit offsets, ids per round, deterministic staging, ungrouped negatives -- a call
+    without id arrays, or without touched_ent, is refused before anything is launched (every buffer unchanged), with the code
+    score_impl's order of checks gives; with ids, flags and ref_count it runs the ref_count form and resets the counts."""
+    from multike_amd import _lib
+    L = _lib.lib()
+    NULL, SHAPE, UNSUPPORTED = -1, -2, -3
+    c = select_cw(16, tag="free")[0].case
+    o = sc.ops(c)
+    n_ent, n_rel = sc.sizes(c)
+    n_slots = 3 * c.n_pos * (c.npp + 1)
+    full = sc.Form(0, 1, 1, 1, 0, 1)
+    want = sc.reference(c, full)
+
+    def fresh():
+        d = {k: dev(getattr(o, k)) for k in ("ent", "rel", "acc", "ph", "pr", "pt", "pw", "nh", "nr", "nt", "nw", "ref_count")}
+        d["grad_ent"], d["grad_rel"] = dev(sc.initial("grad_ent", want)), dev(sc.initial("grad_rel", want))
+        d["touched_ent"], d["touched_rel"] = dev(np.full(n_ent + 64, OLD_TAG, np.int32)), dev(np.full(n_rel + 64, OLD_TAG, np.int32))
+        d["partials"] = dev(np.full(sc.LOSS_PARTIALS, np.nan))
+        d["neg_code"] = dev(np.concatenate([sc.codes_of(c), np.full(CODE_PAD, CODE_POISON, np.int32)]))
+        d["stage_rows"], d["stage_keys"] = dev(sentinel(n_slots, c.stride)), dev(np.full(n_slots + 1, sc.KEY_FILL, dtype=np.int64))
+        return d
+
+    def call(d, where, drop):
+        """mke_triple_score_step with the buffers named in `drop` passed as NULL, in the setting `where` that makes the form illegal."""
+        use = {k: (None if k in drop else v) for k, v in d.items()}
+        knobs = dict(score_splits=1, score_half_groups=0, score_offsets32=int(where != "o64"), score_lane_ids=int(where != "rounds"))
+        tune = _lib.tuning(**knobs)
+        a = refusal_args(c, use, tuning=C.addressof(tune))
+        if where == "det":
+            a.stage_rows, a.stage_keys, a.stage_slots = addr(d["stage_rows"]), addr(d["stage_keys"]), n_slots
+        if where == "ungrouped":
+            a.neg_per_pos = 0
+        return L.mke_triple_score_step(C.byref(a), _lib._stream())
+
+    ids, flag, counts = ("nh", "nr", "nt"), ("touched_ent",), ("ref_count",)
+    expected = {  # (buffers left out) -> code per setting
+        ids + counts: dict(o64=UNSUPPORTED, rounds=UNSUPPORTED, det=UNSUPPORTED, ungrouped=UNSUPPORTED),
+        ids: dict(o64=UNSUPPORTED, rounds=UNSUPPORTED, det=UNSUPPORTED, ungrouped=UNSUPPORTED),
+        flag + counts: dict(o64=UNSUPPORTED, rounds=UNSUPPORTED, det=UNSUPPORTED, ungrouped=NULL),      # neg_code without ref_count comes first
+        flag: dict(o64=NULL, rounds=NULL, det=NULL, ungrouped=NULL),
+        ids + flag: dict(o64=UNSUPPORTED, rounds=UNSUPPORTED, det=UNSUPPORTED, ungrouped=UNSUPPORTED),
+    }
+    for drop, codes in expected.items():
+        for where, code in codes.items():
+            d = fresh()
+            before = {k: v.clone() for k, v in d.items() if v is not None}
+            assert call(d, where, drop) == code, (drop, where, L.mke_last_error())
+            sync()
+            for k, v in before.items():
+                assert torch.equal(d[k].view(torch.int32), v.view(torch.int32)), (drop, where, k, "changed by a refused call")
+    # the legal setting takes every one of these calls
+    for drop in expected:
+        tune = _lib.tuning(score_splits=1, score_half_groups=0, score_offsets32=1, score_lane_ids=1)
+        d = fresh()
+        a = refusal_args(c, {k: (None if k in drop else v) for k, v in d.items()}, tuning=C.addressof(tune))
+        assert L.mke_triple_score_step(C.byref(a), _lib._stream()) == 0, (drop, L.mke_last_error())
+        sync()
+        assert torch.equal(d["ref_count"], dev(o.ref_count))
+    # neg_code beside ref_count where the code-word form is not legal: the ref_count form runs and resets the counts
+    for where, f in (("o64", sc.Form(0, 1, 0, 1, 0, 1)), ("rounds", sc.Form(0, 1, 1, 0, 0, 1)), ("det", sc.Form(1, 1, 1, 1, 0, 1))):
+        d = fresh()
+        assert call(d, where, ()) == 0, (where, L.mke_last_error())
+        sync()
+        w = sc.reference(c, f)
+        got = {k: host(d[k]) for k in ("partials", "ent", "acc", "ref_count", "touched_ent", "touched_rel")}
+        if where == "det":
+            got.update(stage_rows=host(d["stage_rows"]), stage_keys=host(d["stage_keys"]))
+        else:
+            got.update(grad_ent=host(d["grad_ent"]), grad_rel=host(d["grad_rel"]))
+        problems, _ = sc.compare(got, w)
+        assert not problems, (where, problems)
+        assert not got["ref_count"][w["in_place_rows"]].any() and len(w["in_place_rows"])
 
 
 def test_refusals_launch_nothing():

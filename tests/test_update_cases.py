@@ -2,7 +2,8 @@
 chunk, row shape, listed value and grid cap of the update kernels; every exact case stays within 24 bits; the float32
 arithmetic, run one rounding at a time (plain and with the two a - b c contracted), equals the float64 reference where that
 is exact and stays within half the derived bound where it is not; and every mutant of the reference -- a kernel that is
-subtly wrong -- breaks the comparison the device test makes, on at least one case.  Runs without a GPU."""
+subtly wrong -- breaks the comparison the device test makes, on at least one case.  Bitmap tables (BIT_CASES, BIT_LAUNCHES: the
+visited set from a bitmap row and the step's positives) are held the same way, with nine mutants of their own.  Runs without a GPU."""
 import numpy as np
 import pytest
 
@@ -327,6 +328,180 @@ def test_routing_and_count_mutants_break_a_launch():
     for L in uc.LAUNCHES:
         if L.count and L.count.total > 100:
             assert not np.array_equal(uc.count_reference(L.count), uc.count_reference(L.count, "count_repeats")), L.name
+
+
+# ----------------------------------------------------------------------------------------------------- bitmap tables
+BITS = uc.BIT_CASES
+BIT_SMALL = [c for c in BITS if c.n <= 1023]
+
+
+def list_stats(c, o):
+    """Per wavefront of the list segment: how many of its entries name a row with pair 01."""
+    pair = uc.pairs_of(o.bits, c.n)
+    ent = np.concatenate([o.pos_h[:c.n_pos], o.pos_t[:c.n_pos]])
+    return [int((pair[ent[lo:lo + uc.LIST_WAVE]] == 1).sum()) for lo in range(0, 2 * c.n_pos, uc.LIST_WAVE)]
+
+
+def check_bit_operands(c, o):
+    n, P = c.n, c.n_pos
+    words = (n + 15) // 16
+    assert o.bits.dtype == np.uint32 and o.bits.shape == (words + 2,) and (o.bits[words:] == 0xFFFFFFFF).all()
+    if n % 16:
+        assert o.bits[words - 1] >> np.uint32(2 * (n % 16)) == (1 << (2 * (16 - n % 16))) - 1          # the junk pairs: 11
+    assert o.pos_h.shape == o.pos_t.shape == (P + uc.LIST_PAD,) and o.pos_h.dtype == np.int32
+    pair = uc.pairs_of(o.bits, n)
+    ent = np.concatenate([o.pos_h[:P], o.pos_t[:P]])
+    assert ((ent >= 0) & (ent < n)).all()
+    named = np.bincount(ent, minlength=n)
+    # the bake's invariant: a pair-01 row is named at most once; a row named twice or by h and t of one positive is 11 or unvisited
+    assert (named[pair == 1] <= 1).all()
+    assert not ((o.pos_h[:P] == o.pos_t[:P]) & (pair[o.pos_h[:P]] == 1)).any()
+    assert np.array_equal(o.visited, (pair == 3) | ((pair == 1) & (named > 0)))
+    for pad in (o.pos_h[P:], o.pos_t[P:]):                      # behind the lists: rows a visit would spoil
+        assert ((pair[pad] == 1) & (named[pad] == 0)).all() or not ((pair == 1) & (named == 0)).any()
+    # the gradient of an unvisited row is SENTINEL whatever its pair
+    assert (o.grad[:n][~o.visited] == uc.SENTINEL).all() and rc.is_quarters(o.grad[:n][o.visited])
+    assert o.touched is None or (o.touched == uc.TAG).all()
+    return pair, named
+
+
+def test_bitmap_table_covers_the_shapes():
+    assert uc.N_BITS == (1, 15, 16, 17, 31, 32, 33, 255, 257) and uc.N_POS == (0, 1, 3, 4, 5, 8, 9, 15, 16, 17, 33, 300) and uc.LIST_WAVE == 8
+    small = [c for c in BITS if c.n <= 257 and not c.n_hot]
+    assert {c.n_pos for c in small} == set(uc.N_POS) and {c.lpat for c in small} == set(uc.LIST_PATTERNS)
+    kinds = {k: 0 for k in ("01 unnamed", "00 named", "10", "10 named", "11 named twice", "h == t")}
+    for stride in uc.STRIDES:
+        mine = [c for c in BITS if c.stride == stride]
+        assert {c.n for c in mine} >= set(uc.N_BITS) | set(uc.N_BITS_LARGE), stride
+        assert {(c.n, c.chunk) for c in mine if c.n > uc.N_SMALL_MAX and not c.n_hot} == {(n, ch) for n in uc.N_BITS_LARGE for ch in (16, 64)}
+        assert {uc.row_shape(c.n, stride, c.chunk) for c in mine if c.chunk == 64} == {"wave" if stride % 64 == 0 else "quarter64"}
+        assert {(c.opt, c.normalize) for c in mine} >= {("sgd", 0), ("sgd", 1), ("adagrad", 0), ("adagrad", 1)}
+        assert {c.lr for c in mine} == set(uc.LRS) and {c.refcount for c in mine} == {True, False} and any(c.special for c in mine)
+        # every q of the list walk with k = 0 and k = 1, and every q of the chunk walk, at a ragged dim of this width
+        deal = [c for c in mine if c.n == 1023 and c.n_pos == 100]
+        assert {c.lpat for c in deal} == {"q0", "q1", "q2", "q3"} and {c.pattern for c in deal} == {"q0", "q1", "q2"}
+        assert all(c.dim < stride for c in deal)
+        for c in deal:
+            q = int(c.lpat[1])
+            st = list_stats(c, uc.rows_ops(c))
+            assert len(st) == 25 and st == [4 * (i % 2) + 1 + q for i in range(25)], (c.id, st[:6])
+        large = [c for c in mine if c.n > uc.N_SMALL_MAX and not c.n_hot]          # the chunk walk's q patterns where a chunk has 16 and 64 pairs
+        assert {c.pattern for c in large} == {"q0", "q1", "q2", "q3"} and all(c.dim < stride for c in large)
+    for c in BITS:
+        if c.n > 1023 and c.stride not in (16, 80, 64):
+            continue
+        o = uc.rows_ops(c)
+        pair, named = check_bit_operands(c, o)
+        kinds["01 unnamed"] += int(((pair == 1) & (named == 0)).any())
+        kinds["00 named"] += int(((pair == 0) & (named > 0)).any())
+        kinds["10"] += int(((pair == 2) & (named == 0)).any())
+        kinds["10 named"] += int(((pair == 2) & (named > 0)).any())
+        kinds["11 named twice"] += int(((pair == 3) & (named > 1)).any())
+        kinds["h == t"] += int((o.pos_h[:c.n_pos] == o.pos_t[:c.n_pos]).any())
+        if c.lpat == "all" and c.n_pos >= 4 and c.n >= 255 and c.pattern not in ("all", "q3"):
+            assert list_stats(c, o)[0] == uc.LIST_WAVE                                # all eight entries of a wavefront set
+        if c.lpat == "none":
+            assert not any(list_stats(c, o))
+        if c.special and c.lpat != "none":
+            assert o.visited[:3].all() and pair[1] == 1 and pair[0] == 3          # the 2^-30 row goes through the list
+        if c.n_hot:
+            hub = np.nonzero(o.hot_slot[:c.n] >= 0)[0]
+            assert len(hub) == c.n_hot
+            by_list, by_chunk = hub[(pair[hub] == 1) & o.visited[hub]], hub[pair[hub] == 3]
+            assert (len(by_list) >= 1 and len(by_chunk) >= 1) if c.n_hot > 1 else (len(by_list) + len(by_chunk) == 1), c.id
+    assert all(kinds.values()), kinds
+    hub = [c for c in BITS if c.n_hot]
+    assert {(c.n_hot, c.hot_copies) for c in hub if c.n == 65} == {(h, k) for h in uc.N_HOT for k in uc.HOT_COPIES}
+    assert {uc.row_shape(c.n, c.stride, c.chunk) for c in hub} == {"quarter", "quarter64", "wave"}
+    one = [uc.pairs_of(uc.rows_ops(c).bits, c.n)[uc.rows_ops(c).hot_slot[:c.n] >= 0][0] for c in hub if c.n_hot == 1 and c.n == 65]
+    assert set(one) == {1, 3}                                   # the single hub row: through the list, and through the chunk walk
+    # launches: production (flagged relation table with copies, then the bitmap table), with the rider, alone, without positives
+    names = {L.name: L for L in uc.BIT_LAUNCHES}
+    prod = [L for L in uc.BIT_LAUNCHES if L.name.startswith("production-s")]
+    assert {(L.tables[0].copies, L.tables[0].bits, L.tables[1].bits) for L in prod} == {(2, False, True), (8, False, True)}
+    assert sorted(L.count.total for L in uc.BIT_LAUNCHES if L.count)[:3] == [1, 255, 257] and sum(bool(L.count) for L in uc.BIT_LAUNCHES) == 4
+    assert all(uc.list_blocks(L) > 0 and L.tables[1].bits for L in uc.BIT_LAUNCHES if L.count)
+    assert len(names["bitmap-alone"].tables) == 1 and names["bitmap-no-positives"].tables[1].n_pos == 0
+    assert uc.list_blocks(names["bitmap-no-positives"]) == 0 and uc.list_blocks(names["bitmap-alone"]) == 3
+    assert {uc.list_blocks(uc.Launch("x", (c,))) for c in small} >= {0, 1, 2, 19}      # partial last block of 32 entries: 2 n_pos = 34, 66, 600
+
+
+@pytest.mark.parametrize("stride", uc.STRIDES)
+def test_bitmap_cases_are_exact_or_bounded(stride):
+    ratios = {}
+    for c in BITS:
+        if c.stride == stride and (c.n <= 1023 or c.chunk == 64):
+            o = uc.rows_ops(c)
+            o.bound.check()
+            want = uc.rows_reference(c)
+            assert np.array_equal(want["rows"], np.nonzero(o.visited)[0]), c.id
+            problems, _ = uc.check_rows(o, uc.apply_reference(o, want), want)
+            assert not problems, (c.id, problems)
+            assert not want["grad"][:c.n][want["rows"]].any() and (np.delete(want["grad"][:c.n], want["rows"], 0) == uc.SENTINEL).all()
+            if c.n > 1023:
+                continue
+            for mode in ("f32", "fma"):
+                problems, r = uc.check_rows(o, uc.apply_reference(o, uc.rows_reference(c, mode)), want)
+                assert not problems, (c.id, mode, problems)
+                for k, x in r.items():
+                    assert x <= 0.5, (c.id, mode, k, x)
+                    ratios[(c.opt, c.normalize, k)] = max(ratios.get((c.opt, c.normalize, k), 0.0), x)
+    assert {k[:2] for k in ratios} == {("sgd", 1), ("adagrad", 0), ("adagrad", 1)}, ratios
+
+
+def test_bitmap_launches():
+    for L in uc.BIT_LAUNCHES:
+        for t, want in zip(L.tables, uc.launch_reference(L)):
+            o = uc.rows_ops(t)
+            o.bound.check()
+            if t.bits:
+                check_bit_operands(t, o)
+            assert not uc.check_rows(o, uc.apply_reference(o, want), want)[0], (L.name, t.id)
+
+
+BIT_PICK = {
+    "chunk_takes_01": lambda c: c.n <= 1023,
+    "list_takes_11": lambda c: c.n <= 1023 and c.n_pos,
+    "list_h_only": lambda c: c.n <= 1023 and c.n_pos,
+    "tail_not_rebased": lambda c: c.n <= 1023 and c.n_pos,
+    "skip_fifth_entry": lambda c: c.n <= 1023 and c.n_pos,
+    "drop_last_wave": lambda c: c.n <= 1023 and c.n_pos,
+    "pair_word_r5": lambda c: c.n <= 1023,
+    "junk_pairs_honoured": lambda c: c.n <= 1023,
+}
+
+
+@pytest.mark.parametrize("mutant", list(BIT_PICK))
+def test_every_bitmap_mutant_breaks_a_case(mutant):
+    """(The unmutated reference passes the same comparison on every case: test_bitmap_cases_are_exact_or_bounded.)"""
+    hit = broken_by(mutant, [c for c in BITS if BIT_PICK[mutant](c)])
+    assert len(hit) >= 2, mutant
+    ids = {c.id for c, _ in hit}
+    if mutant == "skip_fifth_entry":        # only wavefronts with five or more set entries: k = 1 of every q, and "all"
+        assert all(max(list_stats(c, uc.rows_ops(c)), default=0) >= 5 for c, _ in hit)
+        assert {c.lpat for c, _ in hit} >= {"q0", "q1", "q2", "q3", "all"}
+    if mutant == "drop_last_wave":
+        assert all((2 * c.n_pos) % uc.LIST_WAVE for c, _ in hit) and {c.n_pos for c, _ in hit} >= {1, 3, 5, 9, 17, 33}
+    if mutant == "tail_not_rebased":
+        assert {c.n_pos for c, _ in hit} >= {1, 3, 4, 8, 16, 300}
+    if mutant == "junk_pairs_honoured":
+        assert all(c.n % 16 for c, _ in hit) and {c.n for c, _ in hit} >= {1, 15, 17, 31, 33, 255, 257}
+    if mutant == "list_takes_11":
+        assert any("exact reference" in " ".join(p) for _, p in hit)
+    assert ids
+
+
+def test_list_blocks_counted_as_update_blocks_breaks_the_first_table():
+    hit = []
+    for L in uc.BIT_LAUNCHES:
+        if not uc.list_blocks(L):
+            continue
+        for t, w, b in zip(L.tables, uc.launch_reference(L), uc.launch_reference(L, mutant="list_blocks_as_update")):
+            o = uc.rows_ops(t)
+            if uc.check_rows(o, uc.apply_reference(o, b), w)[0]:
+                hit.append((L.name, t.tag))
+    assert ("production-s80-c2", "rel") in hit and ("production-count-257", "rel") in hit and ("bitmap-alone", "ent") in hit, hit
+    assert set(BIT_PICK) | {"list_blocks_as_update"} == set(uc.BIT_MUTANTS) and len(uc.BIT_MUTANTS) == 9
 
 
 def test_mutant_list_is_the_issues():

@@ -27,6 +27,18 @@ Worst error / bound observed on the MI355X (gfx950), per kernel and output (w: t
 The figures next to 0.5 are elements whose error is the last rounding alone (half an ulp, charged a whole one); where both
 ran the same case the device gave the figure of the float32 NumPy emulation of test_update_cases.py, so the 2 ulp allowed for
 rsqrtf, rsq, sqrtf and the division were not needed by these operands.
+
+Bitmap tables (mke_update_table.bits / pos_h / pos_t / n_pos: walk_chunk on pair 11, walk_list on pair 01 named by the step's
+positives; update_cases.BIT_CASES and BIT_LAUNCHES) run through the same comparison; SGD without normalisation matched bit for
+bit at every row count, list length and pattern, alone and in the production launch with and without the count rider.  Worst
+error / bound:
+
+  bitmap tables                         quarter-wave rows                        whole-wave rows          64-bit mask
+    SGD, normalised                     w 0.4989
+    Adagrad                             w 0.4947                                 w 0.3826                 w 0.3826
+    Adagrad, normalised                 w 0.4993  acc 0.4524                     w 0.4978  acc 0.4545
+
+test_update_cases.py shows that nine kinds of kernel that walk the bitmap or the list wrongly fail these comparisons.
 """
 import ctypes as C
 
@@ -56,6 +68,14 @@ def addr(t):
 def opt_code(c):
     from multike_amd import _lib
     return {"sgd": _lib.OPT_SGD, "adagrad": _lib.OPT_ADAGRAD, "adam": _lib.OPT_ADAM, "adadelta": _lib.OPT_ADADELTA}[c.opt]
+
+
+def sync():
+    """A device error ends the session: nothing more is started on a card that has faulted."""
+    try:
+        torch.cuda.synchronize()
+    except RuntimeError as e:
+        pytest.exit(f"device error: {e}", returncode=3)
 
 
 class chunk_option:
@@ -92,6 +112,8 @@ def table_struct(c, d):
         t.src_rows, t.slot_of, t.n_ranks, t.capacity = addr(d["src_rows"]), addr(d["slot_of"]), c.n_ranks, uc.rows_ops(c).capacity
     if c.n_hot:
         t.hot = _lib.HotRowsStruct(addr(d["hot_slot"]), c.n_hot, c.hot_copies, c.n)           # row0 = n_rows
+    if c.bits:                                                       # the bitmap row and the step's positives in place of the flags
+        t.bits, t.pos_h, t.pos_t, t.n_pos = addr(d["bits"]), addr(d["pos_h"]), addr(d["pos_t"]), c.n_pos
     return t
 
 
@@ -114,7 +136,7 @@ def launch_multi(tables, count=None):
             code = _lib.lib().mke_rows_update_multi_count(*args, C.byref(cj), _lib._stream())
             counted = cd[4]
     assert code == 0, _lib.lib().mke_last_error()
-    torch.cuda.synchronize()
+    sync()
     return [{k: host(v) for k, v in d.items()} for d in ds], host(counted)
 
 
@@ -229,6 +251,70 @@ def test_count_rider(L):
     for t, got, alone, want in zip(L.tables, gots, plain, uc.launch_reference(L)):
         problems, _ = uc.check_rows(uc.rows_ops(t), got, want)
         assert not problems and same_buffers(got, alone), (L.name, t.id, problems)
+
+
+# ----------------------------------------------------------------------------------------------------- bitmap tables
+BITMAP = grouped(uc.BIT_CASES, lambda c: f"s{c.stride}" + ("-hub" if c.n_hot else ""))
+
+
+def shape_name_bits(c):
+    return "bits-" + uc.row_shape(c.n, c.stride, c.chunk)
+
+
+@pytest.mark.parametrize("key", list(BITMAP))
+def test_bitmap_rows(key):
+    """mke_update_table.bits: the visited rows are pair 11 (walk_chunk) and pair 01 named by an entry of pos_h ++ pos_t
+    (walk_list).  Everything else -- pair 01 that no entry names, pair 00 that one names, pair 10, the junk pairs behind the last
+    row -- keeps table, accumulator and its SENTINEL gradient row bit for bit."""
+    for c in BITMAP[key]:
+        o, want = uc.rows_ops(c), uc.rows_reference(c)
+        (got,), _ = launch_multi([c])
+        problems, ratios = uc.check_rows(o, got, want)
+        report(ratios, shape_name_bits(c), c)
+        assert not problems, (c.id, problems)
+
+
+@pytest.mark.parametrize("L", uc.BIT_LAUNCHES, ids=lambda L: L.name)
+def test_bitmap_launches(L):
+    """The production launch (a flagged relation table with privatised copies, then the bitmap table), with the count rider (list
+    blocks, rider blocks, update blocks), the bitmap table alone, first, and without positives: every table against its
+    reference and, bit for bit, against what it gives alone; the rider's counts by the mke_count_entity_refs rule."""
+    gots, counted = launch_multi(L.tables, L.count)
+    if L.count:
+        assert np.array_equal(counted, uc.count_reference(L.count)), L.name
+    for t, got, want in zip(L.tables, gots, uc.launch_reference(L)):
+        problems, ratios = uc.check_rows(uc.rows_ops(t), got, want)
+        report(ratios, shape_name_bits(t) if t.bits else shape_name(t), t)
+        assert not problems, (L.name, t.id, problems)
+        (alone,), _ = launch_multi([t])
+        assert same_buffers(got, alone), (L.name, t.id)
+
+
+def test_bitmap_refusals_launch_nothing():
+    """A bitmap beside slot_of or grad_copies > 1, a second bitmap table, NULL lists: refused before any launch."""
+    from multike_amd import _lib
+    c = next(c for c in uc.BIT_CASES if c.n == 33 and c.stride == 16)
+    d = upload(c)
+    before = {k: v.clone() for k, v in d.items() if v is not None}
+
+    def call(*structs):
+        arr = (_lib.UpdateTableStruct * len(structs))(*structs)
+        return _lib.lib().mke_rows_update_multi(arr, C.c_int(len(structs)), C.c_int32(TAG), C.c_int(c.stride), C.c_int(c.dim), C.c_int(opt_code(c)),
+                                                C.c_float(c.lr), _lib._stream())
+
+    t = table_struct(c, d)
+    t.grad_copies = 2
+    assert call(t) == -3
+    assert call(table_struct(c, d), table_struct(c, d)) == -3
+    t = table_struct(c, d)
+    t.pos_t = None
+    assert call(t) == -1
+    t = table_struct(c, d)
+    t.n_pos = -1
+    assert call(t) == -2
+    sync()
+    for k, v in before.items():
+        assert torch.equal(d[k].view(torch.int32), v.view(torch.int32)), k
 
 
 # ----------------------------------------------------------------------------------------------------- the dense rules

@@ -71,6 +71,14 @@ U = 2.0 ** -23
 TINY = 2.0 ** -149
 ACC_PAD = f32(0.1)
 STEPS = 3
+N_BITS = (1, 15, 16, 17, 31, 32, 33, 255, 257)                  # bitmap tables: chunk 4, the edges of the bitmap's words
+N_BITS_LARGE = (16385, 16449)                                   # chunks 16 and 64, by option
+N_POS = (0, 1, 3, 4, 5, 8, 9, 15, 16, 17, 33, 300)              # no list blocks; the h / t split inside a wavefront's eight entries; partial last wavefront / block
+LIST_WAVE = 8                                                   # entries of pos_h ++ pos_t per wavefront of the list segment
+LIST_PATTERNS = ("q0", "q1", "q2", "q3", "all", "none")        # wavefront i holds exactly 4 (i mod 2) + 1 + q entries that name a pair-01 row
+LIST_PAD = 64                                                   # entries behind pos_h and pos_t: rows with pair 01 that no entry of the lists names
+BIT_MUTANTS = ("chunk_takes_01", "list_takes_11", "list_h_only", "tail_not_rebased", "skip_fifth_entry", "drop_last_wave", "pair_word_r5",
+               "list_blocks_as_update", "junk_pairs_honoured")
 MUTANTS = ("skip_last_copy", "copies_not_zeroed", "last_hub_twice", "coef_one_inv", "keep_projection", "old_acc", "stale_tag",
            "skip_fifth_bit", "pad_written", "reset_below_16", "route_first_block", "refcount_all", "count_repeats")
 
@@ -121,6 +129,9 @@ class UCase(NamedTuple):
     special: bool = False  # tier 2: rows 0..2 are the zero row, the 2^-30 row and the row of norm 1, all visited
     hyper: str = ""        # dense rules: half | tf
     tag: str = ""
+    bits: bool = False     # rows: the visited set comes from a bitmap row and the lists pos_h / pos_t (mke_update_table.bits);
+    n_pos: int = 0         #   `pattern` then places the pairs 11, `lpat` the list entries that name a pair-01 row
+    lpat: str = ""         #   one of LIST_PATTERNS
 
     @property
     def id(self):
@@ -129,7 +140,8 @@ class UCase(NamedTuple):
             s += f"-{self.pattern}-lr{self.lr:g}"
         for v in (f"ch{self.chunk}" if self.chunk else "", f"c{self.copies}" if self.copies > 1 else "",
                   f"hot{self.n_hot}x{self.hot_copies}" if self.n_hot else "", f"ranks{self.n_ranks}" if self.n_ranks else "",
-                  "rc" if self.refcount else "", "special" if self.special else "", self.hyper, self.tag):
+                  "rc" if self.refcount else "", "special" if self.special else "", self.hyper, self.tag,
+                  f"bits-p{self.n_pos}-{self.lpat}" if self.bits else ""):
             if v:
                 s += "-" + v
         return s
@@ -345,6 +357,82 @@ class RowsOps(NamedTuple):
     capacity: int
     visited: np.ndarray     # bool [n]
     bound: Bound
+    bits: np.ndarray = None     # uint32 [(n + 15) // 16 + 2]: two bits per row; junk pairs of the last word 11, two words of ones behind
+    pos_h: np.ndarray = None    # int32 [n_pos + LIST_PAD]
+    pos_t: np.ndarray = None
+
+
+def pairs_of(bits, n, mutant=""):
+    """code_pair of mke_update.hip for rows [0, n)."""
+    r = np.arange(n)
+    word = r >> (5 if mutant == "pair_word_r5" else 4)
+    return ((bits[word] >> ((r & 15) * 2).astype(np.uint32)) & 3).astype(np.int64)
+
+
+def _bitmap(c: UCase, rng, base11):
+    """(bits, pos_h, pos_t, visited, hub rows) of a bitmap table.  `base11` (from c.pattern) are the rows of the chunk walk.
+    The other rows are dealt to: pair 00 named by entries, pair 10 (named or not), pair 01 named by exactly ONE entry (the rows
+    of the list walk, as many as c.lpat asks for), pair 01 named by none (finished by the score launch), pair 00 unnamed.
+    The bake's invariant holds: a row named twice, or by the head and the tail of one positive, has pair 11 (or is not visited
+    at all), so no row is visited twice."""
+    n, P = c.n, c.n_pos
+    pair = np.zeros(n, dtype=np.int64)
+    pair[base11] = 3
+    rest = rng.permutation(np.nonzero(~base11)[0])
+    if c.special and n >= 3 and P and base11[1]:                 # the 2^-30 row goes through the list
+        pair[1] = 0
+        base11 = base11.copy()
+        base11[1] = False
+        rest = np.concatenate([[1], rest])
+        forced = 1
+    else:
+        forced = 0
+    n_waves = -(-2 * P // LIST_WAVE)
+    want = []
+    for i in range(n_waves):
+        size = min(LIST_WAVE, 2 * P - i * LIST_WAVE)
+        q = {"all": LIST_WAVE, "none": 0}.get(c.lpat, 4 * (i % 2) + 1 + int(c.lpat[1]) if c.lpat[0] == "q" else 0)
+        want.append(min(q, size))
+    # pools: the entries that must not lead to a visit need a row to name
+    k = len(rest) - forced
+    n_c = min(k, 2) if (P and k > 1) or not base11.any() else 0          # pair 00, named
+    n_f = min(k - n_c, 2)                                                # pair 10: one named, one not
+    n_b = min(k - n_c - n_f, max(2, k // 8))                             # pair 01, unnamed
+    n_a = min(sum(want), max(k - n_c - n_f - n_b, 0)) + forced           # pair 01, named once
+    a_rows = rest[:n_a]
+    body = rest[n_a:]
+    c_rows, f_rows, b_rows = body[:n_c], body[n_c:n_c + n_f], body[n_c + n_f:n_c + n_f + n_b]
+    pair[a_rows], pair[b_rows], pair[f_rows] = 1, 1, 2
+    pool = np.concatenate([np.nonzero(base11)[0], c_rows, f_rows[:1]]).astype(np.int64)
+    entries = np.zeros(2 * P, dtype=np.int64)
+    left = list(a_rows)
+    for i in range(n_waves):
+        lo = i * LIST_WAVE
+        size = min(LIST_WAVE, 2 * P - lo)
+        take = min(want[i], len(left))
+        at = rng.choice(size, take, replace=False)
+        fill = np.ones(size, bool)
+        fill[at] = False
+        entries[lo + at] = [left.pop() for _ in range(take)]
+        if fill.any():
+            entries[lo + np.nonzero(fill)[0]] = rng.choice(pool, int(fill.sum()))
+    pair[np.array(left, dtype=np.int64)] = 1                            # rows the lists had no room for: pair 01, unnamed
+    b_all = np.nonzero(pair == 1)[0]
+    named = np.zeros(n, bool)
+    named[entries] = True
+    unnamed01 = b_all[~named[b_all]]
+    pad = rng.choice(unnamed01, LIST_PAD) if len(unnamed01) else np.zeros(LIST_PAD, dtype=np.int64)
+    pos_h = np.concatenate([entries[:P], pad]).astype(np.int32)
+    pos_t = np.concatenate([entries[P:], pad[::-1]]).astype(np.int32)
+    words = (n + 15) // 16
+    bits = np.zeros(words + 2, dtype=np.uint32)
+    full = np.full(words * 16, 3, dtype=np.int64)                        # the junk pairs of the last word: 11
+    full[:n] = pair
+    r = np.arange(words * 16)
+    np.bitwise_or.at(bits, r >> 4, (full << ((r & 15) * 2)).astype(np.uint32))
+    bits[words:] = 0xFFFFFFFF
+    visited = (pair == 3) | ((pair == 1) & named)
+    return bits, pos_h, pos_t, visited, (a_rows if P else a_rows[:0]), np.nonzero(base11)[0]
 
 
 def _flags(c: UCase, rng):
@@ -446,7 +534,20 @@ def rows_ops(c: UCase) -> RowsOps:
     else:
         touched, visited = _flags(c, rng)
         hub = np.zeros(0, dtype=np.int64)
-        if c.n_hot:
+        bitmap = pos_h = pos_t = None
+        if c.bits:
+            assert c.copies == 1 and c.pattern not in ("null", "old") and c.lpat in LIST_PATTERNS
+            bitmap, pos_h, pos_t, visited, by_list, by_chunk = _bitmap(c, rng, visited)
+            touched = np.full(n + 64, TAG, dtype=np.int32) if n % 2 else None      # not read (it may be NULL)
+            if c.n_hot:                                         # one hub row in the list walk, one in the chunk walk
+                placed = by_list[visited[by_list]]
+                first = placed[:1] if (c.n_hot > 1 or c.hot_copies % 2) and len(placed) else by_chunk[:1]
+                second = by_chunk[:1] if len(first) and first[0] not in by_chunk else by_chunk[1:2]
+                others = np.setdiff1d(np.arange(n), np.concatenate([first, second]))
+                hub = np.concatenate([first, second, rng.permutation(others)])[:c.n_hot].astype(np.int64)
+                hot_slot = np.full(n + 1, -1, dtype=np.int32)
+                hot_slot[hub] = np.arange(c.n_hot, dtype=np.int32)
+        elif c.n_hot:
             hot_slot, hub = _hot_rows(c, rng, touched, visited)
         n_grad = c.copies * n + (c.hot_copies * c.n_hot if c.n_hot else 0)
         grad = np.full((n_grad + 1, st), SENTINEL, dtype=f32)
@@ -473,11 +574,49 @@ def rows_ops(c: UCase) -> RowsOps:
     if c.exact_table:
         bd.add("value", 1 + c.lr * max(contrib, 1), c.lr / 4)
     assert (1 + contrib) ** 2 * 2 ** 27 < 2 ** 52               # g g + a is exact in float64: g g in 1/16, a in [0.1, 1.1] at 2^-27
+    if not c.n_ranks and c.bits:
+        return RowsOps(table, acc, grad, touched, ref_count, hot_slot, slot_of, src_rows, capacity, visited, bd, bitmap, pos_h, pos_t)
     return RowsOps(table, acc, grad, touched, ref_count, hot_slot, slot_of, src_rows, capacity, visited, bd)
 
 
 # ----------------------------------------------------------------------------------------------------- k_rows_update*: reference
-def _visited(c: UCase, o: RowsOps, mutant, skip_block=False):
+def list_visits(c: UCase, o: RowsOps, mutant=""):
+    """walk_list of mke_update.hip, entry by entry: the rows the list segment visits, and the rows it visits although the chunk
+    walk has them (a mutant's second visit)."""
+    P, n = c.n_pos, c.n
+    pair = pairs_of(o.bits, n, mutant)
+    i = np.arange(2 * P)
+    if mutant == "list_h_only":
+        rows = o.pos_h[np.where(i < P, i, i - P)]
+    elif mutant == "tail_not_rebased":                           # pos_t[i] for i >= n_pos: the pad behind the list, then nothing
+        rows = np.where(i < P, o.pos_h[np.minimum(i, P + LIST_PAD - 1)], np.where(i < P + LIST_PAD, o.pos_t[np.minimum(i, P + LIST_PAD - 1)], -1))
+    else:
+        rows = np.where(i < P, o.pos_h[np.minimum(i, max(P - 1, 0))], o.pos_t[np.maximum(i - P, 0)]) if P else np.zeros(0, dtype=np.int64)
+    rows = rows.astype(np.int64)
+    ok = (rows >= 0) & (rows < n)
+    p = np.where(ok, pair[np.where(ok, rows, 0)], 0)
+    take = p == 1
+    twice = (p == 3) if mutant == "list_takes_11" else np.zeros(2 * P, bool)
+    if mutant == "skip_fifth_entry":
+        rank = np.zeros(2 * P, dtype=np.int64)
+        for lo in range(0, 2 * P, LIST_WAVE):
+            rank[lo:lo + LIST_WAVE] = np.cumsum(take[lo:lo + LIST_WAVE]) - 1
+        take &= rank != 4
+    if mutant == "drop_last_wave" and (2 * P) % LIST_WAVE:
+        take[2 * P - (2 * P) % LIST_WAVE:] = False
+    return rows[take], rows[twice]
+
+
+def _visited(c: UCase, o: RowsOps, mutant, skip_block=False, skip_rows=0):
+    """(visited rows, rows whose gradient a mutant applies twice)."""
+    if c.bits:                                                   # pair 11, and pair 01 where an entry of pos_h ++ pos_t names the row
+        pair = pairs_of(o.bits, c.n, mutant)
+        vis = (pair == 3) | ((pair == 1) if mutant == "chunk_takes_01" else False)
+        vis[:skip_rows] = False
+        by_list, twice = list_visits(c, o, mutant)
+        twice = np.concatenate([twice, by_list[vis[by_list]]])
+        vis[by_list] = True
+        return np.nonzero(vis)[0], np.unique(twice)
     vis = o.visited.copy()
     if mutant == "stale_tag" and o.touched is not None:
         vis |= o.touched[:c.n] == OLD_TAG
@@ -489,16 +628,56 @@ def _visited(c: UCase, o: RowsOps, mutant, skip_block=False):
         vis[idx[np.arange(len(idx)) - first == 4]] = False
     if skip_block:
         vis[:(BLOCK // 64) * ch] = False
-    return np.nonzero(vis)[0]
+    vis[:skip_rows] = False
+    return np.nonzero(vis)[0], np.zeros(0, dtype=np.int64)
 
 
-def rows_reference(c: UCase, mode="bound", mutant="", skip_block=False) -> dict:
+def rows_rule(c: UCase, W0, A0, G, mode="bound", mutant="", G_err=None) -> dict:
+    """The update of rows "given their gradient": float64 operands W0 (table rows), A0 (accumulator rows) and G (the summed
+    gradient rows, exact inputs) -> {"table": (values, error bound or None = bit for bit), "acc": ...}.  G_err: an error bound on
+    G (a sum of copies the caller could not form exactly); with it nothing is held bit for bit."""
+    ar = Arith(mode)
+    st, d = c.stride, c.dim
+    out = {}
+    exact = G_err is None
+    w, g = ar.lift(W0), (ar.lift(G) if exact or not ar.bound else V(G, G_err))
+    if c.normalize:
+        g = jacobian(ar, w, g, st // 16 + 6, mutant)
+    a2 = None
+    if c.opt == "adagrad":
+        w2, a2 = rule_adagrad(ar, w, g, ar.lift(A0), c.lr, mutant)
+    else:
+        w2 = rule_sgd(ar, w, g, c.lr)
+    wv, we = ar.out(w2)
+    wv = np.array(wv)
+    if mutant == "pad_written":
+        wv[:, d:] = 2.0 ** -20
+    elif mode == "bound" and not mutant:
+        assert not wv[:, d:].any()                              # pad columns: 0 - lr 0 rsq(0.1) stays exactly zero
+    if mode == "bound":
+        we = np.array(we)
+        we[:, d:] = 0.0
+        if c.exact_table and exact:
+            wv, we = wv.astype(f32), None                       # exact in float64, and (Bound) a float32 value
+    out["table"] = (wv, we)
+    if a2 is not None:
+        av, ae = ar.out(a2)
+        if mode == "bound":
+            assert mutant or np.array_equal(av[:, d:], A0[:, d:])
+            ae = np.array(ae)
+            ae[:, d:] = 0.0
+            if not c.normalize and exact:
+                av, ae = av.astype(f32), None                   # one rounding of an exact float64 sum
+        out["acc"] = (av, ae)
+    return out
+
+
+def rows_reference(c: UCase, mode="bound", mutant="", skip_block=False, skip_rows=0) -> dict:
     """What one table of a k_rows_update / k_rows_update_multi launch must hold afterwards: "rows" (the visited rows),
     "table" / "acc" as (values of those rows, error bound or None = bit for bit), and the whole grad / slot_of / ref_count."""
     o = rows_ops(c)
-    ar = Arith(mode)
     n, st, d = c.n, c.stride, c.dim
-    v = _visited(c, o, mutant, skip_block)
+    v, twice = _visited(c, o, mutant, skip_block, skip_rows)
     out = {"rows": v}
     G = np.zeros((len(v), st))
     if c.n_ranks:
@@ -528,40 +707,15 @@ def rows_reference(c: UCase, mode="bound", mutant="", skip_block=False) -> dict:
         rcnt[:n if mutant == "refcount_all" else 0] = 0
         rcnt[v] = 0
         out["ref_count"] = rcnt
-    W0, A0 = o.table[v].astype(f64), o.acc[v].astype(f64)
-    w, g = ar.lift(W0), ar.lift(G)
-    if c.normalize:
-        g = jacobian(ar, w, g, st // 16 + 6, mutant)
-    a2 = None
-    if c.opt == "adagrad":
-        w2, a2 = rule_adagrad(ar, w, g, ar.lift(A0), c.lr, mutant)
-    else:
-        w2 = rule_sgd(ar, w, g, c.lr)
-    wv, we = ar.out(w2)
-    wv = np.array(wv)
-    if mutant == "pad_written":
-        wv[:, d:] = 2.0 ** -20
-    elif mode == "bound" and not mutant:
-        assert not wv[:, d:].any()                              # pad columns: 0 - lr 0 rsq(0.1) stays exactly zero
-    if mode == "bound":
-        we = np.array(we)
-        we[:, d:] = 0.0
-        if c.exact_table:
-            wv, we = wv.astype(f32), None                       # exact in float64, and (Bound) a float32 value
-    out["table"] = (wv, we)
-    if a2 is not None:
-        av, ae = ar.out(a2)
-        if mode == "bound":
-            assert mutant or np.array_equal(av[:, d:], A0[:, d:])
-            ae = np.array(ae)
-            ae[:, d:] = 0.0
-            if not c.normalize:
-                av, ae = av.astype(f32), None                   # one rounding of an exact float64 sum
-        out["acc"] = (av, ae)
+    if len(twice):                                               # two visits that both read the gradient before either zeroes it
+        G[np.isin(v, twice)] *= 2.0
+    if mutant == "junk_pairs_honoured" and c.bits and n % 16:    # the pairs behind the table's last row are 11: a visit of row n
+        out["grad"][n] = 0.0
+    out.update(rows_rule(c, o.table[v].astype(f64), o.acc[v].astype(f64), G, mode, mutant))
     return out
 
 
-BUFFERS = ("table", "acc", "grad", "touched", "ref_count", "hot_slot", "slot_of", "src_rows")
+BUFFERS = ("table", "acc", "grad", "touched", "ref_count", "hot_slot", "slot_of", "src_rows", "bits", "pos_h", "pos_t")
 
 
 def bits(a):
@@ -602,7 +756,7 @@ def check_rows(o: RowsOps, got: dict, want: dict):
     for name in ("grad", "slot_of", "ref_count"):
         if name in want and not np.array_equal(bits(got[name]), bits(want[name])):
             problems.append(f"{name}: differs from the reference")
-    for name in ("touched", "hot_slot", "src_rows"):
+    for name in ("touched", "hot_slot", "src_rows", "bits", "pos_h", "pos_t"):
         if got.get(name) is not None and not np.array_equal(bits(got[name]), bits(getattr(o, name))):
             problems.append(f"{name}: a read-only buffer changed")
     return problems, ratios
@@ -683,11 +837,22 @@ def launch_blocks(L: Launch):
     return [-(-t.n // ((BLOCK // 64) * chunk_of(t.n, t.chunk))) for t in L.tables]
 
 
+def list_blocks(L: Launch) -> int:
+    """Blocks of the list segment, ahead of the rider and the update blocks: LIST_WAVE entries per wavefront."""
+    return sum(-(-2 * t.n_pos // ((BLOCK // 64) * LIST_WAVE)) for t in L.tables if t.bits)
+
+
 def launch_reference(L: Launch, mode="bound", mutant=""):
     """Every table comes out as it does alone.  (The mutant that routes the second table's first block to the first table
     leaves that block's rows unvisited.)"""
     second = [k for k, b in enumerate(launch_blocks(L)) if b][1:2]
-    return [rows_reference(t, mode, mutant, skip_block=(mutant == "route_first_block" and [k] == second))
+    skip = [0] * len(L.tables)
+    if mutant == "list_blocks_as_update":                       # the first list_blocks update blocks take the list's place: their rows are lost
+        left = list_blocks(L)
+        for k, (t, b) in enumerate(zip(L.tables, launch_blocks(L))):
+            skip[k] = min(left, b) * (BLOCK // 64) * chunk_of(t.n, t.chunk)
+            left -= min(left, b)
+    return [rows_reference(t, mode, mutant, skip_block=(mutant == "route_first_block" and [k] == second), skip_rows=skip[k])
             for k, t in enumerate(L.tables)]
 
 
@@ -917,6 +1082,66 @@ def _build():
 
 
 ALL_CASES, LAUNCHES = _build()
+
+
+def _build_bits():
+    """Bitmap tables (beside ALL_CASES and LAUNCHES, which they leave as they are): (cases run alone, launches)."""
+    cases, launches = [], []
+    B = lambda **kw: cases.append(UCase("rows", bits=True, **kw))
+    PAT = ("q0", "q1", "q2", "q3", "all", "none", "fifth", "first", "last")
+    for si, stride in enumerate(STRIDES):
+        dims = rc.table_dims(stride)
+        ragged = [d for d in dims if d != stride]
+        # tier 1, chunk 4: every row count; the list lengths, list patterns and pair-11 patterns rotate through the widths
+        for ni, n in enumerate(N_BITS):
+            k = ni + 4 * si
+            B(n=n, dim=dims[k % len(dims)], stride=stride, pattern=PAT[(ni + 2 * si) % len(PAT)], n_pos=N_POS[k % len(N_POS)],
+              lpat=LIST_PATTERNS[(ni + si) % 6], lr=LRS[k % 2], refcount=k % 2 == 0, opt=("sgd", "adagrad")[k % 4 == 3])
+        # the deal to the quarter-waves: every q of the list with both k at a ragged dim (25 wavefronts; at chunk 4 the chunk walk's q3
+        # is every row, which leaves the list none: its own q patterns run at chunks 16 and 64 below)
+        for qi in range(4):
+            B(n=1023, dim=ragged[qi % len(ragged)], stride=stride, pattern=f"q{(qi + si) % 3}", n_pos=100, lpat=f"q{qi}", lr=LRS[qi % 2])
+        # tier 2: the three arithmetic forms with the planted rows, the 2^-30 row through the list
+        for k, (opt, norm) in enumerate((("sgd", 1), ("adagrad", 0), ("adagrad", 1))):
+            B(n=33, dim=dims[(k + si) % len(dims)], stride=stride, pattern=("fifth", "all", "q1")[k], n_pos=17, lpat=("all", "q2", "q0")[k],
+              lr=LRS[(k + si) % 3], opt=opt, normalize=norm, special=True)
+        # chunks 16 and 64 by option: whole-wave rows at the strides divisible by 64, the 64-bit mask over quarter-waves at the others
+        for ci, ch in enumerate((16, 64)):
+            for ni, n in enumerate(N_BITS_LARGE):
+                k = 2 * ci + ni
+                B(n=n, dim=ragged[(ni + ci) % len(ragged)], stride=stride, chunk=ch, pattern=f"q{(k + si) % 4}", n_pos=(300, 33, 16, 9)[(k + si) % 4],
+                  lpat=f"q{(k + 2 * si + 1) % 4}", lr=LRS[ni % 2], refcount=ni == 1, opt=("sgd", "adagrad")[(k + si) % 5 == 0])
+    # hub rows: one in the list, one in the chunk walk; HB = 4 up to FPL 5, 2 beyond; the three row shapes
+    for stride, n, ch in ((16, 65, 0), (80, 65, 0), (320, 65, 0), (64, 16449, 64), (80, 16449, 64), (80, 16449, 16)):
+        for hi, n_hot in enumerate(N_HOT):
+            for ki, hc in enumerate(HOT_COPIES):
+                if (ki + hi) % 2 == 0 or n == 65:
+                    B(n=n, dim=stride - (5 if stride == 80 else 1), stride=stride, chunk=ch, n_hot=n_hot, hot_copies=hc, pattern=("fifth", "q0")[ki % 2],
+                      n_pos=(33, 17)[hi], lpat=("q1", "all")[ki % 2], lr=LRS[ki % 2], refcount=ki == 2)
+    T = lambda n, **kw: UCase("rows", n=n, **{"dim": 75, "stride": 80, "pattern": "fifth", "lr": 0.25, **kw})
+    L = lambda name, *tables, count=None: launches.append(Launch(name, tuple(tables), count))
+    for stride, dim in ((16, 15), (80, 75), (256, 255)):
+        for copies in (2, 8):                                    # the production launch: flagged relation table, then the bitmap table
+            L(f"production-s{stride}-c{copies}", T(65, dim=dim, stride=stride, copies=copies, pattern="q1", tag="rel"),
+              T(300, dim=dim, stride=stride, bits=True, n_pos=33, lpat="q2", pattern="q3", refcount=True, tag="ent"))
+    for total in COUNT_TOTALS:                                   # ... with the count rider: list blocks, rider blocks, update blocks
+        cc = {1: CountCase(1, 0), 255: CountCase(85, 2), 257: CountCase(1, 256)}.get(total, CountCase(-(-total // 5), 4))
+        L(f"production-count-{total}", T(20, dim=31, stride=32, copies=(2, 8)[total % 2], tag="rel"),
+          T(300, dim=31, stride=32, bits=True, n_pos=(5, 300)[total % 2], lpat="q1", pattern="q0", refcount=True, tag="ent"), count=cc)
+    L("production-adagrad-64", T(65, dim=64, stride=64, chunk=64, copies=2, opt="adagrad", pattern="q1", tag="rel"),
+      T(16449, dim=64, stride=64, chunk=64, bits=True, n_pos=300, lpat="q3", pattern="q2", opt="adagrad", normalize=1, tag="ent"))
+    L("production-hub", T(65, copies=8, pattern="all", tag="rel"), T(300, bits=True, n_pos=17, lpat="all", n_hot=5, hot_copies=3, tag="ent"))
+    L("bitmap-alone", T(300, bits=True, n_pos=33, lpat="q0", tag="ent"))
+    L("bitmap-no-positives", T(65, copies=2, pattern="all", tag="rel"), T(300, bits=True, n_pos=0, lpat="none", pattern="q1", tag="ent"))
+    L("bitmap-first", T(300, bits=True, n_pos=9, lpat="q3", tag="ent"), T(65, copies=2, pattern="all", tag="rel"), T(20, tag="t2"))
+    assert len({c.id for c in cases}) == len(cases)
+    for Ln in launches:
+        assert len({(t.stride, t.dim, t.opt, t.lr, t.chunk) for t in Ln.tables}) == 1 and sum(t.bits for t in Ln.tables) == 1, Ln.name
+        assert len({t.id for t in Ln.tables}) == len(Ln.tables)
+    return cases, launches
+
+
+BIT_CASES, BIT_LAUNCHES = _build_bits()
 
 
 def cases_of(kernel, **kw):
