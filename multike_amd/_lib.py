@@ -544,6 +544,95 @@ def links_edit(held, match, a, b, kpad, metric=METRIC_INNER, sq_a=None, sq_b=Non
     return o, score, counts
 
 
+SPARSE_SO_PATH = os.path.join(_HERE, "libmultike_sparse.so")   # include/multike_sparse.h: a library and a generated module of its own
+_sparse = None
+
+
+def sparse_lib():
+    """Load libmultike_sparse.so (once), typed from _abi_sparse.py as lib() is from _abi.py.  Raises if it has not been built."""
+    global _sparse
+    if _sparse is None:
+        from . import _abi_sparse
+        if not os.path.exists(SPARSE_SO_PATH):
+            raise MultiKEHipError(f"{SPARSE_SO_PATH} not found: build it with `make -C multike_amd/csrc`.  multike_amd has no CPU fallback.")
+        L = C.CDLL(SPARSE_SO_PATH)
+        for name, (restype, argtypes) in _abi_sparse.FUNCTIONS.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _sparse = L
+    return _sparse
+
+
+def _sparse_check(rc, what):
+    if rc != 0:
+        raise MultiKEHipError(f"{what} failed (code {rc}): {sparse_lib().mke_sparse_last_error().decode('utf-8', 'replace')}")
+
+
+class SparseSupport:
+    """The device arrays mke_sparse_support writes (include/multike_sparse.h) and the sizes they were built for.  `count` is a
+    device word: nothing is read back to build or to iterate."""
+    __slots__ = ("n_a", "n_b", "capacity", "row_off", "row_seg", "ent_col", "ent_val", "col_off", "col_seg", "ent_row", "ent_idx",
+                 "count", "lse_temp")
+
+    def entries(self):
+        """The entry count, read back (reports and tests only)."""
+        return int(self.count.item())
+
+
+def sparse_support(val_r, col_r, val_c, row_c, out=None):
+    """mke_sparse_support over the row lists val_r / col_r [n_a, cut_r] and the column lists val_c / row_c [n_b, cut_c] -> a
+    SparseSupport.  `out` = a SparseSupport whose arrays are written in place of fresh ones (tests: poisoned buffers)."""
+    from . import _abi_sparse
+    (n_a, cut_r), (n_b, cut_c) = col_r.shape, row_c.shape
+    if val_r.shape != col_r.shape or val_c.shape != row_c.shape:
+        raise MultiKEHipError("sparse_support: a list's values and indices differ in shape")
+    dev = col_r.device
+    L = sparse_lib()
+    need = L.mke_sparse_support_temp_bytes(n_a, n_b, cut_r, cut_c)
+    if need < 0:
+        _sparse_check(int(need), "mke_sparse_support_temp_bytes")
+    s = out
+    if s is None:
+        s = SparseSupport()
+        s.n_a, s.n_b, s.capacity = n_a, n_b, n_a * cut_r + n_b * cut_c
+        s.row_off = torch.empty(n_a + 1, dtype=torch.int64, device=dev)
+        s.col_off = torch.empty(n_b + 1, dtype=torch.int64, device=dev)
+        s.row_seg = torch.empty(n_a + 1, dtype=torch.int32, device=dev)
+        s.col_seg = torch.empty(n_b + 1, dtype=torch.int32, device=dev)
+        s.ent_col, s.ent_row, s.ent_idx = (torch.empty(s.capacity, dtype=torch.int32, device=dev) for _ in range(3))
+        s.ent_val = torch.empty(s.capacity, dtype=torch.float32, device=dev)
+        s.count = torch.empty(1, dtype=torch.int64, device=dev)
+        s.lse_temp = torch.empty(max(int(L.mke_sparse_lse_temp_bytes(s.capacity)), 8) // 4, dtype=torch.int32, device=dev)
+    temp = torch.empty(max(int(need), 4) // 4, dtype=torch.int32, device=dev)
+    args = _abi_sparse.mke_sparse_support_args(
+        ptr(val_r, torch.float32, "val_r"), ptr(col_r, torch.int32, "col_r"), ptr(val_c, torch.float32, "val_c"),
+        ptr(row_c, torch.int32, "row_c"), n_a, n_b, cut_r, cut_c, s.capacity,
+        ptr(s.row_off, torch.int64, "row_off"), ptr(s.row_seg, torch.int32, "row_seg"), ptr(s.ent_col, torch.int32, "ent_col"),
+        ptr(s.ent_val, torch.float32, "ent_val"), ptr(s.col_off, torch.int64, "col_off"), ptr(s.col_seg, torch.int32, "col_seg"),
+        ptr(s.ent_row, torch.int32, "ent_row"), ptr(s.ent_idx, torch.int32, "ent_idx"), ptr(s.count, torch.int64, "count"),
+        ptr(temp, torch.int32, "temp"), temp.numel() * 4)
+    _sparse_check(L.mke_sparse_support(C.byref(args), _stream()), "mke_sparse_support")
+    return s
+
+
+def sparse_lse(s, columns, tau, sub=None, out=None):
+    """One mke_sparse_lse call over the rows (columns = False) or the columns (True) of a SparseSupport: out float32 [n],
+    out[i] = tau log sum over the list's entries of exp((value - sub[the entry's other index]) / tau); sub None = zeros."""
+    from . import _abi_sparse
+    n = s.n_b if columns else s.n_a
+    if sub is not None and sub.numel() != (s.n_a if columns else s.n_b):
+        raise MultiKEHipError(f"sparse_lse: sub has {sub.numel()} elements, the other side {s.n_a if columns else s.n_b}")
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=s.row_off.device)
+    off, seg, other, idx = (s.col_off, s.col_seg, s.ent_row, s.ent_idx) if columns else (s.row_off, s.row_seg, s.ent_col, None)
+    args = _abi_sparse.mke_sparse_lse_args(n, ptr(off, torch.int64, "off"), ptr(seg, torch.int32, "seg"), ptr(other, torch.int32, "other"),
+                                           ptr(s.ent_val, torch.float32, "val"), ptr(idx, torch.int32, "idx"),
+                                           ptr(sub, torch.float32, "sub"), float(tau), ptr(out, torch.float32, "out"), s.capacity,
+                                           ptr(s.lse_temp, torch.int32, "temp"), s.lse_temp.numel() * 4)
+    _sparse_check(sparse_lib().mke_sparse_lse(C.byref(args), _stream()), "mke_sparse_lse")
+    return out
+
+
 def mapping_scratch_floats(n: int, dim: int) -> int:
     return int(lib().mke_mapping_scratch_floats(n, dim))
 

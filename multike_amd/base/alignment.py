@@ -2,7 +2,9 @@
 the gold counterpart under the (normalised) inner-product similarity — on the f32 matrix cores via `mke_align_rank`; the
 euclidean metric and CSLS re-scoring via `mke_align_topk_mean` + `mke_align_rank_ex`; `stable_alignment` (:82-128) — the
 one-to-one Gale-Shapley matching — via `mke_stable_lists` + `mke_stable_rounds` + `mke_stable_finish`; Sinkhorn re-scoring
-(`sinkhorn=(iters, tau)`, the soft one-to-one decoder) via `mke_align_lse`, whose potentials ride the CSLS plumbing.
+(`sinkhorn=(iters, tau)`, the soft one-to-one decoder) via `mke_align_lse`, whose potentials ride the CSLS plumbing;
+`sinkhorn=(iters, tau, cut)` iterates them on the support of both sides' `cut` best candidates instead (`mke_sparse_support` +
+`mke_sparse_lse` of libmultike_sparse.so: two list sweeps, then no sweep per iteration).
 `mutual_pairs` / `mutual_alignment` (no counterpart in the reference) — the pairs that are each other's best, with precision /
 recall / F1 — via `mke_align_mutual` + `mke_mutual_pairs`: one sweep folds every similarity into both directions.
 `assignment_matching` / `assignment_alignment` (no counterpart either) — the one-to-one pairing that maximises the total
@@ -78,18 +80,26 @@ def csls_means(a, b, kpad, metric_code, sq_a, sq_b, csls_k):
 
 
 def _check_rescoring(csls_k, sinkhorn, csls=None):
-    """(csls_k as an int, 0 = none; (iters, tau) of a `sinkhorn=` argument, or None).  Sinkhorn and CSLS are two re-scorings of
-    one similarity, not a chain.  csls_k is truncated first, as greedy_alignment and stable_alignment always did: None, a
-    negative or a fraction below 1 is no CSLS."""
+    """(csls_k as an int, 0 = none; (iters, tau) or (iters, tau, cut) of a `sinkhorn=` argument, or None).  Sinkhorn and CSLS are
+    two re-scorings of one similarity, not a chain.  csls_k is truncated first, as greedy_alignment and stable_alignment always
+    did: None, a negative or a fraction below 1 is no CSLS.  A third element `cut` >= 1 asks for the potentials on the support
+    of the `cut`-long candidate lists (sparse_sinkhorn_potentials); it is clamped to each side's size where the lists are made."""
     csls_k = max(int(csls_k or 0), 0)
     if sinkhorn is None:
         return csls_k, None
-    iters, tau = sinkhorn
+    if len(sinkhorn) == 3:
+        iters, tau, cut = sinkhorn
+    else:
+        (iters, tau), cut = sinkhorn, None
     if csls_k > 0 or csls is not None:
         raise _lib.MultiKEHipError("sinkhorn and csls_k are both set: choose one re-scoring")
     if int(iters) != iters or int(iters) < 1 or not (float(tau) > 0.0) or not np.isfinite(float(tau)):
         raise _lib.MultiKEHipError(f"sinkhorn=(iters, tau) needs iters >= 1 and a finite tau > 0, got ({iters}, {tau})")
-    return csls_k, (int(iters), float(tau))
+    if cut is None:
+        return csls_k, (int(iters), float(tau))
+    if int(cut) != cut or int(cut) < 1:
+        raise _lib.MultiKEHipError(f"sinkhorn=(iters, tau, cut) needs a whole cut >= 1, got {cut}")
+    return csls_k, (int(iters), float(tau), int(cut))
 
 
 def sinkhorn_potentials(a, b, kpad, metric_code, sq_a, sq_b, iters, tau):
@@ -110,9 +120,49 @@ def sinkhorn_terms(a, b, kpad, metric_code, sq_a, sq_b, iters, tau):
     return 2.0 * pa, 2.0 * pb
 
 
+def sparse_support(operands, cut):
+    """The support of the sparse Sinkhorn re-scoring from prepare_operands' tuple: every pair (i, j) in which j is among row
+    i's `cut` best columns or i among column j's `cut` best rows under the plain metric (`cut` clamped to each side's size),
+    as a _lib.SparseSupport on the device — two list sweeps (candidate_lists without re-scoring, flagged rows redone as there)
+    and mke_sparse_support; a pair both lists name is one entry with the row list's value."""
+    a, b, kpad, code, sq_a, sq_b = operands
+    n1, n2 = a.shape[0], b.shape[0]
+    cut_r, cut_c = max(1, min(int(cut), n2)), max(1, min(int(cut), n1))
+    dev = a.device
+    empty = lambda n, c: (torch.full((n, c), float("-inf"), dtype=torch.float32, device=dev), torch.full((n, c), -1, dtype=torch.int32, device=dev))
+    if n1 == 0 or n2 == 0:                                   # no sweep over nothing: every list is padding
+        (val_r, col_r), (val_c, row_c) = empty(n1, cut_r), empty(n2, cut_c)
+    else:
+        val_r, col_r, _ = candidate_lists(a, b, kpad, cut_r, code, sq_a, sq_b)
+        val_c, row_c, _ = candidate_lists(b, a, kpad, cut_c, code, sq_b, sq_a)
+    return _lib.sparse_support(val_r.contiguous(), col_r.contiguous(), val_c.contiguous(), row_c.contiguous())
+
+
+def sparse_sinkhorn_potentials(support, iters, tau):
+    """(a-potential [n1], b-potential [n2]) of sinkhorn_potentials' recurrence with every sum restricted to the support:
+    a_i = tau log sum_{j: (i, j) in support} exp((s_ij - b_j) / tau), then b_j likewise over its column with the a just
+    computed, b starting at zero — 2 * iters calls of mke_sparse_lse, no sweep.  An approximation of the dense potentials,
+    equal to them at full support."""
+    pa, pb = None, None
+    for _ in range(int(iters)):
+        pa = _lib.sparse_lse(support, False, tau, pb)
+        pb = _lib.sparse_lse(support, True, tau, pa)
+    return pa, pb
+
+
+def sparse_sinkhorn_terms(operands, iters, tau, cut):
+    """(r_t, r_s) = twice the sparse potentials, for `csls_row` / `csls_col` of the rank, list and mutual kernels as
+    sinkhorn_terms' are."""
+    pa, pb = sparse_sinkhorn_potentials(sparse_support(operands, cut), iters, tau)
+    return 2.0 * pa, 2.0 * pb
+
+
 def _rescoring_terms(operands, csls_k, sinkhorn):
     """(row_term [n1], col_term [n2]) of the re-scoring (2 s - row_term[i]) - col_term[j] from prepare_operands' tuple and the
-    checked (csls_k, sinkhorn): the CSLS means, or twice the Sinkhorn potentials; None when there is no re-scoring."""
+    checked (csls_k, sinkhorn): the CSLS means, or twice the Sinkhorn potentials — dense for (iters, tau), on the lists'
+    support for (iters, tau, cut); None when there is no re-scoring."""
+    if sinkhorn is not None and len(sinkhorn) == 3:
+        return sparse_sinkhorn_terms(operands, *sinkhorn)
     if sinkhorn is not None:
         return sinkhorn_terms(*operands, *sinkhorn)
     return csls_means(*operands, csls_k) if csls_k > 0 else None
@@ -472,7 +522,7 @@ def assignment_alignment(embed1, embed2, metric, normalize, csls_k, nums_threads
 def print_results(top_k, hits, mr, mrr, cost, accurate, csls_k=0, sinkhorn=None):
     """The reference's result lines (code/base/alignment.py:64-73); with sinkhorn = (iters, tau) lines of the same shape."""
     if sinkhorn is not None:
-        how = " with sinkhorn: iters={}, tau={},".format(*sinkhorn)
+        how = " with sinkhorn: iters={}, tau={},".format(*sinkhorn[:2]) + (" cut={},".format(sinkhorn[2]) if len(sinkhorn) == 3 else "")
     else:
         how = " with csls: csls={},".format(csls_k) if csls_k > 0 else ":"
     rest = ", mr = {:.3f}, mrr = {:.6f}".format(mr, mrr) if accurate else ""

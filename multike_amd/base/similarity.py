@@ -22,8 +22,12 @@ def _device_products(a, b):
 
 def sim(embed1, embed2, metric='inner', normalize=False, csls_k=0, sinkhorn=None):
     """code/base/similarity.py:9-53: the n1 x n2 similarity matrix (float32) under `metric`, CSLS re-scored when csls_k > 0,
-    Sinkhorn re-scored with sinkhorn = (iters, tau) (one or the other)."""
+    Sinkhorn re-scored with sinkhorn = (iters, tau) (one or the other).  sinkhorn = (iters, tau, cut) is refused: the matrix is
+    all here, and the support of the candidate lists belongs to the matrix-free decoders of base.alignment."""
     _check_metric(metric, "sim", "")
+    if sinkhorn is not None and len(sinkhorn) != 2:
+        raise _lib.MultiKEHipError("sim: sinkhorn=(iters, tau, cut) is the matrix-free decoders' sparse re-scoring (base.alignment); "
+                                   "the similarity matrix is re-scored densely: pass sinkhorn=(iters, tau)")
     if sinkhorn is not None and csls_k > 0:
         raise _lib.MultiKEHipError("sim: sinkhorn and csls_k are both set: choose one re-scoring")
     if isinstance(embed1, torch.Tensor) or isinstance(embed2, torch.Tensor):

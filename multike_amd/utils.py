@@ -54,7 +54,9 @@ def default_args(**over):
         # one-to-one (Gale-Shapley) alignment of the final tests over every suitor's `stable_cut` best targets (0 = off)
         stable_cut=0,
         # Sinkhorn re-scoring of the final tests: `sinkhorn_iters` iterations (0 = off) at temperature `sinkhorn_tau`; not with `csls`
-        sinkhorn_iters=0, sinkhorn_tau=0.05,
+        # `sinkhorn_cut` > 0 iterates on the support of the `sinkhorn_cut`-long candidate lists of both sides instead of on all pairs
+        # (0 = dense): two list sweeps and no sweep per iteration, for million-entity tests
+        sinkhorn_iters=0, sinkhorn_tau=0.05, sinkhorn_cut=0,
         # mutual nearest-neighbour alignment of the final tests (0 = off): precision / recall / F1 of the pairs that are each
         # other's best, at or above `mutual_threshold` (None = none; in units of the re-scored value when `csls` / Sinkhorn is on)
         mutual=0, mutual_threshold=None,
@@ -81,7 +83,8 @@ def default_args(**over):
 
 
 def sinkhorn_option(args):
-    """(iters, tau) of the hyper-parameters `sinkhorn_iters` / `sinkhorn_tau`, or None when off (0, or the keys absent).
+    """(iters, tau) of the hyper-parameters `sinkhorn_iters` / `sinkhorn_tau`, or None when off (0, or the keys absent);
+    (iters, tau, cut) when `sinkhorn_cut` > 0 (the sparse re-scoring on the candidate lists' support).
     `csls` and `sinkhorn_iters` both set is an error: they are two re-scorings of the same similarity."""
     iters = int(getattr(args, "sinkhorn_iters", 0) or 0)
     if iters <= 0:
@@ -89,7 +92,9 @@ def sinkhorn_option(args):
     if int(getattr(args, "csls", 0) or 0) > 0:
         from ._lib import MultiKEHipError
         raise MultiKEHipError("csls and sinkhorn_iters are both set: choose one re-scoring of the final tests")
-    return iters, float(getattr(args, "sinkhorn_tau", 0.05))
+    cut = int(getattr(args, "sinkhorn_cut", 0) or 0)
+    tau = float(getattr(args, "sinkhorn_tau", 0.05))
+    return (iters, tau, cut) if cut > 0 else (iters, tau)
 
 
 def task_divide(idx, n):
